@@ -227,7 +227,12 @@ def main():
                     "is ~80 %% landscape / 20 %% portrait); the hipGraph cache then holds two geometries per stream")
     ap.add_argument("--size", default=None, help="WxH of the synthetic query images (default 1600x1200, the size the metric "
                                                  "is quoted on; e.g. 1024x1024 for BASELINE configs[3])")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last timed step returned "
+                    "(keypoints, scores, descriptors; matches, match_scores unless --extract-only) as DIR/<name>.npy, float32 / float64, "
+                    "~5 MB; rank 0 only.  Inputs are seeded: two builds run with the same arguments can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     global H, W
     if args.size:
         W, H = (int(v) for v in args.size.lower().split("x"))
@@ -326,6 +331,21 @@ def main():
         for ln in lanes:
             ln.ctx.sync()
 
+    def dump_outputs(i):
+        """--dump-outputs: the arrays step(i) left in its lane's buffers, cut to the key-point count of that extraction (the later legs
+        reuse the buffers, so this runs right after the timed region)."""
+        ln = lanes[i % len(lanes)]
+        n = ctypes.c_int(0)
+        _lib.check(lib.sfd2_extract_count(ln.ctx.h, ctypes.byref(n)))
+        k = max(0, min(n.value, TOPK))
+        outs = {"keypoints": ln.kpts[:k], "scores": ln.scores[:k], "descriptors": ln.desc[:k]}
+        if not args.extract_only:
+            outs["matches"] = ln.matches[:, :k].to(torch.float64)      # (-1 = no match; exact in float64)
+            outs["match_scores"] = ln.mscores[:, :k]
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, t in outs.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), t.cpu().numpy())
+
     def barrier():
         if dist is not None:
             dist.barrier()
@@ -387,6 +407,8 @@ def main():
     dt = time.perf_counter() - t0
     layers = ctx.layer_timings()
     ctx.set_profiling(0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.steps - 1)
 
     def max_over_ranks(x):
         t = torch.tensor([x], dtype=torch.float64, device=dev)

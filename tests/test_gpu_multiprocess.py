@@ -60,6 +60,29 @@ def test_bench_under_torch_distributed_run():
     assert d["n_gpus"] == 1 and d["value"] > 0
 
 
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """--dump-outputs: the last timed step's arrays as .npy (float32 / float64, at most 64 MB), the same bits from two runs with the same
+    arguments -- also when the number of steps, and so the last step's lane and image, is odd."""
+    import numpy as np
+    cmd = BENCH + ["--no-pipeline", "--no-configs", "--steps", "5"]     # (a later --steps overrides BENCH's)
+    got = []
+    for run in ("a", "b"):
+        r = subprocess.run(cmd + ["--dump-outputs", str(tmp_path / run)], env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"),
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+        assert r.returncode == 0, r.stderr.decode()[-2000:]
+        d = _one_json_line(r.stdout.decode())
+        assert d["steps"] == 5 and d["ms_per_step"] > 0
+        got.append({n: np.load(tmp_path / run / (n + ".npy")) for n in ("keypoints", "scores", "descriptors", "matches", "match_scores")})
+    a, b = got
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert a["keypoints"].shape == (4096, 2) and a["descriptors"].shape == (4096, 128) and a["matches"].shape == (50, 4096)
+    for n in a:
+        assert a[n].dtype in (np.float32, np.float64), n
+        assert np.array_equal(a[n], b[n]), n
+    assert np.allclose(np.linalg.norm(a["descriptors"], axis=1), 1.0, atol=1e-3)
+    assert (a["matches"] >= 0).any() and np.array_equal(a["matches"], np.round(a["matches"]))
+
+
 def test_bench_refuses_unrequested_world():
     env = dict(os.environ, RANK="0", LOCAL_RANK="0", WORLD_SIZE="2", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()))
     r = subprocess.run(BENCH, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
