@@ -62,12 +62,12 @@ extern "C" int sfd2_det(sfd2_ctx *c, const float *x, int x_on_device, int H, int
     if (!c->weights_loaded) return fail("sfd2_det: weights not loaded");
     if (stability && !c->has_sta) return fail("sfd2_det: stability requested but the loaded state_dict has no ConvSta");
     HIPCHECK(hipSetDevice(c->device));
-    set_path(c, true);   // det is the parity entry point: every activation stays readable unless "fuse_det" is set
-    if (ensure_workspace(c, H, W)) return -1;
+    const PassPlan plan = plan_pass(c, PASS_DET, H, W);   // det is the parity entry point: every activation stays readable unless "fuse_det" is set
+    if (ensure_workspace(c, plan, H, W)) return -1;
     const float *img = nullptr;
     if (stage_image(c, x, x_on_device, H, W, &img)) return -1;
     prof_step_begin(c);
-    if (run_network(c, img, (flags & SFD2_FLAG_IMG_NORMALISED) ? 0 : 1)) return -1;
+    if (run_network(c, plan, img, (flags & SFD2_FLAG_IMG_NORMALISED) ? 0 : 1)) return -1;
     if (release_image_slot(c)) return -1;
     prof_step_end(c);
     const int HS = 8 * c->H8, WS = 8 * c->W8;
@@ -153,8 +153,8 @@ extern "C" int sfd2_extract(sfd2_ctx *c, const void *img, int img_on_device, int
         return fail("sfd2_extract: the loaded state_dict has no ConvSta; pass SFD2_FLAG_NO_STABILITY (use_stability=False)");
     HIPCHECK(hipSetDevice(c->device));
     if (extract_begin(c, flags)) return -1;
-    set_path(c, false);
-    if (ensure_workspace(c, H, W)) return -1;
+    const PassPlan plan = plan_pass(c, PASS_EXTRACT, H, W, top_k, desc != nullptr);
+    if (ensure_workspace(c, plan, H, W)) return -1;
     const float *img_dev = nullptr;
     const int u8 = (flags & SFD2_FLAG_IMG_U8_HWC) ? 1 : 0;
     if (u8 && (flags & SFD2_FLAG_IMG_NORMALISED)) return fail("sfd2_extract: a uint8 image cannot be pre-normalised");
@@ -164,44 +164,19 @@ extern "C" int sfd2_extract(sfd2_ctx *c, const void *img, int img_on_device, int
     HIPCHECK(hipEventRecord(c->ev[0], c->stream));
     prof_step_begin(c);
     const int in_mode = ((flags & SFD2_FLAG_IMG_NORMALISED) ? 0 : 1) | (u8 ? 2 : 0) | ((flags & SFD2_FLAG_IMG_BGR) ? 4 : 0);
-    // H, W multiples of 8 (every BASELINE geometry): the score map needs no resize, so the detector soft-max and the
-    // stability weighting run as ONE kernel that writes the heat map directly; the score map is never materialised
-    const bool fuse_post = c->opt_fuse_post && H % 8 == 0 && W % 8 == 0;
-    c->skip_head_now = fuse_post ? 1 : 0;
-    const bool fuse_pb = fuse_post && c->opt_fuse_pb && c->fuse_now && !c->opt_branches && c->pb.cout_pad >= 96;
-    c->skip_pb_now = fuse_pb ? 1 : 0;
-    // Sparse descriptor head: convDb is 1x1 and only the bilinear corners of the selected key points are sampled, so on the
-    // throughput path it runs after the selection, on 4 x K gathered pixels instead of the whole 1/4-resolution map (the
-    // 61 MB fp32 descriptor map is never written; bit-identical descriptors).  Dense when more than a quarter of the map
-    // would be gathered (top_k <= 0: every candidate).
-    const int sel_bound = top_k > 0 ? top_k : c->cand_cap;
-    const bool sparse_desc = c->opt_sparse_desc && c->fuse_now && desc && top_k > 0 && (size_t)16 * sel_bound <= (size_t)c->H4 * c->W4;
-    c->skip_db_now = sparse_desc ? 1 : 0;
-    // ... and convDa.3 (3x3) is needed at those corners only as well: 4 x K pixels instead of the whole map (sparse_da3_kernel).
-    // Not with compensated head branches (option "comp_heads": convDa.0's output then has a corr plane this kernel does not read).
-    const bool comp_heads_now = c->precision == SFD2_PREC_F16C && c->opt_comp_heads && c->opt_comp_rb;
-    const bool sparse_da3 = sparse_desc && c->opt_sparse_da3 && !comp_heads_now && !c->opt_branches;
-    // SFD2_PREC_F16X3: the same two steps in that mode's arithmetic (planes of convDa.0's output, three MFMA passes, fp32 results)
-    const bool sparse_x3 = c->precision == SFD2_PREC_F16X3 && c->opt_sparse_desc && c->opt_sparse_da3 && c->opt_x3_pp && desc && top_k > 0 &&
-                           (size_t)16 * sel_bound <= (size_t)c->H4 * c->W4;
-    c->skip_da3_now = (sparse_da3 || sparse_x3) ? 1 : 0;
-    const int net_rc = run_network(c, img_dev, in_mode);
-    c->skip_head_now = 0;
-    c->skip_db_now = 0;
-    c->skip_da3_now = 0;
-    c->skip_pb_now = 0;
-    if (net_rc) return -1;
+    // (the heads fused into the post-processing below and the sparse descriptor head: plan_pass)
+    if (run_network(c, plan, img_dev, in_mode)) return -1;
     if (release_image_slot(c)) return -1;
     HIPCHECK(hipEventRecord(c->ev[1], c->stream));
     const int HS = 8 * c->H8, WS = 8 * c->W8;
-    if (fuse_pb) {
+    if (plan.skip_pb) {
         ProfScope ps(c, "convPb+heads+heatmap", "pb_heads_heat_kernel", 2.0 * c->H8 * c->W8 * 65 * 256,
                      (double)c->H8 * c->W8 * 512 + (double)H * W * 4);
         launch_pb_heads_heat(c->stream, c->pa_cur, c->H8, c->W8, c->pb.w.as<half_t>(), c->pb.cout_pad, c->pb.scale.as<float>(),
                              c->pb.shift.as<float>(), (flags & SFD2_FLAG_NO_STABILITY) ? nullptr : c->sta.as<float>(), c->H4, c->W4,
                              H, W, c->heat.as<float>(), c->counters.as<unsigned int>(), SFD2_COUNTER_BYTES / 4);
         c->counters_clean = pb_heads_heat_clears(c->H8, c->W8, SFD2_COUNTER_BYTES / 4);
-    } else if (fuse_post) {
+    } else if (plan.skip_head) {
         ProfScope ps(c, "heads+heatmap", "heads_heat_kernel", 0.0, (double)c->H8 * c->W8 * 65 * 4 + (double)H * W * 4);
         launch_heads_heat(c->stream, c->logits.as<float>(), 128, c->H8, c->W8,
                           (flags & SFD2_FLAG_NO_STABILITY) ? nullptr : c->sta.as<float>(), c->H4, c->W4, H, W, c->heat.as<float>());
@@ -228,7 +203,7 @@ extern "C" int sfd2_extract(sfd2_ctx *c, const void *img, int img_on_device, int
             HIPCHECK(c->kdesc.ensure((size_t)sel_cap * 128 * sizeof(float)));
             desc_dst = c->kdesc.as<float>();
         }
-        if (sparse_x3 && !c->x3_desc16_now) {
+        if (plan.sparse_x3 && !plan.desc16) {
             const size_t nin = (size_t)c->H4 * c->W4 * 256;
             const int rows32 = (sel_cap * 4 + 31) / 32;           // the compact pixels as a [rows32][32] image for the generic 1x1 kernel
             HIPCHECK(c->da3_sparse.ensure((size_t)rows32 * 32 * 256 * sizeof(float)));
@@ -252,11 +227,11 @@ extern "C" int sfd2_extract(sfd2_ctx *c, const void *img, int img_on_device, int
                                      c->counters.as<unsigned int>() + 1, sel_cap, c->da3_sparse.as<float>(), c->zero_page.as<half_t>());
             }
             // convDb (1x1) on the compact [sel_cap x 4] "image" with the mode's generic kernel, then the sampler on its compact output
-            if (convf(c, "convDb", c->fdb, c->da3_sparse, rows32, 32, c->db_sparse, rows32, 32, 0)) return -1;
+            if (convf(c, plan, "convDb", c->fdb, c->da3_sparse, rows32, 32, c->db_sparse, rows32, 32, 0)) return -1;
             ProfScope ps(c, "sample_desc", "sample_desc_kernel", 0.0, (double)sel_cap * 128 * 4 * 5);
             launch_sample_desc(c->stream, c->db_sparse.as<float>(), c->H4, c->W4, H, W, c->kpts_cur, c->counters.as<unsigned int>() + 1,
                                sel_cap, desc_dst, 1);
-        } else if (sparse_da3 || (sparse_x3 && c->x3_desc16_now)) {      // (option "x3_desc16": f16x3's key points, the fp16 sparse head on convDa.0's fp16 output)
+        } else if (plan.sparse_da3 || (plan.sparse_x3 && plan.desc16)) {      // (option "x3_desc16": f16x3's key points, the fp16 sparse head on convDa.0's fp16 output)
             HIPCHECK(c->da3_sparse.ensure((size_t)sel_cap * 4 * 256 * sizeof(half_t)));
             {
                 ProfScope ps(c, "convDa.3", "sparse_da3_kernel", 2.0 * 4 * sel_cap * 256.0 * 256.0 * 9, (double)sel_cap * (16 * 512 + 4 * 512) + 2.0 * 256 * 256 * 9);
@@ -267,7 +242,7 @@ extern "C" int sfd2_extract(sfd2_ctx *c, const void *img, int img_on_device, int
             ProfScope ps(c, "desc_head", "desc_head_kernel", 2.0 * 4 * sel_cap * 128 * 256, (double)sel_cap * (4 * 512 + 512));
             launch_desc_head(c->stream, c->da3_sparse.as<half_t>(), c->H4, c->W4, H, W, c->db.w.as<half_t>(), c->db.cout_pad, c->db.scale.as<float>(),
                              c->db.shift.as<float>(), c->kpts_cur, c->counters.as<unsigned int>() + 1, sel_cap, desc_dst, 1);
-        } else if (sparse_desc) {
+        } else if (plan.sparse_desc) {
             ProfScope ps(c, "desc_head", "desc_head_kernel", 2.0 * 4 * sel_cap * 128 * 256, (double)sel_cap * (4 * 512 + 512));
             launch_desc_head(c->stream, c->da_cur, c->H4, c->W4, H, W, c->db.w.as<half_t>(), c->db.cout_pad, c->db.scale.as<float>(),
                              c->db.shift.as<float>(), c->kpts_cur, c->counters.as<unsigned int>() + 1, sel_cap, desc_dst);
@@ -398,9 +373,9 @@ extern "C" int sfd2_extract_multiscale(sfd2_ctx *c, const void *img, int img_on_
             lvl_img = c->img_scaled.as<float>();
             mode = 0;
         }
-        set_path(c, false);
-        if (ensure_workspace(c, nh[l], nw[l])) return -1;
-        if (run_network(c, lvl_img, mode)) return -1;
+        const PassPlan plan = plan_pass(c, PASS_DENSE, nh[l], nw[l]);
+        if (ensure_workspace(c, plan, nh[l], nw[l])) return -1;
+        if (run_network(c, plan, lvl_img, mode)) return -1;
         launch_heatmap(c->stream, c->score.as<float>(), 8 * c->H8, 8 * c->W8,
                        (flags & SFD2_FLAG_NO_STABILITY) ? nullptr : c->sta.as<float>(), c->H4, c->W4, nh[l], nw[l],
                        c->heat.as<float>(), nullptr);
@@ -522,12 +497,12 @@ extern "C" int sfd2_extract_spp(sfd2_ctx *c, const float *x, int x_on_device, in
         return fail("sfd2_extract_spp: the loaded state_dict has no ConvSta; pass SFD2_FLAG_NO_STABILITY");
     HIPCHECK(hipSetDevice(c->device));
     if (extract_begin(c, 0)) return -1;
-    set_path(c, false);
-    if (ensure_workspace(c, H, W)) return -1;
+    const PassPlan plan = plan_pass(c, PASS_DENSE, H, W);
+    if (ensure_workspace(c, plan, H, W)) return -1;
     const float *img_dev = nullptr;
     if (stage_image(c, x, x_on_device, H, W, &img_dev)) return -1;
     prof_step_begin(c);
-    if (run_network(c, img_dev, 0)) return -1;   // the caller normalised the image (extract.py:280-287)
+    if (run_network(c, plan, img_dev, 0)) return -1;   // the caller normalised the image (extract.py:280-287)
     if (release_image_slot(c)) return -1;
     const int HS = 8 * c->H8, WS = 8 * c->W8;
     launch_heatmap(c->stream, c->score.as<float>(), HS, WS, (flags & SFD2_FLAG_NO_STABILITY) ? nullptr : c->sta.as<float>(),
@@ -599,9 +574,9 @@ extern "C" int sfd2_extract_spp_levels(sfd2_ctx *c, const float *x, int x_on_dev
             cur = dst.as<float>();
         }
         if (!emit[l]) continue;
-        set_path(c, false);
-        if ((rc = ensure_workspace(c, nh[l], nw[l])) != 0) break;
-        if ((rc = run_network(c, cur, 0)) != 0) break;
+        const PassPlan plan = plan_pass(c, PASS_DENSE, nh[l], nw[l]);
+        if ((rc = ensure_workspace(c, plan, nh[l], nw[l])) != 0) break;
+        if ((rc = run_network(c, plan, cur, 0)) != 0) break;
         launch_heatmap(c->stream, c->score.as<float>(), 8 * c->H8, 8 * c->W8, nullptr, c->H4, c->W4, nh[l], nw[l],
                        c->heat.as<float>(), nullptr);
         if ((rc = run_greedy_nms(c, c->heat.as<float>(), nh[l], nw[l], conf_th, 4)) != 0) break;

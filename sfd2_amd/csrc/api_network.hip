@@ -4,17 +4,135 @@
 // ------------------------------------------------------------------------------------------ workspace
 static int down2(int n) { return (n - 1) / 2 + 1; }  // 3x3 stride 2 pad 1
 
-void set_path(sfd2_ctx *c, bool parity_entry)
+// which throughput kernel takes a layer of SFD2_PREC_F16X3 from hi / lo' planes: 0 none (generic, fp32 in / out), 1 conv3x3_pp, 2 conv3x3_rf
+// (small outputs and stride 2: conv2b, convPa.0 / convPa.3 at 1600x1200, every 256-channel layer of a 640x480 image -- as in f16)
+static int x3_fast_kind(const PassPlan &p, const ConvW &L, bool has_res, int Ho, int Wo)
 {
-    const bool f16 = c->precision == SFD2_PREC_F16 || c->precision == SFD2_PREC_F16C;
-    c->fuse_now = f16 && (parity_entry ? c->fuse_det : c->fuse);
-    c->alias_now = c->fuse_now && !parity_entry && c->opt_alias;
-    c->x3_fast_rb_now = c->precision == SFD2_PREC_F16X3 && !parity_entry && c->opt_x3_pp;
+    if (!p.x3_pp || has_res || L.ks != 3 || L.cin % 64 != 0) return 0;
+    if ((L.cout_pad == 256 || (L.cout_pad == 128 && L.stride == 2)) && conv3x3_rf_serves(3, L.stride, L.cout_pad, L.cin, Ho, Wo)) return 2;
+    return (L.stride == 1 && L.cout_pad % 128 == 0) ? 1 : 0;
+}
+
+// The one place that combines the options for a network pass (sfd2_ctx.h, PassPlan).  top_k and desc: sfd2_extract's arguments.
+PassPlan plan_pass(const sfd2_ctx *c, PassEntry entry, int H, int W, int top_k, bool desc)
+{
+    PassPlan p;
+    const int H2 = down2(H), W2 = down2(W), H4 = down2(H2), W4 = down2(W2);
+    const bool det = entry == PASS_DET, x3 = c->precision == SFD2_PREC_F16X3;
+    p.f32 = x3 || c->precision == SFD2_PREC_F32;
+    p.comp = c->precision == SFD2_PREC_F16C;
+    p.fuse = !p.f32 && (det ? c->fuse_det : c->fuse);   // det keeps every intermediate readable unless "fuse_det" is set
+    p.alias = p.fuse && !det && c->opt_alias;
+    p.generic_c = p.comp && c->opt_generic_c;
+    p.no_rf_c = c->opt_no_rf_c;
+    p.fp6_filters = c->opt_fp6_filters;
+    p.fused_stem = p.fuse && !p.generic_c;
+    p.comp_rb = p.comp && c->opt_comp_rb;
+    bool wrm = true, wk = true;
+    for (int b = 0; b < 3; ++b) {
+        wrm = wrm && c->rb1[b].wrm.p && c->rb3[b].wrm.p;
+        wk = wk && c->rb1[b].wfl.p && c->rb3[b].wfl.p && c->rb2[b].wlk.p;
+    }
+    // a ResBlock in plain fp16 (nets/sfd2.py:25-55): the fused kernel wherever the fused path runs (SFD2_FUSED_RB=0 in experiment builds: three kernels
+    // per block, through t1 / t2 buffers that ensure_workspace then allocates)
+    const char *frb = sfd2_env("SFD2_FUSED_RB");
+    p.rb_fused = p.fuse && !p.comp_rb && !(frb && frb[0] == '0') && wrm;
+    p.rb_inner = (p.comp_rb && !p.generic_c && wk) ? c->opt_rb_inner : 0;
+    p.rb23 = p.rb_inner >= 2 && c->opt_fuse_rb23;
+    if (p.comp) {
+        // Option "fp6_acts": three tensors have conv3x3_pp<comp> as their only reader -- conv1b's output (-> conv2a), conv2b's (-> conv3a) and
+        // conv3a's (-> conv3b).  Their corr records leave the producer as block-scaled fp6 half-records, and the consumer's correction is one
+        // fp6 x fp6 scaled MFMA per unit: 33.5 cycles where a unit with fp8 on either side takes 66 (profiles/r04_mfma_probe.txt).  Decided
+        // per tensor: the producer must be the kernel that can write them (the fused stem, conv3x3_rf<2,comp>, conv3x3_pp<comp>).
+        const bool use6 = c->opt_fp6_acts && !p.generic_c && c->c2a.wc66.p && c->c3a.wc66.p && c->c3b.wc66.p;
+        p.s6 = use6 && p.fuse && c->w1b_stem_c6.p;
+        p.b6 = use6 && !p.no_rf_c && conv3x3_rf_c_serves(3, 2, c->c2b.cout_pad, c->c2b.cin, H4, W4);
+        p.a6 = use6;
+        // Option "s2d" (throughput path only: the tensor is not readable by sfd2_debug_activation in that layout): conv2a stores its output as
+        // four parity planes at quarter resolution, conv2b reads them as a stride-1 layer (conv2b_s2d_kernel.hip)
+        p.d2 = c->opt_s2d && p.alias && p.s6 && !p.no_rf_c && conv2b_s2d_serves(H2, W2, c->c2b.cin, c->c2b.cout_pad) && H4 * 2 == H2 && W4 * 2 == W2;
+        // Option "c3b_plain" (the load-time self-check decides, api_weights.hip): conv3b takes the hi plane of conv3a's output only; conv3a keeps writing
+        // its records unless SFD2_C3A_KEEP_CORR says otherwise (experiment switch until measured)
+        static const bool c3a_plain_out = sfd2_env("SFD2_C3A_KEEP_CORR") == nullptr;
+        p.p3b = c->opt_c3b_plain && p.a6 && p.b6 && !p.generic_c;
+        p.p3a = p.p3b && c3a_plain_out;
+        // Option "trunk_r1": the three tensors the ResBlocks read as block input (conv3b's output, the outputs of blocks 0 and 1) with the residual
+        // byte only -- their readers are conv1x1_c256_c<.., 2, ..> (value bytes rebuilt from the hi plane) and rb23_c_kernel's skip path
+        p.tr1 = c->opt_trunk_r1 && p.a6 && p.rb23 && c->rb1[0].wfr.p && c->rb3[0].wf8l.p;
+        // option "comp_heads": the four 3x3 layers of the head branches compensated as well (their inputs then need corr planes: the
+        // backbone output has one when the ResBlocks are compensated); convPb / convDb / ConvSta read hi planes either way
+        // option "comp_det": the detector branch only (convPa.0, convPa.3) -- its score goes through exp(), which is what moves key points
+        p.ch = p.comp_rb && c->opt_comp_heads;
+        p.chp = p.ch || (p.comp_rb && c->opt_comp_det);
+    }
+    p.branches = c->opt_branches;
+    if (entry == PASS_EXTRACT) {
+        // H, W multiples of 8 (every BASELINE geometry): the score map needs no resize, so the detector soft-max and the
+        // stability weighting run as ONE kernel that writes the heat map directly; the score map is never materialised
+        p.skip_head = c->opt_fuse_post && H % 8 == 0 && W % 8 == 0;
+        p.skip_pb = p.skip_head && c->opt_fuse_pb && p.fuse && !p.branches && c->pb.cout_pad >= 96;
+        // Sparse descriptor head: convDb is 1x1 and only the bilinear corners of the selected key points are sampled, so on the
+        // throughput path it runs after the selection, on 4 x K gathered pixels instead of the whole 1/4-resolution map (the
+        // 61 MB fp32 descriptor map is never written; bit-identical descriptors).  Dense when more than a quarter of the map
+        // would be gathered (top_k <= 0: every candidate).
+        const bool few = desc && top_k > 0 && (size_t)16 * top_k <= (size_t)H4 * W4;
+        p.sparse_desc = c->opt_sparse_desc && p.fuse && few;
+        // ... and convDa.3 (3x3) is needed at those corners only as well: 4 x K pixels instead of the whole map (sparse_da3_kernel).
+        // Not with compensated head branches (option "comp_heads": convDa.0's output then has a corr plane this kernel does not read).
+        p.sparse_da3 = p.sparse_desc && c->opt_sparse_da3 && !p.ch && !p.branches;
+        // SFD2_PREC_F16X3: the same two steps in that mode's arithmetic (planes of convDa.0's output, three MFMA passes, fp32 results)
+        p.sparse_x3 = x3 && c->opt_sparse_desc && c->opt_sparse_da3 && c->opt_x3_pp && few;
+        p.skip_db = p.sparse_desc;
+        p.skip_da3 = p.sparse_da3 || p.sparse_x3;
+    }
+    // ConvSta before the head branches when convPb is fused into the post-processing (convDa.3 then takes the backbone output's slot); option
+    // "sta_side": on the side stream (not with "branches": that option owns the side stream)
+    p.sta_early = p.alias && p.skip_pb;
+    p.sta_side = c->has_sta && p.sta_early && c->opt_sta_side && !p.branches;
+    if (p.alias) {
+        // Activation placement.  det (the parity entry point) keeps every activation in its own buffer for
+        // sfd2_debug_activation.  The throughput path packs the whole chain into three 61 MB slots of one
+        // arena (at 1600x1200), reusing a slot as soon as its tensor is dead, so the working set fits the 256 MB
+        // Infinity Cache and a layer mostly reads what the previous one just wrote (measured: ResBlocks 400 -> 344 us;
+        // four slots measure the same as three).  A ResBlock's output overwrites its own t1 (dead once conv3 starts), the
+        // next block's t1 takes the slot of the previous input.
+        p.slot = {0, 1 /* spans slots 1-2 */, 0, 1, 2, {0, 2, 0} /* x = slot 2, 0, 2 */, {1, 1, 1}, {0, 2, 0} /* -> final x = slot 0 */,
+                  1, 1 /* behind convPa.0 */, 2, 1 /* convDa.3 runs after convPb has consumed slot 1 */, p.branches ? 4 : 3};
+        if (p.rb23) {
+            // rb23_c_kernel reads t1 (with the halo rows of neighbouring tiles) while other tiles already write the block's
+            // output: the output cannot take t1's slot.  No t2 in HBM on this path, so three slots still do.
+            p.slot.t1[1] = 0; p.slot.t1[2] = 1;    // x = slot 2, 1, 2
+            p.slot.ro[0] = 1; p.slot.ro[2] = 0;    // -> final x = slot 0
+        }
+        if (p.branches) p.slot.da = 3;   // the two head branches run concurrently: no slot is shared between them
+        // convPb fused into the detector-head kernel: convPa.3's output must outlive the network pass, so convDa.3
+        // writes over the backbone output instead (slot 0) -- ConvSta, its last reader, then runs before the heads
+        if (p.skip_pb) p.slot.da = 0;
+    }
+    p.x3_pp = x3 && c->opt_x3_pp;
+    p.x3_fast = p.x3_pp && !det;     // (the parity entry point: every tensor as fp32 for sfd2_debug_activation)
+    if (p.x3_fast) {
+        p.x3_stem = c->w1b_stem_x3.p && c->c1a.wc.p;
+        p.x3_rb = c->rb1[0].wfh.p && c->rb1[0].wfl.p && c->rb2[0].w.p && c->rb2[0].wlk.p;
+        // (a layer whose only reader takes planes writes planes and no fp32 tensor: conv2a -> conv2b -> conv3a -> conv3b -> ResBlocks)
+        p.k2b = x3_fast_kind(p, c->f2b, false, H4, W4) != 0;
+        p.k3a = x3_fast_kind(p, c->f3a, false, H4, W4) != 0;
+        p.k3b = x3_fast_kind(p, c->f3b, false, H4, W4) != 0;
+        // Option "s2d" in this mode too (round 5): conv2a (conv3x3_pp<x3>) stores its planes space-to-depth and conv2b runs as a stride-1 layer over
+        // them (conv2b_s2d_kernel<x3>) instead of on the strided conv3x3_rf<2, x3>; planes out for conv3a
+        p.s2d_x3 = c->opt_s2d && p.k2b && p.k3a && x3_fast_kind(p, c->f2a, false, H2, W2) == 1 && conv2b_s2d_serves(H2, W2, c->f2b.cin, c->f2b.cout_pad) &&
+                   H4 * 2 == H2 && W4 * 2 == W2;
+        p.da0_planes = p.skip_da3;   // (the sparse descriptor head reads convDa.0's output as planes)
+        // Option "x3_desc16" (on the backbone output's planes, which the ResBlocks on planes leave behind)
+        p.desc16 = p.da0_planes && c->opt_x3_desc16 && p.x3_rb && c->da0.w.p && c->da0.scale_rawin.p && c->da3.w.p && c->db.w.p;
+    }
+    return p;
 }
 
 // Buffers are allocated for the path that is about to run only: the throughput path needs the 3-slot
-// arena + head outputs, the layer-wise paths one buffer per activation, strict mode the fp32 set.
-int ensure_workspace(sfd2_ctx *c, int H, int W)
+// arena + head outputs, the layer-wise paths one buffer per activation, strict mode the fp32 set.  The activations are
+// registered for sfd2_debug_activation as the plan will leave them.
+int ensure_workspace(sfd2_ctx *c, const PassPlan &p, int H, int W)
 {
     if (H < 8 || W < 8) return fail("image too small (need H, W >= 8)");
     if ((long long)H * W > (1ll << 30)) return fail("image too large");
@@ -24,14 +142,11 @@ int ensure_workspace(sfd2_ctx *c, int H, int W)
     c->H8 = down2(c->H4); c->W8 = down2(c->W4);
     const size_t P1 = (size_t)H * W, P2 = (size_t)c->H2 * c->W2, P4 = (size_t)c->H4 * c->W4, P8 = (size_t)c->H8 * c->W8;
     const size_t hb = sizeof(half_t);
-    const bool f32 = c->precision == SFD2_PREC_F32 || c->precision == SFD2_PREC_F16X3;   // they share the fp32 buffers
-    const bool comp = c->precision == SFD2_PREC_F16C;
-    const bool layers = !f32 && !c->alias_now;      // private fp16 buffer per activation
+    const bool comp = p.comp;
+    const bool layers = !p.f32 && !p.alias;      // private fp16 buffer per activation
     // SFD2_PREC_F16C: every backbone activation is a hi plane followed by its corr plane (same geometry)
     const size_t bb = comp ? 2 * hb : hb;
-    const bool fused_stem = c->fuse_now && !(comp && c->opt_generic_c);
-    const bool fused_rb = c->fuse_now && (!comp || !c->opt_comp_rb);
-    if (!f32 && !fused_stem) HIPCHECK(c->a1a.ensure(P1 * 64 * bb));
+    if (!p.f32 && !p.fused_stem) HIPCHECK(c->a1a.ensure(P1 * 64 * bb));
     if (layers) {
         HIPCHECK(c->a1b.ensure(P2 * 64 * bb));
         HIPCHECK(c->a2a.ensure(P2 * 128 * bb));
@@ -39,7 +154,7 @@ int ensure_workspace(sfd2_ctx *c, int H, int W)
         HIPCHECK(c->a3a.ensure(P4 * 256 * bb));
         HIPCHECK(c->a3b.ensure(P4 * 256 * bb));
         for (int b = 0; b < 3; ++b) {
-            if (!fused_rb) {
+            if (!p.rb_fused) {
                 HIPCHECK(c->rt1[b].ensure(P4 * 256 * bb));
                 HIPCHECK(c->rt2[b].ensure(P4 * 256 * bb));
             }
@@ -62,7 +177,7 @@ int ensure_workspace(sfd2_ctx *c, int H, int W)
     HIPCHECK(c->bnd.ensure(cap * 8));
     HIPCHECK(c->counters.ensure(SFD2_COUNTER_BYTES));
     c->acts.clear();
-    auto reg = [&](const char *nm, const void *ptr, int is_f32, int planar, int ch, int pitch, int h, int w) {
+    auto reg = [&](const char *nm, const void *ptr, int is_f32, int planar, int ch, int pitch, int h, int w) -> ActInfo & {
         ActInfo ai{ptr, is_f32, planar, ch, pitch, h, w};
         // backbone activations of SFD2_PREC_F16C: the corr plane follows the hi plane
         if (comp && !is_f32 && std::strncmp(nm, "convP", 5) != 0 && std::strncmp(nm, "convD", 5) != 0)
@@ -76,7 +191,7 @@ int ensure_workspace(sfd2_ctx *c, int H, int W)
             for (const auto &g : gmap)
                 if (std::strcmp(nm, g.name) == 0) ai.exp2 = c->act_exp[g.group];
         }
-        c->acts[nm] = ai;
+        return c->acts[nm] = ai;
     };
     static const char *n1[3] = {"conv4.0.bn1", "conv4.1.bn1", "conv4.2.bn1"};
     static const char *n2[3] = {"conv4.0.bn2", "conv4.1.bn2", "conv4.2.bn2"};
@@ -84,7 +199,7 @@ int ensure_workspace(sfd2_ctx *c, int H, int W)
     reg("convPb", c->logits.p, 1, 0, 65, 128, c->H8, c->W8);
     reg("convDb", c->draw.p, 1, 0, 128, 128, c->H4, c->W4);
     reg("ConvSta", c->sta.p, 1, 1, 3, 0, c->H4, c->W4);
-    if (f32) {
+    if (p.f32) {
         const size_t fb = sizeof(float);
         HIPCHECK(c->g1a.ensure(P1 * 64 * fb));
         HIPCHECK(c->g1b.ensure(P2 * 64 * fb));
@@ -101,44 +216,44 @@ int ensure_workspace(sfd2_ctx *c, int H, int W)
         HIPCHECK(c->gpa_o.ensure(P8 * 256 * fb));
         HIPCHECK(c->gda0_o.ensure(P4 * 256 * fb));
         HIPCHECK(c->gda_o.ensure(P4 * 256 * fb));
-        reg("conv1a", c->g1a.p, 1, 0, 64, 64, H, W);
-        reg("bn1b", c->g1b.p, 1, 0, 64, 64, c->H2, c->W2);
-        reg("conv2a", c->g2a.p, 1, 0, 128, 128, c->H2, c->W2);
-        reg("bn2b", c->g2b.p, 1, 0, 128, 128, c->H4, c->W4);
-        reg("conv3a", c->g3a.p, 1, 0, 256, 256, c->H4, c->W4);
-        reg("bn3b", c->g3b.p, 1, 0, 256, 256, c->H4, c->W4);
+        // throughput path of SFD2_PREC_F16X3: from the stem to convDa.0 the tensors exist as hi / lo' planes only; the fp32 buffers are
+        // written for the last ResBlock's output and convPa.3's.  sfd2_debug_activation must say so instead of handing back what an
+        // earlier sfd2_det left in them
+        const bool gone = p.x3_fast;
+        reg("conv1a", c->g1a.p, 1, 0, 64, 64, H, W).absent = gone;
+        reg("bn1b", c->g1b.p, 1, 0, 64, 64, c->H2, c->W2).absent = gone;
+        reg("conv2a", c->g2a.p, 1, 0, 128, 128, c->H2, c->W2).absent = gone;
+        reg("bn2b", c->g2b.p, 1, 0, 128, 128, c->H4, c->W4).absent = gone;
+        reg("conv3a", c->g3a.p, 1, 0, 256, 256, c->H4, c->W4).absent = gone;
+        reg("bn3b", c->g3b.p, 1, 0, 256, 256, c->H4, c->W4).absent = gone;
         for (int b = 0; b < 3; ++b) {
-            reg(n1[b], c->grt1[b].p, 1, 0, 256, 256, c->H4, c->W4);
-            reg(n2[b], c->grt2[b].p, 1, 0, 256, 256, c->H4, c->W4);
-            reg(n3[b], c->gro[b].p, 1, 0, 256, 256, c->H4, c->W4);
+            reg(n1[b], c->grt1[b].p, 1, 0, 256, 256, c->H4, c->W4).absent = gone;
+            reg(n2[b], c->grt2[b].p, 1, 0, 256, 256, c->H4, c->W4).absent = gone;
+            reg(n3[b], c->gro[b].p, 1, 0, 256, 256, c->H4, c->W4).absent = gone && b < 2;
         }
-        reg("convPa.0", c->gpa0_o.p, 1, 0, 256, 256, c->H8, c->W8);
+        reg("convPa.0", c->gpa0_o.p, 1, 0, 256, 256, c->H8, c->W8).absent = gone;
         reg("convPa", c->gpa_o.p, 1, 0, 256, 256, c->H8, c->W8);
-        reg("convDa.0", c->gda0_o.p, 1, 0, 256, 256, c->H4, c->W4);
-        reg("convDa", c->gda_o.p, 1, 0, 256, 256, c->H4, c->W4);
-        if (c->x3_fast_rb_now) {
-            // throughput path of SFD2_PREC_F16X3 (sfd2_extract): from the stem to convDa.0 the tensors exist as hi / lo' planes only; the fp32
-            // buffers are written for the last ResBlock's output and convPa.3's.  sfd2_debug_activation must say so instead of handing
-            // back what an earlier sfd2_det left in them
-            for (auto &kv : c->acts)
-                if (kv.first != "conv4.2" && kv.first != "convPa" && kv.first != "convPb" && kv.first != "convDb" && kv.first != "ConvSta")
-                    kv.second.absent = true;
-        }
+        reg("convDa.0", c->gda0_o.p, 1, 0, 256, 256, c->H4, c->W4).absent = gone;
+        reg("convDa", c->gda_o.p, 1, 0, 256, 256, c->H4, c->W4).absent = gone;
         return 0;
     }
     if (!layers) return 0;   // throughput path: intermediates live in aliased arena slots and are not readable
-    if (!fused_stem) reg("conv1a", c->a1a.p, 0, 0, 64, 64, H, W);
-    reg("bn1b", c->a1b.p, 0, 0, 64, 64, c->H2, c->W2);
+    // (SFD2_PREC_F16C: the corr records' format per tensor -- fp6 half-records, residual bytes, none -- as the plan has the producers write them)
+    if (!p.fused_stem) reg("conv1a", c->a1a.p, 0, 0, 64, 64, H, W);
+    reg("bn1b", c->a1b.p, 0, 0, 64, 64, c->H2, c->W2).fmt6 = p.s6;
     reg("conv2a", c->a2a.p, 0, 0, 128, 128, c->H2, c->W2);
-    reg("bn2b", c->a2b.p, 0, 0, 128, 128, c->H4, c->W4);
-    reg("conv3a", c->a3a.p, 0, 0, 256, 256, c->H4, c->W4);
-    reg("bn3b", c->a3b.p, 0, 0, 256, 256, c->H4, c->W4);
+    reg("bn2b", c->a2b.p, 0, 0, 128, 128, c->H4, c->W4).fmt6 = p.b6;
+    ActInfo &a3 = reg("conv3a", c->a3a.p, 0, 0, 256, 256, c->H4, c->W4);
+    a3.fmt6 = p.a6 && !p.p3a;
+    if (p.p3a) a3.pc = nullptr;
+    reg("bn3b", c->a3b.p, 0, 0, 256, 256, c->H4, c->W4).r1 = p.tr1;
     for (int b = 0; b < 3; ++b) {
-        if (!fused_rb) {
-            reg(n1[b], c->rt1[b].p, 0, 0, 256, 256, c->H4, c->W4);
-            reg(n2[b], c->rt2[b].p, 0, 0, 256, 256, c->H4, c->W4);
+        if (!p.rb_fused) {      // "rb_inner": t1 (2) and t2 (1, 2) plain fp16; t2 stays on chip in rb23_c_kernel
+            ActInfo &t1 = reg(n1[b], c->rt1[b].p, 0, 0, 256, 256, c->H4, c->W4), &t2 = reg(n2[b], c->rt2[b].p, 0, 0, 256, 256, c->H4, c->W4);
+            if (p.rb_inner >= 2) t1.pc = nullptr;
+            if (p.rb_inner) { t2.pc = nullptr; t2.absent = p.rb23; }
         }
-        reg(n3[b], c->ro[b].p, 0, 0, 256, 256, c->H4, c->W4);
+        reg(n3[b], c->ro[b].p, 0, 0, 256, 256, c->H4, c->W4).r1 = p.tr1 && (b < 2 || !p.chp);   // (the last one keeps its units for compensated heads)
     }
     reg("convPa.0", c->pa0_o.p, 0, 0, 256, 256, c->H8, c->W8);
     reg("convPa", c->pa_o.p, 0, 0, 256, 256, c->H8, c->W8);
@@ -182,7 +297,7 @@ static unsigned int *range_slot(sfd2_ctx *c, int id)
     return (id >= 0 && c->range_stat.p) ? c->range_stat.as<unsigned int>() + id * SFD2_RANGE_SUB : nullptr;
 }
 static half_t *corr_of(const DevPtr &b, size_t px, int pitch) { return b.as<half_t>() + px * (size_t)pitch; }
-static void convc(sfd2_ctx *c, const char *name, const ConvW &L, const DevPtr &in, int H, int W, const DevPtr &out,
+static void convc(sfd2_ctx *c, const PassPlan &p, const char *name, const ConvW &L, const DevPtr &in, int H, int W, const DevPtr &out,
                   int Ho, int Wo, int relu, bool in_comp, bool out_comp, const DevPtr *res = nullptr, int rs_id = -1 /* SFD2_RS_*: the output's range-status slot */,
                   int fmt6 = 0 /* option "fp6_acts": bit 0 = the input's corr records are fp6 half-records, bit 1 = the output's are to be */)
 {
@@ -196,7 +311,7 @@ static void convc(sfd2_ctx *c, const char *name, const ConvW &L, const DevPtr &i
     const half_t *in_c = in_comp ? corr_of(in, (size_t)H * W, L.cin) : nullptr;
     half_t *out_c = out_comp ? corr_of(out, (size_t)Ho * Wo, L.cout_pad) : nullptr;
     // conv3x3_pp's tile is 128 channels wide: in its compensated form it also takes conv2a (64 -> 128 channels, four chunks)
-    if (!res && !c->opt_generic_c && L.ks == 3 && L.stride == 1 && L.cout_pad % 128 == 0 && L.cin % 64 == 0) {
+    if (!res && !p.generic_c && L.ks == 3 && L.stride == 1 && L.cout_pad % 128 == 0 && L.cin % 64 == 0) {
         ProfScope ps(c, name, (in_c && out_c) ? "conv3x3_pp<comp>" : (in_c ? "conv3x3_pp<comp,plain out>" : "conv3x3_pp<comp out>"), flops, bytes);
         if (relu && ((!in_c && out_c) || (in_c && !out_c && (fmt6 & 1) && L.wc66.p && L.sa66.p))) {
             // option "c3b_plain": conv3b over the hi plane of its input alone (the hi chunks at the start of any of the layer's arrays; the output's corr
@@ -215,19 +330,19 @@ static void convc(sfd2_ctx *c, const char *name, const ConvW &L, const DevPtr &i
             return;
         }
         if (fmt6) { c->net_error = 1; (void)fail(std::string(name) + ": fp6 records requested from a layer without fp6 filter strings"); return; }
-        const bool f6 = c->opt_fp6_filters && in_c && out_c && L.wc6.p && L.sa6.p;      // corr filters as fp6 (option "fp6_filters")
+        const bool f6 = p.fp6_filters && in_c && out_c && L.wc6.p && L.sa6.p;      // corr filters as fp6 (option "fp6_filters")
         launch_conv3x3_pp_c(c->cur_stream, in.as<half_t>(), in_c, H, W, L.cin, f6 ? L.wc6.as<half_t>() : L.wc.as<half_t>(), L.scale.as<float>(),
                             L.shift.as<float>(), L.cout_pad, relu, out.as<half_t>(), out_c, Ho, Wo, c->zero_page.as<half_t>(), L.sbyte,
                             f6 ? L.sa6.as<float>() : nullptr, rs);
         return;
     }
-    if ((fmt6 & 1) || ((fmt6 & 2) && !(!c->opt_generic_c && !c->opt_no_rf_c && conv3x3_rf_c_serves(L.ks, L.stride, L.cout_pad, L.cin, Ho, Wo) && relu))) {
+    if ((fmt6 & 1) || ((fmt6 & 2) && !(!p.generic_c && !p.no_rf_c && conv3x3_rf_c_serves(L.ks, L.stride, L.cout_pad, L.cin, Ho, Wo) && relu))) {
         // (run_network decides the format per tensor from the same predicates: reaching this is a bug, reported as an error of the call)
         c->net_error = 1;
         (void)fail(std::string(name) + ": fp6 records on a path that cannot read / write them");
         return;
     }
-    if (!c->opt_generic_c && !c->opt_no_rf_c && in_c && out_c && !res && L.ks == 3 && L.stride == 2 && L.cout_pad == 128) {   // conv2b
+    if (!p.generic_c && !p.no_rf_c && in_c && out_c && !res && L.ks == 3 && L.stride == 2 && L.cout_pad == 128) {   // conv2b
         ProfScope ps(c, name, "conv3x3_rf<2,comp>", flops, bytes);
         if (!launch_conv3x3_rf_c(c->cur_stream, in.as<half_t>(), in_c, H, W, L.cin, L.wc.as<half_t>(), L.scale.as<float>(),
                                 L.shift.as<float>(), L.cout_pad, L.stride, relu, out.as<half_t>(), out_c, Ho, Wo,
@@ -236,7 +351,7 @@ static void convc(sfd2_ctx *c, const char *name, const ConvW &L, const DevPtr &i
         else
             return;
     }
-    if (!c->opt_generic_c && in_c && out_c && L.wfh.p && L.wfc.p) {   // the ResBlocks' 1x1 layers: persistent streaming kernel
+    if (!p.generic_c && in_c && out_c && L.wfh.p && L.wfc.p) {   // the ResBlocks' 1x1 layers: persistent streaming kernel
         snprintf(kn, sizeof(kn), "conv1x1_c256<comp>%s", res ? "+res" : "");
         ProfScope ps(c, name, kn, flops, bytes);
         launch_conv1x1_c256_c(c->cur_stream, in.as<half_t>(), in_c, Ho * Wo, L.wfh.as<half_t>(), L.wfc.as<half_t>(), L.scale.as<float>(),
@@ -245,7 +360,7 @@ static void convc(sfd2_ctx *c, const char *name, const ConvW &L, const DevPtr &i
                               c->zero_page.as<half_t>(), L.sbyte, rs);
         return;
     }
-    if (!c->opt_generic_c && in_c && out_c && L.cout_pad % 128 == 0 && ((L.ks == 1 && L.stride == 1) || (L.ks == 3 && L.stride == 2 && !res))) {
+    if (!p.generic_c && in_c && out_c && L.cout_pad % 128 == 0 && ((L.ks == 1 && L.stride == 1) || (L.ks == 3 && L.stride == 2 && !res))) {
         snprintf(kn, sizeof(kn), "conv_igemm2<%d,%d,comp>%s", L.ks, L.stride, res ? "+res" : "");
         ProfScope ps(c, name, kn, flops, bytes);
         if (!launch_conv_igemm2_c(c->cur_stream, in.as<half_t>(), in_c, H, W, L.cin, L.wc.as<half_t>(), L.scale.as<float>(),
@@ -264,21 +379,12 @@ static void convc(sfd2_ctx *c, const char *name, const ConvW &L, const DevPtr &i
                        out.as<half_t>(), out_comp ? corr_of(out, (size_t)Ho * Wo, L.cout_pad) : nullptr, Ho, Wo, L.sbyte, rs);
 }
 
-// which throughput kernel takes a layer of SFD2_PREC_F16X3 from hi / lo' planes: 0 none (generic, fp32 in / out), 1 conv3x3_pp, 2 conv3x3_rf
-// (small outputs and stride 2: conv2b, convPa.0 / convPa.3 at 1600x1200, every 256-channel layer of a 640x480 image -- as in f16)
-static int x3_fast_kind(const sfd2_ctx *c, const ConvW &L, bool has_res, int Ho, int Wo)
-{
-    if (c->precision != SFD2_PREC_F16X3 || !c->opt_x3_pp || has_res || L.ks != 3 || L.cin % 64 != 0) return 0;
-    if ((L.cout_pad == 256 || (L.cout_pad == 128 && L.stride == 2)) && conv3x3_rf_serves(3, L.stride, L.cout_pad, L.cin, Ho, Wo)) return 2;
-    return (L.stride == 1 && L.cout_pad % 128 == 0) ? 1 : 0;
-}
-
-int convf(sfd2_ctx *c, const char *name, const ConvW &L, const DevPtr &in, int H, int W, const DevPtr &out,
-          int Ho, int Wo, int relu, const float *res)
+int convf(sfd2_ctx *c, const PassPlan &p, const char *name, const ConvW &L, const DevPtr &in, int H, int W, const DevPtr &out,
+          int Ho, int Wo, int relu, const float *res, X3Planes planes, bool s2d)
 {
     char kn[64];
     const bool x3 = c->precision == SFD2_PREC_F16X3;
-    const int kind = x3_fast_kind(c, L, res != nullptr, Ho, Wo);
+    const int kind = x3_fast_kind(p, L, res != nullptr, Ho, Wo);
     const bool use_rf = kind == 2;
     if (kind != 0) {
         // The 3x3 layers (half of this mode's time) on the throughput kernels: the input is split ONCE into hi / lo'
@@ -299,8 +405,8 @@ int convf(sfd2_ctx *c, const char *name, const ConvW &L, const DevPtr &in, int H
         }
         const size_t nout = (size_t)Ho * Wo * L.cout_pad;
         half_t *oh = nullptr, *ol = nullptr;
-        if (c->x3_planes_out_now) {      // planes out (the only reader is the next 3x3 layer / the ResBlocks / the sparse descriptor head)
-            DevBuf &dst = c->x3_planes_out_now == 2 ? c->x3_da0_planes : c->x3_planes_out_now == 3 ? c->x3_rb_planes[0]
+        if (planes != X3_NONE) {      // planes out (the only reader is the next 3x3 layer / the ResBlocks / the sparse descriptor head)
+            DevBuf &dst = planes == X3_DA0 ? c->x3_da0_planes : planes == X3_RB ? c->x3_rb_planes[0]
                           : (ph == c->x3_chain.as<half_t>() ? c->x3_chain2 : c->x3_chain);
             if (dst.ensure(nout * 2 * sizeof(half_t)) != hipSuccess) return fail("out of device memory (f16x3 activation planes)");
             oh = dst.as<half_t>(); ol = oh + nout;
@@ -314,7 +420,7 @@ int convf(sfd2_ctx *c, const char *name, const ConvW &L, const DevPtr &in, int H
             return 0;
         if (L.stride != 1) { ps.cancel(); return fail("conv3x3_rf<x3>: no instantiation for this layer (x3_fast_kind and the launcher disagree)"); }
         launch_conv3x3_pp_x3(c->stream, ph, pl, H, W, L.cin, L.wx3p.as<half_t>(), L.scale.as<float>(), L.shift.as<float>(), L.cout_pad, relu,
-                             oh, ol, oh ? nullptr : out.as<float>(), Ho, Wo, c->zero_page.as<half_t>(), (oh && c->x3_s2d_out_now) ? 1 : 0);
+                             oh, ol, oh ? nullptr : out.as<float>(), Ho, Wo, c->zero_page.as<half_t>(), (oh && s2d) ? 1 : 0);
         return 0;
     }
     if (x3 && !L.wx3.p) {      // split the packed filters once: the kernel then stages them without arithmetic
@@ -333,14 +439,13 @@ int convf(sfd2_ctx *c, const char *name, const ConvW &L, const DevPtr &in, int H
 }
 
 // strict mode: identical layer sequence on fp32 activations (conv_f32_kernels.hip)
-static int run_network_f32(sfd2_ctx *c, const float *img_dev, int normalise)
+static int run_network_f32(sfd2_ctx *c, const PassPlan &p, const float *img_dev, int normalise)
 {
     hipStream_t st = c->stream;
     const int H = c->H, W = c->W, H2 = c->H2, W2 = c->W2, H4 = c->H4, W4 = c->W4, H8 = c->H8, W8 = c->W8;
     const double P1 = (double)H * W, P4 = (double)H4 * W4, P8 = (double)H8 * W8;
     c->x3_pre_src = nullptr;           // (no planes of an earlier pass are left over)
-    c->x3_planes_out_now = 0;
-    if (c->x3_fast_rb_now && c->w1b_stem_x3.p && c->c1a.wc.p) {
+    if (p.x3_stem) {
         // throughput path of SFD2_PREC_F16X3: the fused stem in three-pass arithmetic (conv1a's image and filters as hi + lo fp16 as
         // in the compensated mode, conv1b on hi / lo' planes of conv1a's tile in LDS), its output as planes for conv2a
         const size_t nout = (size_t)H2 * W2 * 64;
@@ -356,23 +461,12 @@ static int run_network_f32(sfd2_ctx *c, const float *img_dev, int normalise)
         launch_conv1a_f32(st, img_dev, H, W, normalise, c->f1a.w.as<float>(), c->f1a.scale.as<float>(),
                           c->f1a.shift.as<float>(), c->g1a.as<float>());
     }
-    if (convf(c, "conv1b", c->f1b, c->g1a, H, W, c->g1b, H2, W2, 1)) return -1;
+    if (convf(c, p, "conv1b", c->f1b, c->g1a, H, W, c->g1b, H2, W2, 1)) return -1;
     }
     // (throughput path: a layer whose only reader takes planes writes planes and no fp32 tensor: conv2a -> conv2b -> conv3a -> conv3b ->
     // ResBlocks, convDa.0 -> the sparse descriptor head)
-    const bool fast_rb = c->x3_fast_rb_now && c->rb1[0].wfh.p && c->rb1[0].wfl.p && c->rb2[0].w.p && c->rb2[0].wlk.p;
-    const bool k2b = c->x3_fast_rb_now && x3_fast_kind(c, c->f2b, false, H4, W4) != 0, k3a = c->x3_fast_rb_now && x3_fast_kind(c, c->f3a, false, H4, W4) != 0;
-    const bool k3b = c->x3_fast_rb_now && x3_fast_kind(c, c->f3b, false, H4, W4) != 0;
-    // Option "s2d" in this mode too (round 5): conv2a (conv3x3_pp<x3>) stores its planes space-to-depth and conv2b runs as a stride-1 layer over
-    // them (conv2b_s2d_kernel<x3>) instead of on the strided conv3x3_rf<2, x3>; planes out for conv3a
-    const bool s2d_x3 = c->opt_s2d && k2b && k3a && x3_fast_kind(c, c->f2a, false, H2, W2) == 1 && conv2b_s2d_serves(H2, W2, c->f2b.cin, c->f2b.cout_pad) &&
-                        H4 * 2 == H2 && W4 * 2 == W2;
-    c->x3_planes_out_now = k2b ? 1 : 0;
-    c->x3_s2d_out_now = s2d_x3 ? 1 : 0;
-    if (convf(c, "conv2a", c->f2a, c->g1b, H2, W2, c->g2a, H2, W2, 1)) return -1;
-    c->x3_s2d_out_now = 0;
-    c->x3_planes_out_now = k3a ? 1 : 0;
-    if (s2d_x3 && c->x3_pre_src == c->g2a.p && c->x3_pre_hi) {
+    if (convf(c, p, "conv2a", c->f2a, c->g1b, H2, W2, c->g2a, H2, W2, 1, nullptr, p.k2b ? X3_CHAIN : X3_NONE, p.s2d_x3)) return -1;
+    if (p.s2d_x3 && c->x3_pre_src == c->g2a.p && c->x3_pre_hi) {
         ConvW &L = c->f2b;
         const size_t nfl = (size_t)9 * L.cout_pad * L.cin, nout = (size_t)H4 * W4 * L.cout_pad;
         if (!L.wx3p.p) {
@@ -388,19 +482,16 @@ static int run_network_f32(sfd2_ctx *c, const float *img_dev, int normalise)
             launch_conv2b_s2d_x3(st, ph, pl, H4, W4, L.wx3p.as<half_t>(), L.scale.as<float>(), L.shift.as<float>(), 1, oh, ol, c->zero_page.as<half_t>());
         }
         c->x3_pre_src = c->g2b.p; c->x3_pre_hi = oh; c->x3_pre_lo = ol;
-    } else if (convf(c, "conv2b", c->f2b, c->g2a, H2, W2, c->g2b, H4, W4, 1)) return -1;
-    c->x3_planes_out_now = k3b ? 1 : 0;
-    if (convf(c, "conv3a", c->f3a, c->g2b, H4, W4, c->g3a, H4, W4, 1)) return -1;
-    c->x3_planes_out_now = (fast_rb && k3b) ? 3 : 0;
-    if (convf(c, "conv3b", c->f3b, c->g3a, H4, W4, c->g3b, H4, W4, 1)) return -1;
-    c->x3_planes_out_now = 0;
+    } else if (convf(c, p, "conv2b", c->f2b, c->g2a, H2, W2, c->g2b, H4, W4, 1, nullptr, p.k3a ? X3_CHAIN : X3_NONE)) return -1;
+    if (convf(c, p, "conv3a", c->f3a, c->g2b, H4, W4, c->g3a, H4, W4, 1, nullptr, p.k3b ? X3_CHAIN : X3_NONE)) return -1;
+    if (convf(c, p, "conv3b", c->f3b, c->g3a, H4, W4, c->g3b, H4, W4, 1, nullptr, (p.x3_rb && p.k3b) ? X3_RB : X3_NONE)) return -1;
     const bool rb_in_planes = c->x3_pre_src == c->g3b.p;      // conv3b left the ResBlocks' input planes in x3_rb_planes[0]
     c->x3_pre_src = nullptr;
     const DevPtr *x = &c->g3b;
     static const char *nm1[3] = {"conv4.0.conv1", "conv4.1.conv1", "conv4.2.conv1"};
     static const char *nm2[3] = {"conv4.0.conv2", "conv4.1.conv2", "conv4.2.conv2"};
     static const char *nm3[3] = {"conv4.0.conv3", "conv4.1.conv3", "conv4.2.conv3"};
-    if (fast_rb) {
+    if (p.x3_rb) {
         // ResBlocks of SFD2_PREC_F16X3 on the throughput path: every tensor of a block lives as hi / lo' planes (the input is split
         // once in front of the first block).  conv1 and conv3 on the streaming three-pass 1x1 kernel (filters = the fp16 set's
         // fragment-ordered hi / lo' arrays: the same split of the same fp32 weights), the grouped conv on gconv_c_kernel<X3>
@@ -435,8 +526,8 @@ static int run_network_f32(sfd2_ctx *c, const float *img_dev, int normalise)
         x = &c->gro[2];
         c->x3_pre_src = x->p; c->x3_pre_hi = xh; c->x3_pre_lo = xl;     // the backbone output's planes: convDa.0 takes them as they are
     }
-    for (int b = 0; b < (fast_rb ? 0 : 3); ++b) {
-        if (convf(c, nm1[b], c->frb1[b], *x, H4, W4, c->grt1[b], H4, W4, 1)) return -1;
+    for (int b = 0; b < (p.x3_rb ? 0 : 3); ++b) {
+        if (convf(c, p, nm1[b], c->frb1[b], *x, H4, W4, c->grt1[b], H4, W4, 1)) return -1;
         {
             if (c->precision == SFD2_PREC_F16X3) {
                 if (!c->frb2[b].wx3.p) {
@@ -452,24 +543,20 @@ static int run_network_f32(sfd2_ctx *c, const float *img_dev, int normalise)
                                  c->frb2[b].shift.as<float>(), c->grt2[b].as<float>());
             }
         }
-        if (convf(c, nm3[b], c->frb3[b], c->grt2[b], H4, W4, c->gro[b], H4, W4, 1, x->as<float>())) return -1;
+        if (convf(c, p, nm3[b], c->frb3[b], c->grt2[b], H4, W4, c->gro[b], H4, W4, 1, x->as<float>())) return -1;
         x = &c->gro[b];
     }
     // (throughput path: convPa.0 reads the backbone output's planes and leaves its own output as planes for convPa.3)
     const void *bb_src = c->x3_pre_src;
     const half_t *bb_hi = c->x3_pre_hi, *bb_lo = c->x3_pre_lo;
-    c->x3_planes_out_now = c->x3_fast_rb_now ? 1 : 0;
-    if (convf(c, "convPa.0", c->fpa0, *x, H4, W4, c->gpa0_o, H8, W8, 1)) return -1;
-    c->x3_planes_out_now = 0;
-    if (convf(c, "convPa.3", c->fpa3, c->gpa0_o, H8, W8, c->gpa_o, H8, W8, 0)) return -1;
-    if (convf(c, "convPb", c->fpb, c->gpa_o, H8, W8, c->logits, H8, W8, 0)) return -1;
+    if (convf(c, p, "convPa.0", c->fpa0, *x, H4, W4, c->gpa0_o, H8, W8, 1, nullptr, p.x3_fast ? X3_CHAIN : X3_NONE)) return -1;
+    if (convf(c, p, "convPa.3", c->fpa3, c->gpa0_o, H8, W8, c->gpa_o, H8, W8, 0)) return -1;
+    if (convf(c, p, "convPb", c->fpb, c->gpa_o, H8, W8, c->logits, H8, W8, 0)) return -1;
     c->x3_pre_src = bb_src; c->x3_pre_hi = bb_hi; c->x3_pre_lo = bb_lo;      // convDa.0 takes the same planes
-    const bool da0_planes = c->skip_da3_now && c->x3_fast_rb_now;
     // Option "x3_desc16": the descriptor branch leaves this mode's arithmetic here -- convDa.0 as ONE fp16 pass (conv3x3_pp) over the backbone output's hi
     // plane, at the network's own scale (scale_rawin), its output (times 2^act_exp[AE_DA0], what convDa.3's folded constants expect) in the buffer
     // the planes would have taken; sfd2_extract then runs the fp16 sparse head on it.  The detector branch above is untouched.
-    c->x3_desc16_now = 0;
-    if (da0_planes && c->opt_x3_desc16 && bb_src == x->p && bb_hi && c->da0.w.p && c->da0.scale_rawin.p && c->da3.w.p && c->db.w.p) {
+    if (p.desc16) {
         const size_t nin = (size_t)H4 * W4 * 256;
         HIPCHECK(c->x3_da0_planes.ensure(nin * 2 * sizeof(half_t)));
         DevPtr in, out;
@@ -477,31 +564,26 @@ static int run_network_f32(sfd2_ctx *c, const float *img_dev, int normalise)
         out.p = c->x3_da0_planes.p;
         conv(c, "convDa.0", c->da0, in, H4, W4, out, H4, W4, 1, nullptr, 0, c->da0.scale_rawin.as<float>());
         c->da0_cur = c->x3_da0_planes.as<half_t>();
-        c->x3_desc16_now = 1;
-    } else {
-    c->x3_planes_out_now = da0_planes ? 2 : 0;
-    if (convf(c, "convDa.0", c->fda0, *x, H4, W4, c->gda0_o, H4, W4, 1)) return -1;
-    }
-    c->x3_planes_out_now = 0;
+    } else if (convf(c, p, "convDa.0", c->fda0, *x, H4, W4, c->gda0_o, H4, W4, 1, nullptr, p.da0_planes ? X3_DA0 : X3_NONE)) return -1;
     c->x3_pre_src = nullptr;
-    if (c->x3_desc16_now) {
+    if (p.desc16) {
         // (nothing: convDa.3 and convDb run on the sampled corners, in fp16)
-    } else if (c->skip_da3_now) {      // sparse descriptor head of SFD2_PREC_F16X3 (sfd2_extract): convDa.3 and convDb run on the sampled corners only
+    } else if (p.skip_da3) {      // sparse descriptor head of SFD2_PREC_F16X3 (sfd2_extract): convDa.3 and convDb run on the sampled corners only
         const size_t nin = (size_t)H4 * W4 * 256;
-        if (!da0_planes) {
+        if (!p.da0_planes) {
             HIPCHECK(c->x3_da0_planes.ensure(nin * 2 * sizeof(half_t)));
             ProfScope ps(c, "convDa.0 planes", "x3_split_planes", 0.0, 12.0 * nin);
             launch_x3_split_planes(st, c->gda0_o.as<float>(), nin, c->x3_da0_planes.p, c->x3_da0_planes.as<half_t>() + nin);
         }
     } else {
-        if (convf(c, "convDa.3", c->fda3, c->gda0_o, H4, W4, c->gda_o, H4, W4, 0)) return -1;
-        if (convf(c, "convDb", c->fdb, c->gda_o, H4, W4, c->draw, H4, W4, 0)) return -1;
+        if (convf(c, p, "convDa.3", c->fda3, c->gda0_o, H4, W4, c->gda_o, H4, W4, 0)) return -1;
+        if (convf(c, p, "convDb", c->fdb, c->gda_o, H4, W4, c->draw, H4, W4, 0)) return -1;
     }
     if (c->has_sta) {
         ProfScope ps(c, "ConvSta", "convsta_f32_kernel", 2.0 * P4 * 3 * 256, P4 * (1024 + 12));
         launch_convsta_f32(st, x->as<float>(), H4 * W4, c->sta_w.as<float>(), c->sta_b.as<float>(), c->sta.as<float>());
     }
-    if (!c->skip_head_now) {
+    if (!p.skip_head) {
         ProfScope ps(c, "detector_head", "detector_head_kernel", 0.0, P8 * (65 * 4 + 256));
         launch_detector_head(st, c->logits.as<float>(), 128, H8, W8, c->score.as<float>());
     }
@@ -510,21 +592,16 @@ static int run_network_f32(sfd2_ctx *c, const float *img_dev, int normalise)
 }
 
 // ResSegNetV2.det up to the three head outputs (nets/sfd2.py:314-328, :340-345)
-int run_network(sfd2_ctx *c, const float *img_dev, int normalise)
+int run_network(sfd2_ctx *c, const PassPlan &p, const float *img_dev, int normalise)
 {
     c->cur_stream = c->stream;
     g_sfd2_cu_limit = c->opt_cu_limit;
-    if (c->precision == SFD2_PREC_F32 || c->precision == SFD2_PREC_F16X3) return run_network_f32(c, img_dev, normalise);
-    const bool comp = c->precision == SFD2_PREC_F16C;
+    if (p.f32) return run_network_f32(c, p, img_dev, normalise);
+    const bool comp = p.comp, alias = p.alias;
     hipStream_t st = c->stream;
     const int H = c->H, W = c->W, H2 = c->H2, W2 = c->W2, H4 = c->H4, W4 = c->W4, H8 = c->H8, W8 = c->W8;
     const double P1 = (double)H * W, P4 = (double)H4 * W4, P8 = (double)H8 * W8;
-    // Activation placement.  det (the parity entry point) keeps every activation in its own buffer for
-    // sfd2_debug_activation.  The throughput path (sfd2_extract) packs the whole chain into three 61 MB slots of one
-    // arena (at 1600x1200), reusing a slot as soon as its tensor is dead, so the working set fits the 256 MB
-    // Infinity Cache and a layer mostly reads what the previous one just wrote (measured: ResBlocks 400 -> 344 us;
-    // four slots measure the same as three).
-    const bool alias = c->alias_now != 0;
+    // Activation placement (plan_pass): one buffer per activation, or the arena slots of the throughput path
     DevPtr a1b = c->a1b, a2a = c->a2a, a2b = c->a2b, a3a = c->a3a, a3b = c->a3b, pa0_o = c->pa0_o, pa_o = c->pa_o,
            da0_o = c->da0_o, da_o = c->da_o;   // non-owning views
     DevPtr t1v[3] = {c->rt1[0], c->rt1[1], c->rt1[2]}, t2v[3] = {c->rt2[0], c->rt2[1], c->rt2[2]},
@@ -536,43 +613,23 @@ int run_network(sfd2_ctx *c, const float *img_dev, int normalise)
         S = std::max(S, 2 * (P8s * 256 * 2 + 256));
         if (comp) S *= 2;   // hi plane + corr plane per tensor (the corr plane follows the hi plane inside the slot)
         S = (S + 255) & ~(size_t)255;
-        HIPCHECK(c->arena.ensure((c->opt_branches ? 4 : 3) * S));
+        HIPCHECK(c->arena.ensure(p.slot.n * S));
         char *base = c->arena.as<char>();
         auto slot = [&](int i, size_t off = 0) { DevPtr v; v.p = base + (size_t)i * S + off; v.cap = 0; return v; };
-        {
-            // three slots (184 MB): a ResBlock's output overwrites its own t1 (dead once conv3 starts), the next
-            // block's t1 takes the slot of the previous input
-            a1b = slot(0); a2a = slot(1) /* spans slots 1-2 */; a2b = slot(0); a3a = slot(1); a3b = slot(2);
-            t1v[0] = slot(0); t2v[0] = slot(1); rov[0] = slot(0);    // x = slot 2
-            t1v[1] = slot(2); t2v[1] = slot(1); rov[1] = slot(2);    // x = slot 0
-            t1v[2] = slot(0); t2v[2] = slot(1); rov[2] = slot(0);    // x = slot 2 -> final x = slot 0
-            if (comp && c->opt_comp_rb && !c->opt_generic_c && c->opt_rb_inner >= 2 && c->opt_fuse_rb23) {
-                // rb23_c_kernel reads t1 (with the halo rows of neighbouring tiles) while other tiles already write the block's
-                // output: the output cannot take t1's slot.  No t2 in HBM on this path, so three slots still do.
-                t1v[0] = slot(0); rov[0] = slot(1);    // x = slot 2
-                t1v[1] = slot(0); rov[1] = slot(2);    // x = slot 1
-                t1v[2] = slot(1); rov[2] = slot(0);    // x = slot 2 -> final x = slot 0
-            }
-            pa0_o = slot(1); pa_o = slot(1, (P8s * 256 * 2 * (comp ? 2 : 1) + 255) & ~(size_t)255);   // (convPa.0's corr plane with "comp_heads")
-            da0_o = slot(2); da_o = slot(1);   // convDa.3 runs after convPb has consumed slot 1
-            if (c->opt_branches) da_o = slot(3);   // the two head branches run concurrently: no slot is shared between them
-            // convPb fused into the detector-head kernel: convPa.3's output must outlive the network pass, so convDa.3
-            // writes over the backbone output instead (slot 0) -- ConvSta, its last reader, then runs before the heads
-            if (c->skip_pb_now) da_o = slot(0);
-        }
+        a1b = slot(p.slot.a1b); a2a = slot(p.slot.a2a); a2b = slot(p.slot.a2b); a3a = slot(p.slot.a3a); a3b = slot(p.slot.a3b);
+        for (int b = 0; b < 3; ++b) { t1v[b] = slot(p.slot.t1[b]); t2v[b] = slot(p.slot.t2[b]); rov[b] = slot(p.slot.ro[b]); }
+        pa0_o = slot(p.slot.pa0); pa_o = slot(p.slot.pa, (P8s * 256 * 2 * (comp ? 2 : 1) + 255) & ~(size_t)255);   // (convPa.0's corr plane with "comp_heads")
+        da0_o = slot(p.slot.da0); da_o = slot(p.slot.da);
     }
     const DevPtr *x = &a3b;
     static const char *nm1[3] = {"conv4.0.conv1", "conv4.1.conv1", "conv4.2.conv1"};
     static const char *nm2[3] = {"conv4.0.conv2", "conv4.1.conv2", "conv4.2.conv2"};
     static const char *nm3[3] = {"conv4.0.conv3", "conv4.1.conv3", "conv4.2.conv3"};
-    // one ResBlock (nets/sfd2.py:25-55) in plain fp16: the fused kernel wherever the fused path runs (SFD2_FUSED_RB=0 in
-    // experiment builds: three kernels per block)
-    const char *frb = sfd2_env("SFD2_FUSED_RB");
-    const bool fused_rb = c->fuse_now != 0 && !(frb && frb[0] == '0');
+    // one ResBlock (nets/sfd2.py:25-55) in plain fp16
     static const char *nmf[3] = {"conv4.0", "conv4.1", "conv4.2"};
     auto rb_f16 = [&](int b) {
         DevPtr &t1 = t1v[b], &t2 = t2v[b], &ob = rov[b];
-        if (fused_rb && c->rb1[b].wrm.p && c->rb3[b].wrm.p) {
+        if (p.rb_fused) {
             ProfScope ps(c, nmf[b], "resblock_kernel", 2.0 * P4 * 256 * (256 + 72 + 256), P4 * 256 * 4);
             launch_resblock(st, x->as<half_t>(), H4, W4, c->rb1[b].wrm.as<half_t>(), c->rb1[b].scale.as<float>(),
                             c->rb1[b].shift.as<float>(), c->rb2[b].wgc.as<half_t>(), c->rb2[b].scale.as<float>(),
@@ -591,28 +648,9 @@ int run_network(sfd2_ctx *c, const float *img_dev, int normalise)
         x = &ob;
     };
     if (comp) {
-        // SFD2_PREC_F16C backbone: every activation carries a corr plane, every layer adds the fp8 correction terms
-        // Option "fp6_acts": three tensors have conv3x3_pp<comp> as their only reader -- conv1b's output (-> conv2a), conv2b's (-> conv3a) and
-        // conv3a's (-> conv3b).  Their corr records leave the producer as block-scaled fp6 half-records, and the consumer's correction is one
-        // fp6 x fp6 scaled MFMA per unit: 33.5 cycles where a unit with fp8 on either side takes 66 (profiles/r04_mfma_probe.txt).  Decided
-        // per tensor: the producer must be the kernel that can write them.
-        const bool use6 = c->opt_fp6_acts && !c->opt_generic_c && c->c2a.wc66.p && c->c3a.wc66.p && c->c3b.wc66.p;
-        const bool s6 = use6 && c->fuse_now && c->w1b_stem_c6.p;                                                                   // a1b (the fused stem writes it)
-        const bool b6 = use6 && !c->opt_no_rf_c && conv3x3_rf_c_serves(3, 2, c->c2b.cout_pad, c->c2b.cin, H4, W4);   // a2b (conv3x3_rf<2,comp>)
-        const bool a6 = use6;                                                                                   // a3a (conv3x3_pp<comp>)
-        // Option "s2d" (throughput path only: the tensor is not readable by sfd2_debug_activation in that layout): conv2a stores its output as
-        // four parity planes at quarter resolution, conv2b reads them as a stride-1 layer (conv2b_s2d_kernel.hip)
-        const bool d2 = c->opt_s2d && alias && s6 && !c->opt_no_rf_c && conv2b_s2d_serves(H2, W2, c->c2b.cin, c->c2b.cout_pad) &&
-                        H4 * 2 == H2 && W4 * 2 == W2;
-        {
-            static const char *t6[3] = {"bn1b", "bn2b", "conv3a"};
-            const bool f6[3] = {s6, b6, a6};
-            for (int i = 0; i < 3; ++i) {
-                auto it = c->acts.find(t6[i]);
-                if (it != c->acts.end()) it->second.fmt6 = f6[i];
-            }
-        }
-        if (c->fuse_now && !c->opt_generic_c) {
+        // SFD2_PREC_F16C backbone: every activation carries a corr plane, every layer adds the fp8 correction terms (the formats: plan_pass)
+        const bool s6 = p.s6, b6 = p.b6, a6 = p.a6, d2 = p.d2, p3b = p.p3b, p3a = p.p3a, tr1 = p.tr1;
+        if (p.fused_stem) {
             ProfScope ps(c, "conv1a+conv1b", "fused_stem_c_kernel", 2.0 * P1 * 64 * 27 + 2.0 * (double)H2 * W2 * 64 * 576,
                          P1 * 12 + (double)H2 * W2 * 256);
             launch_fused_stem_c(st, img_dev, H, W, normalise, c->c1a.wc.as<half_t>(), c->c1a.scale.as<float>(),
@@ -624,70 +662,40 @@ int run_network(sfd2_ctx *c, const float *img_dev, int normalise)
                 launch_conv1a_c(st, img_dev, H, W, normalise, c->c1a.wc.as<half_t>(), c->c1a.scale.as<float>(),
                                 c->c1a.shift.as<float>(), c->a1a.as<half_t>(), corr_of(c->a1a, (size_t)H * W, 64), range_slot(c, SFD2_RS_CONV1A));
             }
-            convc(c, "conv1b", c->c1b, c->a1a, H, W, a1b, H2, W2, 1, true, true, nullptr, SFD2_RS_CONV1B);
+            convc(c, p, "conv1b", c->c1b, c->a1a, H, W, a1b, H2, W2, 1, true, true, nullptr, SFD2_RS_CONV1B);
         }
-        convc(c, "conv2a", c->c2a, a1b, H2, W2, a2a, H2, W2, 1, true, true, nullptr, SFD2_RS_CONV2A, (s6 ? 1 : 0) | (d2 ? 4 : 0));
+        convc(c, p, "conv2a", c->c2a, a1b, H2, W2, a2a, H2, W2, 1, true, true, nullptr, SFD2_RS_CONV2A, (s6 ? 1 : 0) | (d2 ? 4 : 0));
         if (d2) {
             const ConvW &L = c->c2b;
             ProfScope ps(c, "conv2b", "conv2b_s2d_kernel", 2.0 * P4 * L.cout * L.cin * 9, 4.0 * ((double)H2 * W2 * L.cin + (double)L.cout * L.cin * 9) + P4 * L.cout_pad * 4.0);
             launch_conv2b_s2d(st, a2a.as<half_t>(), corr_of(a2a, (size_t)H2 * W2, L.cin), H4, W4, L.wc.as<half_t>(), L.scale.as<float>(), L.shift.as<float>(), 1,
                               a2b.as<half_t>(), corr_of(a2b, (size_t)H4 * W4, L.cout_pad), c->zero_page.as<half_t>(), L.sbyte, range_slot(c, SFD2_RS_CONV2B), b6 ? 2 : 0);
         } else
-        convc(c, "conv2b", c->c2b, a2a, H2, W2, a2b, H4, W4, 1, true, true, nullptr, SFD2_RS_CONV2B, b6 ? 2 : 0);
-        // Option "c3b_plain" (the load-time self-check decides, api_weights.hip): conv3b takes the hi plane of conv3a's output only; conv3a keeps writing
-        // its records unless SFD2_C3A_PLAIN_OUT says otherwise (experiment switch until measured)
-        const bool p3b = c->opt_c3b_plain && a6 && b6 && !c->opt_generic_c;
-        static const bool c3a_plain_out = sfd2_env("SFD2_C3A_KEEP_CORR") == nullptr;
-        const bool p3a = p3b && c3a_plain_out;
-        {
-            auto it = c->acts.find("conv3a");
-            if (it != c->acts.end() && it->second.p == a3a.p) {      // (sfd2_debug_activation: the tensor has no corr plane then)
-                it->second.pc = p3a ? nullptr : corr_of(a3a, (size_t)H4 * W4, 256);
-                it->second.fmt6 = a6 && !p3a;
-            }
-        }
-        convc(c, "conv3a", c->c3a, a2b, H4, W4, a3a, H4, W4, 1, true, !p3a, nullptr, SFD2_RS_CONV3A, (b6 ? 1 : 0) | ((a6 && !p3a) ? 2 : 0));
-        // Option "trunk_r1": the three tensors the ResBlocks read as block input (conv3b's output, the outputs of blocks 0 and 1) with the residual
-        // byte only -- their readers are conv1x1_c256_c<.., 2, ..> (value bytes rebuilt from the hi plane) and rb23_c_kernel's skip path
-        const bool tr1 = c->opt_trunk_r1 && a6 && !c->opt_generic_c && c->opt_comp_rb && c->opt_rb_inner >= 2 && c->opt_fuse_rb23 &&
-                         c->rb1[0].wfl.p && c->rb3[0].wfl.p && c->rb2[0].wlk.p && c->rb1[0].wfr.p && c->rb3[0].wf8l.p;
-        {
-            static const char *tr[3] = {"bn3b", "conv4.0", "conv4.1"};
-            for (int i = 0; i < 3; ++i) {
-                auto it = c->acts.find(tr[i]);
-                if (it != c->acts.end()) it->second.r1 = tr1;
-            }
-        }
-        convc(c, "conv3b", c->c3b, a3a, H4, W4, a3b, H4, W4, 1, !p3b, true, nullptr, SFD2_RS_CONV3B, ((a6 && !p3b) ? 1 : 0) | (tr1 ? 8 : 0));
+        convc(c, p, "conv2b", c->c2b, a2a, H2, W2, a2b, H4, W4, 1, true, true, nullptr, SFD2_RS_CONV2B, b6 ? 2 : 0);
+        convc(c, p, "conv3a", c->c3a, a2b, H4, W4, a3a, H4, W4, 1, true, !p3a, nullptr, SFD2_RS_CONV3A, (b6 ? 1 : 0) | ((a6 && !p3a) ? 2 : 0));
+        convc(c, p, "conv3b", c->c3b, a3a, H4, W4, a3b, H4, W4, 1, !p3b, true, nullptr, SFD2_RS_CONV3B, ((a6 && !p3b) ? 1 : 0) | (tr1 ? 8 : 0));
         for (int b = 0; b < 3; ++b) {  // ResBlock (nets/sfd2.py:25-55)
-            if (!c->opt_comp_rb) { rb_f16(b); continue; }   // option "comp_rb" = 0: this block in plain fp16 on the hi planes
+            if (!p.comp_rb) { rb_f16(b); continue; }   // option "comp_rb" = 0: this block in plain fp16 on the hi planes
             DevPtr &t1 = t1v[b], &t2 = t2v[b], &ob = rov[b];
-            const int inner = (!c->opt_generic_c && c->rb1[b].wfl.p && c->rb3[b].wfl.p && c->rb2[b].wlk.p) ? c->opt_rb_inner : 0;
-            if (inner) {
+            if (p.rb_inner) {
                 // Option "rb_inner": the tensors INSIDE the block as plain fp16 (1: t2, 2: t1 and t2).  These kernels are bound
                 // by HBM bytes, a plain tensor is half of a compensated one; the filters stay compensated (over a plain input the
                 // residual term x * lo_w is a second fp16 pass: there is no fp8 value byte of x to feed the scaled MFMA).
                 const size_t PP = (size_t)H4 * W4;
                 const ConvW &L1 = c->rb1[b], &L2 = c->rb2[b], &L3 = c->rb3[b];
-                const bool t1p = inner >= 2;
-                {   // sfd2_debug_activation: these tensors have no corr plane on this path
-                    auto i1 = c->acts.find(std::string(nm1[b]).substr(0, 8) + "bn1"), i2 = c->acts.find(std::string(nm1[b]).substr(0, 8) + "bn2");
-                    if (i1 != c->acts.end() && i1->second.p == t1.p) i1->second.pc = t1p ? nullptr : corr_of(t1, PP, 256);
-                    if (i2 != c->acts.end() && i2->second.p == t2.p) { i2->second.pc = nullptr; i2->second.absent = t1p && c->opt_fuse_rb23; }
-                }
+                const bool t1p = p.rb_inner >= 2;
                 if (t1p) {
                     ProfScope ps(c, nm1[b], "conv1x1_c256<comp,plain out>", 2.0 * P4 * 256.0 * 256.0, P4 * 256.0 * (tr1 ? 5 : 6));
                     launch_conv1x1_c256_c(st, x->as<half_t>(), corr_of(*x, PP, 256), (int)PP, L1.wfh.as<half_t>(), tr1 ? L1.wfr.as<half_t>() : L1.wfc.as<half_t>(),
                                           L1.scale.as<float>(), L1.shift.as<float>(), 1, nullptr, nullptr, t1.as<half_t>(), nullptr,
                                           c->zero_page.as<half_t>(), L1.sbyte, range_slot(c, SFD2_RS_T1_0 + b), tr1 ? 1 : 0);
                 } else {
-                    convc(c, nm1[b], L1, *x, H4, W4, t1, H4, W4, 1, true, true, nullptr, SFD2_RS_T1_0 + b);
+                    convc(c, p, nm1[b], L1, *x, H4, W4, t1, H4, W4, 1, true, true, nullptr, SFD2_RS_T1_0 + b);
                 }
-                if (t1p && c->opt_fuse_rb23) {
+                if (p.rb23) {
                     // (the last block's output keeps its units when a compensated head layer will read them)
-                    const bool out_r1 = b < 2 || !(c->opt_comp_heads || c->opt_comp_det);
+                    const bool out_r1 = b < 2 || !p.chp;
                     const int r1f = tr1 ? (1 | (out_r1 ? 2 : 0)) : 0;
-                    if (b == 2) { auto it = c->acts.find("conv4.2"); if (it != c->acts.end()) it->second.r1 = tr1 && out_r1; }
                     ProfScope ps(c, nm3[b], "rb23_c_kernel", 2.0 * P4 * 256 * 72 + 2.0 * P4 * 256.0 * 256.0, P4 * 256.0 * (10 - (r1f & 1) - ((r1f >> 1) & 1)));
                     launch_rb23_c(st, t1.as<half_t>(), H4, W4, L2.w.as<half_t>(), L2.wlk.as<half_t>(), L2.scale.as<float>(), L2.shift.as<float>(),
                                   L3.wfh.as<half_t>(), L3.wfl.as<half_t>(), L3.scale.as<float>(), L3.shift.as<float>(), x->as<half_t>(),
@@ -709,24 +717,19 @@ int run_network(sfd2_ctx *c, const float *img_dev, int normalise)
                                           c->zero_page.as<half_t>(), L3.sbyte, range_slot(c, SFD2_RS_OUT_0 + b));
                 }
             } else {
-                {
-                    auto i1 = c->acts.find(std::string(nm1[b]).substr(0, 8) + "bn1"), i2 = c->acts.find(std::string(nm1[b]).substr(0, 8) + "bn2");
-                    if (i1 != c->acts.end() && i1->second.p == t1.p) i1->second.pc = corr_of(t1, (size_t)H4 * W4, 256);
-                    if (i2 != c->acts.end() && i2->second.p == t2.p) { i2->second.pc = corr_of(t2, (size_t)H4 * W4, 256); i2->second.absent = false; }
-                }
-                convc(c, nm1[b], c->rb1[b], *x, H4, W4, t1, H4, W4, 1, true, true, nullptr, SFD2_RS_T1_0 + b);
+                convc(c, p, nm1[b], c->rb1[b], *x, H4, W4, t1, H4, W4, 1, true, true, nullptr, SFD2_RS_T1_0 + b);
                 {
                     ProfScope ps(c, nm2[b], "gconv_c_kernel", 2.0 * P4 * 256 * 72, P4 * 256 * 8);
                     launch_gconv_c(st, t1.as<half_t>(), corr_of(t1, (size_t)H4 * W4, 256), H4, W4, c->rb2[b].w.as<half_t>(),
                                    c->rb2[b].wc.p, c->rb2[b].scale.as<float>(), c->rb2[b].shift.as<float>(), t2.as<half_t>(),
                                    corr_of(t2, (size_t)H4 * W4, 256), c->rb2[b].sbyte, 0, H4, range_slot(c, SFD2_RS_T2_0 + b));
                 }
-                convc(c, nm3[b], c->rb3[b], t2, H4, W4, ob, H4, W4, 1, true, true, x, SFD2_RS_OUT_0 + b);
+                convc(c, p, nm3[b], c->rb3[b], t2, H4, W4, ob, H4, W4, 1, true, true, x, SFD2_RS_OUT_0 + b);
             }
             x = &ob;
         }
     } else {
-    if (c->fuse_now) {
+    if (p.fused_stem) {
         ProfScope ps(c, "conv1a+conv1b", "fused_stem_kernel", 2.0 * P1 * 64 * 27 + 2.0 * (double)H2 * W2 * 64 * 576,
                      P1 * 12 + (double)H2 * W2 * 128);
         launch_fused_stem(st, img_dev, H, W, normalise, c->c1a.w.as<half_t>(), c->c1a.scale.as<float>(),
@@ -752,12 +755,11 @@ int run_network(sfd2_ctx *c, const float *img_dev, int normalise)
     // inside a captured hipGraph this becomes a fork in the graph).  Measured (tools/ab_branches.py, interleaved A/B at
     // 1600x1200): 1.260 -> 1.238 ms per extract (-1.7 %), outputs bit-identical.  Off by default: overlapped launches
     // stretch each other's event-timed durations, and bench.py's per-kernel roofline wants uncontended ones.
-    const bool sta_early = alias && c->skip_pb_now;
     // Option "sta_side" (round 6): ConvSta -- 63 MB read at HBM speed, 16 us -- on the side stream beside convPa.0 / convPa.3 / convDa.0 (matrix-bound, another part of
     // the chip's budget); fork here, join at the end of this function (the heat-map kernel behind it is the first reader of its output).  Inside a captured hipGraph: a
-    // fork in the graph.  Same kernel, same bits.  Not with "branches" (that option owns the side stream).
-    const bool sta_side = c->has_sta && sta_early && c->opt_sta_side && !c->opt_branches;
-    if (c->has_sta && sta_early) {
+    // fork in the graph.  Same kernel, same bits.
+    const bool sta_side = p.sta_side;
+    if (c->has_sta && p.sta_early) {
         if (sta_side) {
             HIPCHECK(hipEventRecord(c->ev_fork, st));
             HIPCHECK(hipStreamWaitEvent(c->side_stream, c->ev_fork, 0));
@@ -772,27 +774,22 @@ int run_network(sfd2_ctx *c, const float *img_dev, int normalise)
             c->cur_stream = st;
         }
     }
-    const bool fork = c->opt_branches != 0;
+    const bool fork = p.branches;
     if (fork) {
         HIPCHECK(hipEventRecord(c->ev_fork, st));
         HIPCHECK(hipStreamWaitEvent(c->side_stream, c->ev_fork, 0));
         c->cur_stream = c->side_stream;
     }
-    // option "comp_heads": the four 3x3 layers of the head branches compensated as well (their inputs then need corr planes: the
-    // backbone output has one when the ResBlocks are compensated); convPb / convDb / ConvSta read hi planes either way
-    // option "comp_det": the detector branch only (convPa.0, convPa.3) -- its score goes through exp(), which is what moves key points
-    const bool ch = comp && c->opt_comp_heads && c->opt_comp_rb;
-    const bool chp = ch || (comp && c->opt_comp_det && c->opt_comp_rb);
-    if (chp) {
-        convc(c, "convPa.0", c->pa0, *x, H4, W4, pa0_o, H8, W8, 1, true, true, nullptr, SFD2_RS_PA0);
-        convc(c, "convPa.3", c->pa3, pa0_o, H8, W8, pa_o, H8, W8, 0, true, false);
+    if (p.chp) {      // options "comp_heads" / "comp_det" (plan_pass)
+        convc(c, p, "convPa.0", c->pa0, *x, H4, W4, pa0_o, H8, W8, 1, true, true, nullptr, SFD2_RS_PA0);
+        convc(c, p, "convPa.3", c->pa3, pa0_o, H8, W8, pa_o, H8, W8, 0, true, false);
     } else {
         conv(c, "convPa.0", c->pa0, *x, H4, W4, pa0_o, H8, W8, 1);
         conv(c, "convPa.3", c->pa3, pa0_o, H8, W8, pa_o, H8, W8, 0);
     }
     c->pa_cur = pa_o.as<half_t>();
-    if (!c->skip_pb_now) conv(c, "convPb", c->pb, pa_o, H8, W8, c->logits, H8, W8, 0, nullptr, 1);
-    if (!c->skip_head_now) {
+    if (!p.skip_pb) conv(c, "convPb", c->pb, pa_o, H8, W8, c->logits, H8, W8, 0, nullptr, 1);
+    if (!p.skip_head) {
         ProfScope ps(c, "detector_head", "detector_head_kernel", 0.0, P8 * (65 * 4 + 256));
         launch_detector_head(c->cur_stream, c->logits.as<float>(), 128, H8, W8, c->score.as<float>());
     }
@@ -800,17 +797,17 @@ int run_network(sfd2_ctx *c, const float *img_dev, int normalise)
         HIPCHECK(hipEventRecord(c->ev_join, c->side_stream));
         c->cur_stream = st;
     }
-    if (ch) {
-        convc(c, "convDa.0", c->da0, *x, H4, W4, da0_o, H4, W4, 1, true, true, nullptr, SFD2_RS_DA0);
-        convc(c, "convDa.3", c->da3, da0_o, H4, W4, da_o, H4, W4, 0, true, false);
+    if (p.ch) {
+        convc(c, p, "convDa.0", c->da0, *x, H4, W4, da0_o, H4, W4, 1, true, true, nullptr, SFD2_RS_DA0);
+        convc(c, p, "convDa.3", c->da3, da0_o, H4, W4, da_o, H4, W4, 0, true, false);
     } else {
         conv(c, "convDa.0", c->da0, *x, H4, W4, da0_o, H4, W4, 1);
-        if (!c->skip_da3_now) conv(c, "convDa.3", c->da3, da0_o, H4, W4, da_o, H4, W4, 0);
+        if (!p.skip_da3) conv(c, "convDa.3", c->da3, da0_o, H4, W4, da_o, H4, W4, 0);
     }
     c->da_cur = da_o.as<half_t>();
     c->da0_cur = da0_o.as<half_t>();
-    if (!c->skip_db_now) conv(c, "convDb", c->db, da_o, H4, W4, c->draw, H4, W4, 0, nullptr, 1);
-    if (c->has_sta && !sta_early) {
+    if (!p.skip_db) conv(c, "convDb", c->db, da_o, H4, W4, c->draw, H4, W4, 0, nullptr, 1);
+    if (c->has_sta && !p.sta_early) {
         ProfScope ps(c, "ConvSta", "convsta_kernel", 2.0 * P4 * 3 * 256, P4 * (512 + 12));
         launch_convsta(st, x->as<half_t>(), H4 * W4, c->sta_w16.as<float>(), c->sta_b.as<float>(), c->sta.as<float>());
     }

@@ -137,21 +137,13 @@ struct sfd2_ctx {
     int opt_cu_limit = 0;              // sfd2_set_option "cu_limit": persistent kernels of THIS context launch at most so many blocks
     int fuse_det = 0;                  // sfd2_set_option "fuse_det"
     int use_graphs = 0;                // sfd2_set_option "graphs"
-    int alias_now = 0;                 // set per call
-    int x3_fast_rb_now = 0;            // set per call: f16x3 ResBlocks on the streaming three-pass 1x1 kernel (not on the parity entry point:
-                                       // the grouped conv's output then exists as planes only)
     DevBuf x3_chain2;                  // second buffer of the plane chain (a layer never writes the planes it reads)
     DevBuf x3_rb_planes[3];            // a ResBlock's input, conv1's and the grouped conv's outputs as hi / lo' planes
     const void *x3_pre_src = nullptr;  // set by a producer that wrote its output as planes too: the fp32 tensor they belong to ...
     const half_t *x3_pre_hi = nullptr, *x3_pre_lo = nullptr;   // ... and the planes (consumed by the next convf on that tensor)
-    int x3_s2d_out_now = 0;            // set around conv2a's convf call: its planes are stored space-to-depth for conv2b_s2d_kernel<x3> (option "s2d")
-    int x3_planes_out_now = 0;         // set around a convf call: the 3x3 layer writes hi / lo' planes INTO x3_chain instead of fp32
     DevBuf x3_chain;                   // planes handed from conv3a to conv3b (throughput path of f16x3)
     int opt_fuse_post = 1;             // sfd2_set_option "fuse_post": heads -> heat map -> NMS in one kernel on the extract path
-    int skip_head_now = 0;             // set per call: run_network leaves the detector soft-max to the fused NMS kernel
     int opt_sparse_desc = 1;           // sfd2_set_option "sparse_desc": extract path runs convDb on the sampled corner pixels only
-    int skip_db_now = 0;               // set per call: run_network leaves convDb to the sparse descriptor head
-    int skip_da3_now = 0;              // set per call: run_network leaves convDa.3 to the sparse descriptor path (sparse_da3_kernel)
     const half_t *da0_cur = nullptr;   // convDa.0 output of the last fp16 network pass
     DevBuf da3_sparse;                 // [sel_cap][4][256] fp16: convDa.3 on the sampled corner pixels
     int opt_fp6_acts = 1;              // sfd2_set_option "fp6_acts": the corr records of the three tensors only conv3x3_pp<comp> reads (conv1b's, conv2b's,
@@ -182,12 +174,10 @@ struct sfd2_ctx {
     int opt_x3_desc16 = 0;             // sfd2_set_option "x3_desc16": SFD2_PREC_F16X3 on sfd2_extract with the DESCRIPTOR branch (convDa.0, convDa.3 at the sampled corners,
                                        // convDb) in plain fp16 on the backbone output's hi plane: the key points are this mode's own, the descriptors carry the
                                        // fp16 head's error only (<= 1e-3: north_star's tolerance, not this mode's 2e-5)
-    int x3_desc16_now = 0;             // set per call by run_network: convDa.0's output is the fp16 tensor in x3_da0_planes (da0_cur)
     DevBuf x3_planes;                  // the input of such a layer as hi / lo' planes
     DevBuf x3_da0_planes;              // convDa.0's output as planes (sparse descriptor head of f16x3)
     DevBuf db_sparse;                  // [sel_cap][4][128] fp32: convDb on the sampled corners (f16x3)
     int opt_sparse_da3 = 1;            // sfd2_set_option "sparse_da3": with the sparse descriptor head, convDa.3 on the sampled corners only
-    int skip_pb_now = 0;               // set per call: run_network leaves convPb to the fused detector head
     int opt_fuse_pb = 1;               // sfd2_set_option "fuse_pb": convPb inside the fused detector-head / heat-map kernel
     const half_t *pa_cur = nullptr;    // convPa.3 output of the last fp16 network pass
     const half_t *da_cur = nullptr;    // convDa.3 output of the last fp16 network pass
@@ -221,7 +211,6 @@ struct sfd2_ctx {
     DevBuf w1b_stem_c;                             // the same as register fragments (hi K slices + corr) for the compensated fused stem
     DevBuf w1b_stem_x3;                            // ... with the lo' fragments (fp16 of (w - fp16(w)) * 2^11) in place of the corr fragment: f16x3
     int fuse = 1;                                  // fused kernels on the extract path (SFD2_NO_FUSE=1 disables)
-    int fuse_now = 0;                              // set per call: sfd2_det keeps every intermediate readable
     // strict fp32 mode
     int precision = SFD2_PREC_F16;
     ConvW f1a, f1b, f2a, f2b, f3a, f3b, frb1[3], frb2[3], frb3[3], fpa0, fpa3, fda0, fda3, fpb, fdb;
@@ -319,11 +308,36 @@ struct FallbackScope {      // the repeat: strict arithmetic, no recursion
     }
     ~FallbackScope() { c->precision = prec; c->in_fallback = 0; }
 };
-// api_network.hip
-void set_path(sfd2_ctx *c, bool parity_entry);          // which kernels / buffers the next network pass uses; call before ensure_workspace
-int ensure_workspace(sfd2_ctx *c, int H, int W);
-int run_network(sfd2_ctx *c, const float *img_dev, int normalise);
-int convf(sfd2_ctx *c, const char *name, const ConvW &L, const DevPtr &in, int H, int W, const DevPtr &out, int Ho, int Wo, int relu,
-          const float *res = nullptr);
+// api_network.hip.  What one network pass runs, decided once per call (plan_pass) from the options, the precision, the entry point, the
+// geometry and which packed weight arrays exist; ensure_workspace allocates and registers the activations from it, the dispatch reads it.
+enum PassEntry { PASS_DET /* parity: every activation readable unless "fuse_det" */, PASS_DENSE /* throughput kernels, dense head maps (pyramids,
+                 spp) */, PASS_EXTRACT /* sfd2_extract: the heads fused into the post-processing, the sparse descriptor head */ };
+enum X3Planes { X3_NONE, X3_CHAIN, X3_DA0, X3_RB };   // where a three-pass 3x3 layer (SFD2_PREC_F16X3) stores its output as hi / lo' planes
+struct PassPlan {
+    bool f32 = false, comp = false;          // the fp32 buffers (SFD2_PREC_F32 / F16X3); SFD2_PREC_F16C
+    bool fuse = false, alias = false;        // fused kernels; the arena slots instead of one buffer per activation
+    bool fused_stem = false, rb_fused = false;   // conv1a + conv1b in one kernel; plain fp16 ResBlocks on resblock_kernel (t1, t2 never stored)
+    bool comp_rb = false;                    // SFD2_PREC_F16C: compensated ResBlocks (otherwise plain fp16 on the hi planes)
+    int rb_inner = 0;                        // ... "rb_inner" in effect; rb23: 2 with ResBlock.conv2 + conv3 in rb23_c_kernel (t2 stays on chip)
+    bool rb23 = false, generic_c = false, no_rf_c = false, fp6_filters = false;
+    bool s6 = false, b6 = false, a6 = false; // "fp6_acts": fp6 corr records of conv1b's, conv2b's, conv3a's output
+    bool d2 = false;                         // "s2d": conv2a's output space-to-depth, conv2b on conv2b_s2d_kernel
+    bool p3b = false, p3a = false;           // "c3b_plain": conv3b over conv3a's hi plane; conv3a then writes no corr plane
+    bool tr1 = false;                        // "trunk_r1": the ResBlocks' inputs with one residual byte per channel
+    bool ch = false, chp = false;            // compensated head branches ("comp_heads"); compensated detector branch ("comp_heads" or "comp_det")
+    bool branches = false, sta_early = false, sta_side = false;   // detector branch on the side stream; ConvSta before the heads / on the side stream
+    bool skip_head = false, skip_pb = false, skip_db = false, skip_da3 = false;   // layers left to sfd2_extract's post-processing
+    bool sparse_desc = false, sparse_da3 = false, sparse_x3 = false;           // its sparse descriptor head: fp16, fp16 with convDa.3, f16x3
+    struct { int a1b, a2a, a2b, a3a, a3b, t1[3], t2[3], ro[3], pa0, pa, da0, da, n; } slot = {};   // alias: each tensor's arena slot, slots in all
+    bool x3_pp = false, x3_fast = false;     // f16x3: 3x3 layers on the three-pass kernels ("x3_pp"); the throughput path's plane hand-offs
+    bool x3_stem = false, x3_rb = false;     // ... the fused three-pass stem; ResBlocks on the planes
+    bool k2b = false, k3a = false, k3b = false, s2d_x3 = false;   // conv2b / conv3a / conv3b on a three-pass kernel; conv2a stores space-to-depth
+    bool da0_planes = false, desc16 = false; // convDa.0's output as planes; "x3_desc16": the descriptor branch in fp16 on the backbone's hi plane
+};
+PassPlan plan_pass(const sfd2_ctx *c, PassEntry entry, int H, int W, int top_k = 0, bool desc = false);
+int ensure_workspace(sfd2_ctx *c, const PassPlan &p, int H, int W);
+int run_network(sfd2_ctx *c, const PassPlan &p, const float *img_dev, int normalise);
+int convf(sfd2_ctx *c, const PassPlan &p, const char *name, const ConvW &L, const DevPtr &in, int H, int W, const DevPtr &out, int Ho, int Wo,
+          int relu, const float *res = nullptr, X3Planes planes = X3_NONE, bool s2d = false);
 // api_extract.hip
 int copy_out(sfd2_ctx *c, void *dst, const void *src_dev, size_t bytes, int dst_on_device);

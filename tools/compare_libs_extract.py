@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
 """Bit-compare the extraction outputs (key points, scores, descriptors) of two libsfd2hip builds on the same inputs -- the check for a
 kernel variant that claims the same operations in the same order -- and screen the second for run-to-run differences.
-    python tools/compare_libs_extract.py default build/variants/libX.so [--precision f16c] [--runs 6]
-(a library may carry environment switches for its worker: default@SFD2_AB_OPTS=s2d=0)"""
+    python tools/compare_libs_extract.py default build/variants/libX.so [--precision f16c] [--runs 6] [--labels]
+(a library may carry environment switches for its worker: default@SFD2_AB_OPTS=s2d=0).  --labels: the launch sequence too -- the
+(stage, kernel) rows of layer_timings() of one profiled extract per size -- for a change of the dispatch that claims the same kernels."""
 import argparse
+import itertools
 import os
 import subprocess
 import sys
@@ -39,6 +41,12 @@ for (h, w) in %r:
                     print("NONDETERMINISTIC", sys.argv[1], (h, w), k, "run", r, flush=True)
     for k in ("keypoints", "scores", "descriptors"):
         out[f"{h}x{w}/{k}"] = first[k]
+    if sys.argv[5] == "1":
+        m.context.set_profiling(1)
+        extract_resnet_return(m, x[None], conf_th=0.001, topK=4096, scales=[1.0])
+        out[f"{h}x{w}/labels"] = np.array([t["name"] + " | " + t["kernel"] for t in m.context.layer_timings()])
+        assert len(out[f"{h}x{w}/labels"]) > 0, "no launches profiled"
+        m.context.set_profiling(0)
 np.savez(sys.argv[2], **out)
 ''' % (os.path.abspath(ROOT), SIZES)
 
@@ -56,13 +64,14 @@ ap = argparse.ArgumentParser()
 ap.add_argument("libs", nargs=2)
 ap.add_argument("--precision", default="f16c")
 ap.add_argument("--runs", type=int, default=6)
+ap.add_argument("--labels", action="store_true")
 args = ap.parse_args()
 res = []
 with tempfile.TemporaryDirectory() as td:
     for i, spec in enumerate(args.libs):
         lib, env = split_spec(spec)
         f = os.path.join(td, f"o{i}.npz")
-        r = subprocess.run([sys.executable, "-c", WORKER, lib, f, args.precision, str(args.runs)], env=env, capture_output=True, text=True)
+        r = subprocess.run([sys.executable, "-c", WORKER, lib, f, args.precision, str(args.runs), str(int(args.labels))], env=env, capture_output=True, text=True)
         sys.stdout.write(r.stdout)
         if r.returncode != 0:
             sys.stderr.write(r.stderr[-3000:])
@@ -72,7 +81,10 @@ bad = 0
 for k in sorted(res[0]):
     a, b = res[0][k], res[1][k]
     same = a.shape == b.shape and np.array_equal(a, b)
-    if not same:
+    if not same and k.endswith("/labels"):
+        bad += 1
+        print(f"DIFFERENT {k}:\n  " + "\n  ".join(f"{x!s:60} {y!s}" for x, y in itertools.zip_longest(a, b)))
+    elif not same:
         bad += 1
         d = float(np.abs(a.astype(np.float64) - b.astype(np.float64)).max()) if a.shape == b.shape else float("nan")
         print(f"DIFFERENT {k}: shapes {a.shape} {b.shape}, max abs diff {d:.3e}")
