@@ -44,26 +44,40 @@ PassPlan plan_pass(const sfd2_ctx *c, PassEntry entry, int H, int W, int top_k, 
         // conv3a's (-> conv3b).  Their corr records leave the producer as block-scaled fp6 half-records, and the consumer's correction is one
         // fp6 x fp6 scaled MFMA per unit: 33.5 cycles where a unit with fp8 on either side takes 66 (profiles/r04_mfma_probe.txt).  Decided
         // per tensor: the producer must be the kernel that can write them (the fused stem, conv3x3_rf<2,comp>, conv3x3_pp<comp>).
-        const bool use6 = c->opt_fp6_acts && !p.generic_c && c->c2a.wc66.p && c->c3a.wc66.p && c->c3b.wc66.p;
-        p.s6 = use6 && p.fuse && c->w1b_stem_c6.p;
-        p.b6 = use6 && !p.no_rf_c && conv3x3_rf_c_serves(3, 2, c->c2b.cout_pad, c->c2b.cin, H4, W4);
-        p.a6 = use6;
+        const bool a6 = c->opt_fp6_acts && !p.generic_c && c->c2a.wc66.p && c->c3a.wc66.p && c->c3b.wc66.p;
+        const bool s6 = a6 && p.fuse && c->w1b_stem_c6.p;
+        const bool b6 = a6 && !p.no_rf_c && conv3x3_rf_c_serves(3, 2, c->c2b.cout_pad, c->c2b.cin, H4, W4);
         // Option "s2d" (throughput path only: the tensor is not readable by sfd2_debug_activation in that layout): conv2a stores its output as
         // four parity planes at quarter resolution, conv2b reads them as a stride-1 layer (conv2b_s2d_kernel.hip)
-        p.d2 = c->opt_s2d && p.alias && p.s6 && !p.no_rf_c && conv2b_s2d_serves(H2, W2, c->c2b.cin, c->c2b.cout_pad) && H4 * 2 == H2 && W4 * 2 == W2;
+        p.a2a_s2d = c->opt_s2d && p.alias && s6 && !p.no_rf_c && conv2b_s2d_serves(H2, W2, c->c2b.cin, c->c2b.cout_pad) && H4 * 2 == H2 && W4 * 2 == W2;
         // Option "c3b_plain" (the load-time self-check decides, api_weights.hip): conv3b takes the hi plane of conv3a's output only; conv3a keeps writing
         // its records unless SFD2_C3A_KEEP_CORR says otherwise (experiment switch until measured)
         static const bool c3a_plain_out = sfd2_env("SFD2_C3A_KEEP_CORR") == nullptr;
-        p.p3b = c->opt_c3b_plain && p.a6 && p.b6 && !p.generic_c;
-        p.p3a = p.p3b && c3a_plain_out;
+        const bool p3b = c->opt_c3b_plain && a6 && b6 && !p.generic_c;
+        const bool p3a = p3b && c3a_plain_out;
         // Option "trunk_r1": the three tensors the ResBlocks read as block input (conv3b's output, the outputs of blocks 0 and 1) with the residual
         // byte only -- their readers are conv1x1_c256_c<.., 2, ..> (value bytes rebuilt from the hi plane) and rb23_c_kernel's skip path
-        p.tr1 = c->opt_trunk_r1 && p.a6 && p.rb23 && c->rb1[0].wfr.p && c->rb3[0].wf8l.p;
+        const bool tr1 = c->opt_trunk_r1 && a6 && p.rb23 && c->rb1[0].wfr.p && c->rb3[0].wf8l.p;
         // option "comp_heads": the four 3x3 layers of the head branches compensated as well (their inputs then need corr planes: the
         // backbone output has one when the ResBlocks are compensated); convPb / convDb / ConvSta read hi planes either way
         // option "comp_det": the detector branch only (convPa.0, convPa.3) -- its score goes through exp(), which is what moves key points
         p.ch = p.comp_rb && c->opt_comp_heads;
         p.chp = p.ch || (p.comp_rb && c->opt_comp_det);
+        // The records every stored tensor leaves its producer with, and its readers take (but conv3b with "c3b_plain": a3a_in).  "rb_inner": t1 (2) and
+        // t2 (1, 2) plain fp16; "comp_rb" = 0: the ResBlocks' tensors all plain fp16.  The last block's output keeps its units for compensated heads.
+        p.rec.a1b = s6 ? Rec::Half6 : Rec::Unit8;
+        p.rec.a2a = Rec::Unit8;
+        p.rec.a2b = b6 ? Rec::Half6 : Rec::Unit8;
+        p.rec.a3a = p3a ? Rec::None : a6 ? Rec::Half6 : Rec::Unit8;
+        p.a3a_in = p3b ? Rec::None : p.rec.a3a;
+        p.rec.a3b = tr1 ? Rec::Resid8 : Rec::Unit8;
+        for (int b = 0; b < 3 && p.comp_rb; ++b) {
+            p.rec.t1[b] = p.rb_inner >= 2 ? Rec::None : Rec::Unit8;
+            p.rec.t2[b] = p.rb_inner >= 1 ? Rec::None : Rec::Unit8;
+            p.rec.ro[b] = (tr1 && (b < 2 || !p.chp)) ? Rec::Resid8 : Rec::Unit8;
+        }
+        p.rec.pa0 = p.chp ? Rec::Unit8 : Rec::None;
+        p.rec.da0 = p.ch ? Rec::Unit8 : Rec::None;
     }
     p.branches = c->opt_branches;
     if (entry == PASS_EXTRACT) {
@@ -177,11 +191,8 @@ int ensure_workspace(sfd2_ctx *c, const PassPlan &p, int H, int W)
     HIPCHECK(c->bnd.ensure(cap * 8));
     HIPCHECK(c->counters.ensure(SFD2_COUNTER_BYTES));
     c->acts.clear();
-    auto reg = [&](const char *nm, const void *ptr, int is_f32, int planar, int ch, int pitch, int h, int w) -> ActInfo & {
-        ActInfo ai{ptr, is_f32, planar, ch, pitch, h, w};
-        // backbone activations of SFD2_PREC_F16C: the corr plane follows the hi plane
-        if (comp && !is_f32 && std::strncmp(nm, "convP", 5) != 0 && std::strncmp(nm, "convD", 5) != 0)
-            ai.pc = reinterpret_cast<const half_t *>(ptr) + (size_t)pitch * h * w;
+    auto reg = [&](const char *nm, const void *ptr, int is_f32, int planar, int ch, int pitch, int h, int w, Rec rec = Rec::None) -> ActInfo & {
+        ActInfo ai{ptr, is_f32, planar, ch, pitch, h, w, rec};
         if (!is_f32) {      // the fp16 family stores its tensors times 2^act_exp (sfd2_ctx.h): sfd2_debug_activation divides it out
             static const struct { const char *name; int group; } gmap[] = {
                 {"conv1a", AE_CONV1A}, {"bn1b", AE_CONV1B}, {"conv2a", AE_CONV2A}, {"bn2b", AE_CONV2B}, {"conv3a", AE_CONV3A},
@@ -238,22 +249,19 @@ int ensure_workspace(sfd2_ctx *c, const PassPlan &p, int H, int W)
         return 0;
     }
     if (!layers) return 0;   // throughput path: intermediates live in aliased arena slots and are not readable
-    // (SFD2_PREC_F16C: the corr records' format per tensor -- fp6 half-records, residual bytes, none -- as the plan has the producers write them)
-    if (!p.fused_stem) reg("conv1a", c->a1a.p, 0, 0, 64, 64, H, W);
-    reg("bn1b", c->a1b.p, 0, 0, 64, 64, c->H2, c->W2).fmt6 = p.s6;
-    reg("conv2a", c->a2a.p, 0, 0, 128, 128, c->H2, c->W2);
-    reg("bn2b", c->a2b.p, 0, 0, 128, 128, c->H4, c->W4).fmt6 = p.b6;
-    ActInfo &a3 = reg("conv3a", c->a3a.p, 0, 0, 256, 256, c->H4, c->W4);
-    a3.fmt6 = p.a6 && !p.p3a;
-    if (p.p3a) a3.pc = nullptr;
-    reg("bn3b", c->a3b.p, 0, 0, 256, 256, c->H4, c->W4).r1 = p.tr1;
+    // (SFD2_PREC_F16C: each tensor with the corr records the plan has its producer write; the head branches' tensors as their hi planes)
+    if (!p.fused_stem) reg("conv1a", c->a1a.p, 0, 0, 64, 64, H, W, comp ? Rec::Unit8 : Rec::None);
+    reg("bn1b", c->a1b.p, 0, 0, 64, 64, c->H2, c->W2, p.rec.a1b);
+    reg("conv2a", c->a2a.p, 0, 0, 128, 128, c->H2, c->W2, p.rec.a2a);
+    reg("bn2b", c->a2b.p, 0, 0, 128, 128, c->H4, c->W4, p.rec.a2b);
+    reg("conv3a", c->a3a.p, 0, 0, 256, 256, c->H4, c->W4, p.rec.a3a);
+    reg("bn3b", c->a3b.p, 0, 0, 256, 256, c->H4, c->W4, p.rec.a3b);
     for (int b = 0; b < 3; ++b) {
-        if (!p.rb_fused) {      // "rb_inner": t1 (2) and t2 (1, 2) plain fp16; t2 stays on chip in rb23_c_kernel
-            ActInfo &t1 = reg(n1[b], c->rt1[b].p, 0, 0, 256, 256, c->H4, c->W4), &t2 = reg(n2[b], c->rt2[b].p, 0, 0, 256, 256, c->H4, c->W4);
-            if (p.rb_inner >= 2) t1.pc = nullptr;
-            if (p.rb_inner) { t2.pc = nullptr; t2.absent = p.rb23; }
+        if (!p.rb_fused) {
+            reg(n1[b], c->rt1[b].p, 0, 0, 256, 256, c->H4, c->W4, p.rec.t1[b]);
+            reg(n2[b], c->rt2[b].p, 0, 0, 256, 256, c->H4, c->W4, p.rec.t2[b]).absent = p.rb23;   // (t2 stays on chip in rb23_c_kernel)
         }
-        reg(n3[b], c->ro[b].p, 0, 0, 256, 256, c->H4, c->W4).r1 = p.tr1 && (b < 2 || !p.chp);   // (the last one keeps its units for compensated heads)
+        reg(n3[b], c->ro[b].p, 0, 0, 256, 256, c->H4, c->W4, p.rec.ro[b]);
     }
     reg("convPa.0", c->pa0_o.p, 0, 0, 256, 256, c->H8, c->W8);
     reg("convPa", c->pa_o.p, 0, 0, 256, 256, c->H8, c->W8);
@@ -289,67 +297,57 @@ static void conv(sfd2_ctx *c, const char *name, const ConvW &L, const DevPtr &in
                       c->zero_page.as<half_t>());
 }
 
-// SFD2_PREC_F16C: one compensated layer.  A compensated tensor = hi plane followed by its corr plane; in_comp / out_comp
-// say which of the two tensors have one (a plain-fp16 consumer just reads the hi plane).
 // the range-status slot of a stored tensor of the compensated mode (sfd2_internal.h), null when nothing is recorded
 static unsigned int *range_slot(sfd2_ctx *c, int id)
 {
     return (id >= 0 && c->range_stat.p) ? c->range_stat.as<unsigned int>() + id * SFD2_RANGE_SUB : nullptr;
 }
 static half_t *corr_of(const DevPtr &b, size_t px, int pitch) { return b.as<half_t>() + px * (size_t)pitch; }
+// conv3x3_pp<comp>'s filters for the records of a layer's input and output: the fp6 x fp6 strings over Half6 input records, the fp8 x fp6
+// ones for a Half6 output or (option "fp6_filters") between Unit8 records, the fp8 units otherwise.  shift: [shift | scale bytes] with fp6.
+struct PPFilters { const half_t *w; const float *shift; bool fp6; };
+static PPFilters pp_filters(const PassPlan &p, const ConvW &L, Rec in, Rec out)
+{
+    if (in == Rec::Half6) return {L.wc66.as<half_t>(), L.sa66.as<float>(), true};
+    if (in == Rec::Unit8 && (out == Rec::Half6 || (out == Rec::Unit8 && p.fp6_filters && L.wc6.p && L.sa6.p))) return {L.wc6.as<half_t>(), L.sa6.as<float>(), true};
+    return {L.wc.as<half_t>(), L.shift.as<float>(), false};
+}
+// SFD2_PREC_F16C: one compensated layer.  A compensated tensor = hi plane followed by its corr plane; in / out say in which format the two
+// tensors carry their records (a plain-fp16 consumer just reads the hi plane, Rec::None)
 static void convc(sfd2_ctx *c, const PassPlan &p, const char *name, const ConvW &L, const DevPtr &in, int H, int W, const DevPtr &out,
-                  int Ho, int Wo, int relu, bool in_comp, bool out_comp, const DevPtr *res = nullptr, int rs_id = -1 /* SFD2_RS_*: the output's range-status slot */,
-                  int fmt6 = 0 /* option "fp6_acts": bit 0 = the input's corr records are fp6 half-records, bit 1 = the output's are to be */)
+                  int Ho, int Wo, int relu, Rec rin, Rec rout, const DevPtr *res = nullptr, int rs_id = -1 /* SFD2_RS_*: the output's range-status slot */,
+                  bool s2d_out = false /* option "s2d": the output stored space-to-depth */)
 {
     unsigned int *rs = range_slot(c, rs_id);
     char kn[48];
-    snprintf(kn, sizeof(kn), "convc_igemm<%d,%d>", L.ks, L.stride);
     const double px = (double)Ho * Wo;
     const double flops = 2.0 * px * L.cout * L.cin * L.ks * L.ks;
-    const double bytes = (in_comp ? 4.0 : 2.0) * ((double)H * W * L.cin + (double)L.cout * L.cin * L.ks * L.ks) +
-                         px * L.cout_pad * (out_comp ? 4.0 : 2.0) + (res ? px * L.cout_pad * 4.0 : 0.0);
-    const half_t *in_c = in_comp ? corr_of(in, (size_t)H * W, L.cin) : nullptr;
-    half_t *out_c = out_comp ? corr_of(out, (size_t)Ho * Wo, L.cout_pad) : nullptr;
+    const double bytes = (rin != Rec::None ? 4.0 : 2.0) * ((double)H * W * L.cin + (double)L.cout * L.cin * L.ks * L.ks) +
+                         px * L.cout_pad * (rout != Rec::None ? 4.0 : 2.0) + (res ? px * L.cout_pad * 4.0 : 0.0);
+    const half_t *in_c = rin != Rec::None ? corr_of(in, (size_t)H * W, L.cin) : nullptr;
+    half_t *out_c = rout != Rec::None ? corr_of(out, (size_t)Ho * Wo, L.cout_pad) : nullptr;
     // conv3x3_pp's tile is 128 channels wide: in its compensated form it also takes conv2a (64 -> 128 channels, four chunks)
-    if (!res && !p.generic_c && L.ks == 3 && L.stride == 1 && L.cout_pad % 128 == 0 && L.cin % 64 == 0) {
+    const bool pp = !res && !p.generic_c && L.ks == 3 && L.stride == 1 && L.cout_pad % 128 == 0 && L.cin % 64 == 0;
+    if (pp) {
         ProfScope ps(c, name, (in_c && out_c) ? "conv3x3_pp<comp>" : (in_c ? "conv3x3_pp<comp,plain out>" : "conv3x3_pp<comp out>"), flops, bytes);
-        if (relu && ((!in_c && out_c) || (in_c && !out_c && (fmt6 & 1) && L.wc66.p && L.sa66.p))) {
-            // option "c3b_plain": conv3b over the hi plane of its input alone (the hi chunks at the start of any of the layer's arrays; the output's corr
-            // bytes from the fp32 accumulators as ever: fmt6 bit 3 = the three-byte trunk form), and conv3a, whose corr plane then has no reader
-            launch_conv3x3_pp_c(c->cur_stream, in.as<half_t>(), in_c, H, W, L.cin, in_c ? L.wc66.as<half_t>() : L.wc.as<half_t>(), L.scale.as<float>(),
-                                in_c ? L.shift.as<float>() : L.shift.as<float>(), L.cout_pad, relu, out.as<half_t>(), out_c, Ho, Wo, c->zero_page.as<half_t>(), L.sbyte,
-                                in_c ? L.sa66.as<float>() : nullptr, rs, fmt6);
+        const PPFilters f = pp_filters(p, L, rin, rout);
+        if (f.w && launch_conv3x3_pp_c(c->cur_stream, in.as<half_t>(), in_c, H, W, L.cin, f.w, L.scale.as<float>(), f.shift, L.cout_pad, relu,
+                                       out.as<half_t>(), out_c, Ho, Wo, c->zero_page.as<half_t>(), L.sbyte, rs, rin, rout, s2d_out, f.fp6))
             return;
-        }
-        if (fmt6 && in_c && out_c && relu && L.wc66.p && L.sa66.p && L.wc6.p && L.sa6.p) {
-            // fp6 pixel records on either side: the filter strings in the input records' format (fp6 x fp6 when the input's are fp6)
-            const bool i6 = (fmt6 & 1) != 0;
-            launch_conv3x3_pp_c(c->cur_stream, in.as<half_t>(), in_c, H, W, L.cin, i6 ? L.wc66.as<half_t>() : L.wc6.as<half_t>(), L.scale.as<float>(),
-                                L.shift.as<float>(), L.cout_pad, relu, out.as<half_t>(), out_c, Ho, Wo, c->zero_page.as<half_t>(), L.sbyte,
-                                i6 ? L.sa66.as<float>() : L.sa6.as<float>(), rs, fmt6);      // (bit 2: the output stored space-to-depth, with fp6 input records only)
-            return;
-        }
-        if (fmt6) { c->net_error = 1; (void)fail(std::string(name) + ": fp6 records requested from a layer without fp6 filter strings"); return; }
-        const bool f6 = p.fp6_filters && in_c && out_c && L.wc6.p && L.sa6.p;      // corr filters as fp6 (option "fp6_filters")
-        launch_conv3x3_pp_c(c->cur_stream, in.as<half_t>(), in_c, H, W, L.cin, f6 ? L.wc6.as<half_t>() : L.wc.as<half_t>(), L.scale.as<float>(),
-                            L.shift.as<float>(), L.cout_pad, relu, out.as<half_t>(), out_c, Ho, Wo, c->zero_page.as<half_t>(), L.sbyte,
-                            f6 ? L.sa6.as<float>() : nullptr, rs);
-        return;
-    }
-    if ((fmt6 & 1) || ((fmt6 & 2) && !(!p.generic_c && !p.no_rf_c && conv3x3_rf_c_serves(L.ks, L.stride, L.cout_pad, L.cin, Ho, Wo) && relu))) {
-        // (run_network decides the format per tensor from the same predicates: reaching this is a bug, reported as an error of the call)
-        c->net_error = 1;
-        (void)fail(std::string(name) + ": fp6 records on a path that cannot read / write them");
-        return;
-    }
-    if (!p.generic_c && !p.no_rf_c && in_c && out_c && !res && L.ks == 3 && L.stride == 2 && L.cout_pad == 128) {   // conv2b
+        ps.cancel();
+    } else if (!p.generic_c && !p.no_rf_c && in_c && out_c && !res && L.ks == 3 && L.stride == 2 && L.cout_pad == 128) {   // conv2b
         ProfScope ps(c, name, "conv3x3_rf<2,comp>", flops, bytes);
-        if (!launch_conv3x3_rf_c(c->cur_stream, in.as<half_t>(), in_c, H, W, L.cin, L.wc.as<half_t>(), L.scale.as<float>(),
-                                L.shift.as<float>(), L.cout_pad, L.stride, relu, out.as<half_t>(), out_c, Ho, Wo,
-                                c->zero_page.as<half_t>(), L.sbyte, rs, fmt6 & 2))
-            ps.cancel();     // no instantiation for this geometry: the next candidate takes the layer (and the profile row)
-        else
+        if (launch_conv3x3_rf_c(c->cur_stream, in.as<half_t>(), in_c, H, W, L.cin, L.wc.as<half_t>(), L.scale.as<float>(), L.shift.as<float>(),
+                                L.cout_pad, L.stride, relu, out.as<half_t>(), out_c, Ho, Wo, c->zero_page.as<half_t>(), L.sbyte, rs, rin, rout))
             return;
+        ps.cancel();     // no instantiation for this geometry: the next candidate takes the layer (and the profile row)
+    }
+    // (the kernels below read and write Unit8 records only)
+    const bool unit8 = (rin == Rec::None || rin == Rec::Unit8) && (rout == Rec::None || rout == Rec::Unit8) && !s2d_out;
+    if (pp || !unit8) {
+        c->net_error = 1;
+        (void)fail(std::string(name) + ": no kernel instantiation for the corr-record formats the pass plan asks for");
+        return;
     }
     if (!p.generic_c && in_c && out_c && L.wfh.p && L.wfc.p) {   // the ResBlocks' 1x1 layers: persistent streaming kernel
         snprintf(kn, sizeof(kn), "conv1x1_c256<comp>%s", res ? "+res" : "");
@@ -357,7 +355,7 @@ static void convc(sfd2_ctx *c, const PassPlan &p, const char *name, const ConvW 
         launch_conv1x1_c256_c(c->cur_stream, in.as<half_t>(), in_c, Ho * Wo, L.wfh.as<half_t>(), L.wfc.as<half_t>(), L.scale.as<float>(),
                               L.shift.as<float>(), relu, res ? res->as<half_t>() : nullptr,
                               res ? corr_of(*res, (size_t)Ho * Wo, L.cout_pad) : nullptr, out.as<half_t>(), out_c,
-                              c->zero_page.as<half_t>(), L.sbyte, rs);
+                              c->zero_page.as<half_t>(), L.sbyte, rs, rin, rout);
         return;
     }
     if (!p.generic_c && in_c && out_c && L.cout_pad % 128 == 0 && ((L.ks == 1 && L.stride == 1) || (L.ks == 3 && L.stride == 2 && !res))) {
@@ -373,10 +371,9 @@ static void convc(sfd2_ctx *c, const PassPlan &p, const char *name, const ConvW 
     }
     snprintf(kn, sizeof(kn), "convc_igemm<%d,%d>", L.ks, L.stride);
     ProfScope ps(c, name, kn, flops, bytes);
-    launch_convc_igemm(c->cur_stream, in.as<half_t>(), in_comp ? corr_of(in, (size_t)H * W, L.cin) : nullptr, H, W, L.cin,
-                       L.wc.as<half_t>(), L.scale.as<float>(), L.shift.as<float>(), L.cout_pad, L.ks, L.stride, relu,
-                       res ? res->as<half_t>() : nullptr, res ? corr_of(*res, (size_t)Ho * Wo, L.cout_pad) : nullptr,
-                       out.as<half_t>(), out_comp ? corr_of(out, (size_t)Ho * Wo, L.cout_pad) : nullptr, Ho, Wo, L.sbyte, rs);
+    launch_convc_igemm(c->cur_stream, in.as<half_t>(), in_c, H, W, L.cin, L.wc.as<half_t>(), L.scale.as<float>(), L.shift.as<float>(), L.cout_pad,
+                       L.ks, L.stride, relu, res ? res->as<half_t>() : nullptr, res ? corr_of(*res, (size_t)Ho * Wo, L.cout_pad) : nullptr,
+                       out.as<half_t>(), out_c, Ho, Wo, L.sbyte, rs);
 }
 
 int convf(sfd2_ctx *c, const PassPlan &p, const char *name, const ConvW &L, const DevPtr &in, int H, int W, const DevPtr &out,
@@ -649,58 +646,59 @@ int run_network(sfd2_ctx *c, const PassPlan &p, const float *img_dev, int normal
     };
     if (comp) {
         // SFD2_PREC_F16C backbone: every activation carries a corr plane, every layer adds the fp8 correction terms (the formats: plan_pass)
-        const bool s6 = p.s6, b6 = p.b6, a6 = p.a6, d2 = p.d2, p3b = p.p3b, p3a = p.p3a, tr1 = p.tr1;
         if (p.fused_stem) {
             ProfScope ps(c, "conv1a+conv1b", "fused_stem_c_kernel", 2.0 * P1 * 64 * 27 + 2.0 * (double)H2 * W2 * 64 * 576,
                          P1 * 12 + (double)H2 * W2 * 256);
             launch_fused_stem_c(st, img_dev, H, W, normalise, c->c1a.wc.as<half_t>(), c->c1a.scale.as<float>(),
-                                c->c1a.shift.as<float>(), s6 ? c->w1b_stem_c6.p : c->w1b_stem_c.p, c->c1b.scale.as<float>(), c->c1b.shift.as<float>(),
-                                a1b.as<half_t>(), corr_of(a1b, (size_t)H2 * W2, 64), H2, W2, c->c1b.sbyte, c->range_stat.as<unsigned int>(), s6 ? 2 : 0);
+                                c->c1a.shift.as<float>(), p.rec.a1b == Rec::Half6 ? c->w1b_stem_c6.p : c->w1b_stem_c.p, c->c1b.scale.as<float>(),
+                                c->c1b.shift.as<float>(), a1b.as<half_t>(), corr_of(a1b, (size_t)H2 * W2, 64), H2, W2, c->c1b.sbyte,
+                                c->range_stat.as<unsigned int>(), p.rec.a1b);
         } else {
             {
                 ProfScope ps(c, "conv1a", "conv1a_c_kernel", 2.0 * P1 * 64 * 27, P1 * (12 + 256));
                 launch_conv1a_c(st, img_dev, H, W, normalise, c->c1a.wc.as<half_t>(), c->c1a.scale.as<float>(),
                                 c->c1a.shift.as<float>(), c->a1a.as<half_t>(), corr_of(c->a1a, (size_t)H * W, 64), range_slot(c, SFD2_RS_CONV1A));
             }
-            convc(c, p, "conv1b", c->c1b, c->a1a, H, W, a1b, H2, W2, 1, true, true, nullptr, SFD2_RS_CONV1B);
+            convc(c, p, "conv1b", c->c1b, c->a1a, H, W, a1b, H2, W2, 1, Rec::Unit8, p.rec.a1b, nullptr, SFD2_RS_CONV1B);
         }
-        convc(c, p, "conv2a", c->c2a, a1b, H2, W2, a2a, H2, W2, 1, true, true, nullptr, SFD2_RS_CONV2A, (s6 ? 1 : 0) | (d2 ? 4 : 0));
-        if (d2) {
+        convc(c, p, "conv2a", c->c2a, a1b, H2, W2, a2a, H2, W2, 1, p.rec.a1b, p.rec.a2a, nullptr, SFD2_RS_CONV2A, p.a2a_s2d);
+        if (p.a2a_s2d) {
             const ConvW &L = c->c2b;
             ProfScope ps(c, "conv2b", "conv2b_s2d_kernel", 2.0 * P4 * L.cout * L.cin * 9, 4.0 * ((double)H2 * W2 * L.cin + (double)L.cout * L.cin * 9) + P4 * L.cout_pad * 4.0);
             launch_conv2b_s2d(st, a2a.as<half_t>(), corr_of(a2a, (size_t)H2 * W2, L.cin), H4, W4, L.wc.as<half_t>(), L.scale.as<float>(), L.shift.as<float>(), 1,
-                              a2b.as<half_t>(), corr_of(a2b, (size_t)H4 * W4, L.cout_pad), c->zero_page.as<half_t>(), L.sbyte, range_slot(c, SFD2_RS_CONV2B), b6 ? 2 : 0);
+                              a2b.as<half_t>(), corr_of(a2b, (size_t)H4 * W4, L.cout_pad), c->zero_page.as<half_t>(), L.sbyte, range_slot(c, SFD2_RS_CONV2B), p.rec.a2b);
         } else
-        convc(c, p, "conv2b", c->c2b, a2a, H2, W2, a2b, H4, W4, 1, true, true, nullptr, SFD2_RS_CONV2B, b6 ? 2 : 0);
-        convc(c, p, "conv3a", c->c3a, a2b, H4, W4, a3a, H4, W4, 1, true, !p3a, nullptr, SFD2_RS_CONV3A, (b6 ? 1 : 0) | ((a6 && !p3a) ? 2 : 0));
-        convc(c, p, "conv3b", c->c3b, a3a, H4, W4, a3b, H4, W4, 1, !p3b, true, nullptr, SFD2_RS_CONV3B, ((a6 && !p3b) ? 1 : 0) | (tr1 ? 8 : 0));
+        convc(c, p, "conv2b", c->c2b, a2a, H2, W2, a2b, H4, W4, 1, p.rec.a2a, p.rec.a2b, nullptr, SFD2_RS_CONV2B);
+        convc(c, p, "conv3a", c->c3a, a2b, H4, W4, a3a, H4, W4, 1, p.rec.a2b, p.rec.a3a, nullptr, SFD2_RS_CONV3A);
+        convc(c, p, "conv3b", c->c3b, a3a, H4, W4, a3b, H4, W4, 1, p.a3a_in, p.rec.a3b, nullptr, SFD2_RS_CONV3B);
         for (int b = 0; b < 3; ++b) {  // ResBlock (nets/sfd2.py:25-55)
             if (!p.comp_rb) { rb_f16(b); continue; }   // option "comp_rb" = 0: this block in plain fp16 on the hi planes
             DevPtr &t1 = t1v[b], &t2 = t2v[b], &ob = rov[b];
+            // the records of the block's input, t1, t2 and output (plan_pass)
+            const Rec x_rec = b == 0 ? p.rec.a3b : p.rec.ro[b - 1], t1_rec = p.rec.t1[b], t2_rec = p.rec.t2[b], o_rec = p.rec.ro[b];
             if (p.rb_inner) {
                 // Option "rb_inner": the tensors INSIDE the block as plain fp16 (1: t2, 2: t1 and t2).  These kernels are bound
                 // by HBM bytes, a plain tensor is half of a compensated one; the filters stay compensated (over a plain input the
                 // residual term x * lo_w is a second fp16 pass: there is no fp8 value byte of x to feed the scaled MFMA).
                 const size_t PP = (size_t)H4 * W4;
                 const ConvW &L1 = c->rb1[b], &L2 = c->rb2[b], &L3 = c->rb3[b];
-                const bool t1p = p.rb_inner >= 2;
+                const bool t1p = t1_rec == Rec::None;
                 if (t1p) {
-                    ProfScope ps(c, nm1[b], "conv1x1_c256<comp,plain out>", 2.0 * P4 * 256.0 * 256.0, P4 * 256.0 * (tr1 ? 5 : 6));
-                    launch_conv1x1_c256_c(st, x->as<half_t>(), corr_of(*x, PP, 256), (int)PP, L1.wfh.as<half_t>(), tr1 ? L1.wfr.as<half_t>() : L1.wfc.as<half_t>(),
+                    const bool x_r1 = x_rec == Rec::Resid8;
+                    ProfScope ps(c, nm1[b], "conv1x1_c256<comp,plain out>", 2.0 * P4 * 256.0 * 256.0, P4 * 256.0 * (x_r1 ? 5 : 6));
+                    launch_conv1x1_c256_c(st, x->as<half_t>(), corr_of(*x, PP, 256), (int)PP, L1.wfh.as<half_t>(), x_r1 ? L1.wfr.as<half_t>() : L1.wfc.as<half_t>(),
                                           L1.scale.as<float>(), L1.shift.as<float>(), 1, nullptr, nullptr, t1.as<half_t>(), nullptr,
-                                          c->zero_page.as<half_t>(), L1.sbyte, range_slot(c, SFD2_RS_T1_0 + b), tr1 ? 1 : 0);
+                                          c->zero_page.as<half_t>(), L1.sbyte, range_slot(c, SFD2_RS_T1_0 + b), x_rec, t1_rec);
                 } else {
-                    convc(c, p, nm1[b], L1, *x, H4, W4, t1, H4, W4, 1, true, true, nullptr, SFD2_RS_T1_0 + b);
+                    convc(c, p, nm1[b], L1, *x, H4, W4, t1, H4, W4, 1, x_rec, t1_rec, nullptr, SFD2_RS_T1_0 + b);
                 }
                 if (p.rb23) {
-                    // (the last block's output keeps its units when a compensated head layer will read them)
-                    const bool out_r1 = b < 2 || !p.chp;
-                    const int r1f = tr1 ? (1 | (out_r1 ? 2 : 0)) : 0;
-                    ProfScope ps(c, nm3[b], "rb23_c_kernel", 2.0 * P4 * 256 * 72 + 2.0 * P4 * 256.0 * 256.0, P4 * 256.0 * (10 - (r1f & 1) - ((r1f >> 1) & 1)));
+                    ProfScope ps(c, nm3[b], "rb23_c_kernel", 2.0 * P4 * 256 * 72 + 2.0 * P4 * 256.0 * 256.0,
+                                 P4 * 256.0 * (10 - (x_rec == Rec::Resid8) - (o_rec == Rec::Resid8)));
                     launch_rb23_c(st, t1.as<half_t>(), H4, W4, L2.w.as<half_t>(), L2.wlk.as<half_t>(), L2.scale.as<float>(), L2.shift.as<float>(),
                                   L3.wfh.as<half_t>(), L3.wfl.as<half_t>(), L3.scale.as<float>(), L3.shift.as<float>(), x->as<half_t>(),
                                   corr_of(*x, PP, 256), ob.as<half_t>(), corr_of(ob, PP, 256), c->zero_page.as<half_t>(),
-                                  range_slot(c, SFD2_RS_T2_0 + b), range_slot(c, SFD2_RS_OUT_0 + b), r1f, L3.wf8l.as<half_t>(), L3.sbyte);
+                                  range_slot(c, SFD2_RS_T2_0 + b), range_slot(c, SFD2_RS_OUT_0 + b), x_rec, o_rec, L3.wf8l.as<half_t>(), L3.sbyte);
                     x = &ob;
                     continue;
                 }
@@ -714,17 +712,17 @@ int run_network(sfd2_ctx *c, const PassPlan &p, const float *img_dev, int normal
                     ProfScope ps(c, nm3[b], "conv1x1_c256<comp,plain in>+res", 2.0 * P4 * 256.0 * 256.0, P4 * 256.0 * 10);
                     launch_conv1x1_c256_c(st, t2.as<half_t>(), nullptr, (int)PP, L3.wfh.as<half_t>(), L3.wfl.as<half_t>(), L3.scale.as<float>(),
                                           L3.shift.as<float>(), 1, x->as<half_t>(), corr_of(*x, PP, 256), ob.as<half_t>(), corr_of(ob, PP, 256),
-                                          c->zero_page.as<half_t>(), L3.sbyte, range_slot(c, SFD2_RS_OUT_0 + b));
+                                          c->zero_page.as<half_t>(), L3.sbyte, range_slot(c, SFD2_RS_OUT_0 + b), t2_rec, o_rec);
                 }
             } else {
-                convc(c, p, nm1[b], c->rb1[b], *x, H4, W4, t1, H4, W4, 1, true, true, nullptr, SFD2_RS_T1_0 + b);
+                convc(c, p, nm1[b], c->rb1[b], *x, H4, W4, t1, H4, W4, 1, x_rec, t1_rec, nullptr, SFD2_RS_T1_0 + b);
                 {
                     ProfScope ps(c, nm2[b], "gconv_c_kernel", 2.0 * P4 * 256 * 72, P4 * 256 * 8);
                     launch_gconv_c(st, t1.as<half_t>(), corr_of(t1, (size_t)H4 * W4, 256), H4, W4, c->rb2[b].w.as<half_t>(),
                                    c->rb2[b].wc.p, c->rb2[b].scale.as<float>(), c->rb2[b].shift.as<float>(), t2.as<half_t>(),
                                    corr_of(t2, (size_t)H4 * W4, 256), c->rb2[b].sbyte, 0, H4, range_slot(c, SFD2_RS_T2_0 + b));
                 }
-                convc(c, p, nm3[b], c->rb3[b], t2, H4, W4, ob, H4, W4, 1, true, true, x, SFD2_RS_OUT_0 + b);
+                convc(c, p, nm3[b], c->rb3[b], t2, H4, W4, ob, H4, W4, 1, t2_rec, o_rec, x, SFD2_RS_OUT_0 + b);
             }
             x = &ob;
         }
@@ -781,8 +779,8 @@ int run_network(sfd2_ctx *c, const PassPlan &p, const float *img_dev, int normal
         c->cur_stream = c->side_stream;
     }
     if (p.chp) {      // options "comp_heads" / "comp_det" (plan_pass)
-        convc(c, p, "convPa.0", c->pa0, *x, H4, W4, pa0_o, H8, W8, 1, true, true, nullptr, SFD2_RS_PA0);
-        convc(c, p, "convPa.3", c->pa3, pa0_o, H8, W8, pa_o, H8, W8, 0, true, false);
+        convc(c, p, "convPa.0", c->pa0, *x, H4, W4, pa0_o, H8, W8, 1, p.rec.ro[2], p.rec.pa0, nullptr, SFD2_RS_PA0);
+        convc(c, p, "convPa.3", c->pa3, pa0_o, H8, W8, pa_o, H8, W8, 0, p.rec.pa0, Rec::None);
     } else {
         conv(c, "convPa.0", c->pa0, *x, H4, W4, pa0_o, H8, W8, 1);
         conv(c, "convPa.3", c->pa3, pa0_o, H8, W8, pa_o, H8, W8, 0);
@@ -798,8 +796,8 @@ int run_network(sfd2_ctx *c, const PassPlan &p, const float *img_dev, int normal
         c->cur_stream = st;
     }
     if (p.ch) {
-        convc(c, p, "convDa.0", c->da0, *x, H4, W4, da0_o, H4, W4, 1, true, true, nullptr, SFD2_RS_DA0);
-        convc(c, p, "convDa.3", c->da3, da0_o, H4, W4, da_o, H4, W4, 0, true, false);
+        convc(c, p, "convDa.0", c->da0, *x, H4, W4, da0_o, H4, W4, 1, p.rec.ro[2], p.rec.da0, nullptr, SFD2_RS_DA0);
+        convc(c, p, "convDa.3", c->da3, da0_o, H4, W4, da_o, H4, W4, 0, p.rec.da0, Rec::None);
     } else {
         conv(c, "convDa.0", c->da0, *x, H4, W4, da0_o, H4, W4, 1);
         if (!p.skip_da3) conv(c, "convDa.3", c->da3, da0_o, H4, W4, da_o, H4, W4, 0);

@@ -721,13 +721,13 @@ void launch_conv1x1_c256_x3(hipStream_t st, const half_t *in, const half_t *in_l
 
 void launch_conv1x1_c256_c(hipStream_t st, const half_t *in, const half_t *in_c, int npix, const half_t *w_frag,
                            const half_t *wc_frag, const float *scale, const float *shift, int relu, const half_t *res,
-                           const half_t *res_c, half_t *out, half_t *out_c, const half_t *zero_page, int sbyte, unsigned int *range, int in_r1)
-// in_c == null: plain fp16 input, wc_frag = the fp16 filter residuals * 2^11; out_c == null: only the hi plane is written;
-// in_r1: in_c holds residual bytes only (256 B per pixel)
+                           const half_t *res_c, half_t *out, half_t *out_c, const half_t *zero_page, int sbyte, unsigned int *range, Rec rin, Rec rout)
+// rin = None: plain fp16 input, wc_frag = the fp16 filter residuals * 2^11; Resid8: in_c holds residual bytes only (256 B per pixel);
+// rout = None: only the hi plane is written
 {
     static bool attr_done = false;
     static int slots = 256;
-    const size_t lds = in_r1 ? (size_t)SFD2_C256_R1_STAGES * STAGE_R1 + 512 * sizeof(float) : (size_t)NST * STAGE_C + 512 * sizeof(float);
+    const size_t lds = rin == Rec::Resid8 ? (size_t)SFD2_C256_R1_STAGES * STAGE_R1 + 512 * sizeof(float) : (size_t)NST * STAGE_C + 512 * sizeof(float);
     if (!attr_done) {
         const size_t lds_max = std::max((size_t)SFD2_C256_R1_STAGES * STAGE_R1, (size_t)NST * STAGE_C) + 512 * sizeof(float);
 #define C256C_ATTR(R_, I_, O_) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(conv1x1_c256_c_kernel<R_, I_, O_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max);
@@ -745,9 +745,9 @@ void launch_conv1x1_c256_c(hipStream_t st, const half_t *in, const half_t *in_c,
     const int grid = (ngroups + gpb - 1) / gpb;
     const int sa = (sbyte & 255) * 0x01010101;
 #define C256C_GO(R_, I_, O_) hipLaunchKernelGGL((conv1x1_c256_c_kernel<R_, I_, O_>), dim3(grid), dim3(NT1), lds, st, in, in_c, npix, w_frag, wc_frag, scale, shift, relu, res, res_c, out, out_c, gpb, zero_page, sa, range)
-    if (in_r1) { if (in_c && !out_c && !res) C256C_GO(false, 2, false); else abort(); }
+    if (rin == Rec::Resid8) { if (rout == Rec::None && !res) C256C_GO(false, 2, false); else abort(); }
 #ifdef SFD2_C256_TRACE
-    if (in_r1) {
+    if (rin == Rec::Resid8) {
         static int dumps = 0;
         if (npix > 100000 && ++dumps == 40) {
             (void)hipStreamSynchronize(st);
@@ -761,9 +761,9 @@ void launch_conv1x1_c256_c(hipStream_t st, const half_t *in, const half_t *in_c,
         }
     }
 #endif   // ResBlock.conv1 over a residual-only input
-    else if (in_c && out_c) { if (res) C256C_GO(true, 1, true); else C256C_GO(false, 1, true); }
-    else if (in_c && !res) C256C_GO(false, 1, false);           // ResBlock.conv1 writing a plain t1
-    else if (!in_c && out_c && res) C256C_GO(true, 0, true);   // ResBlock.conv3 reading a plain t2
+    else if (rin == Rec::Unit8 && rout == Rec::Unit8) { if (res) C256C_GO(true, 1, true); else C256C_GO(false, 1, true); }
+    else if (rin == Rec::Unit8 && rout == Rec::None && !res) C256C_GO(false, 1, false);   // ResBlock.conv1 writing a plain t1
+    else if (rin == Rec::None && rout == Rec::Unit8 && res) C256C_GO(true, 0, true);      // ResBlock.conv3 reading a plain t2
     else abort();                                                   // no other combination is dispatched
 #undef C256C_GO
 }

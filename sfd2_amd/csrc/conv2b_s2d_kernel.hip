@@ -378,7 +378,7 @@ bool conv2b_s2d_serves(int H2, int W2, int Cin, int CoutP)
 }
 
 void launch_conv2b_s2d(hipStream_t st, const half_t *in, const half_t *in_c, int H4, int W4, const half_t *wpk, const float *scale,
-                       const float *shift, int relu, half_t *out, half_t *out_c, const half_t *zero_page, int sbyte, unsigned int *range, int fmt6)
+                       const float *shift, int relu, half_t *out, half_t *out_c, const half_t *zero_page, int sbyte, unsigned int *range, Rec rout)
 {
     constexpr size_t lds = (size_t)3 * S2_XBYTES + (size_t)2 * S2_FBYTES + 2 * S2_BN * sizeof(float);
     static bool attr_done = false;
@@ -407,7 +407,7 @@ void launch_conv2b_s2d(hipStream_t st, const half_t *in, const half_t *in_c, int
         if (a >= 1 && a <= 3) return;
     }
 #endif
-    if (fmt6 & 2)
+    if (rout == Rec::Half6)
         hipLaunchKernelGGL(conv2b_s2d_kernel<true>, dim3(grid), dim3(512), lds, st, in, in_c, H4, W4, wpk, scale, shift, relu, out, out_c, tiles_x,
                            n_tiles, zero_page, sa, range);
     else

@@ -634,44 +634,38 @@ static void launch_pp_t(hipStream_t st, const half_t *in, int H, int W, int Cin,
 #endif
 }
 
-// compensated instantiations (SFD2_PREC_F16C): wpk = the layer's wc array, sbyte its scale byte
-void launch_conv3x3_pp_c(hipStream_t st, const half_t *in, const half_t *in_c, int H, int W, int Cin, const half_t *wpk,
+// compensated instantiations (SFD2_PREC_F16C): wpk = the layer's wc array (or its fp6 form, fp6_w), sbyte its scale byte.  The COMP bits of the
+// kernel: 1 / 2 = input / output corr plane, 16 = fp6 filter strings, 32 = Half6 input records, 64 = Half6 output records, 128 = output
+// stored space-to-depth, 256 = Resid8 output records.  false = no instantiation for these formats.
+bool launch_conv3x3_pp_c(hipStream_t st, const half_t *in, const half_t *in_c, int H, int W, int Cin, const half_t *wpk,
                          const float *scale, const float *shift, int CoutP, int relu, half_t *out, half_t *out_c,
-                         int Ho, int Wo, const half_t *zero_page, int sbyte, const float *shift_sa6, unsigned int *range, int fmt6)
+                         int Ho, int Wo, const half_t *zero_page, int sbyte, unsigned int *range, Rec rin, Rec rout, bool s2d_out, bool fp6_w)
 {
     const int sa = (sbyte & 255) * 0x01010101;
+#define PPC_GO(ABL_, COMP_) launch_pp_t<1, 1, ABL_, COMP_>(st, in, H, W, Cin, wpk, scale, shift, CoutP, relu, out, Ho, Wo, zero_page, in_c, out_c, sa, range)
+    const bool h6 = rin == Rec::Half6 && fp6_w;      // (fp6 pixel records meet the fp6 x fp6 filter strings only)
+    if (s2d_out && !(h6 && rout == Rec::Unit8)) return false;
     // option "c3b_plain": no corr plane on one side.  Plain input (conv3b): the K loop ends with the hi chunks, the epilogue still writes the output's corr
-    // bytes (fmt6 bit 3: the three-byte trunk form).  Plain output (conv3a, its corr plane having no reader): fp6 x fp6 correction chunks, fp16 epilogue.
-    if (!in_c && out_c) {
-        if (fmt6 & 8) launch_pp_t<1, 1, 0, 2 | 256>(st, in, H, W, Cin, wpk, scale, shift, CoutP, relu, out, Ho, Wo, zero_page, in_c, out_c, sa, range);
-        else launch_pp_t<1, 1, 0, 2>(st, in, H, W, Cin, wpk, scale, shift, CoutP, relu, out, Ho, Wo, zero_page, in_c, out_c, sa, range);
-        return;
-    }
-    if (in_c && !out_c && shift_sa6 && (fmt6 & 1)) {
-        launch_pp_t<1, 1, 0, 1 | 16 | 32>(st, in, H, W, Cin, wpk, scale, shift_sa6, CoutP, relu, out, Ho, Wo, zero_page, in_c, out_c, sa, range);
-        return;
-    }
-    // shift_sa6 != null: wpk's corr rows are fp6 strings and shift_sa6 = [shift[CoutP] | the rows' scale bytes as ints [CoutP]]
-    if (in_c && out_c && shift_sa6 && fmt6 != 0) {      // fp6 corr records: bit 0 of fmt6 = the input's, bit 1 = the output's (filters: the (w, lo'_w) strings)
-        if ((fmt6 & 3) == 3) launch_pp_t<1, 1, 0, 3 | 16 | 32 | 64>(st, in, H, W, Cin, wpk, scale, shift_sa6, CoutP, relu, out, Ho, Wo, zero_page, in_c, out_c, sa, range);
+    // bytes (Resid8: the three-byte trunk form).  Plain output (conv3a, its corr plane having no reader): fp6 x fp6 correction chunks, fp16 epilogue.
+    if (rin == Rec::None && rout == Rec::Resid8) PPC_GO(0, 2 | 256);
+    else if (rin == Rec::None && rout == Rec::Unit8) PPC_GO(0, 2);
+    else if (h6 && rout == Rec::None) PPC_GO(0, 1 | 16 | 32);
+    else if (h6 && rout == Rec::Half6) PPC_GO(0, 3 | 16 | 32 | 64);
 #ifdef SFD2_EXPERIMENTS
-        else if ((fmt6 & 1) && sfd2_env("SFD2_PPC_ABL"))    // timing ablation (wrong results): conv3b's instantiation without its staging copies
-            launch_pp_t<1, 1, 1, 3 | 16 | 32>(st, in, H, W, Cin, wpk, scale, shift_sa6, CoutP, relu, out, Ho, Wo, zero_page, in_c, out_c, sa, range);
+    else if (h6 && sfd2_env("SFD2_PPC_ABL"))    // timing ablation (wrong results): conv3b's instantiation without its staging copies
+        PPC_GO(1, 3 | 16 | 32);
 #endif
-#ifdef SFD2_EXPERIMENTS
-        else if ((fmt6 & 1) && sfd2_env("SFD2_PPC_ABL"))    // timing ablation (wrong results): conv3b's instantiation without its staging copies
-            launch_pp_t<1, 1, 1, 3 | 16 | 32>(st, in, H, W, Cin, wpk, scale, shift_sa6, CoutP, relu, out, Ho, Wo, zero_page, in_c, out_c, sa, range);
-#endif
-        else if ((fmt6 & 9) == 9) launch_pp_t<1, 1, 0, 3 | 16 | 32 | 256>(st, in, H, W, Cin, wpk, scale, shift_sa6, CoutP, relu, out, Ho, Wo, zero_page, in_c, out_c, sa, range);
-        else if ((fmt6 & 5) == 5) launch_pp_t<1, 1, 0, 3 | 16 | 32 | 128>(st, in, H, W, Cin, wpk, scale, shift_sa6, CoutP, relu, out, Ho, Wo, zero_page, in_c, out_c, sa, range);
-        else if (fmt6 & 1) launch_pp_t<1, 1, 0, 3 | 16 | 32>(st, in, H, W, Cin, wpk, scale, shift_sa6, CoutP, relu, out, Ho, Wo, zero_page, in_c, out_c, sa, range);
-        else launch_pp_t<1, 1, 0, 3 | 16 | 64>(st, in, H, W, Cin, wpk, scale, shift_sa6, CoutP, relu, out, Ho, Wo, zero_page, in_c, out_c, sa, range);
-        return;
-    }
-    if (in_c && out_c && (fmt6 & 2)) { launch_pp_t<1, 1, 0, 3 | 64>(st, in, H, W, Cin, wpk, scale, shift, CoutP, relu, out, Ho, Wo, zero_page, in_c, out_c, sa, range); return; }
-    if (in_c && out_c && shift_sa6) launch_pp_t<1, 1, 0, 19>(st, in, H, W, Cin, wpk, scale, shift_sa6, CoutP, relu, out, Ho, Wo, zero_page, in_c, out_c, sa, range);
-    else if (in_c && out_c) launch_pp_t<1, 1, 0, 3>(st, in, H, W, Cin, wpk, scale, shift, CoutP, relu, out, Ho, Wo, zero_page, in_c, out_c, sa, range);
-    else if (in_c) launch_pp_t<1, 1, 0, 1>(st, in, H, W, Cin, wpk, scale, shift, CoutP, relu, out, Ho, Wo, zero_page, in_c, out_c, sa);
+    else if (h6 && rout == Rec::Resid8) PPC_GO(0, 3 | 16 | 32 | 256);
+    else if (h6 && s2d_out) PPC_GO(0, 3 | 16 | 32 | 128);
+    else if (h6 && rout == Rec::Unit8) PPC_GO(0, 3 | 16 | 32);
+    else if (rin == Rec::Unit8 && rout == Rec::Half6 && fp6_w) PPC_GO(0, 3 | 16 | 64);
+    else if (rin == Rec::Unit8 && rout == Rec::Half6) PPC_GO(0, 3 | 64);
+    else if (rin == Rec::Unit8 && rout == Rec::Unit8 && fp6_w) PPC_GO(0, 3 | 16);
+    else if (rin == Rec::Unit8 && rout == Rec::Unit8) PPC_GO(0, 3);
+    else if (rin == Rec::Unit8 && rout == Rec::None && !fp6_w) launch_pp_t<1, 1, 0, 1>(st, in, H, W, Cin, wpk, scale, shift, CoutP, relu, out, Ho, Wo, zero_page, in_c, out_c, sa);
+    else return false;
+#undef PPC_GO
+    return true;
 }
 
 // SFD2_PREC_F16X3 on pre-split planes (hi = fp16(x), lo' = fp16((x - hi) * 2^11), x3_split's arithmetic): in / in_lo = the input's

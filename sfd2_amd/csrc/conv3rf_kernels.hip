@@ -534,7 +534,7 @@ static void launch_rf_t(hipStream_t st, const half_t *in, int H, int W, int Cin,
 }
 
 // compensated instantiations (SFD2_PREC_F16C): the stride-2 layer with 128 output channels (conv2b).  wpk = the layer's wc
-// array (32-wide chunks, hi then corr), sbyte its scale byte.  false = no instantiation for this shape.
+// array (32-wide chunks, hi then corr), sbyte its scale byte; Unit8 records in, Unit8 or Half6 out.  false = no instantiation for these.
 // the geometries launch_conv3x3_rf_c takes (a caller that wants fp6 output records has to know beforehand)
 bool conv3x3_rf_c_serves(int ks, int stride, int CoutP, int Cin, int Ho, int Wo)
 {
@@ -543,9 +543,9 @@ bool conv3x3_rf_c_serves(int ks, int stride, int CoutP, int Cin, int Ho, int Wo)
 }
 bool launch_conv3x3_rf_c(hipStream_t st, const half_t *in, const half_t *in_c, int H, int W, int Cin, const half_t *wpk,
                          const float *scale, const float *shift, int CoutP, int stride, int relu, half_t *out, half_t *out_c,
-                         int Ho, int Wo, const half_t *zero_page, int sbyte, unsigned int *range, int fmt6)
+                         int Ho, int Wo, const half_t *zero_page, int sbyte, unsigned int *range, Rec rin, Rec rout)
 {
-    if (!in_c || !out_c || Cin % 64 != 0) return false;
+    if (rin != Rec::Unit8 || (rout != Rec::Unit8 && rout != Rec::Half6) || Cin % 64 != 0) return false;
     if ((long long)(Ho * stride + 2) * (Wo * stride + 2) * Cin * (long long)sizeof(half_t) >= (1ll << 31)) return false;
     const int sa = (sbyte & 255) * 0x01010101;
     if (CoutP == 128 && stride == 2) {
@@ -559,7 +559,7 @@ bool launch_conv3x3_rf_c(hipStream_t st, const half_t *in, const half_t *in_c, i
             }
         }
 #endif
-        if (fmt6 & 2) launch_rf_t<2, 128, 0, false, 3 | 64>(st, in, H, W, Cin, wpk, scale, shift, CoutP, relu, out, Ho, Wo, zero_page, in_c, out_c, sa, range);
+        if (rout == Rec::Half6) launch_rf_t<2, 128, 0, false, 3 | 64>(st, in, H, W, Cin, wpk, scale, shift, CoutP, relu, out, Ho, Wo, zero_page, in_c, out_c, sa, range);
         else launch_rf_t<2, 128, 0, false, 3>(st, in, H, W, Cin, wpk, scale, shift, CoutP, relu, out, Ho, Wo, zero_page, in_c, out_c, sa, range);
         return true;
     }

@@ -631,8 +631,9 @@ __global__ void nhwc_hc_to_nchw_f_kernel(const half_t *__restrict__ in, const ha
     const unsigned short u = reinterpret_cast<const unsigned short *>(in_c)[o];
     out[i] = (float)in[o] + sfd2_corr_lo((unsigned)u, 0);
 }
-void launch_nhwc_hc_to_nchw_f(hipStream_t st, const half_t *in, const half_t *in_c, int npix, int pitch, int c, float *out, int fmt6)
+void launch_nhwc_hc_to_nchw_f(hipStream_t st, const half_t *in, const half_t *in_c, int npix, int pitch, int c, float *out, Rec rec)
 {
     const size_t n = (size_t)npix * c;
-    hipLaunchKernelGGL(nhwc_hc_to_nchw_f_kernel, dim3((unsigned)((n + CNT - 1) / CNT)), dim3(CNT), 0, st, in, in_c, npix, pitch, c, out, fmt6);
+    hipLaunchKernelGGL(nhwc_hc_to_nchw_f_kernel, dim3((unsigned)((n + CNT - 1) / CNT)), dim3(CNT), 0, st, in, in_c, npix, pitch, c, out,
+                       rec == Rec::Resid8 ? 2 : (rec == Rec::Half6 ? 1 : 0));
 }

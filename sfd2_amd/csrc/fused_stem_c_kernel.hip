@@ -635,7 +635,7 @@ void fused_stem_c_kernel(const float *__restrict__ img, int H, int W, int normal
 // sbyte < 0: the X3 instantiation (SFD2_PREC_F16X3): w2's second halves are the filters' lo' fragments, out / out_c the hi / lo' planes
 void launch_fused_stem_c(hipStream_t st, const float *img, int H, int W, int normalise, const half_t *w1, const float *sc1,
                          const float *sh1, const void *w2, const float *sc2, const float *sh2, half_t *out, half_t *out_c,
-                         int H2, int W2, int sbyte, unsigned int *range, int fmt6 /* bit 1: fp6 records inside and out; w2 = the fp6 fragment array */)
+                         int H2, int W2, int sbyte, unsigned int *range, Rec rout /* Half6: fp6 records inside and out; w2 = the fp6 fragment array */)
 {
     static bool attr_done = false;
     static int slots = 256;
@@ -655,7 +655,7 @@ void launch_fused_stem_c(hipStream_t st, const float *img, int H, int W, int nor
     if (sbyte < 0)
         hipLaunchKernelGGL(fused_stem_c_kernel<true>, dim3(grid), dim3(SC_NT), SC_LDS, st, img, H, W, normalise, w1, sc1, sh1,
                            reinterpret_cast<const unsigned char *>(w2), sc2, sh2, out, out_c, H2, W2, tiles_x, n_tiles, 0, nullptr);
-    else if (fmt6 & 2)
+    else if (rout == Rec::Half6)
         hipLaunchKernelGGL((fused_stem_c_kernel<false, true>), dim3(grid), dim3(SC_NT), SC_LDS, st, img, H, W, normalise, w1, sc1, sh1,
                            reinterpret_cast<const unsigned char *>(w2), sc2, sh2, out, out_c, H2, W2, tiles_x, n_tiles,
                            (sbyte & 255) * 0x01010101, range);

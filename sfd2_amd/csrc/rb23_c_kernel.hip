@@ -481,8 +481,8 @@ void rb23_c_kernel(const half_t *__restrict__ t1, int H, int W,
 void launch_rb23_c(hipStream_t st, const half_t *t1, int H, int W, const half_t *w2h, const half_t *w2l, const float *sc2,
                    const float *sh2, const half_t *w3h, const half_t *w3l, const float *sc3, const float *sh3,
                    const half_t *res, const half_t *res_c, half_t *out, half_t *out_c, const half_t *zero_page,
-                   unsigned int *range_t2, unsigned int *range_out, int r1 /* bit 0: res_c is residual-only, bit 1: out_c is written residual-only */,
-                   const half_t *w3l8, int sbyte3 /* r1 & 1: conv3's filter residuals as e4m3 ([8][4][64][32 B]) and its corr scale byte */)
+                   unsigned int *range_t2, unsigned int *range_out, Rec rres, Rec rout /* Resid8: res_c is / out_c is written residual-only */,
+                   const half_t *w3l8, int sbyte3 /* rres = Resid8: conv3's filter residuals as e4m3 ([8][4][64][32 B]) and its corr scale byte */)
 {
     constexpr size_t lds = 0;                               // (static LDS: 150 KB)
     static bool attr_done = false;
@@ -498,11 +498,12 @@ void launch_rb23_c(hipStream_t st, const half_t *t1, int H, int W, const half_t 
     if (n_tiles == 0) return;
     const int grid = n_tiles < sfd2_slots(slots) ? n_tiles : sfd2_slots(slots);
     const int sa3 = (sbyte3 & 255) * 0x01010101;
-    if ((r1 & 1) && !w3l8) abort();
+    if (rres == Rec::Resid8 && !w3l8) abort();
 #define R23_GO(a_, b_) hipLaunchKernelGGL((rb23_c_kernel<a_, b_>), dim3(grid), dim3(R23_NT), lds, st, t1, H, W, w2h, w2l, sc2, sh2, w3h, (a_) ? w3l8 : w3l, sc3, sh3, res, res_c, \
                                           out, out_c, tiles_x, n_tiles, range_t2, range_out, sa3)
     // (units in, residual bytes out is not instantiated: it spills 261 registers; the caller converts conv3b's output as well)
-    if ((r1 & 3) == 3) R23_GO(true, true); else if (r1 & 1) R23_GO(true, false); else if (r1 & 2) abort(); else R23_GO(false, false);
+    if (rres == Rec::Resid8) { if (rout == Rec::Resid8) R23_GO(true, true); else R23_GO(true, false); }
+    else if (rout == Rec::Resid8) abort(); else R23_GO(false, false);
 #undef R23_GO
     (void)zero_page;
 #ifdef SFD2_RB23_TRACE

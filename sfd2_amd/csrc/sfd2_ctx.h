@@ -102,7 +102,7 @@ struct ConvW {                 // one folded + packed layer
 enum { AE_CONV1A, AE_CONV1B, AE_CONV2A, AE_CONV2B, AE_CONV3A, AE_TRUNK /* conv3b's and every ResBlock's output: one skip path */,
        AE_T1_0, AE_T1_1, AE_T1_2, AE_T2_0, AE_T2_1, AE_T2_2, AE_PA0, AE_DA0, AE_COUNT };
 
-struct ActInfo { const void *p; int f32; int planar; int c, pitch, h, w; const void *pc = nullptr; /* corr plane (f16c) */ int exp2 = 0; /* stored = value * 2^exp2 (activation exponents of the fp16 family) */ bool absent = false; /* stays on chip on the path taken */ bool fmt6 = false; /* pc holds fp6 half-records (option "fp6_acts") */ bool r1 = false; /* pc holds one residual byte per channel, c bytes per pixel (option "trunk_r1") */ };
+struct ActInfo { const void *p; int f32; int planar; int c, pitch, h, w; Rec rec = Rec::None; /* f16c: the format of the corr records (their plane follows the hi plane) */ int exp2 = 0; /* stored = value * 2^exp2 (activation exponents of the fp16 family) */ bool absent = false; /* stays on chip on the path taken */ };
 
 struct sfd2_ctx {
     int device = 0;
@@ -320,10 +320,10 @@ struct PassPlan {
     bool comp_rb = false;                    // SFD2_PREC_F16C: compensated ResBlocks (otherwise plain fp16 on the hi planes)
     int rb_inner = 0;                        // ... "rb_inner" in effect; rb23: 2 with ResBlock.conv2 + conv3 in rb23_c_kernel (t2 stays on chip)
     bool rb23 = false, generic_c = false, no_rf_c = false, fp6_filters = false;
-    bool s6 = false, b6 = false, a6 = false; // "fp6_acts": fp6 corr records of conv1b's, conv2b's, conv3a's output
-    bool d2 = false;                         // "s2d": conv2a's output space-to-depth, conv2b on conv2b_s2d_kernel
-    bool p3b = false, p3a = false;           // "c3b_plain": conv3b over conv3a's hi plane; conv3a then writes no corr plane
-    bool tr1 = false;                        // "trunk_r1": the ResBlocks' inputs with one residual byte per channel
+    // SFD2_PREC_F16C: the corr records of every stored tensor from conv1b's output to convPa.0's / convDa.0's (Rec::None in other modes)
+    struct { Rec a1b, a2a, a2b, a3a, a3b, t1[3], t2[3], ro[3], pa0, da0; } rec = {};
+    Rec a3a_in = Rec::None;                  // a3a as conv3b reads it: None with "c3b_plain", also where conv3a still stores Half6 (SFD2_C3A_KEEP_CORR)
+    bool a2a_s2d = false;                    // "s2d": conv2a's output stored space-to-depth, conv2b on conv2b_s2d_kernel
     bool ch = false, chp = false;            // compensated head branches ("comp_heads"); compensated detector branch ("comp_heads" or "comp_det")
     bool branches = false, sta_early = false, sta_side = false;   // detector branch on the side stream; ConvSta before the heads / on the side stream
     bool skip_head = false, skip_pb = false, skip_db = false, skip_da3 = false;   // layers left to sfd2_extract's post-processing

@@ -372,25 +372,32 @@ void launch_convsta(hipStream_t st, const half_t *in, int npix, const float *w /
 // ---- compensated fp16 (convc_kernels.hip; SFD2_PREC_F16C): hi plane + corr plane per tensor, see the top of this file
 //   wpk: [2 * Cin / 32][ks * ks][Cout_pad][32] units (fp16 chunks, then corr chunks; the first half only when in_c is null)
 //   in_c / res_c / out_c: corr planes (null = that tensor is plain fp16);  sbyte: the layer's E8M0 scale byte
+enum class Rec {   // the format of a stored tensor's corr records: planned per tensor by the host, taken by the launchers below
+    None,      // plain fp16: the hi plane alone
+    Unit8,     // per channel the 2-byte unit (e4m3 of (x - hi) * 2^9, e4m3 of x * 2^-2): 2 bytes per channel
+    Half6,     // block-scaled fp6 half-records (option "fp6_acts", sfd2_epi16_fp6): per pixel and 16 channels 32 six-bit codes + an E8M0 scale byte in 32 bytes
+    Resid8,    // the residual byte only (option "trunk_r1", sfd2_epi4_r1): e4m3 of (x - hi) * 2^9, 1 byte per channel
+};
 void launch_convc_igemm(hipStream_t st, const half_t *in, const half_t *in_c, int H, int W, int Cin, const half_t *wpk,
                         const float *scale, const float *shift, int Cout_pad, int ks, int stride, int relu,
                         const half_t *res, const half_t *res_c, half_t *out, half_t *out_c, int Ho, int Wo, int sbyte, unsigned int *range = nullptr);
-// the tuned kernels' compensated instantiations (same wpk / planes / sbyte as launch_convc_igemm; null plane = plain fp16)
-void launch_conv3x3_pp_c(hipStream_t st, const half_t *in, const half_t *in_c, int H, int W, int Cin, const half_t *wpk,
+// the tuned kernels' compensated instantiations (same wpk / planes / sbyte as launch_convc_igemm; null plane = plain fp16, Rec::None); false = no
+// instantiation for the formats.  fp6_w: wpk's corr rows are fp6 strings, shift = [shift | scale bytes]; s2d_out: stored for conv2b_s2d_kernel
+bool launch_conv3x3_pp_c(hipStream_t st, const half_t *in, const half_t *in_c, int H, int W, int Cin, const half_t *wpk,
                          const float *scale, const float *shift, int CoutP, int relu, half_t *out, half_t *out_c,
-                         int Ho, int Wo, const half_t *zero_page, int sbyte, const float *shift_sa6 = nullptr /* non-null: wpk's corr rows are fp6; [shift | scale bytes] */,
-                         unsigned int *range = nullptr /* the output tensor's range-status slot (SFD2_RANGE_SUB words), here and below */,
-                         int fmt6 = 0 /* bit 0: in_c holds fp6 half-records (then wpk / shift_sa6 are the fp6 x fp6 arrays), bit 1: out_c is written as fp6 half-records, bit 2 (with bit 0, without bit 1): the output is stored space-to-depth for conv2b_s2d_kernel, bit 3 (with bit 0, without bits 1 / 2): out_c holds the residual byte only (CoutP bytes per pixel) */);
+                         int Ho, int Wo, const half_t *zero_page, int sbyte,
+                         unsigned int *range /* the output tensor's range-status slot (SFD2_RANGE_SUB words), here and below */,
+                         Rec rin, Rec rout, bool s2d_out, bool fp6_w);
 bool conv3x3_rf_c_serves(int ks, int stride, int CoutP, int Cin, int Ho, int Wo);
-// conv2b_s2d_kernel.hip: conv2b over conv2a's output stored space-to-depth (launch_conv3x3_pp_c with bit 2 of fmt6 writes that layout)
+// conv2b_s2d_kernel.hip: conv2b over conv2a's output stored space-to-depth (launch_conv3x3_pp_c with s2d_out writes that layout)
 bool conv2b_s2d_serves(int H2, int W2, int Cin, int CoutP);
 void launch_conv2b_s2d(hipStream_t st, const half_t *in_s2d, const half_t *in_c_s2d, int H4, int W4, const half_t *wpk, const float *scale,
-                       const float *shift, int relu, half_t *out, half_t *out_c, const half_t *zero_page, int sbyte, unsigned int *range, int fmt6 /* bit 1: out_c as fp6 half-records */);
+                       const float *shift, int relu, half_t *out, half_t *out_c, const half_t *zero_page, int sbyte, unsigned int *range, Rec rout /* Unit8 or Half6 */);
 void launch_conv2b_s2d_x3(hipStream_t st, const half_t *in_hi_s2d, const half_t *in_lo_s2d, int H4, int W4, const half_t *wpk /* [4 hi | 4 lo' chunks][9][128][32] */,
                           const float *scale, const float *shift, int relu, half_t *out_hi, half_t *out_lo, const half_t *zero_page);
 bool launch_conv3x3_rf_c(hipStream_t st, const half_t *in, const half_t *in_c, int H, int W, int Cin, const half_t *wpk,
                          const float *scale, const float *shift, int CoutP, int stride, int relu, half_t *out, half_t *out_c,
-                         int Ho, int Wo, const half_t *zero_page, int sbyte, unsigned int *range = nullptr, int fmt6 = 0 /* bit 1: out_c as fp6 half-records */);
+                         int Ho, int Wo, const half_t *zero_page, int sbyte, unsigned int *range, Rec rin /* Unit8 */, Rec rout /* Unit8 or Half6 */);
 bool launch_conv_igemm2_c(hipStream_t st, const half_t *in, const half_t *in_c, int H, int W, int Cin, const half_t *wpk,
                           const float *scale, const float *shift, int CoutP, int ks, int stride, int relu,
                           const half_t *res, const half_t *res_c, half_t *out, half_t *out_c, int Ho, int Wo,
@@ -399,11 +406,11 @@ bool launch_conv_igemm2_c(hipStream_t st, const half_t *in, const half_t *in_c, 
 void launch_fused_stem_c(hipStream_t st, const float *img, int H, int W, int normalise, const half_t *w1, const float *sc1,
                          const float *sh1, const void *w2, const float *sc2, const float *sh2, half_t *out, half_t *out_c,
                          int H2, int W2, int sbyte, unsigned int *range_base = nullptr /* the context's range-status words (conv1a's and conv1b's slots) */,
-                         int fmt6 = 0 /* bit 1: out_c as fp6 half-records */);
+                         Rec rout = Rec::Unit8 /* or Half6: w2 = the fp6 fragment array */);
 void launch_conv1x1_c256_c(hipStream_t st, const half_t *in, const half_t *in_c, int npix, const half_t *w_frag,
                            const half_t *wc_frag, const float *scale, const float *shift, int relu, const half_t *res,
-                           const half_t *res_c, half_t *out, half_t *out_c, const half_t *zero_page, int sbyte, unsigned int *range = nullptr,
-                           int in_r1 = 0 /* in_c = residual bytes only (256 B per pixel): option "trunk_r1" */);
+                           const half_t *res_c, half_t *out, half_t *out_c, const half_t *zero_page, int sbyte, unsigned int *range,
+                           Rec rin /* None, Unit8 or Resid8 */, Rec rout /* None or Unit8 */);
 // sparse_da3_kernel.hip: convDa.3 on the four bilinear corner pixels of every selected key point only -> out [n_max][4][256] fp16
 void launch_sparse_da3(hipStream_t st, const half_t *fmap, int hc, int wc, int nh, int nw, const half_t *wpk, const half_t *wsl, int CoutP,
                        const float *scale, const float *shift, int relu, const float *kpts, const unsigned int *count, int n_max,
@@ -416,9 +423,8 @@ void launch_sparse_da3_x3(hipStream_t st, const half_t *fmap_hi, const half_t *f
 void launch_rb23_c(hipStream_t st, const half_t *t1, int H, int W, const half_t *w2h, const half_t *w2l, const float *sc2,
                    const float *sh2, const half_t *w3h, const half_t *w3l, const float *sc3, const float *sh3,
                    const half_t *res, const half_t *res_c, half_t *out, half_t *out_c, const half_t *zero_page,
-                   unsigned int *range_t2 = nullptr, unsigned int *range_out = nullptr,
-                   int r1 = 0 /* residual-only corr bytes (256 B per pixel): bit 0 = res_c, bit 1 = out_c */,
-                   const half_t *w3l8 = nullptr, int sbyte3 = 0 /* with r1 & 1: conv3's filter residuals as e4m3 in the kernel's K order, its corr scale byte */);
+                   unsigned int *range_t2, unsigned int *range_out, Rec rres, Rec rout /* Unit8 or Resid8 each */,
+                   const half_t *w3l8, int sbyte3 /* with rres = Resid8: conv3's filter residuals as e4m3 in the kernel's K order, its corr scale byte */);
 // conv1x1_kernels.hip: SFD2_PREC_F16X3 streaming 1x1 (256 -> 256): planes in, fp32 (+ planes) out, fp32 residual
 void launch_conv1x1_c256_x3(hipStream_t st, const half_t *in, const half_t *in_lo, int npix, const half_t *w, const half_t *wl,
                             const float *scale, const float *shift, int relu, const void *res, const half_t *res_lo, float *out, half_t *out_hi,
@@ -428,7 +434,7 @@ void launch_conv1a_c(hipStream_t st, const float *img, int H, int W, int normali
 void launch_gconv_c(hipStream_t st, const half_t *in, const half_t *in_c, int H, int W, const half_t *wpk /*fp16 fragments*/,
                     const void *wck /*corr fragments*/, const float *scale, const float *shift, half_t *out, half_t *out_c, int sbyte,
                     int row0, int row1 /*output rows [row0, row1)*/, unsigned int *range = nullptr);
-void launch_nhwc_hc_to_nchw_f(hipStream_t st, const half_t *in, const half_t *in_c, int npix, int pitch, int c, float *out, int fmt6 = 0 /* in_c: fp6 half-records */);
+void launch_nhwc_hc_to_nchw_f(hipStream_t st, const half_t *in, const half_t *in_c, int npix, int pitch, int c, float *out, Rec rec /* in_c's format */);
 
 // ---- strict fp32 mode (conv_f32_kernels.hip): fp32 NHWC activations, f32-input MFMA
 //   wpk [Cin/32][ks*ks][Cout_pad][32] fp32
