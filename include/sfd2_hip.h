@@ -85,7 +85,7 @@ typedef struct {
     int64_t n_candidates; /* N0 after NMS + threshold + border of the last extract          */
 } sfd2_timings;
 
-int sfd2_version(void);   /* 100 = rounds 1-4; 105 adds sfd2_extract_record_async, sfd2_desc_pack and host outputs with SFD2_FLAG_ASYNC; 106 adds sfd2_get_margin_status; 107 adds sfd2_get_relax_status (option "c3b_plain"); 108 adds sfd2_get_option, sfd2_device_pci_bus_id, SFD2_FLAG_DESC_STORE64 */
+int sfd2_version(void);   /* 100 = rounds 1-4; 105 adds sfd2_extract_record_async, sfd2_desc_pack and host outputs with SFD2_FLAG_ASYNC; 106 adds sfd2_get_margin_status; 107 adds sfd2_get_relax_status (option "c3b_plain"); 108 adds sfd2_get_option, sfd2_device_pci_bus_id, SFD2_FLAG_DESC_STORE64; 109 adds the baseline JPEG decoder (sfd2_jpeg_*) */
 const char *sfd2_last_error(void);
 
 int sfd2_ctx_create(int device, sfd2_ctx **out);
@@ -454,6 +454,69 @@ int sfd2_set_profiling(sfd2_ctx *ctx, int max_steps /* 0 = off */);
  * event pair costs ~2-4 us of stream time, so a timed run brackets the kernel it reports on only. */
 int sfd2_set_profile_filter(sfd2_ctx *ctx, const char *substr);
 int sfd2_get_layer_timings(sfd2_ctx *ctx, sfd2_layer_timing *out, int cap, int *n);
+
+/* ------------------------------------------------------------------------------------------------ baseline JPEG decoder
+ * The decoder in front of extract_localization.py:162-165 (cv2.imread / PIL), on the device.  The host parses the headers
+ * (sfd2_jpeg_parse) and removes the byte stuffing in place (sfd2_jpeg_prepare); the device does the Huffman decoding
+ * (self-synchronising, one lane per 256-bit subsequence), dequantisation, the accurate integer IDCT, "fancy" chroma
+ * upsampling and YCbCr -> RGB with libjpeg's fixed-point arithmetic, so the pixels equal what PIL / libjpeg(-turbo) decode
+ * with its defaults (JDCT_ISLOW, do_fancy_upsampling).  Output: uint8 [H][W][4] RGBX on the device, what sfd2_extract /
+ * sfd2_preprocess take with SFD2_FLAG_IMG_U8_HWC | SFD2_FLAG_IMG_U8_X and img_on_device = 1.
+ *
+ * Supported (anything else: supported = 0 and a reason, the caller decodes that file on the CPU):
+ *   SOF0 / SOF1, 8-bit, Huffman; one interleaved scan; 1 component (grey, replicated to RGB) or 3 components YCbCr with
+ *   luma sampling 1x1, 2x1 or 2x2 and chroma 1x1; any DQT / DHT; DRI with RSTn markers. */
+#define SFD2_JPEG_OK 0
+#define SFD2_JPEG_NOT_JPEG 1      /* no SOI, or not a JPEG at all (PNG, ...)                         */
+#define SFD2_JPEG_TRUNCATED 2     /* a segment, the scan or the EOI lies beyond the end of the data   */
+#define SFD2_JPEG_PROGRESSIVE 3   /* SOF2 / SOF6                                                      */
+#define SFD2_JPEG_ARITHMETIC 4    /* SOF9 .. SOF15 (except the hierarchical lossless ones), DAC       */
+#define SFD2_JPEG_PRECISION 5     /* sample precision other than 8 bits                              */
+#define SFD2_JPEG_COLOUR 6        /* 2 or 4 components, Adobe transform 0, 'R','G','B' component ids  */
+#define SFD2_JPEG_SAMPLING 7      /* a sampling layout other than the ones above                     */
+#define SFD2_JPEG_MULTI_SCAN 8    /* more than one scan, or a scan that does not hold every component */
+#define SFD2_JPEG_PROCESS 9       /* lossless or hierarchical SOF, DNL                                */
+#define SFD2_JPEG_MALFORMED 10    /* inconsistent segments, tables, RSTn sequence or image size        */
+typedef struct {
+    int32_t width, height;
+    int32_t n_components;
+    int32_t h_samp[3], v_samp[3];
+    int32_t restart_interval;     /* MCUs per restart interval (DRI), 0 = none                        */
+    int32_t supported;            /* 1: sfd2_jpeg_decode can take this file                           */
+    int32_t reason;               /* SFD2_JPEG_* (0 when supported)                                   */
+    int32_t mcus_x, mcus_y;       /* MCU grid of the scan                                             */
+    int32_t n_intervals;          /* restart intervals of the scan (RSTn markers + 1)                 */
+    int32_t n_blocks;             /* 8x8 blocks the scan codes                                        */
+    int64_t file_bytes;           /* n of the parse                                                   */
+    int64_t scan_begin, scan_end; /* entropy-coded data: [scan_begin, scan_end), scan_end = offset of the EOI */
+    int64_t prepared_cap;         /* bytes the buffer handed to sfd2_jpeg_prepare must hold (>= file_bytes) */
+    /* filled by sfd2_jpeg_prepare */
+    int64_t prepared_bytes;       /* bytes of the prepared buffer sfd2_jpeg_decode uploads             */
+    int32_t n_lanes;              /* Huffman decoding lanes                                           */
+    int32_t prepared;             /* 1 once the buffer holds the prepared form                        */
+} sfd2_jpeg_info;
+
+/* Reads the headers and walks the entropy-coded data (RSTn count and order, the EOI behind the scan).  Host only: no context,
+ * no device.  Never reads outside [data, data + n).  Returns 0 with info->supported = 1, or -1 with info->reason set (and
+ * width / height / components when the frame header was read) and the reason in sfd2_last_error(). */
+int sfd2_jpeg_parse(const uint8_t *data, int64_t n, sfd2_jpeg_info *info);
+
+/* In place: buf holds the file in [0, info->file_bytes) and has room for info->prepared_cap bytes.  Parses again, moves the
+ * entropy-coded data to the front with the byte stuffing (FF 00) and the RSTn markers removed, each restart interval starting
+ * on a byte, and writes behind it the Huffman lookup tables, quantisation tables and the lane table.  The headers are
+ * overwritten.  Returns 0 (info->prepared = 1, info->prepared_bytes set) or -1. */
+int sfd2_jpeg_prepare(uint8_t *buf, int64_t cap, sfd2_jpeg_info *info);
+
+/* Decodes a prepared buffer (data: host, n >= info->prepared_bytes) into out_rgbx_dev (device, uint8 [H][W][4], out_cap bytes).
+ * *status (host, or device when status_on_device) receives 0, or a non-zero anomaly mask (bit 0 invalid Huffman code or a run
+ * past coefficient 63, bit 1 block count / restart interval mismatch, bit 2 an interval that does not end at its marker,
+ * bit 3 the lanes did not synchronise) -- the pixels are then not valid and the caller decodes the file on the CPU.
+ * SFD2_FLAG_ASYNC: data may be pinned host memory; it goes up through the context's copy stream, the decode is queued on
+ * sfd2_get_stream() and *status is written in stream order (a host status must then be pinned too); data and status must stay
+ * valid until the stream has passed.  Without the flag the call synchronises and returns -1 on a non-zero status.
+ * The decoder's scratch belongs to the context, grows on demand and is separate from the network's workspace. */
+int sfd2_jpeg_decode(sfd2_ctx *ctx, const uint8_t *data, int64_t n, const sfd2_jpeg_info *info, int flags,
+                     uint8_t *out_rgbx_dev, int64_t out_cap, uint32_t *status, int status_on_device);
 
 #ifdef __cplusplus
 }

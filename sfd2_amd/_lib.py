@@ -74,6 +74,16 @@ class RangeStatus(ctypes.Structure):
                 ("saturated", ctypes.c_uint32), ("low", ctypes.c_uint32), ("fallbacks", ctypes.c_int32)]
 
 
+class JpegInfo(ctypes.Structure):
+    """sfd2_jpeg_info (include/sfd2_hip.h)."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("n_components", ctypes.c_int32),
+                ("h_samp", ctypes.c_int32 * 3), ("v_samp", ctypes.c_int32 * 3), ("restart_interval", ctypes.c_int32),
+                ("supported", ctypes.c_int32), ("reason", ctypes.c_int32), ("mcus_x", ctypes.c_int32), ("mcus_y", ctypes.c_int32),
+                ("n_intervals", ctypes.c_int32), ("n_blocks", ctypes.c_int32), ("file_bytes", ctypes.c_int64),
+                ("scan_begin", ctypes.c_int64), ("scan_end", ctypes.c_int64), ("prepared_cap", ctypes.c_int64),
+                ("prepared_bytes", ctypes.c_int64), ("n_lanes", ctypes.c_int32), ("prepared", ctypes.c_int32)]
+
+
 # every symbol include/sfd2_hip.h declares (tests/test_abi.py checks the two lists agree)
 EXPORTS = [
     "sfd2_version", "sfd2_last_error", "sfd2_ctx_create", "sfd2_ctx_destroy", "sfd2_get_stream",
@@ -84,6 +94,7 @@ EXPORTS = [
     "sfd2_set_profile_filter", "sfd2_extract_multiscale", "sfd2_set_option", "sfd2_extract_match", "sfd2_preprocess", "sfd2_extract_spp_levels", "sfd2_match_segments",
     "sfd2_get_range_status", "sfd2_range_tensor_name", "sfd2_calibrate_range", "sfd2_get_act_exponents", "sfd2_set_act_exponents",
     "sfd2_extract_record_async", "sfd2_desc_pack", "sfd2_get_margin_status", "sfd2_get_relax_status", "sfd2_get_option", "sfd2_device_pci_bus_id",
+    "sfd2_jpeg_parse", "sfd2_jpeg_prepare", "sfd2_jpeg_decode",
 ]
 
 _lib = None
@@ -164,10 +175,13 @@ def load():
     lib.sfd2_set_act_exponents.argtypes = [vp, vp, ci]
     lib.sfd2_extract_record_async.argtypes = [vp, vp, ci]
     lib.sfd2_desc_pack.argtypes = [vp, ctypes.POINTER(DescSet), ci, vp, ci]
+    lib.sfd2_jpeg_parse.argtypes = [vp, i64, ctypes.POINTER(JpegInfo)]
+    lib.sfd2_jpeg_prepare.argtypes = [vp, i64, ctypes.POINTER(JpegInfo)]
+    lib.sfd2_jpeg_decode.argtypes = [vp, vp, i64, ctypes.POINTER(JpegInfo), ci, vp, i64, vp, ci]
     for name in EXPORTS:
         getattr(lib, name)  # raises AttributeError if the .so lacks a declared symbol
-    if lib.sfd2_version() < 108:
-        raise RuntimeError(f"{LIB_PATH} is version {lib.sfd2_version()}, this binding needs >= 108 (rebuild: __graft_entry__.build())")
+    if lib.sfd2_version() < 109:
+        raise RuntimeError(f"{LIB_PATH} is version {lib.sfd2_version()}, this binding needs >= 109 (rebuild: __graft_entry__.build())")
     _lib = lib
     return lib
 

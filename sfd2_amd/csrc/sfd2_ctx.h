@@ -104,6 +104,32 @@ enum { AE_CONV1A, AE_CONV1B, AE_CONV2A, AE_CONV2B, AE_CONV3A, AE_TRUNK /* conv3b
 
 struct ActInfo { const void *p; int f32; int planar; int c, pitch, h, w; Rec rec = Rec::None; /* f16c: the format of the corr records (their plane follows the hi plane) */ int exp2 = 0; /* stored = value * 2^exp2 (activation exponents of the fp16 family) */ bool absent = false; /* stays on chip on the path taken */ };
 
+// Scratch of the JPEG decoder (api_jpeg.hip).  Its own allocations, not DevBufs: growing them must not bump g_alloc_gen, which would
+// drop the captured graphs of the network (api_graph.hip) that never read these buffers.
+struct JpegBuf {
+    void *p = nullptr;
+    size_t cap = 0;
+    JpegBuf() = default;
+    JpegBuf(const JpegBuf &) = delete;
+    JpegBuf &operator=(const JpegBuf &) = delete;
+    ~JpegBuf() { if (p) (void)hipFree(p); }
+    template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
+};
+struct JpegScratch {
+    JpegBuf in[2];                     // prepared buffers, uploaded through the copy stream (two, so the next upload overlaps this decode)
+    hipEvent_t ev_copied[2] = {}, ev_free[2] = {};
+    int slot = 0;
+    JpegBuf lanes, pre, coef, planes;
+    JpegBuf words;                     // sync flags (SFD2_JPEG_SYNC_LAUNCHES) and the status word
+    ~JpegScratch()
+    {
+        for (int i = 0; i < 2; ++i) {
+            if (ev_copied[i]) (void)hipEventDestroy(ev_copied[i]);
+            if (ev_free[i]) (void)hipEventDestroy(ev_free[i]);
+        }
+    }
+};
+
 struct sfd2_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -231,6 +257,7 @@ struct sfd2_ctx {
     // scale pyramid staging (sfd2_extract_multiscale)
     DevBuf arena;   // aliased activation slots of the throughput path (run_network)
     DevBuf img_u8_packed;              // SFD2_FLAG_IMG_U8_X: the image as three bytes per pixel (unpack_rgbx_kernel)
+    JpegScratch jpeg;                  // sfd2_jpeg_decode
     DevBuf img_scaled, ms_kp, ms_sc, ms_de, ms_keys, ms_sorted, ms_cnt;
     unsigned int ms_cand_seen[8] = {};
     int ms_cand_cap[8] = {};

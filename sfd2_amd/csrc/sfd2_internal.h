@@ -653,3 +653,52 @@ void launch_ms_append(hipStream_t st, const float *kpts, const float *scores, co
 void launch_ms_merge(hipStream_t st, int n_levels, const int *offsets, const unsigned int *level_count, const float *kp_stage,
                      const float *sc_stage, const float *de_stage, int cap_total, int top_k, unsigned long long *keys,
                      unsigned long long *sorted, unsigned int *ms_counters, int n_max, float *kp_out, float *sc_out, float *de_out);
+
+// ------------------------------------------------------------------ baseline JPEG decoder (jpeg_parse.hip, jpeg_kernels.hip, api_jpeg.hip)
+// The prepared buffer sfd2_jpeg_prepare leaves and sfd2_jpeg_decode uploads:
+//   [0, tab_off)            entropy-coded data without stuffing or RSTn, every restart interval starting on a byte, zero padded
+//   JpegTables              Huffman lookup tables and quantisation tables of the scan's components
+//   uint32 lane_start[L+1]  first bit of every lane (lane_start[L] = bits of the data); lanes never cross a restart interval
+//   uint32 lane_int[L]      restart interval of every lane
+//   uint32 int_first[I+1]   first lane of every interval (int_first[I] = L)
+// tab_off = prepared_bytes - jpeg_tail_bytes(L, I).
+#define SFD2_JPEG_LANE_BITS 256       // subsequence a decoding lane starts at (it decodes on to the first block boundary behind it)
+#define SFD2_JPEG_SYNC_LAUNCHES 12    // fixed number of synchronisation launches (each returns at once when the previous one changed nothing)
+#define SFD2_JPEG_BAD_CODE 1u         // status bits (include/sfd2_hip.h sfd2_jpeg_decode)
+#define SFD2_JPEG_BAD_COUNT 2u
+#define SFD2_JPEG_BAD_END 4u
+#define SFD2_JPEG_NO_SYNC 8u
+struct JpegHuff {                     // one Huffman table: 9-bit first-level lookup plus the canonical decoder for longer codes
+    uint16_t lut[512];                // (length << 8) | symbol for codes of <= 9 bits, indexed by the next 9 bits; 0 = longer code
+    int32_t maxcode[18];              // largest code of each length, -1 if none
+    int32_t valoff[18];               // vals index of a code of that length = valoff[len] + code
+    uint8_t vals[256];
+};
+struct JpegTables {
+    JpegHuff huff[3][2];              // [component][DC, AC]
+    uint16_t q[3][64];                // quantisation table of each component, natural order
+};
+static inline int64_t jpeg_tail_bytes(int64_t lanes, int64_t intervals)
+{
+    return (int64_t)sizeof(JpegTables) + 4 * (lanes + 1) + 4 * lanes + 4 * (intervals + 1);
+}
+struct JpegGeom {                     // kernel arguments: the frame's geometry
+    int ncomp, bpm, mcus_x, total_blocks, ri_blocks /* blocks per restart interval, 0 = one interval */, nlanes, nint;
+    uint32_t ecs_words;               // 32-bit words of entropy-coded data (the reader sees zeros beyond)
+    int unit_comp[10], unit_dx[10], unit_dy[10];     // block u of an MCU: its component and offset in the component's MCU cell
+    int hs[3], vs[3];                 // sampling factors (blocks per MCU cell)
+    int bw[3], bh[3];                 // component block grids
+    int blk_base[3];                  // first block of each component in the coefficient array
+    int64_t plane_off[3];             // byte offset of each component's sample plane (pitch bw * 8)
+    int W, H, mode;                   // mode: 0 grey, 1 4:4:4, 2 4:2:2 (h2v1), 3 4:2:0 (h2v2)
+    int cw, ch;                       // chroma plane size in samples (ceil(W / h0), ceil(H / v0))
+};
+struct JpegLane {                     // one lane's decode: where it started and stopped (bit, block of the MCU), blocks and DC sums
+    uint32_t spos, epos;
+    int32_t su, eu, bad, cnt;
+    int32_t dc[3];
+    int32_t pad;
+};
+void launch_jpeg_decode(hipStream_t st, const unsigned char *in, int64_t tab_off, const JpegGeom &g, JpegLane *lanes, int *lane_pre,
+                        int *wg_pre, unsigned int *sync_flags, short *coef, unsigned char *planes, unsigned char *out_rgbx,
+                        unsigned int *status);

@@ -133,11 +133,20 @@ def _read_rgb_u8_cv2(cv2, path, reserve, rgbx):
     return out
 
 
-def _read_rgb_u8(path, reserve=None, rgbx=False):
+def _read_rgb_u8(path, reserve=None, rgbx=False, decoder=None):
     """The decoder: uint8 [H,W,3] RGB (the reference: cv2.imread(..., IMREAD_COLOR)[:, :, ::-1], :162-165).
     reserve(nbytes) -> writable uint8 buffer: the pixels are put there (the pipelined driver's pinned buffers).
-    rgbx (with reserve): [H,W,4] RGBX when PIL allows it (_paste_rgbx), else [H,W,3]."""
-    cv2 = _cv2()
+    rgbx (with reserve): [H,W,4] RGBX when PIL allows it (_paste_rgbx), else [H,W,3].
+    decoder: "pil" / "cv2" force one (an ImageDataset's decoder= keyword); anything else: _cv2()'s choice."""
+    if decoder == "pil":
+        cv2 = None
+    elif decoder == "cv2":
+        try:
+            import cv2
+        except Exception as e:
+            raise RuntimeError("decoder='cv2' but cv2 is not importable") from e
+    else:
+        cv2 = _cv2()
     if cv2 is not None:
         return _read_rgb_u8_cv2(cv2, path, reserve, rgbx)
     try:
@@ -164,6 +173,39 @@ def _read_rgb_u8(path, reserve=None, rgbx=False):
         raise ValueError(f'Cannot read image {str(path)}.') from e   # extract_localization.py:166-167
 
 
+def decoder_name(decoder=None):
+    """decoder keyword, else SFD2_DECODER, else "auto"; one of "auto", "pil", "cv2", "hip"."""
+    d = (decoder if decoder is not None else os.environ.get("SFD2_DECODER", "auto")).lower()
+    if d not in ("auto", "pil", "cv2", "hip"):
+        raise ValueError(f"decoder {d!r}: expected 'auto', 'pil', 'cv2' or 'hip'")
+    return d
+
+
+def _host_buffer(nbytes):
+    return np.empty(int(nbytes), dtype=np.uint8)
+
+
+def cpu_decode(path):
+    """The CPU decoder "auto" uses (cv2 when importable, else PIL): a file the device decoder refused, decoded the way the driver would
+    have decoded it without decoder="hip"."""
+    return _read_rgb_u8(path, None, False, None)
+
+
+def device_image(model, data):
+    """One 'jpeg' item (ImageDataset with decoder="hip") -> torch.uint8 cuda [H, W, 4] RGBX, decoded synchronously on the model's device;
+    None when the device finds the entropy-coded data invalid (the caller decodes the file on the CPU)."""
+    import ctypes
+    import torch
+    from . import _lib
+    ctx = model.context
+    buf, info = data['jpeg']
+    out = torch.empty((int(info.height), int(info.width), 4), dtype=torch.uint8, device=torch.device("cuda", ctx.device))
+    st = np.zeros(1, dtype=np.uint32)
+    rc = ctx.lib.sfd2_jpeg_decode(ctx.h, buf.ctypes.data, int(info.prepared_bytes), ctypes.byref(info), 0, out.data_ptr(), int(out.numel()),
+                                  st.ctypes.data, 0)
+    return out if rc == 0 else None
+
+
 class ImageDataset:
     """extract_localization.py:122-202 without torch's Dataset base: same default_conf, the same file discovery
     (globs under root, or an image list), __getitem__ -> {'name', 'image', 'original_size'}.  'image' is the DECODED
@@ -176,8 +218,9 @@ class ImageDataset:
         'resize_force': False,
     }
 
-    def __init__(self, root, conf, image_list=None, mask_root=None):
+    def __init__(self, root, conf, image_list=None, mask_root=None, decoder=None):
         from pathlib import Path
+        self.decoder = decoder_name(decoder)
         self.conf = {**self.default_conf, **conf}
         if self.conf['grayscale']:
             raise NotImplementedError("grayscale input is not used by the ressegnetv2 confs")
@@ -200,13 +243,31 @@ class ImageDataset:
     def __getitem__(self, idx):
         return self.load(idx)
 
+    def with_decoder(self, decoder):
+        """The same file list read with another decoder."""
+        import copy
+        other = copy.copy(self)
+        other.decoder = decoder_name(decoder)
+        return other
+
     def load(self, idx, reserve=None, rgbx=False):
-        """__getitem__ with the decoded pixels placed in reserve(nbytes) (see _read_rgb_u8); rgbx: four bytes per pixel when possible."""
+        """__getitem__ with the decoded pixels placed in reserve(nbytes) (see _read_rgb_u8); rgbx: four bytes per pixel when possible.
+        decoder "hip": the prepared file in reserve(nbytes) instead, for the files the device decoder takes."""
         path = self.paths[idx]
-        image = _read_rgb_u8(self.root / path, reserve, rgbx)
+        if self.decoder == "hip":
+            from . import jpeg
+            buf, info = jpeg.read_prepared(self.root / path, reserve or _host_buffer)
+            if buf is not None:
+                w, h = int(info.width), int(info.height)
+                return {'name': str(path), 'image': None, 'jpeg': (buf[:int(info.prepared_bytes)], info), 'path': str(self.root / path),
+                        'original_size': np.array((w, h)), 'resize': resized_shape(w, h, self.conf['resize_max'], self.conf['resize_force'])}
+        image = _read_rgb_u8(self.root / path, reserve, rgbx, None if self.decoder == "hip" else self.decoder)
         h, w = image.shape[:2]
-        return {'name': str(path), 'image': image, 'original_size': np.array((w, h)),
+        item = {'name': str(path), 'image': image, 'original_size': np.array((w, h)),
                 'resize': resized_shape(w, h, self.conf['resize_max'], self.conf['resize_force'])}
+        if self.decoder == "hip":
+            item['fallback'] = True
+        return item
 
 
 def preprocess(model, image_u8, resize=None, bgr=False):
@@ -222,6 +283,62 @@ def preprocess(model, image_u8, resize=None, bgr=False):
     _lib.check(ctx.lib.sfd2_preprocess(ctx.h, a.ctypes.data, 0, H, W, _lib.FLAG_IMG_BGR if bgr else 0, h_new, w_new,
                                        out.data_ptr()))
     return out
+
+
+def preprocess_device_rgbx(model, rgbx, resize):
+    """preprocess() of a device uint8 [H, W, 4] RGBX image (the device decoder's output)."""
+    import torch
+    from . import _lib
+    ctx = model.context
+    H, W = int(rgbx.shape[0]), int(rgbx.shape[1])
+    w_new, h_new = resize
+    out = torch.empty((1, 3, h_new, w_new), dtype=torch.float32, device=torch.device("cuda", ctx.device))
+    _lib.check(ctx.lib.sfd2_preprocess(ctx.h, rgbx.data_ptr(), 1, H, W, _lib.FLAG_IMG_U8_X, h_new, w_new, out.data_ptr()))
+    return out
+
+
+def _extract_rgbx(model, rgbx, top_k, conf_th):
+    """extract_resnet_return's single-scale call on a device uint8 [H, W, 4] RGBX image (SFD2_FLAG_IMG_U8_HWC | SFD2_FLAG_IMG_U8_X)."""
+    import ctypes
+    from . import _lib
+    ctx = model.context
+    H, W = int(rgbx.shape[0]), int(rgbx.shape[1])
+    flags = (0 if getattr(model, "require_stability", True) else _lib.FLAG_NO_STABILITY) | _lib.FLAG_IMG_U8_HWC | _lib.FLAG_IMG_U8_X
+    cap = int(top_k) if top_k > 0 else max(65536, (H * W) // 8)
+    kp = np.empty((cap, 2), dtype=np.float32)
+    sc = np.empty((cap,), dtype=np.float32)
+    de = np.empty((cap, 128), dtype=np.float32)
+    n = ctypes.c_int(0)
+    _lib.check(ctx.lib.sfd2_extract(ctx.h, rgbx.data_ptr(), 1, H, W, float(conf_th), int(top_k), flags, kp.ctypes.data, sc.ctypes.data,
+                                    de.ctypes.data, 0, cap, ctypes.byref(n)))
+    n = n.value
+    return {"keypoints": kp[:n].astype(np.float64), "descriptors": de[:n].astype(np.float64), "scores": sc[:n].astype(np.float64)}
+
+
+def _extract_item(model, extractor, data, mconf, stats):
+    """main()'s extractor call for one item -> (pred, size).  'jpeg' items are decoded on the device (a failed decode: on the CPU)."""
+    if data.get('jpeg') is not None:
+        rgbx = device_image(model, data) if extractor is extract_resnet_return else None
+        if rgbx is not None and [float(x) for x in mconf["scales"]] == [1.0]:
+            stats['gpu_decoded'] += 1
+            W, H = int(rgbx.shape[1]), int(rgbx.shape[0])
+            resize = tuple(data.get('resize', (W, H)))
+            if resize != (W, H):
+                feed = preprocess_device_rgbx(model, rgbx, resize)
+                pred = extractor(model, img=feed, topK=mconf["max_keypoints"], mask=None, conf_th=mconf["conf_th"], scales=mconf["scales"])
+                return pred, np.array(resize)
+            return _extract_rgbx(model, rgbx, mconf["max_keypoints"], mconf["conf_th"]), np.array((W, H))
+        if rgbx is not None:
+            stats['gpu_decoded'] += 1
+            data = dict(data, image=np.ascontiguousarray(rgbx[:, :, :3].cpu().numpy()))
+        else:
+            stats['fallbacks'] += 1
+            data = dict(data, image=cpu_decode(data['path']))
+    elif data.get('fallback'):
+        stats['fallbacks'] += 1
+    feed, size = _feed_of(model, data)
+    pred = extractor(model, img=feed, topK=mconf["max_keypoints"], mask=None, conf_th=mconf["conf_th"], scales=mconf["scales"])
+    return pred, size
 
 
 def extract_one(model, extractor, image, original_size, conf):
@@ -242,7 +359,7 @@ def _part_path(export_dir, conf, rank, world):
     return base + '.h5' if world == 1 else f'{base}.part{rank}of{world}.h5'
 
 
-def _extract_pipelined(model, extractor, conf, images, indices, tag, store, names, num_workers, writers, depth, lanes=1):
+def _extract_pipelined(model, extractor, conf, images, indices, tag, store, names, num_workers, writers, depth, lanes=1, stats=None):
     """The loop of main() with its three stages running side by side (sfd2_amd/pipeline.py): `num_workers` decoder threads
     (the reference: DataLoader(num_workers=4), extract_localization.py:230-233) fill pinned buffers in item order, the
     device runs up to `depth` asynchronous extractions, `writers` threads build the float64 groups and append them.
@@ -315,6 +432,11 @@ def _extract_pipelined(model, extractor, conf, images, indices, tag, store, name
                     continue
                 img = data['image']
                 original_size = np.asarray(data['original_size'])
+                if ax is not None and data.get('jpeg') is not None:
+                    ax.submit_encoded(data['jpeg'], tuple(data['resize']), (idx, data['name'], original_size), data['path'], inbuf=buf)
+                    continue
+                if ax is not None and data.get('fallback') and stats is not None:
+                    stats['fallbacks'] += 1
                 if ax is not None and getattr(img, "dtype", None) == np.uint8 and img.ndim == 3:
                     H, W = img.shape[:2]
                     ax.submit(img, H, W, tuple(data.get('resize', (W, H))), (idx, data['name'], original_size), inbuf=buf)
@@ -322,10 +444,16 @@ def _extract_pipelined(model, extractor, conf, images, indices, tag, store, name
                 if ax is not None:
                     while ax.inflight:          # keep the store in item order: everything queued before this item first
                         drain_one()
+                if buf is not None and data.get('jpeg') is None:
+                    pool.release(buf)
+                    buf = None
+                if ax is None or data.get('jpeg') is not None:
+                    pred, size = _extract_item(model, extractor, data, mconf, stats if stats is not None else _new_stats(""))
+                else:
+                    feed, size = _feed_of(model, data)
+                    pred = extractor(model, img=feed, topK=top_k, mask=None, conf_th=conf_th, scales=mconf["scales"])
                 if buf is not None:
                     pool.release(buf)
-                feed, size = _feed_of(model, data)
-                pred = extractor(model, img=feed, topK=top_k, mask=None, conf_th=conf_th, scales=mconf["scales"])
                 wp.put((idx, data['name'], original_size, size, (pred['keypoints'], pred['scores'], pred['descriptors']), None))
             elif ax is not None and ax.inflight:
                 drain_one()
@@ -334,6 +462,9 @@ def _extract_pipelined(model, extractor, conf, images, indices, tag, store, name
     finally:
         pf.close()
         wp.close()
+        if ax is not None and stats is not None:
+            stats['gpu_decoded'] += ax.gpu_decoded
+            stats['fallbacks'] += ax.decode_fallbacks
     # the serial loop appends in item order; writers finish out of order by a few items
     names.sort()
 
@@ -350,8 +481,13 @@ def _feed_of(model, data):
     return (img[None] if img.ndim == 3 else img), np.array(img.shape[-2:][::-1])
 
 
+def _new_stats(decoder):
+    return {'decoder': decoder, 'gpu_decoded': 0, 'fallbacks': 0}
+
+
 def main(conf, images, export_dir, state_dict=None, device=0, tag=None, precision="f16x3", world=1, rank=0,
-         barrier=None, model_and_extractor=None, num_workers=4, writers=2, depth=None, lanes=None, affinity=None):
+         barrier=None, model_and_extractor=None, num_workers=4, writers=2, depth=None, lanes=None, affinity=None, decoder=None,
+         report=None):
     """extract_localization.py:221-279.  ``images``: an ImageDataset (decoded from files, resized per
     conf['preprocessing']) or any indexable / iterable of {'name', 'image': uint8 [H,W,3] RGB or float [3,H,W] in
     [0,1], 'original_size': (w, h)[, 'resize': (w, h)]}.  uint8 input is exact only together with the device resize
@@ -366,6 +502,9 @@ def main(conf, images, export_dir, state_dict=None, device=0, tag=None, precisio
     loop (_extract_pipelined: that many decoder threads, `depth` images in flight on the device (default: three per lane) over `lanes`
     contexts (HIP streams; default: 2 from 64 images on, else 1 -- the second context is made once per model, model.lanes), `writers` writer
     threads); 0: the reference's loop body strictly in turn per image.  Both write the same groups.
+    decoder: None (default) = the ImageDataset's own (its decoder= keyword, else SFD2_DECODER, else "auto"); "hip" decodes baseline JPEG files
+    on the device (ImageDataset docstring), every other file on the CPU.  report: a dict that receives {'decoder', 'gpu_decoded',
+    'fallbacks'} (also logged, logger "sfd2_amd").
     affinity: None (default) = with world > 1 the process pins itself, before its decoder / writer threads exist, to its share of the CPUs of the socket
     GPU `device` hangs off (sharding.pin_to_gpu_socket; SFD2_CPU_AFFINITY=0 disables); True / False force it on / off.
     Returns the final store path (rank 0) or the part path (other ranks)."""
@@ -380,6 +519,9 @@ def main(conf, images, export_dir, state_dict=None, device=0, tag=None, precisio
     else:
         model, extractor = model_and_extractor
     os.makedirs(str(export_dir), exist_ok=True)
+    if decoder is not None and hasattr(images, 'with_decoder'):
+        images = images.with_decoder(decoder)
+    stats = _new_stats(getattr(images, 'decoder', decoder_name(decoder) if decoder is not None else None))
     if not hasattr(images, '__getitem__'):
         images = list(images)
     n_items = len(images)
@@ -394,14 +536,12 @@ def main(conf, images, export_dir, state_dict=None, device=0, tag=None, precisio
             n_lanes = max(1, int(lanes)) if lanes is not None else (2 if len(idx_list) >= 64 else 1)
             n_depth = max(1, int(depth)) if depth is not None else 3 * n_lanes
             _extract_pipelined(model, extractor, conf, images, idx_list, tag, store, names,
-                               int(num_workers), max(1, int(writers)), n_depth, n_lanes)
+                               int(num_workers), max(1, int(writers)), n_depth, n_lanes, stats)
         for idx in (() if num_workers and num_workers > 0 else shard_indices(n_items, rank, world)):
             data = images[idx]
             if tag is not None and data['name'].find(tag) < 0:
                 continue
-            feed, size = _feed_of(model, data)
-            pred = extractor(model, img=feed, topK=conf["model"]["max_keypoints"], mask=None,
-                             conf_th=conf["model"]["conf_th"], scales=conf["model"]["scales"])
+            pred, size = _extract_item(model, extractor, data, conf["model"], stats)
             pred['descriptors'] = pred['descriptors'].transpose()
             pred['image_size'] = original_size = np.asarray(data['original_size'])
             pred['keypoints'] = rescale_keypoints(pred['keypoints'], original_size, size)
@@ -410,6 +550,12 @@ def main(conf, images, export_dir, state_dict=None, device=0, tag=None, precisio
         actual = getattr(store, 'path', getattr(store, 'filename', path))
     finally:
         store.close()
+    if stats['decoder'] is not None:
+        import logging
+        logging.getLogger("sfd2_amd").info("extract_localization: decoder %s, %d images decoded on the device, %d on the CPU (fallbacks)",
+                                           stats['decoder'], stats['gpu_decoded'], stats['fallbacks'])
+    if report is not None:
+        report.update(stats)
     if world == 1:
         return actual
     import json

@@ -115,6 +115,8 @@ class AsyncExtractor:
         self._turn = 0
         self.inflight = collections.deque()
         self.repeats = 0                # images re-run synchronously (range fallback)
+        self.gpu_decoded = 0            # submit_encoded: files the device decoded
+        self.decode_fallbacks = 0       # ... and files whose device decode failed (decoded on the CPU, extracted synchronously)
 
     def submit(self, image_u8, H, W, resize, meta, inbuf=None):
         """image_u8: uint8 [H,W,3] RGB or [H,W,4] RGBX view (pinned for a truly asynchronous upload); resize (w, h) or None."""
@@ -149,27 +151,88 @@ class AsyncExtractor:
         slot.event.record(self.streams[lane])
         self.inflight.append(slot)
 
+    def submit_encoded(self, jpeg_item, resize, meta, path, inbuf=None):
+        """jpeg_item: (prepared pinned buffer, sfd2_jpeg_info) of ImageDataset(decoder="hip").load.  The decode is queued on the lane's
+        stream in front of the extract, into the slot's own device RGBX image (kept until the slot is released: a range-saturation repeat
+        reads it again); finish() checks the decode's status and, if it failed, decodes `path` on the CPU and extracts synchronously."""
+        from . import jpeg
+        buf, info = jpeg_item
+        W, H = int(info.width), int(info.height)
+        slot = self._free.get()
+        lane = self._turn % len(self.models)
+        self._turn += 1
+        ctx, torch = self.models[lane].context, self.torch
+        lib = ctx.lib
+        if getattr(slot, "rgbx", None) is None or slot.rgbx.numel() < H * W * 4:
+            slot.rgbx = None
+            slot.rgbx = torch.empty(H * W * 4, dtype=torch.uint8, device=self.device)
+            slot.jstatus_t = torch.zeros(1, dtype=torch.int32, pin_memory=True)
+            slot.jstatus = slot.jstatus_t.numpy().view(np.uint32)
+        slot.jstatus[0] = 0
+        img = slot.rgbx[:H * W * 4].view(H, W, 4)
+        jpeg.decode_async(ctx, buf, info, img, slot.jstatus)
+        slot.lane = lane
+        slot.meta, slot.inbuf, slot.sync_result = meta, inbuf, None
+        slot.image, slot.dev_image, slot.path = None, img, path
+        src, on_dev, h, w = img.data_ptr(), 1, H, W
+        flags = self.flags | _lib.FLAG_ASYNC
+        if resize is not None and tuple(resize) != (W, H):
+            w, h = int(resize[0]), int(resize[1])
+            if self._resized[lane] is None or self._resized[lane].numel() < 3 * h * w:
+                ctx.sync()
+                self._resized[lane] = torch.empty(3 * h * w, dtype=torch.float32, device=self.device)
+            _lib.check(lib.sfd2_preprocess(ctx.h, src, 1, H, W, _lib.FLAG_ASYNC | _lib.FLAG_IMG_U8_X, h, w, self._resized[lane].data_ptr()))
+            src = self._resized[lane].data_ptr()
+        else:
+            flags |= _lib.FLAG_IMG_U8_HWC | _lib.FLAG_IMG_U8_X
+        slot.size = (w, h)
+        slot.resize = None if (w, h) == (W, H) else (w, h)
+        n = ctypes.c_int(0)
+        _lib.check(lib.sfd2_extract(ctx.h, src, on_dev, h, w, self.conf_th, self.top_k, flags | _lib.FLAG_DESC_STORE64, slot.kp.ctypes.data,
+                                    slot.sc.ctypes.data, slot.de64.ctypes.data, 0, slot.cap, ctypes.byref(n)))
+        _lib.check(lib.sfd2_extract_record_async(ctx.h, slot.rec.ctypes.data, 0))
+        slot.event.record(self.streams[lane])
+        self.inflight.append(slot)
+
     def finish(self):
         """Oldest image in flight -> its slot (n, kp, sc, de valid; give it back with release())."""
         slot = self.inflight.popleft()
         slot.event.synchronize()
+        dev_image, slot.dev_image = getattr(slot, "dev_image", None), None
+        if dev_image is not None:
+            if int(slot.jstatus[0]) != 0:   # the device found the entropy-coded data invalid: the CPU decoder's pixels, synchronously
+                from .extract_localization import cpu_decode
+                slot.image = cpu_decode(slot.path)
+                slot.rec[:] = 0
+                self.decode_fallbacks += 1
+                self._repeat(slot)
+                slot.n = 0
+                slot.image = None
+                return slot
+            self.gpu_decoded += 1
         n, _, saturated, flags = (int(v) for v in slot.rec.view(np.uint32))
         if flags & 1:
             raise RuntimeError("libsfd2hip: candidate buffer overflow in a pipelined extract")
         if saturated:
             # SFD2_PREC_F16C left its range on this image: the synchronous call repeats it in SFD2_PREC_F16X3 by itself
-            from .extractor import extract_resnet_return
-            img, model = slot.image, self.models[slot.lane]
-            if img.shape[-1] == 4:
-                img = np.ascontiguousarray(img[:, :, :3])
-            if slot.resize is not None:
-                from .extract_localization import preprocess
-                img = preprocess(model, img, slot.resize)
-            slot.sync_result = extract_resnet_return(model, img=img, topK=self.top_k, conf_th=self.conf_th)
+            if dev_image is not None:          # (device-decoded: the pixels are in the slot's device image)
+                slot.image = np.ascontiguousarray(dev_image[:, :, :3].cpu().numpy())
+            self._repeat(slot)
             self.repeats += 1
         slot.n = n
         slot.image = None
         return slot
+
+    def _repeat(self, slot):
+        """The synchronous extract of slot.image (host uint8 pixels) in the slot's lane, at the slot's size."""
+        from .extractor import extract_resnet_return
+        img, model = slot.image, self.models[slot.lane]
+        if img.shape[-1] == 4:
+            img = np.ascontiguousarray(img[:, :, :3])
+        if slot.resize is not None:
+            from .extract_localization import preprocess
+            img = preprocess(model, img, slot.resize)
+        slot.sync_result = extract_resnet_return(model, img=img, topK=self.top_k, conf_th=self.conf_th)
 
     def release(self, slot):
         self._free.put(slot)
