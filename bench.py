@@ -17,12 +17,17 @@ Multi-GPU: one process per GPU, images sharded, no collective on the data path
 `value` is the fastest mode whose tests assert BASELINE.json north_star's tolerance (descriptors within 1e-3 of the fp32
 reference): precision 'f16c', compensated fp16 -- fp16 MFMA operands plus one block-scaled MFMA per 32 channels that adds the
 two first-order rounding terms (fp6 x fp6 records on conv2a / conv3a / conv3b, option fp6_acts, the default; fp8 elsewhere;
-tests/test_gpu_f16c.py asserts 1e-3 at every BASELINE geometry; measured <= 6.2e-4 as shipped -- conv3b without its correction chunks where the load-time self-check finds the room: profiles/r06g_f16c_parity_measured.txt).  Other modes of the same workload, same bracket, in the same line: `approx_f16` (plain fp16, descriptors within
+tests/test_gpu_f16c.py asserts 1e-3 at every BASELINE geometry; measured <= 6.2e-4 as shipped -- conv3b without its correction chunks where the load-time self-check finds the room: profiles/r06g_f16c_parity_measured.txt).  Other modes of the same workload, same bracket, in the same line with --full: `approx_f16` (plain fp16, descriptors within
 3e-3: OUTSIDE the tolerance, reported for reference only), `strict_f32` (fp32 on the f32-input MFMA: descriptors within
 2e-5, key-point list equal up to near-ties), `strict_f16x3` (three hi / lo fp16 passes, same tolerances as f32) and
 `strict_kp_f16x3d` (f16x3's backbone and detector branch -- its key points bit for bit -- with the descriptor branch in plain fp16:
 descriptors within 1e-3, i.e. north_star's contract as written: key-point list equal up to near-ties AND descriptors within 1e-3).
 Tolerances are asserted by tests/, not here.
+
+A plain run does what `value` needs and nothing else: it sets up, warms up (the ~1 s pre-heat, the W steps and the untimed
+three-step pre-pass that `value` has always been measured behind), times the K steps, writes --dump-outputs and prints the
+line.  --full adds every leg that takes a run of its own: the per-kernel breakdown and the roofline (with its single-stream
+leg), `sustained`, the other BASELINE configs, the other precisions, the files -> stores `pipeline` and the CPU baseline.
 """
 import argparse
 import ctypes
@@ -195,9 +200,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true", help="also run the legs beyond `value` (per-kernel breakdown and roofline, single-stream, "
+                    "sustained, other configs, other precisions, pipeline, CPU baseline); --no-cpu-baseline, --no-strict, --no-pipeline, "
+                    "--no-configs and --sustain 0 leave some out again")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--extract-only", action="store_true", help="configs[1]: extract without matching")
-    ap.add_argument("--dump-layers", action="store_true", help="per-layer device times to stderr")
+    ap.add_argument("--dump-layers", action="store_true", help="per-layer device times to stderr (needs --full)")
     ap.add_argument("--streams", type=int, default=2, help="contexts (HIP streams) per GPU processing different images concurrently "
                     "(default 2: the kernels of one image leave CUs idle -- tile tails, the small selection kernels, the row-marching "
                     "ResBlocks -- that a second image's kernels fill: +17 %% images/sec on one MI355X; 3 measures no better)")
@@ -233,6 +241,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.dump_layers and not args.full:
+        ap.error("--dump-layers needs --full (per-kernel figures are part of the full run)")
     global H, W
     if args.size:
         W, H = (int(v) for v in args.size.lower().split("x"))
@@ -386,7 +396,8 @@ def main():
             f["layers"].append(r["name"])
         return fam
 
-    # untimed pre-pass with every launch bracketed: per-kernel breakdown + which family dominates
+    # untimed pre-pass with every launch bracketed: per-kernel breakdown (reported with --full) + which family dominates.  Every run
+    # makes it: `value` has always been measured behind it, and without it the hipGraph headline measured ~2 % faster on one MI355X
     ctx.set_profiling(8)
     for i in range(3):
         step(0, lanes[0], eager=True)
@@ -434,7 +445,7 @@ def main():
     # stream; the concurrent region's figures are reported next to it.
     single = None
     layers_concurrent = None
-    if (len(lanes) > 1 or use_graphs) and not args.no_profile:
+    if args.full and (len(lanes) > 1 or use_graphs) and not args.no_profile:
         layers_concurrent = layers
         ctx.set_profiling(2 * args.steps + 2, dom_filter)
         barrier()
@@ -452,7 +463,7 @@ def main():
     # extra leg (not `value`): the same steps for ~args.sustain seconds without any per-launch events, to show the
     # K-step number is not a boost-clock artefact
     sustained = None
-    if args.sustain > 0:
+    if args.full and args.sustain > 0:
         n_s = max(args.steps, int(args.sustain / max(dt / args.steps, 1e-6)))
         barrier()
         t0 = time.perf_counter()
@@ -499,7 +510,7 @@ def main():
                 "launch": "hipGraph replay per image" if use_graphs else "eager", "dtype": args.precision}
 
     configs_obj = None
-    if not args.no_configs and not args.extract_only and not args.size and not args.mix:
+    if args.full and not args.no_configs and not args.extract_only and not args.size and not args.mix:
         n_c = max(20, min(args.steps, 60))
         configs_obj = {
             "aachen_mix_80_20": config_leg("SURVEY C2: aachen_v1.1 queries, every fifth image portrait (1200x1600), K = 50 (BASELINE configs[2])",
@@ -510,7 +521,8 @@ def main():
             # space-to-depth conv2b); extract only -- database images are not queries
             "aachen_db_1600x1063": config_leg("aachen_v1.1 database images 1600x1063 (odd geometry: heat-map resize path), extract only", [(1063, 1600)] * 4, 0, n_c, 600),
         }
-    # what the compensated mode's range status saw over everything above (include/sfd2_hip.h "Range management"): nothing may have saturated
+    # what the compensated mode's range status saw over everything above (the headline's steps; with --full the legs as well; include/sfd2_hip.h
+    # "Range management"): nothing may have saturated
     range_seen = None
     if args.precision == "f16c":
         sts = [ln.ctx.range_status() for ln in lanes]
@@ -563,7 +575,7 @@ def main():
                 "launch": "hipGraph replay per image (sfd2_extract_match)" if replay else "eager", "parity": par}
 
     strict = strict_x3 = strict_kp = approx = north_star_strict = None
-    if not args.no_strict:
+    if args.full and not args.no_strict:
         strict = parity_leg("f32")
         strict_x3 = parity_leg("f16x3")
         strict_kp = parity_leg("f16x3d")
@@ -575,6 +587,36 @@ def main():
         approx = parity_leg("f16" if args.precision == "f16c" else "f16c")
 
     if rank == 0:
+        # the headline line: what the set-up and the timed region give
+        out = {
+            "metric": "images/sec extract" + ("" if args.extract_only else "+match") + f" ({W}x{H}, n4096)",
+            "value": round(args.steps * world / dt, 3), "unit": "images/sec", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": args.precision, "data": "synthetic",
+            "config": {"workload": ("aachen_v1.1 day query, extract-only (BASELINE configs[1])" if args.extract_only else
+                                    "aachen_v1.1 query extract + NNM match vs netvlad-50 resident db sets (BASELINE configs[2])"),
+                       "image": f"{W}x{H}" + (" (every fifth image portrait)" if args.mix else ""), "max_keypoints": TOPK, "db_sets_per_query": 0 if args.extract_only else K_DB,
+                       "db_keypoints": N_DB, "weights": "synthetic seeded ResSegNetV2 (checkpoint not shipped)",
+                       "parallelism": f"images sharded over {world} GPU(s), no collective", "streams_per_gpu": len(lanes),
+                       "launch": "hipGraph replay per image (sfd2_extract_match)" if use_graphs else "eager"},
+            "mutual_matches_last_step": n_matched,
+            "parity": ({"mode": "f16c: compensated fp16 (fp16 MFMA + one block-scaled MFMA of the rounding residuals per 32 channels -- "
+                                + ("fp6 x fp6 on conv2a / conv3a / conv3b (option fp6_acts), fp8 elsewhere" if args.fp6_acts else "fp8 operands") + " -- fp32 accumulate)"
+                                + (f"; backbone compensated, tensors inside the ResBlocks per option rb_inner = {args.rb_inner}" if args.comp_rb else "; option comp_rb = 0 (ResBlocks plain fp16)"),
+                        "descriptors_max_abs": "<= 1e-3 asserted = north_star's tolerance (measured "
+                                               + (("<= 6.2e-4 as shipped (option c3b_plain on where the self-check allows: margin_selfcheck.c3b_plain; 4.9e-4 with it off)", "<= 3.8e-4", "<= 3.5e-4")[2 - max(0, min(2, args.rb_inner))] if args.comp_rb else "<= 8.5e-4") + " at 480x640 .. 2048x1536)",
+                        "keypoint_set_iou": ">= 0.985 asserted (measured 0.992 - 1.0)" if args.comp_rb else ">= 0.97 asserted (measured 0.991 - 0.996)",
+                        "keypoint_order": "asserted among the points whose stability class did not flip: Spearman >= 0.999, rank shift <= n / 32 (measured <= 90 of 4096); the ordered LIST of the reference is `north_star_strict`'s contract",
+                        "selection_given_heat_map": "bit-exact", "asserted_in": "tests/test_gpu_f16c.py",
+                        "measured_in": "profiles/r06g_f16c_parity_measured.txt"} if args.precision == "f16c" else
+                       {"mode": "f16 throughput (OUTSIDE north_star's 1e-3)", "descriptors_max_abs": "<= 3e-3 (measured 1.8e-3)", "keypoint_set_iou": ">= 0.93",
+                        "selection_given_heat_map": "bit-exact", "asserted_in": "tests/test_gpu_parity.py"}),
+            "range_status": range_seen,
+            "margin_selfcheck": (lanes[0].ctx.margin_status() if args.precision == "f16c" else None),
+            "per_rank": {"ms_per_step": [round(d / args.steps * 1e3, 4) for d in dt_ranks], "min": round(min(dt_ranks) / args.steps * 1e3, 4),
+                         "max": round(max(dt_ranks) / args.steps * 1e3, 4), "cpu_placement_rank0": {k: placement[k] for k in ("pinned", "why")}},
+        }
+    if rank == 0 and args.full:
         # dominant kernel family = largest summed device time
         fam = dominant_family(layers)
         if not fam:
@@ -642,37 +684,12 @@ def main():
                 print(f"{r['name']:16s} {r['kernel']:34s} {ms*1e3:9.1f} us  {r['flops']/1e9:8.2f} GF {tf:8.1f} TF/s  "
                       f"{r['bytes']/1e6:8.1f} MB {gb:8.0f} GB/s", file=sys.stderr)
         breakdown = {k: round(v["ms"] / 3, 4) for k, v in sorted(fam_all.items(), key=lambda kv: -kv[1]["ms"])}
-        out = {
-            "metric": "images/sec extract" + ("" if args.extract_only else "+match") + f" ({W}x{H}, n4096)",
-            "value": round(args.steps * world / dt, 3), "unit": "images/sec", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": args.precision, "data": "synthetic",
-            "config": {"workload": ("aachen_v1.1 day query, extract-only (BASELINE configs[1])" if args.extract_only else
-                                    "aachen_v1.1 query extract + NNM match vs netvlad-50 resident db sets (BASELINE configs[2])"),
-                       "image": f"{W}x{H}" + (" (every fifth image portrait)" if args.mix else ""), "max_keypoints": TOPK, "db_sets_per_query": 0 if args.extract_only else K_DB,
-                       "db_keypoints": N_DB, "weights": "synthetic seeded ResSegNetV2 (checkpoint not shipped)",
-                       "parallelism": f"images sharded over {world} GPU(s), no collective", "streams_per_gpu": len(lanes),
-                       "launch": "hipGraph replay per image (sfd2_extract_match)" if use_graphs else "eager"},
+        out.update({
             "roofline": roof, "kernel_ms_per_step": breakdown, "device_ms_per_step": round(total_ms, 4),
-            "mutual_matches_last_step": n_matched,
-            "parity": ({"mode": "f16c: compensated fp16 (fp16 MFMA + one block-scaled MFMA of the rounding residuals per 32 channels -- "
-                                + ("fp6 x fp6 on conv2a / conv3a / conv3b (option fp6_acts), fp8 elsewhere" if args.fp6_acts else "fp8 operands") + " -- fp32 accumulate)"
-                                + (f"; backbone compensated, tensors inside the ResBlocks per option rb_inner = {args.rb_inner}" if args.comp_rb else "; option comp_rb = 0 (ResBlocks plain fp16)"),
-                        "descriptors_max_abs": "<= 1e-3 asserted = north_star's tolerance (measured "
-                                               + (("<= 6.2e-4 as shipped (option c3b_plain on where the self-check allows: margin_selfcheck.c3b_plain; 4.9e-4 with it off)", "<= 3.8e-4", "<= 3.5e-4")[2 - max(0, min(2, args.rb_inner))] if args.comp_rb else "<= 8.5e-4") + " at 480x640 .. 2048x1536)",
-                        "keypoint_set_iou": ">= 0.985 asserted (measured 0.992 - 1.0)" if args.comp_rb else ">= 0.97 asserted (measured 0.991 - 0.996)",
-                        "keypoint_order": "asserted among the points whose stability class did not flip: Spearman >= 0.999, rank shift <= n / 32 (measured <= 90 of 4096); the ordered LIST of the reference is `north_star_strict`'s contract",
-                        "selection_given_heat_map": "bit-exact", "asserted_in": "tests/test_gpu_f16c.py",
-                        "measured_in": "profiles/r06g_f16c_parity_measured.txt"} if args.precision == "f16c" else
-                       {"mode": "f16 throughput (OUTSIDE north_star's 1e-3)", "descriptors_max_abs": "<= 3e-3 (measured 1.8e-3)", "keypoint_set_iou": ">= 0.93",
-                        "selection_given_heat_map": "bit-exact", "asserted_in": "tests/test_gpu_parity.py"}),
-            "single_stream": single, "sustained": sustained, "configs": configs_obj, "range_status": range_seen,
-            "margin_selfcheck": (lanes[0].ctx.margin_status() if args.precision == "f16c" else None),
+            "single_stream": single, "sustained": sustained, "configs": configs_obj,
             "strict_f32": strict, "strict_f16x3": strict_x3, "strict_kp_f16x3d": strict_kp, "north_star_strict": north_star_strict,
-            "per_rank": {"ms_per_step": [round(d / args.steps * 1e3, 4) for d in dt_ranks], "min": round(min(dt_ranks) / args.steps * 1e3, 4),
-                         "max": round(max(dt_ranks) / args.steps * 1e3, 4), "cpu_placement_rank0": {k: placement[k] for k in ("pinned", "why")}},
             ("approx_f16" if args.precision == "f16c" else "f16c"): approx,
-        }
+        })
         if world == 1 and not args.no_pipeline and not args.extract_only and not args.size and args.precision == "f16c":
             # not `value`: what the reference-shaped DRIVERS reach from JPEG files and stores (host decode, PCIe, float64 stores included)
             try:
@@ -690,6 +707,7 @@ def main():
                 out["pipeline"] = {"error": repr(e)}
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(sd)
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.barrier()

@@ -38,7 +38,7 @@ def test_bench_distributed_bracket_on_one_gpu():
     region, all_reduce(MAX) of the elapsed time) with WORLD_SIZE = 1."""
     env = dict(os.environ, SFD2_BENCH_FORCE_DIST="1", RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1",
                MASTER_PORT=str(_free_port()), HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run(BENCH, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    r = subprocess.run(BENCH + ["--full"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     d = _one_json_line(r.stdout.decode())
     assert d["n_gpus"] == 1 and d["steps"] == 3 and d["value"] > 0 and d["scaling"] == "weak"
@@ -81,6 +81,20 @@ def test_bench_dump_outputs_repeatable(tmp_path):
         assert np.array_equal(a[n], b[n]), n
     assert np.allclose(np.linalg.norm(a["descriptors"], axis=1), 1.0, atol=1e-3)
     assert (a["matches"] >= 0).any() and np.array_equal(a["matches"], np.round(a["matches"]))
+
+
+def test_bench_plain_run_is_the_headline_alone():
+    """Without --full the line carries the headline and what the timed region itself gave; no leg that needs a run of its own."""
+    r = subprocess.run(BENCH, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    d = _one_json_line(r.stdout.decode())
+    assert d["metric"] == "images/sec extract+match (1600x1200, n4096)" and d["unit"] == "images/sec" and d["higher_is_better"] is True
+    assert d["dtype"] == "f16c" and d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0
+    assert abs(d["value"] - 1e3 / d["ms_per_step"]) <= 1e-3 * d["value"]
+    assert "range_status" in d and d["margin_selfcheck"]["c3b_plain"] in (True, False)
+    for k in ("roofline", "kernel_ms_per_step", "single_stream", "sustained", "configs", "strict_f32", "north_star_strict", "approx_f16",
+              "pipeline", "cpu_baseline"):
+        assert k not in d, k
 
 
 def test_bench_refuses_unrequested_world():

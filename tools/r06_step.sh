@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 out=$R/gpurun_out/$tag
 mkdir -p $out
 cd $R
-B="python bench.py --no-cpu-baseline --no-strict --no-pipeline --no-configs"
+B="python bench.py --full --no-cpu-baseline --no-strict --no-pipeline --no-configs"
 for what in "$@"; do
 case $what in
   relax_probe) python tools/relax_probe.py 3 > $out/relax_probe.txt 2>&1 ;;
@@ -21,8 +21,8 @@ case $what in
     $B --steps 20 --warmup 5 --streams 1 --no-graphs --dump-layers --opt c3b_plain=0 > $out/bench_streams1_eager_c3b0.json 2> $out/layer_table_c3b0.txt
     ;;
   layers) $B --steps 20 --warmup 5 --streams 1 --no-graphs --dump-layers > $out/bench_streams1_eager.json 2> $out/layer_table.txt ;;
-  bench) python bench.py > $out/bench.json 2> $out/bench.err ;;
-  bench_quick) python bench.py --no-cpu-baseline --no-pipeline > $out/bench_quick.json 2> $out/bench_quick.err ;;
+  bench) python bench.py --full > $out/bench.json 2> $out/bench.err ;;
+  bench_quick) python bench.py --full --no-cpu-baseline --no-pipeline > $out/bench_quick.json 2> $out/bench_quick.err ;;
   smoke) python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $out/smoke.txt 2>&1 ;;
   soak) python tools/host_soak.py --ranks 8 > $out/host_soak_8ranks.json 2> $out/host_soak.err ;;
   *) echo "unknown step $what" ;;
