@@ -518,6 +518,53 @@ int sfd2_jpeg_prepare(uint8_t *buf, int64_t cap, sfd2_jpeg_info *info);
 int sfd2_jpeg_decode(sfd2_ctx *ctx, const uint8_t *data, int64_t n, const sfd2_jpeg_info *info, int flags,
                      uint8_t *out_rgbx_dev, int64_t out_cap, uint32_t *status, int status_on_device);
 
+/* ------------------------------------------------------------------------------------------------ absolute pose
+ * pycolmap.absolute_pose_estimation (it_loc/localize_cv2.py:731, :390) and pycolmap.pose_refinement (:451) on the device, for
+ * many problems of any sizes in one launch.  LO-RANSAC over P3P (Lambda Twist) with fp32 scoring on centred coordinates and an
+ * fp64 local optimisation, then the refinement of pycolmap's RefineAbsolutePose with the intrinsics fixed: Cauchy loss (1 px
+ * scale) on the reprojection error in pixels over the RANSAC inliers.  Results depend on the problem and the seed only (not on
+ * the batch, its order or the scheduling) and are bit-reproducible.
+ * Pose convention (COLMAP): x_cam = R(qvec) X + tvec, qvec = (w, x, y, z) unit, world to camera; points2D are pixel coordinates
+ * as given (the localiser adds its +0.5, localize_cv2.py:647). */
+#define SFD2_CAM_SIMPLE_PINHOLE 0   /* f, cx, cy                          (COLMAP camera model ids and parameter order) */
+#define SFD2_CAM_PINHOLE 1          /* fx, fy, cx, cy                                                                      */
+#define SFD2_CAM_SIMPLE_RADIAL 2    /* f, cx, cy, k                                                                        */
+#define SFD2_CAM_OPENCV 4           /* fx, fy, cx, cy, k1, k2, p1, p2                                                      */
+typedef struct {
+    int32_t n;                      /* correspondences                                                                     */
+    int32_t model;                  /* SFD2_CAM_*; any other id is an error                                                */
+    const double *points2D;         /* host [n][2] pixels                                                                  */
+    const double *points3D;         /* host [n][3] world                                                                   */
+    double params[8];               /* the model's parameters in COLMAP order (unused tail ignored)                       */
+    int32_t width, height;
+    double max_error_px;            /* RANSAC inlier threshold in pixels (the `thresh` of localize_cv2.py:731)             */
+} sfd2_pose_problem;
+typedef struct {
+    double min_inlier_ratio;        /* limits max_num_trials as COLMAP's RANSAC does                                       */
+    int64_t min_num_trials, max_num_trials;
+    double confidence;
+    uint64_t seed;                  /* trial i of every problem draws its sample from (seed, i) only                      */
+} sfd2_pose_conf;
+typedef struct {
+    int32_t success;                /* 0: fewer than 4 correspondences or no pose with >= 3 inliers (outputs finite)       */
+    int32_t num_inliers;            /* RANSAC inliers (absolute pose) or the mask's count (refinement)                     */
+    int32_t num_trials;             /* RANSAC trials run (0 for the refinement)                                            */
+    int32_t reserved;
+    double qvec[4];                 /* w, x, y, z                                                                          */
+    double tvec[3];
+} sfd2_pose_result;
+
+/* k problems; results[k]; inlier_mask_u8: host, sum(n) bytes, the problems' RANSAC inlier masks concatenated in problem order.
+ * Non-finite input or a bad model / parameter is an error (-1).  flags: 0.  Replaces pycolmap.absolute_pose_estimation(mkpq,
+ * mp3d, cfg, thresh), it_loc/localize_cv2.py:731. */
+int sfd2_absolute_pose_batch(sfd2_ctx *ctx, const sfd2_pose_problem *problems, int k, const sfd2_pose_conf *conf,
+                             sfd2_pose_result *results, uint8_t *inlier_mask_u8, int flags);
+/* The refinement alone, from qvec_tvec_in[k][7] (qw qx qy qz tx ty tz) over the inliers of inlier_mask_u8 (host, sum(n) bytes,
+ * problems concatenated).  max_error_px is not used.  flags: 0.  Replaces pycolmap.pose_refinement(tvec, qvec, mkpq, mp3d,
+ * inlier_mask, cfg), it_loc/localize_cv2.py:451. */
+int sfd2_pose_refine_batch(sfd2_ctx *ctx, const sfd2_pose_problem *problems, int k, const double *qvec_tvec_in,
+                           const uint8_t *inlier_mask_u8, sfd2_pose_result *results, int flags);
+
 #ifdef __cplusplus
 }
 #endif

@@ -84,6 +84,24 @@ class JpegInfo(ctypes.Structure):
                 ("prepared_bytes", ctypes.c_int64), ("n_lanes", ctypes.c_int32), ("prepared", ctypes.c_int32)]
 
 
+class PoseProblem(ctypes.Structure):
+    """sfd2_pose_problem (include/sfd2_hip.h)."""
+    _fields_ = [("n", ctypes.c_int32), ("model", ctypes.c_int32), ("points2D", ctypes.c_void_p), ("points3D", ctypes.c_void_p),
+                ("params", ctypes.c_double * 8), ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("max_error_px", ctypes.c_double)]
+
+
+class PoseConf(ctypes.Structure):
+    """sfd2_pose_conf (include/sfd2_hip.h)."""
+    _fields_ = [("min_inlier_ratio", ctypes.c_double), ("min_num_trials", ctypes.c_int64), ("max_num_trials", ctypes.c_int64),
+                ("confidence", ctypes.c_double), ("seed", ctypes.c_uint64)]
+
+
+class PoseResult(ctypes.Structure):
+    """sfd2_pose_result (include/sfd2_hip.h)."""
+    _fields_ = [("success", ctypes.c_int32), ("num_inliers", ctypes.c_int32), ("num_trials", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("qvec", ctypes.c_double * 4), ("tvec", ctypes.c_double * 3)]
+
+
 # every symbol include/sfd2_hip.h declares (tests/test_abi.py checks the two lists agree)
 EXPORTS = [
     "sfd2_version", "sfd2_last_error", "sfd2_ctx_create", "sfd2_ctx_destroy", "sfd2_get_stream",
@@ -94,7 +112,7 @@ EXPORTS = [
     "sfd2_set_profile_filter", "sfd2_extract_multiscale", "sfd2_set_option", "sfd2_extract_match", "sfd2_preprocess", "sfd2_extract_spp_levels", "sfd2_match_segments",
     "sfd2_get_range_status", "sfd2_range_tensor_name", "sfd2_calibrate_range", "sfd2_get_act_exponents", "sfd2_set_act_exponents",
     "sfd2_extract_record_async", "sfd2_desc_pack", "sfd2_get_margin_status", "sfd2_get_relax_status", "sfd2_get_option", "sfd2_device_pci_bus_id",
-    "sfd2_jpeg_parse", "sfd2_jpeg_prepare", "sfd2_jpeg_decode",
+    "sfd2_jpeg_parse", "sfd2_jpeg_prepare", "sfd2_jpeg_decode", "sfd2_absolute_pose_batch", "sfd2_pose_refine_batch",
 ]
 
 _lib = None
@@ -178,6 +196,8 @@ def load():
     lib.sfd2_jpeg_parse.argtypes = [vp, i64, ctypes.POINTER(JpegInfo)]
     lib.sfd2_jpeg_prepare.argtypes = [vp, i64, ctypes.POINTER(JpegInfo)]
     lib.sfd2_jpeg_decode.argtypes = [vp, vp, i64, ctypes.POINTER(JpegInfo), ci, vp, i64, vp, ci]
+    lib.sfd2_absolute_pose_batch.argtypes = [vp, ctypes.POINTER(PoseProblem), ci, ctypes.POINTER(PoseConf), ctypes.POINTER(PoseResult), vp, ci]
+    lib.sfd2_pose_refine_batch.argtypes = [vp, ctypes.POINTER(PoseProblem), ci, vp, vp, ctypes.POINTER(PoseResult), ci]
     for name in EXPORTS:
         getattr(lib, name)  # raises AttributeError if the .so lacks a declared symbol
     if lib.sfd2_version() < 109:

@@ -258,6 +258,7 @@ struct sfd2_ctx {
     DevBuf arena;   // aliased activation slots of the throughput path (run_network)
     DevBuf img_u8_packed;              // SFD2_FLAG_IMG_U8_X: the image as three bytes per pixel (unpack_rgbx_kernel)
     JpegScratch jpeg;                  // sfd2_jpeg_decode
+    JpegBuf pose_in, pose_ws, pose_out; // sfd2_absolute_pose_batch / sfd2_pose_refine_batch (api_pose.hip): inputs, per-point work, results
     DevBuf img_scaled, ms_kp, ms_sc, ms_de, ms_keys, ms_sorted, ms_cnt;
     unsigned int ms_cand_seen[8] = {};
     int ms_cand_cap[8] = {};

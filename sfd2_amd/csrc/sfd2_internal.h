@@ -702,3 +702,30 @@ struct JpegLane {                     // one lane's decode: where it started and
 void launch_jpeg_decode(hipStream_t st, const unsigned char *in, int64_t tab_off, const JpegGeom &g, JpegLane *lanes, int *lane_pre,
                         int *wg_pre, unsigned int *sync_flags, short *coef, unsigned char *planes, unsigned char *out_rgbx,
                         unsigned int *status);
+
+// ------------------------------------------------------------------------------------------------ absolute pose (pose_kernels.hip)
+#define SFD2_POSE_WG 256              // threads of a problem's workgroup = RANSAC trials per round
+struct PoseCam {                      // a COLMAP camera in OPENCV form (SIMPLE_* / PINHOLE: zero distortion, SIMPLE_RADIAL: k1 only)
+    double f[2], c[2];
+    double k1, k2, p1, p2;
+    int32_t distorted, pad;
+};
+struct PoseProbDev {
+    int64_t off;                      // first correspondence of the problem in the concatenated arrays
+    int32_t n, pad;
+    PoseCam cam;
+    double thresh2;                   // (max_error_px / mean focal)^2: the inlier threshold on the squared normalised error
+    double qt[7];                     // refinement only: the start pose (qw qx qy qz tx ty tz)
+};
+struct PoseConfDev {
+    int64_t max_trials, min_trials;   // max_trials already limited by min_inlier_ratio (COLMAP's RANSAC constructor)
+    double confidence;
+    uint64_t seed;
+    int32_t refine_only, pad;
+};
+struct PoseResDev {
+    double q[4], t[3];
+    int32_t success, num_inliers, num_trials, pad;
+};
+void launch_pose(hipStream_t st, const PoseProbDev *probs, int k, const PoseConfDev &conf, const double *p2, const double *p3, float4 *xf4,
+                 float2 *xf2, double2 *xn, double *hyp, const unsigned char *mask_in, unsigned char *mask_out, PoseResDev *res);

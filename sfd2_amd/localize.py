@@ -120,3 +120,108 @@ class StoreMatcher:
 
     def close(self):
         self.sets.close()
+
+
+def match_cluster_2D(kpq, matches_list, db_point3D_ids_list, points3D, obs_th=0, db_names=None):
+    """it_loc/localize_cv2.py:563-650 match_cluster_2D on matches already computed (StoreMatcher.match / feature_matching_batch):
+    matches_list[i] is database image i's matches0 (indices into its key points, -1 = none), db_point3D_ids_list[i] its point3D_ids.
+    Applies the -1 skips, the obs_th rule on len(points3D[id].image_ids), the per-query-keypoint de-duplication of 3D ids and the
+    +0.5 pixel offset (:647).  points3D: any mapping id -> object with .xyz and .image_ids (read_write_model's).  db_names: the keys
+    of cluster_info (default: the image's position in the lists).  Returns (cluster_info, mp3d [m,3], mkpq [m,2], mp3d_ids, q_ids);
+    cluster_info[name] holds 'mkpq', 'qids', 'matches', 'mp_3d_ids', 'mp3d' (:637-643, without the database key points)."""
+    kpq = np.asarray(kpq)
+    all_mp3d, all_mkpq, all_mp3d_ids, all_q_ids = [], [], [], []
+    outputs = {}
+    valid = {}
+    for i, (matches, ids) in enumerate(zip(matches_list, db_point3D_ids_list)):
+        name = i if db_names is None else db_names[i]
+        ids = np.asarray(ids)
+        if ids.size == 0:                                    # :578-580
+            continue
+        matches = np.asarray(matches)
+        mp3d, mp3d_ids, q_ids, mkpq, vm = [], [], [], [], []
+        for idx in range(matches.shape[0]):
+            m = matches[idx]
+            if m == -1 or ids[m] == -1:
+                continue
+            id_3D = ids[m]
+            if len(points3D[id_3D].image_ids) < obs_th:
+                continue
+            seen = valid.setdefault(idx, [])
+            if id_3D in seen:
+                continue
+            seen.append(id_3D)
+            mp3d.append(points3D[id_3D].xyz)
+            mp3d_ids.append(id_3D)
+            all_mp3d_ids.append(id_3D)
+            mkpq.append(kpq[idx])
+            q_ids.append(idx)
+            all_q_ids.append(idx)
+            all_mkpq.append(kpq[idx])
+            all_mp3d.append(points3D[id_3D].xyz)
+            vm.append(m)
+        outputs[name] = {"mkpq": mkpq, "qids": q_ids, "matches": np.array(vm, dtype=int), "mp_3d_ids": mp3d_ids,
+                         "mp3d": np.array(mp3d, dtype=float).reshape(-1, 3)}
+    all_mp3d = np.array(all_mp3d, float).reshape(-1, 3)
+    all_mkpq = np.array(all_mkpq, float).reshape(-1, 2) + 0.5
+    return outputs, all_mp3d, all_mkpq, all_mp3d_ids, all_q_ids
+
+
+def pose_from_clusters(kpq, clusters, camera, thresh, inlier_th=50, *, points3D, obs_th=3, qname=None, estimator=None, **ransac):
+    """The initialisation loop of it_loc/localize_cv2.py:653-1273 pose_from_cluster_with_matcher with do_covisility_opt=False, on
+    matches already computed.  clusters: a list over the retrieved clusters, each a list of (db_image, matches0) pairs (db_image with
+    .name, .qvec, .tvec, .point3D_ids as read_write_model returns them; matches0 from StoreMatcher.match / feature_matching_batch).
+
+    Every cluster with >= 8 correspondences (:719) goes into ONE absolute_pose_estimation_batch call (estimator: a replacement
+    taking a list of (points2D, points3D, camera, thresh) and returning pose dicts; **ransac goes to the default one).  The
+    sequential decisions are then replayed in cluster order: best_inliers per db image (:742-760), keep / continue (:930-966), the
+    first success returns its num_inliers (:1124-1130); otherwise, when the kept result has >= 10 inliers, the pose of the LAST
+    estimate made is returned with 0, as the reference does (:1132-1265 reads `ret`; if that estimate failed, the kept pose is
+    used); otherwise the first db image's pose with -1 (:1267-1273).  Returns (qvec, tvec, n, best_results)."""
+    if estimator is None:
+        from . import pose as _pose
+
+        def estimator(problems):
+            return _pose.absolute_pose_estimation_batch(problems, **ransac)
+    n_q = len(kpq)
+    first = clusters[0][0][0]
+    best_results = {"tvec": None, "qvec": None, "num_inliers": 0, "single_num_inliers": 0, "db_id": -1, "order": -1, "qname": qname,
+                    "optimize": False, "dbname": first.name, "ret_source": "", "inliers": []}
+    prepared = []
+    for cl in clusters:
+        info, mp3d, mkpq, mp3d_ids, q_ids = match_cluster_2D(kpq, [m for _, m in cl], [im.point3D_ids for im, _ in cl], points3D,
+                                                             obs_th=obs_th, db_names=[im.name for im, _ in cl])
+        prepared.append((info, mp3d, mkpq, mp3d_ids, q_ids))
+    live = [i for i, p in enumerate(prepared) if p[1].shape[0] >= 8]
+    rets = dict(zip(live, estimator([(prepared[i][2], prepared[i][1], camera, thresh) for i in live]) if live else []))
+    last = None
+    for cluster_idx, (info, mp3d, mkpq, mp3d_ids, q_ids) in enumerate(prepared):
+        if cluster_idx not in rets:
+            continue
+        ret = last = rets[cluster_idx]
+        if not ret["success"]:
+            continue
+        inliers = ret["inliers"]
+        q_p3d_ids = np.full(n_q, -1, dtype=np.int64)
+        for idx, qid in enumerate(q_ids):
+            if inliers[idx]:
+                q_p3d_ids[qid] = mp3d_ids[idx]
+        best_dbname, best_inliers = None, -1
+        for db_name, ci in info.items():
+            n = sum(1 for idx, qid in enumerate(ci["qids"]) if ci["mp_3d_ids"][idx] == q_p3d_ids[qid])
+            if n > best_inliers:
+                best_inliers, best_dbname = n, db_name
+        keep = not (best_inliers < 8 or ret["num_inliers"] <= best_results["num_inliers"])
+        upd = {"qvec": ret["qvec"], "tvec": ret["tvec"], "inlier": ret["inliers"], "num_inliers": ret["num_inliers"],
+               "single_num_inliers": best_inliers, "dbname": best_dbname, "order": cluster_idx + 1}
+        if keep:
+            best_results.update(upd)
+        if ret["num_inliers"] < inlier_th or best_inliers < 10:
+            continue
+        if not keep:
+            best_results.update(upd)
+        return ret["qvec"], ret["tvec"], ret["num_inliers"], best_results
+    if best_results["num_inliers"] >= 10:
+        src = last if (last is not None and last["success"]) else best_results
+        return src["qvec"], src["tvec"], 0, best_results
+    return first.qvec, first.tvec, -1, best_results
