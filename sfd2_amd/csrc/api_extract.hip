@@ -208,18 +208,7 @@ extern "C" int sfd2_extract(sfd2_ctx *c, const void *img, int img_on_device, int
             const int rows32 = (sel_cap * 4 + 31) / 32;           // the compact pixels as a [rows32][32] image for the generic 1x1 kernel
             HIPCHECK(c->da3_sparse.ensure((size_t)rows32 * 32 * 256 * sizeof(float)));
             HIPCHECK(c->db_sparse.ensure((size_t)rows32 * 32 * 128 * sizeof(float)));
-            ConvW &L3 = c->fda3;
-            if (!L3.wx3p.p) {
-                const size_t nfl = (size_t)9 * L3.cout_pad * L3.cin;
-                HIPCHECK(L3.wx3p.ensure(nfl * 2 * sizeof(half_t)));
-                launch_x3_split_planes(c->stream, L3.w.as<float>(), nfl, L3.wx3p.p, L3.wx3p.as<half_t>() + nfl);
-            }
-            if (!L3.wsl.p && L3.cin == 256) {                     // both planes in sparse_da3_kernel's fragment order (ConvW::wsl)
-                const size_t nfl = (size_t)9 * L3.cout_pad * L3.cin;
-                HIPCHECK(L3.wsl.ensure(nfl * 2 * sizeof(half_t)));
-                launch_sparse_da3_repack(c->stream, L3.wx3p.as<half_t>(), L3.wsl.as<half_t>(), L3.cout_pad, L3.cin);
-                launch_sparse_da3_repack(c->stream, L3.wx3p.as<half_t>() + nfl, L3.wsl.as<half_t>() + nfl, L3.cout_pad, L3.cin);
-            }
+            const ConvW &L3 = c->fda3;                            // (its filter planes and wsl: ensure_strict_filters)
             {
                 ProfScope ps(c, "convDa.3", "sparse_da3_kernel<x3>", 2.0 * 4 * sel_cap * 256.0 * 256.0 * 9, (double)sel_cap * (16 * 1024 + 4 * 1024));
                 launch_sparse_da3_x3(c->stream, c->x3_da0_planes.as<half_t>(), c->x3_da0_planes.as<half_t>() + nin, c->H4, c->W4, H, W,
@@ -227,7 +216,7 @@ extern "C" int sfd2_extract(sfd2_ctx *c, const void *img, int img_on_device, int
                                      c->counters.as<unsigned int>() + 1, sel_cap, c->da3_sparse.as<float>(), c->zero_page.as<half_t>());
             }
             // convDb (1x1) on the compact [sel_cap x 4] "image" with the mode's generic kernel, then the sampler on its compact output
-            if (convf(c, plan, "convDb", c->fdb, c->da3_sparse, rows32, 32, c->db_sparse, rows32, 32, 0)) return -1;
+            if (convf(c, StrictConv{}, "convDb", c->fdb, c->da3_sparse, rows32, 32, c->db_sparse, rows32, 32, 0)) return -1;
             ProfScope ps(c, "sample_desc", "sample_desc_kernel", 0.0, (double)sel_cap * 128 * 4 * 5);
             launch_sample_desc(c->stream, c->db_sparse.as<float>(), c->H4, c->W4, H, W, c->kpts_cur, c->counters.as<unsigned int>() + 1,
                                sel_cap, desc_dst, 1);

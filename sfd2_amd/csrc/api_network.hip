@@ -4,14 +4,18 @@
 // ------------------------------------------------------------------------------------------ workspace
 static int down2(int n) { return (n - 1) / 2 + 1; }  // 3x3 stride 2 pad 1
 
-// which throughput kernel takes a layer of SFD2_PREC_F16X3 from hi / lo' planes: 0 none (generic, fp32 in / out), 1 conv3x3_pp, 2 conv3x3_rf
-// (small outputs and stride 2: conv2b, convPa.0 / convPa.3 at 1600x1200, every 256-channel layer of a 640x480 image -- as in f16)
-static int x3_fast_kind(const PassPlan &p, const ConvW &L, bool has_res, int Ho, int Wo)
+// which throughput kernel takes a layer of SFD2_PREC_F16X3 from hi / lo' planes: conv3x3_rf for small outputs and stride 2 (conv2b, convPa.0 / convPa.3
+// at 1600x1200, every 256-channel layer of a 640x480 image -- as in f16), conv3x3_pp for the other 3x3 stride-1 layers, none (the generic kernel) otherwise
+static X3Kind x3_fast_kind(const PassPlan &p, const ConvW &L, bool has_res, int Ho, int Wo)
 {
-    if (!p.x3_pp || has_res || L.ks != 3 || L.cin % 64 != 0) return 0;
-    if ((L.cout_pad == 256 || (L.cout_pad == 128 && L.stride == 2)) && conv3x3_rf_serves(3, L.stride, L.cout_pad, L.cin, Ho, Wo)) return 2;
-    return (L.stride == 1 && L.cout_pad % 128 == 0) ? 1 : 0;
+    if (!p.x3_pp || has_res || L.ks != 3 || L.cin % 64 != 0) return XK_GENERIC;
+    if ((L.cout_pad == 256 || (L.cout_pad == 128 && L.stride == 2)) && conv3x3_rf_serves(3, L.stride, L.cout_pad, L.cin, Ho, Wo)) return XK_RF;
+    return (L.stride == 1 && L.cout_pad % 128 == 0) ? XK_PP : XK_GENERIC;
 }
+// the resolution level (0: H x W ... 3: 1/8) of a strict layer's input; its output: one further with stride 2
+static const int sl_level[] = {0 /* conv1b */, 1, 1 /* conv2a, conv2b */, 2, 2, 2, 2, 2, 2, 2, 2, 2 /* ... convPa.0 */, 3, 3 /* convPa.3, convPb */, 2, 2, 2};
+static_assert(sizeof(sl_level) == SL_COUNT * sizeof(int), "one level per StrictLayer");
+static bool on_planes(const StrictConv &s) { return s.kind == XK_PP || s.kind == XK_RF || s.kind == XK_S2D; }
 
 // The one place that combines the options for a network pass (sfd2_ctx.h, PassPlan).  top_k and desc: sfd2_extract's arguments.
 PassPlan plan_pass(const sfd2_ctx *c, PassEntry entry, int H, int W, int top_k, bool desc)
@@ -122,30 +126,64 @@ PassPlan plan_pass(const sfd2_ctx *c, PassEntry entry, int H, int W, int top_k, 
         // convPb fused into the detector-head kernel: convPa.3's output must outlive the network pass, so convDa.3
         // writes over the backbone output instead (slot 0) -- ConvSta, its last reader, then runs before the heads
         if (p.skip_pb) p.slot.da = 0;
+        const size_t P2 = (size_t)H2 * W2, P4 = (size_t)H4 * W4, P8 = (size_t)down2(H4) * down2(W4);
+        size_t S = std::max(P2 * 64 * 2, P4 * 256 * 2);
+        S = std::max(S, (P2 * 128 * 2 + 1) / 2);
+        S = std::max(S, 2 * (P8 * 256 * 2 + 256));
+        if (p.comp) S *= 2;   // hi plane + corr plane per tensor (the corr plane follows the hi plane inside the slot)
+        p.slot.bytes = (S + 255) & ~(size_t)255;
     }
     p.x3_pp = x3 && c->opt_x3_pp;
     p.x3_fast = p.x3_pp && !det;     // (the parity entry point: every tensor as fp32 for sfd2_debug_activation)
-    if (p.x3_fast) {
-        p.x3_stem = c->w1b_stem_x3.p && c->c1a.wc.p;
-        p.x3_rb = c->rb1[0].wfh.p && c->rb1[0].wfl.p && c->rb2[0].w.p && c->rb2[0].wlk.p;
-        // (a layer whose only reader takes planes writes planes and no fp32 tensor: conv2a -> conv2b -> conv3a -> conv3b -> ResBlocks)
-        p.k2b = x3_fast_kind(p, c->f2b, false, H4, W4) != 0;
-        p.k3a = x3_fast_kind(p, c->f3a, false, H4, W4) != 0;
-        p.k3b = x3_fast_kind(p, c->f3b, false, H4, W4) != 0;
-        // Option "s2d" in this mode too (round 5): conv2a (conv3x3_pp<x3>) stores its planes space-to-depth and conv2b runs as a stride-1 layer over
-        // them (conv2b_s2d_kernel<x3>) instead of on the strided conv3x3_rf<2, x3>; planes out for conv3a
-        p.s2d_x3 = c->opt_s2d && p.k2b && p.k3a && x3_fast_kind(p, c->f2a, false, H2, W2) == 1 && conv2b_s2d_serves(H2, W2, c->f2b.cin, c->f2b.cout_pad) &&
-                   H4 * 2 == H2 && W4 * 2 == W2;
-        p.da0_planes = p.skip_da3;   // (the sparse descriptor head reads convDa.0's output as planes)
-        // Option "x3_desc16" (on the backbone output's planes, which the ResBlocks on planes leave behind)
-        p.desc16 = p.da0_planes && c->opt_x3_desc16 && p.x3_rb && c->da0.w.p && c->da0.scale_rawin.p && c->da3.w.p && c->db.w.p;
+    if (!p.f32) return p;
+    const int Hl[4] = {H, H2, H4, down2(H4)}, Wl[4] = {W, W2, W4, down2(W4)};
+    for (int i = 0; i < SL_COUNT; ++i) {
+        const ConvW &L = strict_layer(c, i);
+        const int lo = sl_level[i] + (L.stride == 2);
+        p.sl[i].kind = x3_fast_kind(p, L, i >= SL_RB3 && i < SL_RB3 + 3 /* + skip connection */, Hl[lo], Wl[lo]);
     }
+    if (p.skip_da3) p.sl[SL_DA3].kind = p.sl[SL_DB].kind = XK_SKIP;   // (sfd2_extract runs them on the sampled corners)
+    if (!p.x3_fast) return p;        // every three-pass layer splits its fp32 input into the scratch planes and writes fp32
+    p.x3_stem = c->w1b_stem_x3.p && c->c1a.wc.p;
+    p.x3_rb = c->rb1[0].wfh.p && c->rb1[0].wfl.p && c->rb2[0].w.p && c->rb2[0].wlk.p;
+    // Option "x3_desc16" (on the backbone output's planes, which the ResBlocks on planes leave behind)
+    p.desc16 = p.skip_da3 && c->opt_x3_desc16 && p.x3_rb && c->da0.w.p && c->da0.scale_rawin.p && c->da3.w.p && c->db.w.p;
+    if (p.x3_stem) p.sl[SL_C1B].kind = XK_SKIP;
+    for (int i = SL_RB1; i < SL_RB3 + 3 && p.x3_rb; ++i) p.sl[i].kind = XK_SKIP;
+    if (p.desc16) p.sl[SL_DA0].kind = XK_SKIP;
+    // Option "s2d" in this mode too (round 5): conv2a (conv3x3_pp<x3>) stores its planes space-to-depth and conv2b runs as a stride-1 layer over
+    // them (conv2b_s2d_kernel<x3>) instead of on the strided conv3x3_rf<2, x3>; planes out for conv3a
+    if (c->opt_s2d && on_planes(p.sl[SL_C2B]) && on_planes(p.sl[SL_C3A]) && p.sl[SL_C2A].kind == XK_PP &&
+        conv2b_s2d_serves(H2, W2, c->f2b.cin, c->f2b.cout_pad) && H4 * 2 == H2 && W4 * 2 == W2) {
+        p.sl[SL_C2A].s2d_out = true, p.sl[SL_C2B].kind = XK_S2D;
+    }
+    // Plane hand-offs: a three-pass layer whose only reader takes planes writes planes and no fp32 tensor (conv2a -> conv2b -> conv3a -> conv3b ->
+    // ResBlocks, convPa.0 -> convPa.3, convDa.0 -> the sparse descriptor head).  `have`: where the tensor in front of the layer at hand lives.
+    // route(layer, its reader takes planes, where): where = X3_CHAIN_A stands for "the chain": buffer B when the input sits in A, A otherwise
+    X3Out have = p.x3_stem ? X3_CHAIN_A : X3_F32;
+    auto route = [&](int i, bool planes_out, X3Out where = X3_CHAIN_A) {
+        StrictConv &s = p.sl[i];
+        s.planes_in = on_planes(s) && have != X3_F32;
+        if (on_planes(s) && planes_out) s.out = (where == X3_CHAIN_A && s.planes_in && have == X3_CHAIN_A) ? X3_CHAIN_B : where;
+        have = s.out;
+    };
+    route(SL_C2A, on_planes(p.sl[SL_C2B]));
+    route(SL_C2B, on_planes(p.sl[SL_C3A]));
+    route(SL_C3A, on_planes(p.sl[SL_C3B]));
+    route(SL_C3B, p.x3_rb, X3_RB);
+    const X3Out backbone = p.x3_rb ? X3_RB : X3_F32;      // (the last ResBlock on planes writes its fp32 tensor as well: generic readers take that)
+    have = backbone;
+    route(SL_PA0, on_planes(p.sl[SL_PA3]));
+    route(SL_PA3, false);
+    have = backbone;
+    if (!p.desc16) route(SL_DA0, p.skip_da3, X3_DA0);
+    if (!p.skip_da3) route(SL_DA3, false);
     return p;
 }
 
-// Buffers are allocated for the path that is about to run only: the throughput path needs the 3-slot
-// arena + head outputs, the layer-wise paths one buffer per activation, strict mode the fp32 set.  The activations are
-// registered for sfd2_debug_activation as the plan will leave them.
+// Everything the pass about to run touches is allocated here, and nothing else: the throughput path gets the arena + head outputs, the layer-wise
+// paths one buffer per activation, the strict family the fp32 set, the plane buffers its plan routes a layer through and the split filter forms its kernels
+// read (ensure_strict_filters); run_network allocates nothing.  The activations are registered for sfd2_debug_activation as the plan will leave them.
 int ensure_workspace(sfd2_ctx *c, const PassPlan &p, int H, int W)
 {
     if (H < 8 || W < 8) return fail("image too small (need H, W >= 8)");
@@ -161,6 +199,7 @@ int ensure_workspace(sfd2_ctx *c, const PassPlan &p, int H, int W)
     // SFD2_PREC_F16C: every backbone activation is a hi plane followed by its corr plane (same geometry)
     const size_t bb = comp ? 2 * hb : hb;
     if (!p.f32 && !p.fused_stem) HIPCHECK(c->a1a.ensure(P1 * 64 * bb));
+    if (p.alias) HIPCHECK(c->arena.ensure(p.slot.n * p.slot.bytes));
     if (layers) {
         HIPCHECK(c->a1b.ensure(P2 * 64 * bb));
         HIPCHECK(c->a2a.ensure(P2 * 128 * bb));
@@ -227,6 +266,24 @@ int ensure_workspace(sfd2_ctx *c, const PassPlan &p, int H, int W)
         HIPCHECK(c->gpa_o.ensure(P8 * 256 * fb));
         HIPCHECK(c->gda0_o.ensure(P4 * 256 * fb));
         HIPCHECK(c->gda_o.ensure(P4 * 256 * fb));
+        // SFD2_PREC_F16X3 (none of this with "x3_pp" = 0): the scratch planes for the largest input split in front of its layer, each hand-off buffer for the largest output routed into it
+        if (p.sparse_x3 && !p.desc16 && p.sl[SL_DA0].out != X3_DA0) return fail("f16x3: the sparse descriptor head needs convDa.0 on a three-pass kernel (planes out)");
+        const size_t Pl[4] = {P1, P2, P4, P8}, pb = 2 * hb;
+        size_t scratch = 0, chain[2] = {p.x3_stem ? std::max(P2 * 64, P4 * 256) : 0, 0}, da0 = p.desc16 ? P4 * 256 : 0;
+        for (int i = 0; i < SL_COUNT; ++i) {
+            const StrictConv &s = p.sl[i];
+            const ConvW &L = strict_layer(c, i);
+            if (!on_planes(s)) continue;
+            const size_t nout = Pl[sl_level[i] + (L.stride == 2)] * L.cout_pad;
+            if (!s.planes_in) scratch = std::max(scratch, Pl[sl_level[i]] * L.cin);
+            if (s.out == X3_CHAIN_A || s.out == X3_CHAIN_B) chain[s.out - X3_CHAIN_A] = std::max(chain[s.out - X3_CHAIN_A], nout);
+            if (s.out == X3_DA0) da0 = nout;
+        }
+        HIPCHECK(c->x3_planes.ensure(scratch * pb));
+        for (int k = 0; k < 2; ++k) HIPCHECK(c->x3_chain[k].ensure(chain[k] * pb));
+        for (int k = 0; k < 3 && p.x3_rb; ++k) HIPCHECK(c->x3_rb_planes[k].ensure(P4 * 256 * pb));
+        HIPCHECK(c->x3_da0_planes.ensure(da0 * pb));
+        if (ensure_strict_filters(c, p)) return -1;
         // throughput path of SFD2_PREC_F16X3: from the stem to convDa.0 the tensors exist as hi / lo' planes only; the fp32 buffers are
         // written for the last ResBlock's output and convPa.3's.  sfd2_debug_activation must say so instead of handing back what an
         // earlier sfd2_det left in them
@@ -376,56 +433,43 @@ static void convc(sfd2_ctx *c, const PassPlan &p, const char *name, const ConvW 
                        out.as<half_t>(), out_c, Ho, Wo, L.sbyte, rs);
 }
 
-int convf(sfd2_ctx *c, const PassPlan &p, const char *name, const ConvW &L, const DevPtr &in, int H, int W, const DevPtr &out,
-          int Ho, int Wo, int relu, const float *res, X3Planes planes, bool s2d)
+static X3Pair planes_of(const DevBuf &b, size_t n) { return {b.as<half_t>(), b.as<half_t>() + n}; }
+static const DevBuf &plane_buf(const sfd2_ctx *c, X3Out o) { return o == X3_CHAIN_A ? c->x3_chain[0] : o == X3_CHAIN_B ? c->x3_chain[1] : o == X3_RB ? c->x3_rb_planes[0] : c->x3_da0_planes; }
+
+int convf(sfd2_ctx *c, const StrictConv &s, const char *name, const ConvW &L, const DevPtr &in, int H, int W, const DevPtr &out,
+          int Ho, int Wo, int relu, const float *res, X3Pair *planes)
 {
     char kn[64];
     const bool x3 = c->precision == SFD2_PREC_F16X3;
-    const int kind = x3_fast_kind(p, L, res != nullptr, Ho, Wo);
-    const bool use_rf = kind == 2;
-    if (kind != 0) {
-        // The 3x3 layers (half of this mode's time) on the throughput kernels: the input is split ONCE into hi / lo'
-        // planes (the generic kernel splits every staged piece, per tile and chunk), conv3x3_pp / conv3x3_rf stage the planes by direct
-        // copies and run their fp16 K loop three times (hi x hi, hi x lo', lo' x hi) into one accumulator; fp32 or planes out.
-        ConvW &Lm = const_cast<ConvW &>(L);
-        const size_t nfl = (size_t)L.ks * L.ks * L.cout_pad * L.cin, nin = (size_t)H * W * L.cin;
-        if (!L.wx3p.p) {
-            if (Lm.wx3p.ensure(nfl * 2 * sizeof(half_t)) != hipSuccess) return fail("out of device memory (f16x3 filter planes)");
-            launch_x3_split_planes(c->stream, L.w.as<float>(), nfl, Lm.wx3p.p, Lm.wx3p.as<half_t>() + nfl);
+    if (s.kind == XK_SKIP) return fail(std::string(name) + ": the pass plan does not run this layer");
+    if (s.kind != XK_GENERIC) {
+        // The 3x3 layers (half of this mode's time) on the throughput kernels: the input is split ONCE into hi / lo' planes (the generic kernel
+        // splits every staged piece, per tile and chunk) unless its producer left them behind, the kernel stages the planes by direct copies and runs
+        // its fp16 K loop three times (hi x hi, hi x lo', lo' x hi) into one accumulator; fp32 out, or planes where the only reader takes planes.
+        const size_t nin = (size_t)H * W * L.cin, nout = (size_t)Ho * Wo * L.cout_pad;
+        const bool pre = s.planes_in;
+        const X3Pair pi = pre ? *planes : planes_of(c->x3_planes, nin);
+        const X3Pair po = s.out == X3_F32 ? X3Pair{} : planes_of(plane_buf(c, s.out), nout);
+        const half_t *wp = L.wx3p.as<half_t>();
+        if (planes) *planes = po;
+        if (s.kind == XK_S2D) {
+            ProfScope ps(c, name, "conv2b_s2d_kernel<x3>", 2.0 * (double)Ho * Wo * L.cout * L.cin * 9, 4.0 * nin + 4.0 * nout);
+            launch_conv2b_s2d_x3(c->stream, pi.hi, pi.lo, Ho, Wo, wp, L.scale.as<float>(), L.shift.as<float>(), relu, po.hi, po.lo, c->zero_page.as<half_t>());
+            return 0;
         }
-        const half_t *ph = nullptr, *pl = nullptr;
-        const bool pre = c->x3_pre_src == in.p && c->x3_pre_hi;     // the producer left the planes behind: no split
-        if (pre) { ph = c->x3_pre_hi; pl = c->x3_pre_lo; c->x3_pre_src = nullptr; }
-        else {
-            if (c->x3_planes.ensure(nin * 2 * sizeof(half_t)) != hipSuccess) return fail("out of device memory (f16x3 activation planes)");
-            ph = c->x3_planes.as<half_t>(); pl = ph + nin;
-        }
-        const size_t nout = (size_t)Ho * Wo * L.cout_pad;
-        half_t *oh = nullptr, *ol = nullptr;
-        if (planes != X3_NONE) {      // planes out (the only reader is the next 3x3 layer / the ResBlocks / the sparse descriptor head)
-            DevBuf &dst = planes == X3_DA0 ? c->x3_da0_planes : planes == X3_RB ? c->x3_rb_planes[0]
-                          : (ph == c->x3_chain.as<half_t>() ? c->x3_chain2 : c->x3_chain);
-            if (dst.ensure(nout * 2 * sizeof(half_t)) != hipSuccess) return fail("out of device memory (f16x3 activation planes)");
-            oh = dst.as<half_t>(); ol = oh + nout;
-            c->x3_pre_src = out.p; c->x3_pre_hi = oh; c->x3_pre_lo = ol;
-        }
-        snprintf(kn, sizeof(kn), "%sconv3x3_%s<x3%s>", pre ? "" : "x3_split_planes + ", use_rf ? "rf" : "pp", oh ? ", planes out" : "");
+        snprintf(kn, sizeof(kn), "%sconv3x3_%s<x3%s>", pre ? "" : "x3_split_planes + ", s.kind == XK_RF ? "rf" : "pp", po.hi ? ", planes out" : "");
         ProfScope ps(c, name, kn, 2.0 * (double)Ho * Wo * L.cout * L.cin * 9, (pre ? 4.0 : 12.0) * nin + 4.0 * nout);
-        if (!pre) launch_x3_split_planes(c->stream, in.as<float>(), nin, const_cast<half_t *>(ph), const_cast<half_t *>(pl));
-        if (use_rf && launch_conv3x3_rf_x3(c->stream, ph, pl, H, W, L.cin, L.wx3p.as<half_t>(), L.scale.as<float>(), L.shift.as<float>(), L.cout_pad,
-                                           L.stride, relu, oh, ol, oh ? nullptr : out.as<float>(), Ho, Wo, c->zero_page.as<half_t>()))
+        if (!pre) launch_x3_split_planes(c->stream, in.as<float>(), nin, pi.hi, pi.lo);
+        if (s.kind == XK_RF && launch_conv3x3_rf_x3(c->stream, pi.hi, pi.lo, H, W, L.cin, wp, L.scale.as<float>(), L.shift.as<float>(), L.cout_pad,
+                                                    L.stride, relu, po.hi, po.lo, po.hi ? nullptr : out.as<float>(), Ho, Wo, c->zero_page.as<half_t>()))
             return 0;
         if (L.stride != 1) { ps.cancel(); return fail("conv3x3_rf<x3>: no instantiation for this layer (x3_fast_kind and the launcher disagree)"); }
-        launch_conv3x3_pp_x3(c->stream, ph, pl, H, W, L.cin, L.wx3p.as<half_t>(), L.scale.as<float>(), L.shift.as<float>(), L.cout_pad, relu,
-                             oh, ol, oh ? nullptr : out.as<float>(), Ho, Wo, c->zero_page.as<half_t>(), (oh && s2d) ? 1 : 0);
+        launch_conv3x3_pp_x3(c->stream, pi.hi, pi.lo, H, W, L.cin, wp, L.scale.as<float>(), L.shift.as<float>(), L.cout_pad, relu,
+                             po.hi, po.lo, po.hi ? nullptr : out.as<float>(), Ho, Wo, c->zero_page.as<half_t>(), (po.hi && s.s2d_out) ? 1 : 0);
         return 0;
     }
-    if (x3 && !L.wx3.p) {      // split the packed filters once: the kernel then stages them without arithmetic
-        ConvW &Lm = const_cast<ConvW &>(L);
-        const size_t nfl = (size_t)L.ks * L.ks * L.cout_pad * L.cin;
-        if (Lm.wx3.ensure(nfl * sizeof(float)) != hipSuccess) return fail("out of device memory (f16x3 filters)");
-        launch_x3_split(c->stream, L.w.as<float>(), nfl, Lm.wx3.p);
-    }
+    if (planes) *planes = X3Pair{};
+    // (SFD2_PREC_F16X3: the packed filters split once, ConvW::wx3 -- the kernel then stages them without arithmetic)
     snprintf(kn, sizeof(kn), "conv_igemm_%s<%d,%d,%d>", x3 ? "x3" : "f32", L.ks, L.stride, (L.cout_pad % 128 == 0) ? 128 : 64);
     const double px = (double)Ho * Wo;
     ProfScope ps(c, name, kn, 2.0 * px * L.cout * L.cin * L.ks * L.ks,
@@ -441,49 +485,26 @@ static int run_network_f32(sfd2_ctx *c, const PassPlan &p, const float *img_dev,
     hipStream_t st = c->stream;
     const int H = c->H, W = c->W, H2 = c->H2, W2 = c->W2, H4 = c->H4, W4 = c->W4, H8 = c->H8, W8 = c->W8;
     const double P1 = (double)H * W, P4 = (double)H4 * W4, P8 = (double)H8 * W8;
-    c->x3_pre_src = nullptr;           // (no planes of an earlier pass are left over)
+    X3Pair pl;      // the planes of the tensor in front of the next layer, where its producer left them (plan_pass)
     if (p.x3_stem) {
         // throughput path of SFD2_PREC_F16X3: the fused stem in three-pass arithmetic (conv1a's image and filters as hi + lo fp16 as
         // in the compensated mode, conv1b on hi / lo' planes of conv1a's tile in LDS), its output as planes for conv2a
-        const size_t nout = (size_t)H2 * W2 * 64;
-        HIPCHECK(c->x3_chain.ensure(std::max(nout, (size_t)H4 * W4 * 256) * 2 * sizeof(half_t)));
+        pl = planes_of(c->x3_chain[0], (size_t)H2 * W2 * 64);
         ProfScope ps(c, "conv1a+conv1b", "fused_stem_c_kernel<x3>", 2.0 * P1 * 64 * 27 + 2.0 * (double)H2 * W2 * 64 * 576, P1 * 12 + (double)H2 * W2 * 256);
         launch_fused_stem_c(st, img_dev, H, W, normalise, c->c1a.wc.as<half_t>(), c->f1a.scale.as<float>(), c->f1a.shift.as<float>(),
-                            c->w1b_stem_x3.p, c->f1b.scale.as<float>(), c->f1b.shift.as<float>(), c->x3_chain.as<half_t>(),
-                            c->x3_chain.as<half_t>() + nout, H2, W2, -1);
-        c->x3_pre_src = c->g1b.p; c->x3_pre_hi = c->x3_chain.as<half_t>(); c->x3_pre_lo = c->x3_chain.as<half_t>() + nout;
+                            c->w1b_stem_x3.p, c->f1b.scale.as<float>(), c->f1b.shift.as<float>(), pl.hi, pl.lo, H2, W2, -1);
     } else {
     {
         ProfScope ps(c, "conv1a", "conv1a_f32_kernel", 2.0 * P1 * 64 * 27, P1 * (12 + 256));
         launch_conv1a_f32(st, img_dev, H, W, normalise, c->f1a.w.as<float>(), c->f1a.scale.as<float>(),
                           c->f1a.shift.as<float>(), c->g1a.as<float>());
     }
-    if (convf(c, p, "conv1b", c->f1b, c->g1a, H, W, c->g1b, H2, W2, 1)) return -1;
+    if (convf(c, p.sl[SL_C1B], "conv1b", c->f1b, c->g1a, H, W, c->g1b, H2, W2, 1)) return -1;
     }
-    // (throughput path: a layer whose only reader takes planes writes planes and no fp32 tensor: conv2a -> conv2b -> conv3a -> conv3b ->
-    // ResBlocks, convDa.0 -> the sparse descriptor head)
-    if (convf(c, p, "conv2a", c->f2a, c->g1b, H2, W2, c->g2a, H2, W2, 1, nullptr, p.k2b ? X3_CHAIN : X3_NONE, p.s2d_x3)) return -1;
-    if (p.s2d_x3 && c->x3_pre_src == c->g2a.p && c->x3_pre_hi) {
-        ConvW &L = c->f2b;
-        const size_t nfl = (size_t)9 * L.cout_pad * L.cin, nout = (size_t)H4 * W4 * L.cout_pad;
-        if (!L.wx3p.p) {
-            HIPCHECK(L.wx3p.ensure(nfl * 2 * sizeof(half_t)));
-            launch_x3_split_planes(st, L.w.as<float>(), nfl, L.wx3p.p, L.wx3p.as<half_t>() + nfl);
-        }
-        const half_t *ph = c->x3_pre_hi, *pl = c->x3_pre_lo;
-        DevBuf &dst = (ph == c->x3_chain.as<half_t>()) ? c->x3_chain2 : c->x3_chain;
-        HIPCHECK(dst.ensure(nout * 2 * sizeof(half_t)));
-        half_t *oh = dst.as<half_t>(), *ol = oh + nout;
-        {
-            ProfScope ps(c, "conv2b", "conv2b_s2d_kernel<x3>", 2.0 * (double)H4 * W4 * L.cout * L.cin * 9, 4.0 * (double)H2 * W2 * L.cin + 4.0 * nout);
-            launch_conv2b_s2d_x3(st, ph, pl, H4, W4, L.wx3p.as<half_t>(), L.scale.as<float>(), L.shift.as<float>(), 1, oh, ol, c->zero_page.as<half_t>());
-        }
-        c->x3_pre_src = c->g2b.p; c->x3_pre_hi = oh; c->x3_pre_lo = ol;
-    } else if (convf(c, p, "conv2b", c->f2b, c->g2a, H2, W2, c->g2b, H4, W4, 1, nullptr, p.k3a ? X3_CHAIN : X3_NONE)) return -1;
-    if (convf(c, p, "conv3a", c->f3a, c->g2b, H4, W4, c->g3a, H4, W4, 1, nullptr, p.k3b ? X3_CHAIN : X3_NONE)) return -1;
-    if (convf(c, p, "conv3b", c->f3b, c->g3a, H4, W4, c->g3b, H4, W4, 1, nullptr, (p.x3_rb && p.k3b) ? X3_RB : X3_NONE)) return -1;
-    const bool rb_in_planes = c->x3_pre_src == c->g3b.p;      // conv3b left the ResBlocks' input planes in x3_rb_planes[0]
-    c->x3_pre_src = nullptr;
+    if (convf(c, p.sl[SL_C2A], "conv2a", c->f2a, c->g1b, H2, W2, c->g2a, H2, W2, 1, nullptr, &pl)) return -1;
+    if (convf(c, p.sl[SL_C2B], "conv2b", c->f2b, c->g2a, H2, W2, c->g2b, H4, W4, 1, nullptr, &pl)) return -1;
+    if (convf(c, p.sl[SL_C3A], "conv3a", c->f3a, c->g2b, H4, W4, c->g3a, H4, W4, 1, nullptr, &pl)) return -1;
+    if (convf(c, p.sl[SL_C3B], "conv3b", c->f3b, c->g3a, H4, W4, c->g3b, H4, W4, 1, nullptr, &pl)) return -1;
     const DevPtr *x = &c->g3b;
     static const char *nm1[3] = {"conv4.0.conv1", "conv4.1.conv1", "conv4.2.conv1"};
     static const char *nm2[3] = {"conv4.0.conv2", "conv4.1.conv2", "conv4.2.conv2"};
@@ -495,10 +516,9 @@ static int run_network_f32(sfd2_ctx *c, const PassPlan &p, const float *img_dev,
         // (pre-split operands, direct plane stores); the skip connection is read from the planes (22 significant bits) and only the
         // last block also writes the fp32 tensor its generic readers (convPa.0, ConvSta) take.
         const size_t nin = (size_t)H4 * W4 * 256;
-        for (int k = 0; k < 3; ++k) HIPCHECK(c->x3_rb_planes[k].ensure(nin * 2 * sizeof(half_t)));
         half_t *xh = c->x3_rb_planes[0].as<half_t>(), *xl = xh + nin, *th = c->x3_rb_planes[1].as<half_t>(), *tl = th + nin;
         half_t *uh = c->x3_rb_planes[2].as<half_t>(), *ul = uh + nin;
-        if (!rb_in_planes) {
+        if (p.sl[SL_C3B].out != X3_RB) {      // conv3b on the generic kernel
             ProfScope ps(c, "conv3b planes", "x3_split_planes", 0.0, 12.0 * nin);
             launch_x3_split_planes(st, x->as<float>(), nin, xh, xl);
         }
@@ -521,16 +541,12 @@ static int run_network_f32(sfd2_ctx *c, const PassPlan &p, const float *img_dev,
             }
         }
         x = &c->gro[2];
-        c->x3_pre_src = x->p; c->x3_pre_hi = xh; c->x3_pre_lo = xl;     // the backbone output's planes: convDa.0 takes them as they are
+        pl = {xh, xl};
     }
     for (int b = 0; b < (p.x3_rb ? 0 : 3); ++b) {
-        if (convf(c, p, nm1[b], c->frb1[b], *x, H4, W4, c->grt1[b], H4, W4, 1)) return -1;
+        if (convf(c, p.sl[SL_RB1 + b], nm1[b], c->frb1[b], *x, H4, W4, c->grt1[b], H4, W4, 1)) return -1;
         {
             if (c->precision == SFD2_PREC_F16X3) {
-                if (!c->frb2[b].wx3.p) {
-                    HIPCHECK(c->frb2[b].wx3.ensure((size_t)16 * 5 * 64 * 16 * sizeof(half_t)));
-                    launch_gconv_x3_pack(st, c->frb2[b].w.as<float>(), c->frb2[b].wx3.p);
-                }
                 ProfScope ps(c, nm2[b], "gconv_x3_kernel", 2.0 * P4 * 256 * 72, P4 * 256 * 8);
                 launch_gconv_x3(st, c->grt1[b].as<float>(), H4, W4, c->frb2[b].wx3.p, c->frb2[b].scale.as<float>(),
                                 c->frb2[b].shift.as<float>(), c->grt2[b].as<float>());
@@ -540,41 +556,28 @@ static int run_network_f32(sfd2_ctx *c, const PassPlan &p, const float *img_dev,
                                  c->frb2[b].shift.as<float>(), c->grt2[b].as<float>());
             }
         }
-        if (convf(c, p, nm3[b], c->frb3[b], c->grt2[b], H4, W4, c->gro[b], H4, W4, 1, x->as<float>())) return -1;
+        if (convf(c, p.sl[SL_RB3 + b], nm3[b], c->frb3[b], c->grt2[b], H4, W4, c->gro[b], H4, W4, 1, x->as<float>())) return -1;
         x = &c->gro[b];
     }
-    // (throughput path: convPa.0 reads the backbone output's planes and leaves its own output as planes for convPa.3)
-    const void *bb_src = c->x3_pre_src;
-    const half_t *bb_hi = c->x3_pre_hi, *bb_lo = c->x3_pre_lo;
-    if (convf(c, p, "convPa.0", c->fpa0, *x, H4, W4, c->gpa0_o, H8, W8, 1, nullptr, p.x3_fast ? X3_CHAIN : X3_NONE)) return -1;
-    if (convf(c, p, "convPa.3", c->fpa3, c->gpa0_o, H8, W8, c->gpa_o, H8, W8, 0)) return -1;
-    if (convf(c, p, "convPb", c->fpb, c->gpa_o, H8, W8, c->logits, H8, W8, 0)) return -1;
-    c->x3_pre_src = bb_src; c->x3_pre_hi = bb_hi; c->x3_pre_lo = bb_lo;      // convDa.0 takes the same planes
+    // (throughput path: both head branches read the backbone output's planes; convPa.0 leaves its own output as planes for convPa.3)
+    const X3Pair backbone = pl;
+    if (convf(c, p.sl[SL_PA0], "convPa.0", c->fpa0, *x, H4, W4, c->gpa0_o, H8, W8, 1, nullptr, &pl)) return -1;
+    if (convf(c, p.sl[SL_PA3], "convPa.3", c->fpa3, c->gpa0_o, H8, W8, c->gpa_o, H8, W8, 0, nullptr, &pl)) return -1;
+    if (convf(c, p.sl[SL_PB], "convPb", c->fpb, c->gpa_o, H8, W8, c->logits, H8, W8, 0)) return -1;
+    pl = backbone;
     // Option "x3_desc16": the descriptor branch leaves this mode's arithmetic here -- convDa.0 as ONE fp16 pass (conv3x3_pp) over the backbone output's hi
     // plane, at the network's own scale (scale_rawin), its output (times 2^act_exp[AE_DA0], what convDa.3's folded constants expect) in the buffer
     // the planes would have taken; sfd2_extract then runs the fp16 sparse head on it.  The detector branch above is untouched.
     if (p.desc16) {
-        const size_t nin = (size_t)H4 * W4 * 256;
-        HIPCHECK(c->x3_da0_planes.ensure(nin * 2 * sizeof(half_t)));
         DevPtr in, out;
-        in.p = const_cast<half_t *>(bb_hi);
+        in.p = backbone.hi;
         out.p = c->x3_da0_planes.p;
         conv(c, "convDa.0", c->da0, in, H4, W4, out, H4, W4, 1, nullptr, 0, c->da0.scale_rawin.as<float>());
         c->da0_cur = c->x3_da0_planes.as<half_t>();
-    } else if (convf(c, p, "convDa.0", c->fda0, *x, H4, W4, c->gda0_o, H4, W4, 1, nullptr, p.da0_planes ? X3_DA0 : X3_NONE)) return -1;
-    c->x3_pre_src = nullptr;
-    if (p.desc16) {
-        // (nothing: convDa.3 and convDb run on the sampled corners, in fp16)
-    } else if (p.skip_da3) {      // sparse descriptor head of SFD2_PREC_F16X3 (sfd2_extract): convDa.3 and convDb run on the sampled corners only
-        const size_t nin = (size_t)H4 * W4 * 256;
-        if (!p.da0_planes) {
-            HIPCHECK(c->x3_da0_planes.ensure(nin * 2 * sizeof(half_t)));
-            ProfScope ps(c, "convDa.0 planes", "x3_split_planes", 0.0, 12.0 * nin);
-            launch_x3_split_planes(st, c->gda0_o.as<float>(), nin, c->x3_da0_planes.p, c->x3_da0_planes.as<half_t>() + nin);
-        }
-    } else {
-        if (convf(c, p, "convDa.3", c->fda3, c->gda0_o, H4, W4, c->gda_o, H4, W4, 0)) return -1;
-        if (convf(c, p, "convDb", c->fdb, c->gda_o, H4, W4, c->draw, H4, W4, 0)) return -1;
+    } else if (convf(c, p.sl[SL_DA0], "convDa.0", c->fda0, *x, H4, W4, c->gda0_o, H4, W4, 1, nullptr, &pl)) return -1;
+    if (!p.skip_da3) {      // (otherwise sfd2_extract's sparse descriptor head runs them on the sampled corners: on convDa.0's planes, or in fp16 with "x3_desc16")
+        if (convf(c, p.sl[SL_DA3], "convDa.3", c->fda3, c->gda0_o, H4, W4, c->gda_o, H4, W4, 0, nullptr, &pl)) return -1;
+        if (convf(c, p.sl[SL_DB], "convDb", c->fdb, c->gda_o, H4, W4, c->draw, H4, W4, 0)) return -1;
     }
     if (c->has_sta) {
         ProfScope ps(c, "ConvSta", "convsta_f32_kernel", 2.0 * P4 * 3 * 256, P4 * (1024 + 12));
@@ -604,13 +607,7 @@ int run_network(sfd2_ctx *c, const PassPlan &p, const float *img_dev, int normal
     DevPtr t1v[3] = {c->rt1[0], c->rt1[1], c->rt1[2]}, t2v[3] = {c->rt2[0], c->rt2[1], c->rt2[2]},
            rov[3] = {c->ro[0], c->ro[1], c->ro[2]};
     if (alias) {
-        const size_t P2 = (size_t)H2 * W2, P4s = (size_t)H4 * W4, P8s = (size_t)H8 * W8;
-        size_t S = std::max(P2 * 64 * 2, P4s * 256 * 2);
-        S = std::max(S, (P2 * 128 * 2 + 1) / 2);
-        S = std::max(S, 2 * (P8s * 256 * 2 + 256));
-        if (comp) S *= 2;   // hi plane + corr plane per tensor (the corr plane follows the hi plane inside the slot)
-        S = (S + 255) & ~(size_t)255;
-        HIPCHECK(c->arena.ensure(p.slot.n * S));
+        const size_t P8s = (size_t)H8 * W8, S = p.slot.bytes;
         char *base = c->arena.as<char>();
         auto slot = [&](int i, size_t off = 0) { DevPtr v; v.p = base + (size_t)i * S + off; v.cap = 0; return v; };
         a1b = slot(p.slot.a1b); a2a = slot(p.slot.a2a); a2b = slot(p.slot.a2b); a3a = slot(p.slot.a3a); a3b = slot(p.slot.a3b);

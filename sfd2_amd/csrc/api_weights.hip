@@ -449,6 +449,43 @@ static int pack_all_f32(sfd2_ctx *c, const TMap &m)
     return 0;
 }
 
+// SFD2_PREC_F16X3 reads the fp32 layers' filters pre-split into fp16 parts, in the form the kernel of the plan at hand takes: ConvW::wx3 for the
+// generic igemm and the grouped conv, wx3p (hi plane, lo' plane) for the three-pass 3x3 kernels, convDa.3's wx3p + wsl for the sparse descriptor
+// head.  Made here, on c->stream in front of the pass (ensure_workspace), for exactly the layers that plan runs -- not by sfd2_load_weights:
+// precision and options may be set after loading, and a mode that never reads a form should not pay its memory.  Kept until the next load.
+int ensure_strict_filters(sfd2_ctx *c, const PassPlan &p)
+{
+    if (c->precision != SFD2_PREC_F16X3) return 0;
+    auto split = [&](ConvW &L, bool planes) -> int {
+        const size_t nfl = (size_t)L.ks * L.ks * L.cout_pad * L.cin;
+        DevBuf &dst = planes ? L.wx3p : L.wx3;
+        if (dst.p) return 0;
+        if (dst.ensure(nfl * 2 * sizeof(half_t)) != hipSuccess) return fail("out of device memory (f16x3 filters)");
+        if (planes) launch_x3_split_planes(c->stream, L.w.as<float>(), nfl, dst.p, dst.as<half_t>() + nfl);
+        else launch_x3_split(c->stream, L.w.as<float>(), nfl, dst.p);
+        return 0;
+    };
+    for (int i = 0; i < SL_COUNT; ++i)
+        if (p.sl[i].kind != XK_SKIP && split(strict_layer(c, i), p.sl[i].kind != XK_GENERIC)) return -1;
+    for (int b = 0; b < 3 && p.sl[SL_RB1].kind != XK_SKIP; ++b) {      // the grouped conv of the ResBlocks off the planes (gconv_x3_kernel)
+        ConvW &L = c->frb2[b];
+        if (L.wx3.p) continue;
+        HIPCHECK(L.wx3.ensure((size_t)16 * 5 * 64 * 16 * sizeof(half_t)));
+        launch_gconv_x3_pack(c->stream, L.w.as<float>(), L.wx3.p);
+    }
+    if (p.sparse_x3 && !p.desc16) {      // sfd2_extract's sparse descriptor head: sparse_da3_kernel<x3>, then convDb on the compact pixels (generic kernel)
+        ConvW &L3 = c->fda3;
+        if (split(L3, true) || split(c->fdb, false)) return -1;
+        if (!L3.wsl.p && L3.cin == 256) {                     // both planes in sparse_da3_kernel's fragment order (ConvW::wsl)
+            const size_t nfl = (size_t)9 * L3.cout_pad * L3.cin;
+            HIPCHECK(L3.wsl.ensure(nfl * 2 * sizeof(half_t)));
+            launch_sparse_da3_repack(c->stream, L3.wx3p.as<half_t>(), L3.wsl.as<half_t>(), L3.cout_pad, L3.cin);
+            launch_sparse_da3_repack(c->stream, L3.wx3p.as<half_t>() + nfl, L3.wsl.as<half_t>() + nfl, L3.cout_pad, L3.cin);
+        }
+    }
+    return 0;
+}
+
 static int calibrate_on_probe(sfd2_ctx *c);
 
 extern "C" int sfd2_load_weights(sfd2_ctx *c, const sfd2_tensor *tensors, int n)
@@ -458,7 +495,7 @@ extern "C" int sfd2_load_weights(sfd2_ctx *c, const sfd2_tensor *tensors, int n)
     HIPCHECK(hipStreamSynchronize(c->stream));
     c->weights_loaded = false;   // a failure part-way must not leave a half-replaced set usable
     graphs_release(c);           // captured units hold pointers into the filter buffers
-    {   // SFD2_PREC_F16X3 keeps split copies of the fp32 filters, made on first use: they belong to the OLD weights
+    {   // SFD2_PREC_F16X3 keeps split copies of the fp32 filters (ensure_strict_filters): they belong to the OLD weights
         ConvW *fl[] = {&c->f1a, &c->f1b, &c->f2a, &c->f2b, &c->f3a, &c->f3b, &c->frb1[0], &c->frb1[1], &c->frb1[2], &c->frb2[0],
                        &c->frb2[1], &c->frb2[2], &c->frb3[0], &c->frb3[1], &c->frb3[2], &c->fpa0, &c->fpa3, &c->fda0, &c->fda3,
                        &c->fpb, &c->fdb};

@@ -78,8 +78,8 @@ struct ConvW {                 // one folded + packed layer
                                // fp16 pass over a PLAIN input, option "rb_inner") in the kernel's fragment order [8 waves][8][64 lanes][16]
     DevBuf wlk;                // grouped 3x3: the same residuals in w's fragment layout (gconv_c_kernel<false, false>)
     DevBuf wgc;                // grouped 3x3: compact [256 oc][9 taps][8 in] fp16 (resblock_kernel)
-    DevBuf wx3;                // fp32 layers, SFD2_PREC_F16X3: every float4 of w as (4 hi, 4 lo) fp16, made on first use
-    DevBuf wx3p;               // ... or as two planes (hi, lo') for conv3x3_pp's three-pass instantiation (3x3 stride-1 layers)
+    DevBuf wx3;                // fp32 layers, SFD2_PREC_F16X3: every float4 of w as (4 hi, 4 lo) fp16 for the generic kernel (grouped conv: gconv_x3_kernel's packing) ...
+    DevBuf wx3p;               // ... or as two planes (hi, lo') for the three-pass 3x3 kernels; both (and convDa.3's wsl in this mode) made by ensure_strict_filters for the plan about to run
     DevBuf wc;                 // SFD2_PREC_F16C: [2 * cin / 32][taps][cout_pad][32] units -- the fp16 filters in 32-wide chunks, then the
                                // corr units (fp8 of w * 2^b0, fp8 of (w - fp16(w)) * 2^(b0 + 11)); conv1a / grouped conv: hi then lo fragments
     int sbyte = 127;           // E8M0 scale byte of the layer's corr MFMAs: 127 - 9 - b0
@@ -163,11 +163,8 @@ struct sfd2_ctx {
     int opt_cu_limit = 0;              // sfd2_set_option "cu_limit": persistent kernels of THIS context launch at most so many blocks
     int fuse_det = 0;                  // sfd2_set_option "fuse_det"
     int use_graphs = 0;                // sfd2_set_option "graphs"
-    DevBuf x3_chain2;                  // second buffer of the plane chain (a layer never writes the planes it reads)
-    DevBuf x3_rb_planes[3];            // a ResBlock's input, conv1's and the grouped conv's outputs as hi / lo' planes
-    const void *x3_pre_src = nullptr;  // set by a producer that wrote its output as planes too: the fp32 tensor they belong to ...
-    const half_t *x3_pre_hi = nullptr, *x3_pre_lo = nullptr;   // ... and the planes (consumed by the next convf on that tensor)
-    DevBuf x3_chain;                   // planes handed from conv3a to conv3b (throughput path of f16x3)
+    DevBuf x3_chain[2];                // f16x3 tensors as hi / lo' planes (hi, then lo'; who reads and writes which buffer: PassPlan::sl).  X3_CHAIN_A / B: handed from one 3x3 layer to the next
+    DevBuf x3_rb_planes[3];            // a ResBlock's input (X3_RB), conv1's and the grouped conv's outputs
     int opt_fuse_post = 1;             // sfd2_set_option "fuse_post": heads -> heat map -> NMS in one kernel on the extract path
     int opt_sparse_desc = 1;           // sfd2_set_option "sparse_desc": extract path runs convDb on the sampled corner pixels only
     const half_t *da0_cur = nullptr;   // convDa.0 output of the last fp16 network pass
@@ -200,8 +197,8 @@ struct sfd2_ctx {
     int opt_x3_desc16 = 0;             // sfd2_set_option "x3_desc16": SFD2_PREC_F16X3 on sfd2_extract with the DESCRIPTOR branch (convDa.0, convDa.3 at the sampled corners,
                                        // convDb) in plain fp16 on the backbone output's hi plane: the key points are this mode's own, the descriptors carry the
                                        // fp16 head's error only (<= 1e-3: north_star's tolerance, not this mode's 2e-5)
-    DevBuf x3_planes;                  // the input of such a layer as hi / lo' planes
-    DevBuf x3_da0_planes;              // convDa.0's output as planes (sparse descriptor head of f16x3)
+    DevBuf x3_planes;                  // scratch planes: the fp32 input of a three-pass 3x3 layer whose producer left no planes, split in front of it
+    DevBuf x3_da0_planes;              // X3_DA0: convDa.0's output as planes (sparse descriptor head of f16x3); with "x3_desc16" its fp16 output
     DevBuf db_sparse;                  // [sel_cap][4][128] fp32: convDb on the sampled corners (f16x3)
     int opt_sparse_da3 = 1;            // sfd2_set_option "sparse_da3": with the sparse descriptor head, convDa.3 on the sampled corners only
     int opt_fuse_pb = 1;               // sfd2_set_option "fuse_pb": convPb inside the fused detector-head / heat-map kernel
@@ -255,7 +252,7 @@ struct sfd2_ctx {
     int last_sel_cap = 0;
     float *kpts_cur = nullptr, *kscores_cur = nullptr;   // where the last selection wrote its key points
     // scale pyramid staging (sfd2_extract_multiscale)
-    DevBuf arena;   // aliased activation slots of the throughput path (run_network)
+    DevBuf arena;   // aliased activation slots of the throughput path (placed by plan_pass, sized by ensure_workspace)
     DevBuf img_u8_packed;              // SFD2_FLAG_IMG_U8_X: the image as three bytes per pixel (unpack_rgbx_kernel)
     JpegScratch jpeg;                  // sfd2_jpeg_decode
     JpegBuf pose_in, pose_ws, pose_out; // sfd2_absolute_pose_batch / sfd2_pose_refine_batch (api_pose.hip): inputs, per-point work, results
@@ -340,7 +337,21 @@ struct FallbackScope {      // the repeat: strict arithmetic, no recursion
 // geometry and which packed weight arrays exist; ensure_workspace allocates and registers the activations from it, the dispatch reads it.
 enum PassEntry { PASS_DET /* parity: every activation readable unless "fuse_det" */, PASS_DENSE /* throughput kernels, dense head maps (pyramids,
                  spp) */, PASS_EXTRACT /* sfd2_extract: the heads fused into the post-processing, the sparse descriptor head */ };
-enum X3Planes { X3_NONE, X3_CHAIN, X3_DA0, X3_RB };   // where a three-pass 3x3 layer (SFD2_PREC_F16X3) stores its output as hi / lo' planes
+// The conv layers of the strict pass (SFD2_PREC_F32 / F16X3) that go through convf, in pass order; the ResBlocks' 1x1 layers: + block
+enum StrictLayer { SL_C1B, SL_C2A, SL_C2B, SL_C3A, SL_C3B, SL_RB1, SL_RB3 = SL_RB1 + 3, SL_PA0 = SL_RB3 + 3, SL_PA3, SL_PB, SL_DA0, SL_DA3, SL_DB, SL_COUNT };
+template <class Ctx> auto &strict_layer(Ctx *c, int i)     // (Ctx: sfd2_ctx or const sfd2_ctx)
+{
+    decltype(&c->f1b) t[] = {&c->f1b, &c->f2a, &c->f2b, &c->f3a, &c->f3b, &c->frb1[0], &c->frb1[1], &c->frb1[2], &c->frb3[0], &c->frb3[1], &c->frb3[2],
+                             &c->fpa0, &c->fpa3, &c->fpb, &c->fda0, &c->fda3, &c->fdb};
+    static_assert(sizeof(t) == SL_COUNT * sizeof(t[0]), "one entry per StrictLayer");
+    return *t[i];
+}
+// The kernel such a layer runs on: the generic igemm (fp32 in / out: conv_igemm_f32, conv_igemm_x3) or one of SFD2_PREC_F16X3's three-pass 3x3 kernels on hi / lo' planes
+// (conv3x3_pp<x3>, conv3x3_rf<x3>, conv2b_s2d_kernel<x3>).  XK_SKIP: not run by this pass (the fused stem, the ResBlocks on planes, sfd2_extract's sparse descriptor head)
+enum X3Kind { XK_GENERIC, XK_PP, XK_RF, XK_S2D, XK_SKIP };
+enum X3Out { X3_F32, X3_CHAIN_A, X3_CHAIN_B, X3_RB, X3_DA0 };   // where its output goes: the fp32 tensor, or planes only in one of the context's plane buffers
+struct StrictConv { X3Kind kind = XK_GENERIC; bool planes_in = false; X3Out out = X3_F32; bool s2d_out = false; };   // planes_in: the producer left the input as planes (otherwise split into x3_planes first); s2d_out: planes stored space-to-depth (conv2a, for XK_S2D)
+struct X3Pair { half_t *hi = nullptr, *lo = nullptr; };   // the planes of one tensor
 struct PassPlan {
     bool f32 = false, comp = false;          // the fp32 buffers (SFD2_PREC_F32 / F16X3); SFD2_PREC_F16C
     bool fuse = false, alias = false;        // fused kernels; the arena slots instead of one buffer per activation
@@ -356,16 +367,19 @@ struct PassPlan {
     bool branches = false, sta_early = false, sta_side = false;   // detector branch on the side stream; ConvSta before the heads / on the side stream
     bool skip_head = false, skip_pb = false, skip_db = false, skip_da3 = false;   // layers left to sfd2_extract's post-processing
     bool sparse_desc = false, sparse_da3 = false, sparse_x3 = false;           // its sparse descriptor head: fp16, fp16 with convDa.3, f16x3
-    struct { int a1b, a2a, a2b, a3a, a3b, t1[3], t2[3], ro[3], pa0, pa, da0, da, n; } slot = {};   // alias: each tensor's arena slot, slots in all
+    struct { int a1b, a2a, a2b, a3a, a3b, t1[3], t2[3], ro[3], pa0, pa, da0, da, n; size_t bytes; } slot = {};   // alias: each tensor's arena slot, slots in all, bytes per slot
     bool x3_pp = false, x3_fast = false;     // f16x3: 3x3 layers on the three-pass kernels ("x3_pp"); the throughput path's plane hand-offs
-    bool x3_stem = false, x3_rb = false;     // ... the fused three-pass stem; ResBlocks on the planes
-    bool k2b = false, k3a = false, k3b = false, s2d_x3 = false;   // conv2b / conv3a / conv3b on a three-pass kernel; conv2a stores space-to-depth
-    bool da0_planes = false, desc16 = false; // convDa.0's output as planes; "x3_desc16": the descriptor branch in fp16 on the backbone's hi plane
+    bool x3_stem = false, x3_rb = false;     // ... the fused three-pass stem (planes in X3_CHAIN_A); ResBlocks on the planes
+    bool desc16 = false;                     // "x3_desc16": the descriptor branch in fp16 on the backbone's hi plane
+    StrictConv sl[SL_COUNT];                 // f32 / f16x3: every layer's kernel and where its planes come from and go
 };
 PassPlan plan_pass(const sfd2_ctx *c, PassEntry entry, int H, int W, int top_k = 0, bool desc = false);
-int ensure_workspace(sfd2_ctx *c, const PassPlan &p, int H, int W);
-int run_network(sfd2_ctx *c, const PassPlan &p, const float *img_dev, int normalise);
-int convf(sfd2_ctx *c, const PassPlan &p, const char *name, const ConvW &L, const DevPtr &in, int H, int W, const DevPtr &out, int Ho, int Wo,
-          int relu, const float *res = nullptr, X3Planes planes = X3_NONE, bool s2d = false);
+int ensure_workspace(sfd2_ctx *c, const PassPlan &p, int H, int W);   // allocates every buffer the pass touches and makes the filter forms it reads
+int run_network(sfd2_ctx *c, const PassPlan &p, const float *img_dev, int normalise);   // launches only
+// one layer of the strict family.  planes: in, the input's planes where s.planes_in; out, the output's (null pair: it went to the fp32 tensor)
+int convf(sfd2_ctx *c, const StrictConv &s, const char *name, const ConvW &L, const DevPtr &in, int H, int W, const DevPtr &out, int Ho, int Wo,
+          int relu, const float *res = nullptr, X3Pair *planes = nullptr);
+// api_weights.hip
+int ensure_strict_filters(sfd2_ctx *c, const PassPlan &p);   // SFD2_PREC_F16X3: the split filter forms (ConvW::wx3, wx3p, wsl) the plan's kernels read
 // api_extract.hip
 int copy_out(sfd2_ctx *c, void *dst, const void *src_dev, size_t bytes, int dst_on_device);

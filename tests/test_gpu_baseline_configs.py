@@ -666,6 +666,29 @@ def test_f16x3_throughput_kernels_equal_generic_path(synth_sd, h, w, topk):
 
 
 @pytest.mark.gpu
+def test_f16x3_one_context_across_entry_points_and_sizes_equals_fresh_contexts(synth_sd):
+    """Nothing of one f16x3 pass is state of the next: which planes a layer reads and writes, and how large the plane buffers are, is decided
+    per call.  One context through det -> extract -> extract at another size (odd: conv2b on the strided kernel) -> det -> extract at the
+    first size, both sizes with the sparse descriptor head: every result bit-equal to the same call on a fresh context."""
+    import oracle.oracle as orc
+    from sfd2_amd.extractor import extract_resnet_return
+    img_a, img_b = synth.make_image(240, 320, 802), synth.make_image(333, 517, 803)
+
+    def call(m, kind, img, topk):
+        if kind == "det":
+            return [np.asarray(t) for t in m.det(orc.norm_rgb(img)[None])]
+        g = extract_resnet_return(m, img[None], conf_th=0.001, topK=topk, scales=[1.0])
+        assert len(g["keypoints"]) > 0
+        return [g["keypoints"], g["scores"], g["descriptors"]]
+
+    one = _make(synth_sd, "f16x3")
+    for step, (kind, img, topk) in enumerate([("det", img_a, 0), ("extract", img_a, 200), ("extract", img_b, 300), ("det", img_b, 0), ("extract", img_a, 200)]):
+        got, want = call(one, kind, img, topk), call(_make(synth_sd, "f16x3"), kind, img, topk)
+        for g, w in zip(got, want):
+            np.testing.assert_array_equal(g, w, err_msg=f"step {step} ({kind})")
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("h,w,topk", [(480, 640, 1024), (200, 264, 300), (1200, 1600, 4096)])
 def test_f16x3_s2d_conv2b_equals_strided_kernel(synth_sd, h, w, topk):
     """Round 5: f16x3's conv2b as a stride-1 layer over conv2a's planes stored space-to-depth (conv2b_s2d_kernel<x3>, option 's2d') against
