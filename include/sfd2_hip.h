@@ -565,6 +565,61 @@ int sfd2_absolute_pose_batch(sfd2_ctx *ctx, const sfd2_pose_problem *problems, i
 int sfd2_pose_refine_batch(sfd2_ctx *ctx, const sfd2_pose_problem *problems, int k, const double *qvec_tvec_in,
                            const uint8_t *inlier_mask_u8, sfd2_pose_result *results, int flags);
 
+/* ------------------------------------------------------------------------------------------------ 2D-3D assembly
+ * Matches -> 2D-3D correspondences for a batch of jobs in one call: the per-key-point loops of it_loc/localize_cv2.py:571-632
+ * (match_cluster_2D) and :286-360 (pose_refinement_covisibility, with the reprojection gate).  A job is one query against its k
+ * database images.  For image i = 0..k-1, query key point idx ascending, a match is dropped when matches0 < 0, when the image's
+ * table has no 3D point for the matched key point, when the point's track length is < obs_th, when an earlier image of the job
+ * already took the same 3D point for this idx (the entry is made BEFORE the gate: a gated-out point still blocks its later
+ * duplicates), and, with gate != 0, when the point projected with (qvec, tvec, camera) in fp64 lies more than radius pixels from
+ * the key point (compared as `error > radius`, so a NaN error is kept; no depth test; the key point WITHOUT the +0.5 the output
+ * adds).  What survives is appended: order = image ascending, then idx ascending.  The order comes from prefix sums, never from
+ * atomics, so a job's output bytes depend on the job alone, not on the batch, its order or the run. */
+typedef struct {
+    const double *xyz;              /* device [n_points][3]                                                                */
+    const int32_t *track_len;       /* device [n_points]: len(points3D[id].image_ids)                                      */
+    int32_t n_points;
+    int32_t reserved;
+} sfd2_point_table;
+typedef struct {
+    const int32_t *point_rows;      /* device [n1]: key point -> row of the point table, or -1                             */
+    int32_t n1;                     /* 0: the image is skipped (localize_cv2.py:293-296, :577-580)                         */
+    int32_t match_row;              /* row of the job's matches0 that holds this image's matches; -1: an image without
+                                     * matches (one the <= 3 rule kept away from the matcher, :537-538)                     */
+} sfd2_assemble_image;
+typedef struct {
+    const int64_t *matches0;        /* device [match_rows][n], as sfd2_match_batch(out_on_device = 1) writes it: indices into
+                                     * the image's UNMASKED key points, < 0 = none.  An index >= n1 is an input error.      */
+    const sfd2_assemble_image *images;  /* host [k]                                                                         */
+    int32_t k, n, match_rows;
+    int32_t inputs_on_device;       /* keypoints / scores: 0 host, 1 device                                                */
+    const float *keypoints;         /* [n][2], as the feature store holds them                                             */
+    const float *scores;            /* [n] or NULL (output scores are then 0)                                              */
+    double obs_th;                  /* compared as (double)track_len < obs_th                                              */
+    int32_t gate;                   /* 0: no reprojection gate (the cluster stage)                                         */
+    int32_t model;                  /* gate: SFD2_CAM_*, params, pose and radius                                           */
+    double params[8];
+    double qvec[4], tvec[3];        /* qvec is normalised as the reference's scipy call does                               */
+    double radius;
+    int32_t capacity;               /* rows of every output buffer below                                                   */
+    int32_t m;                      /* OUT: correspondences of the job (also when m > capacity)                            */
+    int32_t status;                 /* OUT: 0, or bits: 1 a match index >= n1, 2 a table entry >= n_points, 4 m > capacity  */
+    int32_t reserved;
+    double *points2D;               /* OUT [m][2]: key point + 0.5                                                         */
+    double *points3D;               /* OUT [m][3]                                                                          */
+    int32_t *point_row;             /* OUT [m]: row of the point table                                                     */
+    int32_t *query_idx;             /* OUT [m]                                                                             */
+    int32_t *image_idx;             /* OUT [m]: position in images[]                                                       */
+    float *score;                   /* OUT [m]                                                                             */
+    int32_t *image_counts;          /* OUT, HOST [k]: correspondences per image                                            */
+} sfd2_assemble_job;
+/* Runs on sfd2_get_stream() behind whatever was queued there (an sfd2_match_batch with SFD2_FLAG_ASYNC and out_on_device = 1
+ * needs no synchronisation in between) and synchronises before it returns.  out_on_device: the six row buffers of every job are
+ * device (1) or host (0) memory; m, status and image_counts are always host.  Returns -1 when any job has a non-zero status (every
+ * job's m and status are filled; a job with a non-zero status writes no rows, the others are complete) or on a bad argument.
+ * flags: 0. */
+int sfd2_assemble_2d3d(sfd2_ctx *ctx, const sfd2_point_table *map, sfd2_assemble_job *jobs, int n_jobs, int out_on_device, int flags);
+
 #ifdef __cplusplus
 }
 #endif

@@ -102,6 +102,29 @@ class PoseResult(ctypes.Structure):
                 ("qvec", ctypes.c_double * 4), ("tvec", ctypes.c_double * 3)]
 
 
+class PointTable(ctypes.Structure):
+    """sfd2_point_table (include/sfd2_hip.h)."""
+    _fields_ = [("xyz", ctypes.c_void_p), ("track_len", ctypes.c_void_p), ("n_points", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class AssembleImage(ctypes.Structure):
+    """sfd2_assemble_image (include/sfd2_hip.h)."""
+    _fields_ = [("point_rows", ctypes.c_void_p), ("n1", ctypes.c_int32), ("match_row", ctypes.c_int32)]
+
+
+class AssembleJob(ctypes.Structure):
+    """sfd2_assemble_job (include/sfd2_hip.h)."""
+    _fields_ = [("matches0", ctypes.c_void_p), ("images", ctypes.POINTER(AssembleImage)), ("k", ctypes.c_int32), ("n", ctypes.c_int32),
+                ("match_rows", ctypes.c_int32), ("inputs_on_device", ctypes.c_int32), ("keypoints", ctypes.c_void_p), ("scores", ctypes.c_void_p),
+                ("obs_th", ctypes.c_double), ("gate", ctypes.c_int32), ("model", ctypes.c_int32), ("params", ctypes.c_double * 8),
+                ("qvec", ctypes.c_double * 4), ("tvec", ctypes.c_double * 3), ("radius", ctypes.c_double), ("capacity", ctypes.c_int32),
+                ("m", ctypes.c_int32), ("status", ctypes.c_int32), ("reserved", ctypes.c_int32), ("points2D", ctypes.c_void_p),
+                ("points3D", ctypes.c_void_p), ("point_row", ctypes.c_void_p), ("query_idx", ctypes.c_void_p), ("image_idx", ctypes.c_void_p),
+                ("score", ctypes.c_void_p), ("image_counts", ctypes.c_void_p)]
+
+
+ASM_ST_MATCH_RANGE, ASM_ST_ROW_RANGE, ASM_ST_CAPACITY = 1, 2, 4
+
 # every symbol include/sfd2_hip.h declares (tests/test_abi.py checks the two lists agree)
 EXPORTS = [
     "sfd2_version", "sfd2_last_error", "sfd2_ctx_create", "sfd2_ctx_destroy", "sfd2_get_stream",
@@ -113,6 +136,7 @@ EXPORTS = [
     "sfd2_get_range_status", "sfd2_range_tensor_name", "sfd2_calibrate_range", "sfd2_get_act_exponents", "sfd2_set_act_exponents",
     "sfd2_extract_record_async", "sfd2_desc_pack", "sfd2_get_margin_status", "sfd2_get_relax_status", "sfd2_get_option", "sfd2_device_pci_bus_id",
     "sfd2_jpeg_parse", "sfd2_jpeg_prepare", "sfd2_jpeg_decode", "sfd2_absolute_pose_batch", "sfd2_pose_refine_batch",
+    "sfd2_assemble_2d3d",
 ]
 
 _lib = None
@@ -198,10 +222,11 @@ def load():
     lib.sfd2_jpeg_decode.argtypes = [vp, vp, i64, ctypes.POINTER(JpegInfo), ci, vp, i64, vp, ci]
     lib.sfd2_absolute_pose_batch.argtypes = [vp, ctypes.POINTER(PoseProblem), ci, ctypes.POINTER(PoseConf), ctypes.POINTER(PoseResult), vp, ci]
     lib.sfd2_pose_refine_batch.argtypes = [vp, ctypes.POINTER(PoseProblem), ci, vp, vp, ctypes.POINTER(PoseResult), ci]
+    lib.sfd2_assemble_2d3d.argtypes = [vp, ctypes.POINTER(PointTable), ctypes.POINTER(AssembleJob), ci, ci, ci]
     for name in EXPORTS:
         getattr(lib, name)  # raises AttributeError if the .so lacks a declared symbol
-    if lib.sfd2_version() < 109:
-        raise RuntimeError(f"{LIB_PATH} is version {lib.sfd2_version()}, this binding needs >= 109 (rebuild: __graft_entry__.build())")
+    if lib.sfd2_version() < 111:
+        raise RuntimeError(f"{LIB_PATH} is version {lib.sfd2_version()}, this binding needs >= 111 (rebuild: __graft_entry__.build())")
     _lib = lib
     return lib
 

@@ -1,0 +1,195 @@
+"""The map side of the localiser's covisibility stage (it_loc/localize_cv2.py:120-233 and the helpers of it_loc/common.py it uses):
+a dense index over COLMAP's images / points3D dicts, the two covisible-frame selections, vectorised on the host, and the device
+buffers sfd2_assemble_2d3d reads (point table, per-image key point -> point row tables)."""
+import numpy as np
+
+from .pose import CAMERA_MODELS
+
+
+def qvec2rotmat(qvec):
+    """R of COLMAP's (w, x, y, z); the quaternion is normalised first, as scipy's Rotation.from_quat does (common.py:235)."""
+    q = np.asarray(qvec, dtype=np.float64).reshape(4)
+    w, x, y, z = q / np.linalg.norm(q)
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                     [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                     [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+
+
+def _opencv(camera):
+    model = camera["model"]
+    if not isinstance(model, str):
+        model = getattr(model, "name", str(model))
+    if model not in CAMERA_MODELS:
+        raise ValueError(f"camera model {model!r} is not supported (one of {', '.join(CAMERA_MODELS)})")
+    p = np.asarray(camera["params"], dtype=np.float64).reshape(-1)
+    if model == "SIMPLE_PINHOLE":
+        return p[0], p[0], p[1], p[2], 0.0, 0.0, 0.0, 0.0
+    if model == "PINHOLE":
+        return p[0], p[1], p[2], p[3], 0.0, 0.0, 0.0, 0.0
+    if model == "SIMPLE_RADIAL":
+        return p[0], p[0], p[1], p[2], p[3], 0.0, 0.0, 0.0
+    return tuple(p[:8])
+
+
+def reproject(points3D, rvec, tvec, camera):
+    """it_loc/common.py:225-277 reproject for the four models of pose.CAMERA_MODELS: pixels [N, 2] of world points [N, 3] under
+    (rvec = qvec (w, x, y, z), tvec), no depth test."""
+    X = np.asarray(points3D, dtype=np.float64).reshape(-1, 3)
+    P = qvec2rotmat(rvec) @ X.T + np.asarray(tvec, dtype=np.float64).reshape(3, 1)
+    fx, fy, cx, cy, k1, k2, p1, p2 = _opencv(camera)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        u, v = P[0] / P[2], P[1] / P[2]
+        r2 = u * u + v * v
+        rad = k1 * r2 + k2 * r2 * r2
+        ud = u + u * rad + 2 * p1 * u * v + p2 * (r2 + 2 * u * u)
+        vd = v + v * rad + 2 * p2 * u * v + p1 * (r2 + 2 * v * v)
+    return np.stack([ud * fx + cx, vd * fy + cy], 1)
+
+
+def compute_pose_error(pred_qcw, pred_tcw, gt_qcw, gt_tcw):
+    """it_loc/common.py:298-317: (rotation error in degrees, distance of the camera centres, its three components)."""
+    Rp, Rg = qvec2rotmat(pred_qcw), qvec2rotmat(gt_qcw)
+    d = (-Rp.T @ np.asarray(pred_tcw, float).reshape(3, 1)) - (-Rg.T @ np.asarray(gt_tcw, float).reshape(3, 1))
+    t_error = np.sqrt(np.sum(d ** 2))
+    qp = np.asarray(pred_qcw, float).reshape(4)
+    qg = np.asarray(gt_qcw, float).reshape(4)
+    c = abs(np.dot(qp / np.linalg.norm(qp), qg / np.linalg.norm(qg)))
+    q_error = 2 * np.arccos(min(1.0, max(-1.0, c))) * 180 / np.pi
+    return q_error, t_error, (d[0, 0], d[1, 0], d[2, 0])
+
+
+class MapIndex:
+    """images, points3D: the dicts COLMAP's read_write_model returns (image id -> .name .qvec .tvec .point3D_ids, point id ->
+    .xyz .image_ids).  Holds the dense point table (ids ascending: point_ids, xyz fp64 [P, 3], track_len int32 [P] =
+    len(image_ids), duplicates counted) and, per image, the table key point -> row of the point table (-1 = none).
+    to_device() puts the point table on the GPU; the per-image tables follow on first use and stay (device_rows)."""
+
+    def __init__(self, images, points3D):
+        self.images, self.points3D = images, points3D
+        self.point_ids = np.array(sorted(points3D), dtype=np.int64)
+        P = len(self.point_ids)
+        self.xyz = np.ascontiguousarray(np.array([points3D[int(i)].xyz for i in self.point_ids], dtype=np.float64).reshape(P, 3))
+        self.track_len = np.array([len(points3D[int(i)].image_ids) for i in self.point_ids], dtype=np.int32)
+        self.name_to_id = {im.name: i for i, im in images.items()}
+        self._rows, self._dev_rows = {}, {}
+        self.device = None
+        self._dev_xyz = self._dev_track = None
+
+    # ------------------------------------------------------------------------------------------------ tables
+    def point_rows(self, ids):
+        """Rows of the point table for an array of point3D ids (-1 for -1 and for ids the map does not hold)."""
+        ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+        if len(self.point_ids) == 0:
+            return np.full(ids.shape, -1, dtype=np.int32)
+        pos = np.minimum(np.searchsorted(self.point_ids, ids), len(self.point_ids) - 1)
+        return np.where(self.point_ids[pos] == ids, pos, -1).astype(np.int32)
+
+    def rows(self, image_id):
+        r = self._rows.get(image_id)
+        if r is None:
+            r = self._rows[image_id] = self.point_rows(self.images[image_id].point3D_ids)
+        return r
+
+    def to_device(self, device=0):
+        import torch
+        self.device = torch.device("cuda", int(device))
+        self._dev_xyz = torch.from_numpy(self.xyz if self.xyz.size else np.zeros((1, 3))).to(self.device)
+        self._dev_track = torch.from_numpy(self.track_len if self.track_len.size else np.zeros(1, np.int32)).to(self.device)
+        self._dev_rows = {}
+        return self
+
+    def device_rows(self, image_id):
+        """(device pointer or None, n1) of an image's table; uploaded on first use and kept."""
+        ent = self._dev_rows.get(image_id)
+        if ent is None:
+            import torch
+            r = self.rows(image_id)
+            t = torch.from_numpy(r).to(self.device) if r.size else None
+            ent = self._dev_rows[image_id] = (t, None if t is None else t.data_ptr(), int(r.size))
+        return ent[1], ent[2]
+
+    def point_table(self):
+        from . import _lib
+        if self._dev_xyz is None:
+            raise RuntimeError("MapIndex.to_device() has not been called")
+        return _lib.PointTable(self._dev_xyz.data_ptr(), self._dev_track.data_ptr(), len(self.point_ids), 0)
+
+    # ------------------------------------------------------------------------------------------------ selections
+    def _observed(self, frame_id, ref_3Dpoints):
+        observed = np.asarray(self.images[frame_id].point3D_ids if ref_3Dpoints is None else ref_3Dpoints, dtype=np.int64).reshape(-1)
+        valid = observed[observed != -1]
+        lists = [np.asarray(self.points3D[int(i)].image_ids).reshape(-1) for i in valid]
+        connected = np.unique(np.concatenate(lists)) if lists else np.zeros(0, dtype=np.int64)
+        return valid, connected
+
+    def _counts(self, valid, connected, obs_th):
+        """Per connected frame: how many entries of `valid` (duplicates counted) have a track of >= obs_th and occur in the
+        frame's point3D_ids (localize_cv2.py:135, :195)."""
+        rows = self.point_rows(valid)
+        tl = np.where(rows >= 0, self.track_len[np.maximum(rows, 0)], 0)
+        if (rows < 0).any():
+            raise KeyError(int(valid[rows < 0][0]))
+        v = valid[tl >= obs_th]
+        return np.array([int(np.isin(v, np.asarray(self.images[int(d)].point3D_ids)).sum()) for d in connected], dtype=np.int64)
+
+    def covisible_frames(self, frame_id, covisibility_frame=50, ref_3Dpoints=None, obs_th=0, pred_qvec=None, pred_tvec=None):
+        """get_covisibility_frames (localize_cv2.py:120-169, the `obs` type): the frames sharing 3D points with frame_id, most
+        shared first (equal counts in ascending id order: the reference's stable sort over np.unique's order); with a predicted
+        pose a frame is set aside when it is >= 30 degrees or >= 30 units away or shares <= 30 points; covisibility_frame = 0
+        means no limit; with <= 3 frames left the set-aside ones are appended (:162-166).  Returns a list of image ids."""
+        valid, connected = self._observed(frame_id, ref_3Dpoints)
+        counts = self._counts(valid, connected, obs_th)
+        order = np.argsort(-counts, kind="stable")
+        with_pose = pred_qvec is not None and pred_tvec is not None
+        out, not_used = [], []
+        for o in order:
+            db_id, n = int(connected[o]), int(counts[o])
+            if with_pose:
+                im = self.images[db_id]
+                q_error, t_error, _ = compute_pose_error(pred_qvec, pred_tvec, im.qvec, im.tvec)
+                if q_error >= 30 or t_error >= 30 or n <= 30:
+                    not_used.append(db_id)
+                    continue
+            out.append(db_id)
+            if covisibility_frame > 0 and len(out) >= covisibility_frame:
+                break
+        if len(out) <= 3:
+            for v in not_used:
+                out.append(v)
+                if len(out) >= covisibility_frame:
+                    break
+        return out
+
+    def covisible_frames_by_pose(self, frame_id, pred_qvec, pred_tvec, covisibility_frame=50, q_th=5, obs_th=5, t_th=10, ref_3Dpoints=None):
+        """get_covisibility_frames_by_pose (localize_cv2.py:172-233, the `pos` type): connected frames whose name holds neither
+        'left' nor 'right' and whose rotation differs by <= q_th degrees from the predicted pose, nearest camera centre first; when
+        fewer than covisibility_frame, filled up from the frames by shared points (left / right names still excluded).  t_th is
+        accepted and unused, as in the reference."""
+        valid, connected = self._observed(frame_id, ref_3Dpoints)
+        named = np.array([not (self.images[int(d)].name.find("left") >= 0 or self.images[int(d)].name.find("right") >= 0)
+                          for d in connected], dtype=bool)
+        connected = connected[named]
+        counts = self._counts(valid, connected, obs_th)
+        db_ids, t_dists = [], []
+        for d in connected:
+            im = self.images[int(d)]
+            q_error, t_error, _ = compute_pose_error(pred_qvec, pred_tvec, im.qvec, im.tvec)
+            if q_error > q_th:
+                continue
+            db_ids.append(int(d))
+            t_dists.append(t_error)
+        out = []
+        for did in np.argsort(t_dists):
+            out.append(db_ids[did])
+            if covisibility_frame > 0 and len(out) >= covisibility_frame:
+                break
+        if len(out) >= covisibility_frame:
+            return out
+        for o in np.argsort(-counts, kind="stable"):
+            db_id = int(connected[o])
+            if db_id in out:
+                continue
+            out.append(db_id)
+            if covisibility_frame > 0 and len(out) >= covisibility_frame:
+                break
+        return out

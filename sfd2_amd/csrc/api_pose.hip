@@ -162,6 +162,17 @@ int run(sfd2_ctx *c, const char *fn, const sfd2_pose_problem *problems, int k, c
 
 }  // namespace
 
+// the same camera conversion for sfd2_assemble_2d3d's gate (api_assemble.hip)
+bool sfd2_pose_cam(int model, const double *params, PoseCam &c, std::string &why)
+{
+    sfd2_pose_problem p;
+    memset(&p, 0, sizeof(p));
+    p.model = model;
+    memcpy(p.params, params, sizeof(p.params));
+    double mf = 0;
+    return to_cam(p, c, mf, why);
+}
+
 extern "C" int sfd2_absolute_pose_batch(sfd2_ctx *c, const sfd2_pose_problem *problems, int k, const sfd2_pose_conf *conf,
                                         sfd2_pose_result *results, uint8_t *inlier_mask_u8, int flags)
 {

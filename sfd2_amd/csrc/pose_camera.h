@@ -1,0 +1,38 @@
+// libsfd2hip: the camera model shared by the pose kernels (pose_kernels.hip) and the 2D-3D assembly's reprojection gate
+// (assemble_kernels.hip): COLMAP's cameras in OPENCV form (PoseCam, sfd2_internal.h), fp64, pure arithmetic.
+#pragma once
+#include "sfd2_internal.h"
+
+#define SFD2_PD __host__ __device__ __forceinline__   // pure arithmetic, also compiled for the host
+
+// distortion of normalised (u, v) and its 2x2 Jacobian (OPENCV form; zero coefficients for the simpler models)
+SFD2_PD void distort(const PoseCam &c, double u, double v, double &ud, double &vd, double J[4])
+{
+    const double u2 = u * u, v2 = v * v, uv = u * v, r2 = u2 + v2;
+    const double rad = c.k1 * r2 + c.k2 * r2 * r2;
+    const double drad = c.k1 + 2.0 * c.k2 * r2;            // d rad / d r2
+    ud = u + u * rad + 2.0 * c.p1 * uv + c.p2 * (r2 + 2.0 * u2);
+    vd = v + v * rad + 2.0 * c.p2 * uv + c.p1 * (r2 + 2.0 * v2);
+    J[0] = 1.0 + rad + 2.0 * u2 * drad + 2.0 * c.p1 * v + 6.0 * c.p2 * u;
+    J[1] = 2.0 * uv * drad + 2.0 * c.p1 * u + 2.0 * c.p2 * v;
+    J[2] = 2.0 * uv * drad + 2.0 * c.p2 * v + 2.0 * c.p1 * u;
+    J[3] = 1.0 + rad + 2.0 * v2 * drad + 2.0 * c.p2 * u + 6.0 * c.p1 * v;
+}
+
+// camera-frame point -> pixel, no depth test (a point on or behind the image plane gives what the division gives)
+SFD2_PD void project_px(const PoseCam &c, const double Pc[3], double &px, double &py)
+{
+    const double u = Pc[0] / Pc[2], v = Pc[1] / Pc[2];
+    double ud, vd, J[4];
+    distort(c, u, v, ud, vd, J);
+    px = c.f[0] * ud + c.c[0];
+    py = c.f[1] * vd + c.c[1];
+}
+
+// R (row-major) from a unit quaternion (w, x, y, z)
+SFD2_PD void quat_to_rot(double w, double x, double y, double z, double R[9])
+{
+    R[0] = 1 - 2 * (y * y + z * z); R[1] = 2 * (x * y - w * z);     R[2] = 2 * (x * z + w * y);
+    R[3] = 2 * (x * y + w * z);     R[4] = 1 - 2 * (x * x + z * z); R[5] = 2 * (y * z - w * x);
+    R[6] = 2 * (x * z - w * y);     R[7] = 2 * (y * z + w * x);     R[8] = 1 - 2 * (x * x + y * y);
+}

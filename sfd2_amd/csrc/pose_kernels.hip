@@ -19,10 +19,9 @@
 // Every reduction runs in a fixed order (wave butterflies, then the waves in index order) and nothing depends on another
 // workgroup, so results are bit-identical whatever the batch, its order and the scheduling.  All loops are bounded.
 #include "sfd2_internal.h"
+#include "pose_camera.h"              // SFD2_PD, distort: the camera model, shared with assemble_kernels.hip
 
 namespace {
-
-#define SFD2_PD __host__ __device__ __forceinline__   // pure arithmetic, also compiled for the host
 
 constexpr int kWG = SFD2_POSE_WG;
 constexpr int kWaves = kWG / 64;
@@ -35,20 +34,7 @@ constexpr int kHypD = 12;            // doubles per stored hypothesis (R row-maj
 SFD2_PD bool finite_d(double v) { return __builtin_isfinite(v); }
 
 // ---------------------------------------------------------------------------------------------------------------- camera model
-// distortion of normalised (u, v) and its 2x2 Jacobian (OPENCV form; zero coefficients for the simpler models)
-SFD2_PD void distort(const PoseCam &c, double u, double v, double &ud, double &vd, double J[4])
-{
-    const double u2 = u * u, v2 = v * v, uv = u * v, r2 = u2 + v2;
-    const double rad = c.k1 * r2 + c.k2 * r2 * r2;
-    const double drad = c.k1 + 2.0 * c.k2 * r2;            // d rad / d r2
-    ud = u + u * rad + 2.0 * c.p1 * uv + c.p2 * (r2 + 2.0 * u2);
-    vd = v + v * rad + 2.0 * c.p2 * uv + c.p1 * (r2 + 2.0 * v2);
-    J[0] = 1.0 + rad + 2.0 * u2 * drad + 2.0 * c.p1 * v + 6.0 * c.p2 * u;
-    J[1] = 2.0 * uv * drad + 2.0 * c.p1 * u + 2.0 * c.p2 * v;
-    J[2] = 2.0 * uv * drad + 2.0 * c.p2 * v + 2.0 * c.p1 * u;
-    J[3] = 1.0 + rad + 2.0 * v2 * drad + 2.0 * c.p2 * u + 6.0 * c.p1 * v;
-}
-
+// (distort: pose_camera.h)
 // pixel -> normalised image coordinates (COLMAP CamFromImg / ImageToWorld)
 SFD2_PD void img_to_norm(const PoseCam &c, double px, double py, double &u, double &v)
 {
@@ -85,13 +71,7 @@ SFD2_PD double det_cols(const double a[3], const double b[3], const double c[3])
     return dot3(a, x);
 }
 
-// R (row-major) from a unit quaternion (w, x, y, z)
-SFD2_PD void quat_to_rot(double w, double x, double y, double z, double R[9])
-{
-    R[0] = 1 - 2 * (y * y + z * z); R[1] = 2 * (x * y - w * z);     R[2] = 2 * (x * z + w * y);
-    R[3] = 2 * (x * y + w * z);     R[4] = 1 - 2 * (x * x + z * z); R[5] = 2 * (y * z - w * x);
-    R[6] = 2 * (x * z - w * y);     R[7] = 2 * (y * z + w * x);     R[8] = 1 - 2 * (x * x + y * y);
-}
+// (quat_to_rot: pose_camera.h)
 // unit quaternion (w >= 0) of a (nearly) orthonormal R
 SFD2_PD void rot_to_quat(const double R[9], double q[4])
 {

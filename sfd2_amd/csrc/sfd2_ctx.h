@@ -21,6 +21,8 @@
 
 int sfd2_fail(const std::string &m);          // sets the thread's last-error text, returns -1
 #define fail sfd2_fail
+struct PoseCam;
+bool sfd2_pose_cam(int model, const double *params, PoseCam &c, std::string &why);   // api_pose.hip: a COLMAP camera in the kernels' form
 #define HIPCHECK(expr)                                                                           \
     do {                                                                                          \
         hipError_t e_ = (expr);                                                                   \
@@ -255,6 +257,7 @@ struct sfd2_ctx {
     DevBuf arena;   // aliased activation slots of the throughput path (placed by plan_pass, sized by ensure_workspace)
     DevBuf img_u8_packed;              // SFD2_FLAG_IMG_U8_X: the image as three bytes per pixel (unpack_rgbx_kernel)
     JpegScratch jpeg;                  // sfd2_jpeg_decode
+    JpegBuf asm_in, asm_ws, asm_out;    // sfd2_assemble_2d3d (api_assemble.hip): descriptors and host inputs, per-(image, key point) work, host-bound outputs
     JpegBuf pose_in, pose_ws, pose_out; // sfd2_absolute_pose_batch / sfd2_pose_refine_batch (api_pose.hip): inputs, per-point work, results
     DevBuf img_scaled, ms_kp, ms_sc, ms_de, ms_keys, ms_sorted, ms_cnt;
     unsigned int ms_cand_seen[8] = {};

@@ -729,3 +729,31 @@ struct PoseResDev {
 };
 void launch_pose(hipStream_t st, const PoseProbDev *probs, int k, const PoseConfDev &conf, const double *p2, const double *p3, float4 *xf4,
                  float2 *xf2, double2 *xn, double *hyp, const unsigned char *mask_in, unsigned char *mask_out, PoseResDev *res);
+
+// ------------------------------------------------------------------------------------------------ 2D-3D assembly (assemble_kernels.hip)
+#define SFD2_ASM_WG 256               // key points of one (job, image, chunk) block
+#define SFD2_ASM_ST_MATCH_RANGE 1     // status bits of AsmResDev: a match index >= the image's table length
+#define SFD2_ASM_ST_ROW_RANGE 2       //   a table entry >= the point table's length
+#define SFD2_ASM_ST_CAPACITY 4        //   m above the output capacity (nothing written)
+struct AsmImgDev {
+    const int32_t *tab;               // key point -> row of the point table, or -1; [n1]
+    int32_t n1;                       // 0: the image is skipped
+    int32_t mrow;                     // row of the job's matches0 with this image's matches, or -1: no matches
+};
+struct AsmJobDev {
+    const long long *matches0;        // [rows][n]
+    const AsmImgDev *imgs;            // [k]
+    const float *kpq, *scores;        // [n][2], [n] or null
+    int32_t k, n, nchunk, gate;
+    int64_t ws_off, blk_off, cnt_off; // this job's first element of the resolved rows / keep flags, block counts, per-image counts
+    int32_t cap, pad;
+    double obs_th, radius;
+    double R[9], t[3];
+    PoseCam cam;
+    double *p2, *p3;                  // outputs, capacity cap rows
+    int32_t *prow, *qidx, *iidx;
+    float *score;
+};
+struct AsmResDev { int32_t m, status; };
+void launch_assemble(hipStream_t st, const AsmJobDev *jobs, int n_jobs, int max_blocks, const double *xyz, const int32_t *track, int n_points,
+                     int32_t *rows, unsigned char *keep, int32_t *blk, int32_t *counts, AsmResDev *res);

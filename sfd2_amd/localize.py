@@ -118,16 +118,179 @@ class StoreMatcher:
                 out[i] = np.ones((n0,), dtype=int) * -1
         return out
 
+    def match_assemble(self, map_index, queries):
+        """Matching and 2D-3D assembly on the device for a batch of queries: per query one sfd2_match_batch whose result stays in
+        HBM, then ONE sfd2_assemble_2d3d for all of them behind it on the same stream.  map_index: sfd2_amd.covis.MapIndex;
+        queries: dicts with desc_q (array or the name of a set in the store), kpq [N,2], scores [N] or None, image_ids (the database
+        images, ids of map_index.images), obs_th, gate (None or (qvec, tvec, camera, radius)), optionally capacity.  An image with
+        3 or fewer key points that have a 3D point never reaches the matcher (localize_cv2.py:537-538) and takes part as an image
+        without matches, so image_idx indexes image_ids.  Returns per query what assemble_2d3d returns; equal to match() followed
+        by match_cluster_2D."""
+        import ctypes
+        import torch
+        from . import _lib
+        if map_index.device is None:
+            map_index.to_device(self.ctx.device)
+        seq = self._seq
+        self._seq += 1
+        self.sets.completed_seq = seq - 1          # every earlier call has synchronised
+        conf = self.matcher._conf()
+        keep, jobs = [], []
+        for q in queries:
+            desc_q = q["desc_q"]
+            if isinstance(desc_q, str):
+                qp, n0 = self.sets.get(desc_q, seq)
+                qs = _lib.DescSet(qp, n0, _lib.DT_F16, _lib.LAYOUT_ND, 1, None, 0, 0)
+            else:
+                a = np.ascontiguousarray(desc_q)
+                if a.dtype not in (np.float64, np.float32):
+                    a = a.astype(np.float64)
+                keep.append(a)
+                n0 = a.shape[0]
+                qs = _lib.DescSet(a.ctypes.data, n0, _lib.DT_F64 if a.dtype == np.float64 else _lib.DT_F32, _lib.LAYOUT_ND, 0, None, 0, 0)
+            images, sets, rows = [], [], []
+            for image_id in q["image_ids"]:
+                im = map_index.images[image_id]
+                ids = np.asarray(im.point3D_ids)
+                r = np.flatnonzero(ids != -1).astype(np.int32)
+                if ids.size == 0 or len(r) <= 3:
+                    images.append((image_id, -1))
+                    continue
+                p, n1 = self.sets.get(im.name, seq)
+                if ids.size != n1:
+                    raise ValueError(f"{im.name}: {ids.size} point ids for {n1} key points")
+                images.append((image_id, len(sets)))
+                sets.append((p, n1))
+                rows.append(r)
+            m = None
+            if sets and n0 > 0:
+                db = (_lib.DescSet * len(sets))(*[_lib.DescSet(p, n1, _lib.DT_F16, _lib.LAYOUT_ND, 1, r.ctypes.data, len(r), 0)
+                                                  for (p, n1), r in zip(sets, rows)])
+                m = torch.empty((len(sets), n0), dtype=torch.int64, device=map_index.device)
+                sc = torch.empty((len(sets), n0), dtype=torch.float32, device=map_index.device)
+                keep += [rows, db, sc, qs]
+                _lib.check(self.ctx.lib.sfd2_match_batch(self.ctx.h, ctypes.byref(qs), db, len(sets), 128, ctypes.byref(conf), m.data_ptr(),
+                                                         sc.data_ptr(), 1, _lib.FLAG_ASYNC))
+            else:
+                images = [(i, -1) for i, _ in images]
+            jobs.append(dict(matches0=m, images=images, kpq=q["kpq"], scores=q.get("scores"), obs_th=q.get("obs_th", 0), gate=q.get("gate"),
+                             capacity=q.get("capacity")))
+        return assemble_2d3d(self.ctx, map_index, jobs)
+
     def close(self):
         self.sets.close()
 
 
-def match_cluster_2D(kpq, matches_list, db_point3D_ids_list, points3D, obs_th=0, db_names=None):
+class AssembleError(RuntimeError):
+    """sfd2_assemble_2d3d reported a job with a non-zero status; m and status hold every job's values."""
+
+    def __init__(self, text, m, status):
+        super().__init__(text)
+        self.m, self.status = m, status
+
+
+def assemble_2d3d(ctx, map_index, jobs, out_on_device=False):
+    """sfd2_assemble_2d3d (include/sfd2_hip.h): jobs are dicts with matches0 (a device int64 torch tensor [rows][n], or None), images
+    (a list of (image id of map_index, row of matches0 or -1)), kpq [n,2], scores [n] or None, obs_th, gate (None or (qvec, tvec,
+    camera, radius)) and capacity (default k * n, which cannot overflow).  Returns per job a dict: points2D [m,2], points3D [m,3],
+    point_row, query_idx, image_idx (int32 [m]), score (fp32 [m]), image_counts (int32 [k]), m -- numpy arrays, or torch tensors of
+    `capacity` rows on the device with out_on_device.  Raises AssembleError when a job's status is not 0."""
+    import ctypes
+    from . import _lib
+    from .pose import camera_model
+    if map_index.device is None:
+        map_index.to_device(ctx.device)
+    table = map_index.point_table()
+    arr = (_lib.AssembleJob * max(len(jobs), 1))()
+    keep, outs = [], []
+    if out_on_device:
+        import torch
+
+        def buf(shape, dt):
+            t = torch.empty(shape, dtype={np.float64: torch.float64, np.int32: torch.int32, np.float32: torch.float32}[dt], device=map_index.device)
+            return t, t.data_ptr()
+    else:
+        def buf(shape, dt):
+            a = np.empty(shape, dtype=dt)
+            return a, a.ctypes.data
+    for j, job in zip(arr, jobs):
+        kpq = np.ascontiguousarray(job["kpq"], dtype=np.float32).reshape(-1, 2)
+        n, k = kpq.shape[0], len(job["images"])
+        imgs = (_lib.AssembleImage * max(k, 1))()
+        for a, (image_id, mrow) in zip(imgs, job["images"]):
+            a.point_rows, a.n1 = map_index.device_rows(image_id)
+            a.match_row = int(mrow)
+        m0 = job.get("matches0")
+        j.matches0 = None if m0 is None else m0.data_ptr()
+        j.match_rows = 0 if m0 is None else int(m0.shape[0])
+        if m0 is not None and (m0.dim() != 2 or m0.shape[1] != n or not m0.is_contiguous() or str(m0.dtype) != "torch.int64"):
+            raise ValueError("matches0 must be a contiguous int64 [rows][n] device tensor")
+        j.images, j.k, j.n, j.inputs_on_device = imgs, k, n, 0
+        j.keypoints = kpq.ctypes.data
+        sc = job.get("scores")
+        if sc is not None:
+            sc = np.ascontiguousarray(sc, dtype=np.float32).reshape(-1)
+            if sc.size != n:
+                raise ValueError(f"{sc.size} scores for {n} key points")
+            j.scores = sc.ctypes.data
+        j.obs_th = float(job.get("obs_th", 0))
+        gate = job.get("gate")
+        if gate is not None:
+            qvec, tvec, cam, radius = gate
+            j.gate = 1
+            j.model, params = camera_model(cam)
+            for i in range(8):
+                j.params[i] = params[i]
+            for i in range(4):
+                j.qvec[i] = float(qvec[i])
+            for i in range(3):
+                j.tvec[i] = float(tvec[i])
+            j.radius = float(radius)
+        cap = job.get("capacity")
+        cap = k * n if cap is None else int(cap)
+        j.capacity = cap
+        o = {"points2D": buf((cap, 2), np.float64), "points3D": buf((cap, 3), np.float64), "point_row": buf((cap,), np.int32),
+             "query_idx": buf((cap,), np.int32), "image_idx": buf((cap,), np.int32), "score": buf((cap,), np.float32)}
+        j.points2D, j.points3D, j.point_row = o["points2D"][1], o["points3D"][1], o["point_row"][1]
+        j.query_idx, j.image_idx, j.score = o["query_idx"][1], o["image_idx"][1], o["score"][1]
+        counts = np.zeros(max(k, 1), dtype=np.int32)
+        j.image_counts = counts.ctypes.data
+        keep += [kpq, sc, imgs, counts, m0]
+        outs.append((o, counts, k))
+    rc = ctx.lib.sfd2_assemble_2d3d(ctx.h, ctypes.byref(table), arr, len(jobs), 1 if out_on_device else 0, 0)
+    if rc != 0:
+        text = "libsfd2hip: " + ctx.lib.sfd2_last_error().decode("utf-8", "replace")
+        if any(arr[i].status for i in range(len(jobs))):
+            raise AssembleError(text, [arr[i].m for i in range(len(jobs))], [arr[i].status for i in range(len(jobs))])
+        raise RuntimeError(text)
+    res = []
+    for i, (o, counts, k) in enumerate(outs):
+        m = arr[i].m
+        r = {name: (t if out_on_device else t[:m]) for name, (t, _) in o.items()}
+        r["image_counts"] = counts[:k]
+        r["m"] = m
+        res.append(r)
+    return res
+
+
+def _gate_error(kp, xyz, gate):
+    """The covisibility stage's reprojection gate (it_loc/localize_cv2.py:341-349): distance of the key point (no +0.5) from the 3D
+    point projected with gate = (qvec, tvec, camera, radius)."""
+    from .covis import reproject
+    proj = reproject(np.asarray(xyz, dtype=np.float64).reshape(-1, 3), gate[0], gate[1], gate[2])
+    with np.errstate(invalid="ignore"):
+        return np.sqrt(np.sum((np.asarray(kp) - proj) ** 2))
+
+
+def match_cluster_2D(kpq, matches_list, db_point3D_ids_list, points3D, obs_th=0, db_names=None, gate=None):
     """it_loc/localize_cv2.py:563-650 match_cluster_2D on matches already computed (StoreMatcher.match / feature_matching_batch):
     matches_list[i] is database image i's matches0 (indices into its key points, -1 = none), db_point3D_ids_list[i] its point3D_ids.
     Applies the -1 skips, the obs_th rule on len(points3D[id].image_ids), the per-query-keypoint de-duplication of 3D ids and the
     +0.5 pixel offset (:647).  points3D: any mapping id -> object with .xyz and .image_ids (read_write_model's).  db_names: the keys
-    of cluster_info (default: the image's position in the lists).  Returns (cluster_info, mp3d [m,3], mkpq [m,2], mp3d_ids, q_ids);
+    of cluster_info (default: the image's position in the lists).  gate = (qvec, tvec, camera, radius): the same loop as the
+    covisibility stage runs it (:286-360) -- after the de-duplication entry is made, a point whose projection lies more than
+    radius pixels from the key point is dropped (`error > radius`, a NaN error is kept).  This is the host restatement of
+    sfd2_assemble_2d3d.  Returns (cluster_info, mp3d [m,3], mkpq [m,2], mp3d_ids, q_ids);
     cluster_info[name] holds 'mkpq', 'qids', 'matches', 'mp_3d_ids', 'mp3d' (:637-643, without the database key points)."""
     kpq = np.asarray(kpq)
     all_mp3d, all_mkpq, all_mp3d_ids, all_q_ids = [], [], [], []
@@ -151,6 +314,8 @@ def match_cluster_2D(kpq, matches_list, db_point3D_ids_list, points3D, obs_th=0,
             if id_3D in seen:
                 continue
             seen.append(id_3D)
+            if gate is not None and _gate_error(kpq[idx], points3D[id_3D].xyz, gate) > gate[3]:
+                continue
             mp3d.append(points3D[id_3D].xyz)
             mp3d_ids.append(id_3D)
             all_mp3d_ids.append(id_3D)
@@ -167,22 +332,158 @@ def match_cluster_2D(kpq, matches_list, db_point3D_ids_list, points3D, obs_th=0,
     return outputs, all_mp3d, all_mkpq, all_mp3d_ids, all_q_ids
 
 
-def pose_from_clusters(kpq, clusters, camera, thresh, inlier_th=50, *, points3D, obs_th=3, qname=None, estimator=None, **ransac):
-    """The initialisation loop of it_loc/localize_cv2.py:653-1273 pose_from_cluster_with_matcher with do_covisility_opt=False, on
-    matches already computed.  clusters: a list over the retrieved clusters, each a list of (db_image, matches0) pairs (db_image with
-    .name, .qvec, .tvec, .point3D_ids as read_write_model returns them; matches0 from StoreMatcher.match / feature_matching_batch).
+def _default_estimator(ransac):
+    from . import pose as _pose
 
-    Every cluster with >= 8 correspondences (:719) goes into ONE absolute_pose_estimation_batch call (estimator: a replacement
-    taking a list of (points2D, points3D, camera, thresh) and returning pose dicts; **ransac goes to the default one).  The
-    sequential decisions are then replayed in cluster order: best_inliers per db image (:742-760), keep / continue (:930-966), the
-    first success returns its num_inliers (:1124-1130); otherwise, when the kept result has >= 10 inliers, the pose of the LAST
-    estimate made is returned with 0, as the reference does (:1132-1265 reads `ret`; if that estimate failed, the kept pose is
-    used); otherwise the first db image's pose with -1 (:1267-1273).  Returns (qvec, tvec, n, best_results)."""
-    if estimator is None:
-        from . import pose as _pose
+    def estimator(problems):
+        return _pose.absolute_pose_estimation_batch(problems, **ransac)
+    return estimator
 
-        def estimator(problems):
-            return _pose.absolute_pose_estimation_batch(problems, **ransac)
+
+def _default_refiner(problems):
+    from . import pose as _pose
+    return _pose.pose_refinement_batch(problems)
+
+
+class Covis:
+    """The settings of the covisibility stage (the `--do_covisible_opt` arguments of the reference's localiser) and what it runs
+    on: map_index (sfd2_amd.covis.MapIndex), matcher and feature_file as pose_refinement_covisibility takes them.  opt_type must
+    hold 'clu' (both call sites of localize_cv2.py test it), 'obs' or 'pos' for the frame selection and 'ref' for the refinement,
+    e.g. 'clurefobs' (Aachen: 50 frames, radius 30), 'clurefpos' (RobotCar: 20, 20)."""
+
+    def __init__(self, map_index, matcher, feature_file, opt_type="clurefobs", covisibility_frame=50, iters=1, radius=20, obs_th=3,
+                 opt_th=12, estimator=None, refiner=None):
+        if opt_type.find("clu") < 0:
+            raise ValueError(f"opt_type {opt_type!r}: the covisibility stage runs for the 'clu' types only")
+        self.map_index, self.matcher, self.feature_file = map_index, matcher, feature_file
+        self.opt_type, self.covisibility_frame, self.iters, self.radius = opt_type, covisibility_frame, iters, radius
+        self.obs_th, self.opt_th, self.estimator, self.refiner = obs_th, opt_th, estimator, refiner
+
+    def refine(self, requests):
+        """requests: a list of (qname, camera, db_frame_id, thresh, qvec, tvec); one batched run of the stage."""
+        return pose_refinement_covisibility_batch(
+            [dict(qname=q, cfg=cam, db_frame_id=f, thresh=th, qvec=qv, tvec=tv) for q, cam, f, th, qv, tv in requests],
+            self.feature_file, self.map_index, self.matcher, covisibility_frame=self.covisibility_frame, iters=self.iters,
+            obs_th=self.obs_th, opt_th=self.opt_th, radius=self.radius, opt_type=self.opt_type, estimator=self.estimator,
+            refiner=self.refiner)
+
+
+def _assemble(matcher, map_index, feature_file, jobs):
+    """jobs: dicts with qname, kpq, score_q, db_ids, obs_th, gate.  matcher: a StoreMatcher or anything else with its match_assemble (device: one match launch per query, one
+    sfd2_assemble_2d3d for all of them) or a callable (qname, db_names, point3D_ids_list) -> matches0 per image (then the host loop
+    of match_cluster_2D).  Returns per job (mkpq [m,2], mp3d [m,3], 3D ids, query scores)."""
+    if hasattr(matcher, "match_assemble"):
+        res = matcher.match_assemble(map_index, [dict(desc_q=j["qname"], kpq=j["kpq"], scores=j["score_q"], image_ids=j["db_ids"],
+                                                      obs_th=j["obs_th"], gate=j["gate"]) for j in jobs])
+        return [(r["points2D"], r["points3D"], [int(v) for v in map_index.point_ids[r["point_row"]]], [s for s in r["score"]]) for r in res]
+    out = []
+    for j in jobs:
+        ims = [map_index.images[d] for d in j["db_ids"]]
+        ids_list = [np.asarray(im.point3D_ids) for im in ims]
+        ml = matcher(j["qname"], [im.name for im in ims], ids_list)
+        _, mp3d, mkpq, ids3d, q_ids = match_cluster_2D(j["kpq"], ml, ids_list, map_index.points3D, obs_th=j["obs_th"], gate=j["gate"])
+        out.append((mkpq, mp3d, [int(v) for v in ids3d], [j["score_q"][q] for q in q_ids]))
+    return out
+
+
+def pose_refinement_covisibility_batch(tasks, feature_file, map_index, matcher, covisibility_frame=50, iters=1, obs_th=3, opt_th=12,
+                                       radius=20, opt_type="ref", estimator=None, refiner=None, ref_3Dpoints=None):
+    """pose_refinement_covisibility for many queries at once: tasks are dicts with qname, cfg, db_frame_id, thresh, qvec, tvec.  One
+    match / assemble call, one estimator call and one refiner call per iteration for all of them; each result equals the single
+    call's (the device calls are batch-independent)."""
+    estimator = estimator or _default_estimator({})
+    refiner = refiner or _default_refiner
+    jobs = []
+    for t in tasks:
+        if t["qvec"] is None or t["tvec"] is None:
+            raise ValueError("pose_refinement_covisibility needs the pose to refine (qvec, tvec)")
+        if opt_type.find("obs") >= 0:
+            db_ids = map_index.covisible_frames(t["db_frame_id"], covisibility_frame=covisibility_frame, ref_3Dpoints=ref_3Dpoints,
+                                                obs_th=obs_th, pred_qvec=t["qvec"], pred_tvec=t["tvec"])
+        elif opt_type.find("pos") >= 0:
+            db_ids = map_index.covisible_frames_by_pose(t["db_frame_id"], t["qvec"], t["tvec"], covisibility_frame=covisibility_frame,
+                                                        ref_3Dpoints=ref_3Dpoints, q_th=10, t_th=10, obs_th=obs_th)
+        else:
+            raise ValueError(f"opt_type {opt_type!r} names no method for getting reference images ('obs' or 'pos')")
+        f = feature_file[t["qname"]]
+        jobs.append(dict(qname=t["qname"], kpq=f["keypoints"].__array__(), score_q=f["scores"].__array__(), db_ids=db_ids, obs_th=obs_th,
+                         gate=(t["qvec"], t["tvec"], t["cfg"], radius)))
+    asm = _assemble(matcher, map_index, feature_file, jobs) if jobs else []
+    rets = estimator([(a[0], a[1], t["cfg"], opt_th) for a, t in zip(asm, tasks)]) if tasks else []      # opt_th, not thresh (:390)
+    out = [None] * len(tasks)
+    from .covis import reproject
+    state = {}
+    for i, (t, j, (mkpq, mp3d, ids3d, score_q), ret) in enumerate(zip(tasks, jobs, asm, rets)):
+        ret = dict(ret)
+        extra = {"mkpq": mkpq, "3D_ids": ids3d, "db_ids": j["db_ids"], "score_q": score_q}
+        if not ret["success"]:                                                                            # :392-402
+            ret.update(extra)
+            ret.update({"qvec": t["qvec"], "tvec": t["tvec"], "inliers": [False for _ in range(mkpq.shape[0])], "num_inliers": 0})
+            out[i] = ret
+            continue
+        inliers_rsac = np.asarray(ret["inliers"]).astype(bool)
+        ret["num_inliers"] = np.sum(ret["inliers"])
+        if opt_type.find("ref") >= 0 and np.sum(inliers_rsac) >= 10 and iters > 0:
+            state[i] = dict(qvec=t["qvec"], tvec=t["tvec"], inl=inliers_rsac, extra=extra, ret=ret)
+        else:
+            ret.update(extra)
+            out[i] = ret
+    for _ in range(iters):
+        if not state:
+            break
+        order = sorted(state)
+        probs = []
+        for i in order:
+            st, (mkpq, mp3d, _, _) = state[i], asm[i]
+            proj = reproject(mp3d, st["qvec"], st["tvec"], tasks[i]["cfg"])
+            err = (mkpq - proj) ** 2
+            with np.errstate(invalid="ignore"):
+                err = np.sqrt(err[:, 0] + err[:, 1])
+                st["mask"] = [bool(err[p] <= opt_th and st["inl"][p]) for p in range(err.shape[0])]
+            probs.append((st["tvec"], st["qvec"], mkpq, mp3d, st["mask"], tasks[i]["cfg"]))
+        for i, r in zip(order, refiner(probs)):
+            st = state[i]
+            r = dict(r)
+            st["qvec"], st["tvec"] = r["qvec"], r["tvec"]
+            r["inliers"] = st["mask"]
+            r["num_inliers"] = np.sum(st["mask"])
+            st["ret"] = r
+    for i, st in state.items():
+        st["ret"].update(st["extra"])
+        out[i] = st["ret"]
+    return out
+
+
+def pose_refinement_covisibility(qname, cfg, feature_file, db_frame_id, map_index, thresh, matcher, covisibility_frame=50,
+                                 ref_3Dpoints=None, iters=1, obs_th=3, opt_th=12, qvec=None, tvec=None, radius=20, opt_type="ref",
+                                 estimator=None, refiner=None):
+    """it_loc/localize_cv2.py:236-508 pose_refinement_covisibility: the frames covisible with db_frame_id (opt_type 'obs':
+    MapIndex.covisible_frames, 'pos': covisible_frames_by_pose with q_th 10), the query matched against all of them, the 2D-3D
+    correspondences assembled with the reprojection gate (radius, around the pose passed in), RANSAC, and the refinement.
+    map_index stands for the reference's db_images / points3D pair; matcher: a StoreMatcher (device matching and assembly) or a
+    callable (qname, db_names, point3D_ids_list) -> matches0 per image; estimator / refiner: replacements for
+    pose.absolute_pose_estimation_batch / pose.pose_refinement_batch, taking their problem lists.  Returns the reference's dict:
+    success qvec tvec inliers num_inliers mkpq 3D_ids db_ids score_q (no log_info, no plots).
+
+    Reproduced from the reference as it is written:
+      * RANSAC runs with opt_th, not thresh (:390); thresh is accepted and unused.
+      * RANSAC's pose is NOT used: the refinement starts from the qvec / tvec passed in, and iteration 0's reprojection errors are
+        computed with them (:406, :451).
+      * refinement only when opt_type holds 'ref' and RANSAC has >= 10 inliers; the mask of iteration i is
+        `error <= opt_th and RANSAC inlier`, the error under the pose of iteration i - 1.
+      * RANSAC failure returns its dict with the pose passed in, an all-False inlier list and num_inliers 0 (:392-402).
+      * when no refinement runs the dict returned is RANSAC's own, so the pose is then RANSAC's (:437-441, :503-508).
+      * when it runs, success / qvec / tvec are the last pose_refinement's, inliers / num_inliers the last mask's (:496-497).
+    Deviation: the min / median / max error statistics of :410 and :469, which raise on an empty inlier set, are not computed."""
+    return pose_refinement_covisibility_batch([dict(qname=qname, cfg=cfg, db_frame_id=db_frame_id, thresh=thresh, qvec=qvec, tvec=tvec)],
+                                              feature_file, map_index, matcher, covisibility_frame=covisibility_frame, iters=iters,
+                                              obs_th=obs_th, opt_th=opt_th, radius=radius, opt_type=opt_type, estimator=estimator,
+                                              refiner=refiner, ref_3Dpoints=ref_3Dpoints)[0]
+
+
+def _cluster_steps(kpq, clusters, camera, thresh, inlier_th, points3D, obs_th, qname, covis):
+    """pose_from_clusters as a coroutine: yields ('estimate', problems) once and ('covis', request) at most once per visit of a call
+    site, receives the results; returns what pose_from_clusters returns.  localize_queries drives many of these in rounds."""
     n_q = len(kpq)
     first = clusters[0][0][0]
     best_results = {"tvec": None, "qvec": None, "num_inliers": 0, "single_num_inliers": 0, "db_id": -1, "order": -1, "qname": qname,
@@ -193,7 +494,7 @@ def pose_from_clusters(kpq, clusters, camera, thresh, inlier_th=50, *, points3D,
                                                              obs_th=obs_th, db_names=[im.name for im, _ in cl])
         prepared.append((info, mp3d, mkpq, mp3d_ids, q_ids))
     live = [i for i, p in enumerate(prepared) if p[1].shape[0] >= 8]
-    rets = dict(zip(live, estimator([(prepared[i][2], prepared[i][1], camera, thresh) for i in live]) if live else []))
+    rets = dict(zip(live, (yield ("estimate", [(prepared[i][2], prepared[i][1], camera, thresh) for i in live])) if live else []))
     last = None
     for cluster_idx, (info, mp3d, mkpq, mp3d_ids, q_ids) in enumerate(prepared):
         if cluster_idx not in rets:
@@ -220,8 +521,81 @@ def pose_from_clusters(kpq, clusters, camera, thresh, inlier_th=50, *, points3D,
             continue
         if not keep:
             best_results.update(upd)
+        if covis is not None:                                   # :981-1014
+            ret = last = yield ("covis", (qname, camera, covis.map_index.name_to_id[best_dbname], thresh, ret["qvec"], ret["tvec"]))
+            if not ret["success"]:
+                continue
         return ret["qvec"], ret["tvec"], ret["num_inliers"], best_results
     if best_results["num_inliers"] >= 10:
+        if covis is not None:                                   # :1139-1265: refined from the kept pose, returned with 0 either way
+            ret = yield ("covis", (qname, camera, covis.map_index.name_to_id[best_results["dbname"]], thresh, best_results["qvec"],
+                                   best_results["tvec"]))
+            return ret["qvec"], ret["tvec"], 0, best_results
         src = last if (last is not None and last["success"]) else best_results
         return src["qvec"], src["tvec"], 0, best_results
     return first.qvec, first.tvec, -1, best_results
+
+
+def _drive(gens, estimator, covis):
+    """Runs the coroutines of _cluster_steps in rounds: the pending requests of one kind go out in one call."""
+    results = [None] * len(gens)
+    pending = {}
+    for i, g in enumerate(gens):
+        try:
+            pending[i] = next(g)
+        except StopIteration as e:
+            results[i] = e.value
+    while pending:
+        answers = {}
+        est = [i for i in sorted(pending) if pending[i][0] == "estimate"]
+        if est:
+            flat = [p for i in est for p in pending[i][1]]
+            got = estimator(flat) if flat else []
+            o = 0
+            for i in est:
+                n = len(pending[i][1])
+                answers[i] = got[o:o + n]
+                o += n
+        cov = [i for i in sorted(pending) if pending[i][0] == "covis"]
+        if cov:
+            for i, r in zip(cov, covis.refine([pending[i][1] for i in cov])):
+                answers[i] = r
+        nxt = {}
+        for i, a in answers.items():
+            try:
+                nxt[i] = gens[i].send(a)
+            except StopIteration as e:
+                results[i] = e.value
+        pending = nxt
+    return results
+
+
+def pose_from_clusters(kpq, clusters, camera, thresh, inlier_th=50, *, points3D, obs_th=3, qname=None, estimator=None, covis=None, **ransac):
+    """The initialisation loop of it_loc/localize_cv2.py:653-1273 pose_from_cluster_with_matcher, on matches already computed.
+    clusters: a list over the retrieved clusters, each a list of (db_image, matches0) pairs (db_image with
+    .name, .qvec, .tvec, .point3D_ids as read_write_model returns them; matches0 from StoreMatcher.match / feature_matching_batch).
+
+    Every cluster with >= 8 correspondences (:719) goes into ONE absolute_pose_estimation_batch call (estimator: a replacement
+    taking a list of (points2D, points3D, camera, thresh) and returning pose dicts; **ransac goes to the default one).  The
+    sequential decisions are then replayed in cluster order: best_inliers per db image (:742-760), keep / continue (:930-966), the
+    first success returns its num_inliers (:1124-1130); otherwise, when the kept result has >= 10 inliers, the pose of the LAST
+    estimate made is returned with 0, as the reference does (:1132-1265 reads `ret`; if that estimate failed, the kept pose is
+    used); otherwise the first db image's pose with -1 (:1267-1273).  Returns (qvec, tvec, n, best_results).
+
+    covis: None is do_covisility_opt=False.  A Covis replays the two call sites of pose_refinement_covisibility: after a successful
+    cluster (:981-1014) the pose is refined from the cluster's best database image -- a failed refinement goes on to the next
+    cluster, a successful one returns its pose and num_inliers -- and on the fallback path (:1139-1265) the kept pose is refined
+    and returned with 0 whether or not the refinement succeeded.  qname then names the query's set in covis.feature_file."""
+    if estimator is None:
+        estimator = _default_estimator(ransac)
+    return _drive([_cluster_steps(kpq, clusters, camera, thresh, inlier_th, points3D, obs_th, qname, covis)], estimator, covis)[0]
+
+
+def localize_queries(queries, thresh, inlier_th=50, *, points3D, obs_th=3, estimator=None, covis=None, **ransac):
+    """pose_from_clusters for many queries in rounds: queries is a list of dicts with kpq, clusters, camera and qname.  Stage 1 of
+    all queries is one estimator call; then every covisibility refinement pending in a round is one match / assemble / estimate /
+    refine call each, until no query is pending.  Every result equals the per-query call's exactly."""
+    if estimator is None:
+        estimator = _default_estimator(ransac)
+    gens = [_cluster_steps(q["kpq"], q["clusters"], q["camera"], thresh, inlier_th, points3D, obs_th, q.get("qname"), covis) for q in queries]
+    return _drive(gens, estimator, covis)
