@@ -85,7 +85,7 @@ typedef struct {
     int64_t n_candidates; /* N0 after NMS + threshold + border of the last extract          */
 } sfd2_timings;
 
-int sfd2_version(void);   /* 100 = rounds 1-4; 105 adds sfd2_extract_record_async, sfd2_desc_pack and host outputs with SFD2_FLAG_ASYNC; 106 adds sfd2_get_margin_status; 107 adds sfd2_get_relax_status (option "c3b_plain"); 108 adds sfd2_get_option, sfd2_device_pci_bus_id, SFD2_FLAG_DESC_STORE64; 109 adds the baseline JPEG decoder (sfd2_jpeg_*) */
+int sfd2_version(void);   /* 100 = rounds 1-4; 105 adds sfd2_extract_record_async, sfd2_desc_pack and host outputs with SFD2_FLAG_ASYNC; 106 adds sfd2_get_margin_status; 107 adds sfd2_get_relax_status (option "c3b_plain"); 108 adds sfd2_get_option, sfd2_device_pci_bus_id, SFD2_FLAG_DESC_STORE64; 109 adds the baseline JPEG decoder (sfd2_jpeg_*); 112 adds the SfM map (sfd2_verify_matches_batch, sfd2_build_tracks, sfd2_triangulate_tracks) */
 const char *sfd2_last_error(void);
 
 int sfd2_ctx_create(int device, sfd2_ctx **out);
@@ -619,6 +619,52 @@ typedef struct {
  * job's m and status are filled; a job with a non-zero status writes no rows, the others are complete) or on a bad argument.
  * flags: 0. */
 int sfd2_assemble_2d3d(sfd2_ctx *ctx, const sfd2_point_table *map, sfd2_assemble_job *jobs, int n_jobs, int out_on_device, int flags);
+
+/* ------------------------------------------------------------------------------------------------ SfM map
+ * The map hloc/triangulation.py gets from `colmap matches_importer` and `colmap point_triangulator`, with the reference poses and the
+ * intrinsics fixed (triangulation.py:134-142): known-pose verification of the matches, tracks as connected components, robust
+ * multi-view triangulation with a per-point refinement.  Every call takes concatenated arrays plus offsets, runs on
+ * sfd2_get_stream(), synchronises before it returns, returns -1 on a bad argument or non-finite input and reports per-item trouble
+ * through status words.  Results depend on the inputs (and the seed) only: not on the batch, its order or the scheduling. */
+typedef struct {
+    int32_t model, reserved;        /* SFD2_CAM_*; any other id is an error                                                */
+    double params[8];               /* the model's parameters in COLMAP order                                              */
+    double qvec[4], tvec[3];        /* world to camera, qvec = (w, x, y, z), normalised by the call                         */
+} sfd2_tri_view;
+/* Known-pose geometric verification.  views[n_views]; kp_offsets[n_views + 1] and keypoints[kp_offsets[n_views]][2] (host, as the
+ * feature store holds them: the call adds COLMAP's +0.5, triangulation.py:64); pair p matches view pair_views[2p] against
+ * pair_views[2p + 1] with matches[match_offsets[p] .. match_offsets[p + 1])[2] = (key point in the first, key point in the second),
+ * host, IN/OUT.  A match survives when its point-to-epipolar-line distance in normalised coordinates is <= max_error_px / mean focal
+ * in both images; a pair with fewer than min_num_inliers survivors loses all.  Rejected entries become (-1, -1); entries that come
+ * in negative stay rejected.  pair_counts[p]: the survivors before the min_num_inliers rule; pair_status[p]: 0 or 1 = an index
+ * beyond the image's key points (the call then returns -1).  flags: 0. */
+int sfd2_verify_matches_batch(sfd2_ctx *ctx, const sfd2_tri_view *views, int n_views, const int64_t *kp_offsets, const float *keypoints,
+                              const int32_t *pair_views, const int64_t *match_offsets, int n_pairs, int32_t *matches,
+                              double max_error_px, int min_num_inliers, int32_t *pair_counts, int32_t *pair_status, int flags);
+/* Connected components over n_nodes nodes and edges[n_edges][2] (host; an edge with a negative end is skipped).  labels[n_nodes]:
+ * the smallest node of the node's component.  The components of two or more nodes as a CSR ordered by label, nodes ascending:
+ * track_offsets (capacity n_nodes / 2 + 2) and track_nodes (capacity n_nodes), their lengths in *n_tracks (+ 1) and *n_track_nodes.
+ * status[0]: 0, 1 = an edge beyond n_nodes, 2 = not converged within max_rounds hooking rounds (both return -1, nothing else is
+ * written); status[1]: rounds run.  flags: 0. */
+int sfd2_build_tracks(sfd2_ctx *ctx, int64_t n_nodes, const int32_t *edges, int64_t n_edges, int max_rounds, int32_t *labels,
+                      int32_t *track_offsets, int32_t *track_nodes, int64_t *n_tracks, int64_t *n_track_nodes, int32_t *status, int flags);
+#define SFD2_TRI_MAX_POINTS 4       /* points per track                                                                    */
+typedef struct {
+    double min_tri_angle_deg;           /* hypotheses and the final filter (1.5)                                           */
+    double create_max_angle_error_deg;  /* inliers of a hypothesis (2)                                                     */
+    double filter_max_reproj_error;     /* completion and filter, pixels (4)                                               */
+    uint64_t seed;                      /* a long track's hypothesis h of pass p is drawn from (seed, label, 64 p + h) only */
+    int32_t max_refine_iterations;      /* Levenberg-Marquardt steps per refinement (50)                                   */
+    int32_t reserved;
+} sfd2_tri_conf;
+/* Track t holds the observations track_offsets[t] .. track_offsets[t + 1] (host arrays): obs_view (index into views; the
+ * observations of one view must be consecutive, as sfd2_build_tracks' ascending nodes are) and obs_xy (key point as stored, the call
+ * adds +0.5); track_labels[t] keys the random draws.  Up to SFD2_TRI_MAX_POINTS points per track, slot s = t * SFD2_TRI_MAX_POINTS +
+ * pass: xyz[s][3], error[s] (mean reprojection error, pixels), n_obs[s] (0: no point); obs_point[o]: the pass that took observation
+ * o, or -1; track_status[t]: 0, 1 = fewer than two observations, 2 = a refinement left the finite numbers.  flags: 0. */
+int sfd2_triangulate_tracks(sfd2_ctx *ctx, const sfd2_tri_view *views, int n_views, const int64_t *track_offsets, const int64_t *track_labels,
+                            int n_tracks, const int32_t *obs_view, const float *obs_xy, const sfd2_tri_conf *conf, double *xyz, double *error,
+                            int32_t *n_obs, int8_t *obs_point, int32_t *track_status, int flags);
 
 #ifdef __cplusplus
 }

@@ -125,6 +125,23 @@ class AssembleJob(ctypes.Structure):
 
 ASM_ST_MATCH_RANGE, ASM_ST_ROW_RANGE, ASM_ST_CAPACITY = 1, 2, 4
 
+
+class TriView(ctypes.Structure):
+    """sfd2_tri_view (include/sfd2_hip.h)."""
+    _fields_ = [("model", ctypes.c_int32), ("reserved", ctypes.c_int32), ("params", ctypes.c_double * 8), ("qvec", ctypes.c_double * 4),
+                ("tvec", ctypes.c_double * 3)]
+
+
+class TriConf(ctypes.Structure):
+    """sfd2_tri_conf (include/sfd2_hip.h)."""
+    _fields_ = [("min_tri_angle_deg", ctypes.c_double), ("create_max_angle_error_deg", ctypes.c_double),
+                ("filter_max_reproj_error", ctypes.c_double), ("seed", ctypes.c_uint64), ("max_refine_iterations", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+TRI_MAX_POINTS = 4
+TRI_ST_RANGE, TRI_ST_NOT_CONVERGED = 1, 2
+
 # every symbol include/sfd2_hip.h declares (tests/test_abi.py checks the two lists agree)
 EXPORTS = [
     "sfd2_version", "sfd2_last_error", "sfd2_ctx_create", "sfd2_ctx_destroy", "sfd2_get_stream",
@@ -136,7 +153,7 @@ EXPORTS = [
     "sfd2_get_range_status", "sfd2_range_tensor_name", "sfd2_calibrate_range", "sfd2_get_act_exponents", "sfd2_set_act_exponents",
     "sfd2_extract_record_async", "sfd2_desc_pack", "sfd2_get_margin_status", "sfd2_get_relax_status", "sfd2_get_option", "sfd2_device_pci_bus_id",
     "sfd2_jpeg_parse", "sfd2_jpeg_prepare", "sfd2_jpeg_decode", "sfd2_absolute_pose_batch", "sfd2_pose_refine_batch",
-    "sfd2_assemble_2d3d",
+    "sfd2_assemble_2d3d", "sfd2_verify_matches_batch", "sfd2_build_tracks", "sfd2_triangulate_tracks",
 ]
 
 _lib = None
@@ -223,10 +240,14 @@ def load():
     lib.sfd2_absolute_pose_batch.argtypes = [vp, ctypes.POINTER(PoseProblem), ci, ctypes.POINTER(PoseConf), ctypes.POINTER(PoseResult), vp, ci]
     lib.sfd2_pose_refine_batch.argtypes = [vp, ctypes.POINTER(PoseProblem), ci, vp, vp, ctypes.POINTER(PoseResult), ci]
     lib.sfd2_assemble_2d3d.argtypes = [vp, ctypes.POINTER(PointTable), ctypes.POINTER(AssembleJob), ci, ci, ci]
+    cd = ctypes.c_double
+    lib.sfd2_verify_matches_batch.argtypes = [vp, ctypes.POINTER(TriView), ci, vp, vp, vp, vp, ci, vp, cd, ci, vp, vp, ci]
+    lib.sfd2_build_tracks.argtypes = [vp, i64, vp, i64, ci, vp, vp, vp, ctypes.POINTER(i64), ctypes.POINTER(i64), vp, ci]
+    lib.sfd2_triangulate_tracks.argtypes = [vp, ctypes.POINTER(TriView), ci, vp, vp, ci, vp, vp, ctypes.POINTER(TriConf), vp, vp, vp, vp, vp, ci]
     for name in EXPORTS:
         getattr(lib, name)  # raises AttributeError if the .so lacks a declared symbol
-    if lib.sfd2_version() < 111:
-        raise RuntimeError(f"{LIB_PATH} is version {lib.sfd2_version()}, this binding needs >= 111 (rebuild: __graft_entry__.build())")
+    if lib.sfd2_version() < 112:
+        raise RuntimeError(f"{LIB_PATH} is version {lib.sfd2_version()}, this binding needs >= 112 (rebuild: __graft_entry__.build())")
     _lib = lib
     return lib
 

@@ -1,5 +1,5 @@
-// libsfd2hip: the camera model shared by the pose kernels (pose_kernels.hip) and the 2D-3D assembly's reprojection gate
-// (assemble_kernels.hip): COLMAP's cameras in OPENCV form (PoseCam, sfd2_internal.h), fp64, pure arithmetic.
+// libsfd2hip: the camera model shared by the pose kernels (pose_kernels.hip), the 2D-3D assembly's reprojection gate
+// (assemble_kernels.hip) and the SfM map kernels (tri_kernels.hip): COLMAP's cameras in OPENCV form (PoseCam, sfd2_internal.h), fp64, pure arithmetic.
 #pragma once
 #include "sfd2_internal.h"
 
@@ -17,6 +17,28 @@ SFD2_PD void distort(const PoseCam &c, double u, double v, double &ud, double &v
     J[1] = 2.0 * uv * drad + 2.0 * c.p1 * u + 2.0 * c.p2 * v;
     J[2] = 2.0 * uv * drad + 2.0 * c.p2 * v + 2.0 * c.p1 * u;
     J[3] = 1.0 + rad + 2.0 * v2 * drad + 2.0 * c.p2 * u + 6.0 * c.p1 * v;
+}
+
+constexpr int kPoseUndistIters = 100;   // COLMAP's IterativeUndistortion bound
+
+// pixel -> normalised image coordinates (COLMAP CamFromImg / ImageToWorld)
+SFD2_PD void img_to_norm(const PoseCam &c, double px, double py, double &u, double &v)
+{
+    const double xd = (px - c.c[0]) / c.f[0], yd = (py - c.c[1]) / c.f[1];
+    u = xd;
+    v = yd;
+    if (!c.distorted) return;
+    for (int it = 0; it < kPoseUndistIters; ++it) {
+        double ud, vd, J[4];
+        distort(c, u, v, ud, vd, J);
+        const double fx = ud - xd, fy = vd - yd;
+        const double det = J[0] * J[3] - J[1] * J[2];
+        if (!(fabs(det) > 1e-300)) break;
+        const double du = (J[3] * fx - J[1] * fy) / det, dv = (J[0] * fy - J[2] * fx) / det;
+        u -= du;
+        v -= dv;
+        if (du * du + dv * dv < 1e-30) break;
+    }
 }
 
 // camera-frame point -> pixel, no depth test (a point on or behind the image plane gives what the division gives)

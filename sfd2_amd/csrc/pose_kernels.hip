@@ -19,7 +19,7 @@
 // Every reduction runs in a fixed order (wave butterflies, then the waves in index order) and nothing depends on another
 // workgroup, so results are bit-identical whatever the batch, its order and the scheduling.  All loops are bounded.
 #include "sfd2_internal.h"
-#include "pose_camera.h"              // SFD2_PD, distort: the camera model, shared with assemble_kernels.hip
+#include "pose_camera.h"              // SFD2_PD, distort, img_to_norm: the camera model, shared with assemble_kernels.hip and tri_kernels.hip
 
 namespace {
 
@@ -28,32 +28,13 @@ constexpr int kWaves = kWG / 64;
 constexpr int kLoSteps = 8;          // local optimisation: re-estimations per improvement
 constexpr int kLoGN = 3;             // Gauss-Newton iterations per re-estimation
 constexpr int kRefIters = 100;       // refinement iterations (pycolmap's max_num_iterations)
-constexpr int kUndistIters = 100;    // COLMAP's IterativeUndistortion bound
 constexpr int kHypD = 12;            // doubles per stored hypothesis (R row-major, t)
 
 SFD2_PD bool finite_d(double v) { return __builtin_isfinite(v); }
 
 // ---------------------------------------------------------------------------------------------------------------- camera model
 // (distort: pose_camera.h)
-// pixel -> normalised image coordinates (COLMAP CamFromImg / ImageToWorld)
-SFD2_PD void img_to_norm(const PoseCam &c, double px, double py, double &u, double &v)
-{
-    const double xd = (px - c.c[0]) / c.f[0], yd = (py - c.c[1]) / c.f[1];
-    u = xd;
-    v = yd;
-    if (!c.distorted) return;
-    for (int it = 0; it < kUndistIters; ++it) {
-        double ud, vd, J[4];
-        distort(c, u, v, ud, vd, J);
-        const double fx = ud - xd, fy = vd - yd;
-        const double det = J[0] * J[3] - J[1] * J[2];
-        if (!(fabs(det) > 1e-300)) break;
-        const double du = (J[3] * fx - J[1] * fy) / det, dv = (J[0] * fy - J[2] * fx) / det;
-        u -= du;
-        v -= dv;
-        if (du * du + dv * dv < 1e-30) break;
-    }
-}
+// (img_to_norm: pose_camera.h)
 
 // ---------------------------------------------------------------------------------------------------------------- small algebra
 SFD2_PD void cross3(const double a[3], const double b[3], double o[3])

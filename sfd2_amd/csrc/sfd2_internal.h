@@ -757,3 +757,40 @@ struct AsmJobDev {
 struct AsmResDev { int32_t m, status; };
 void launch_assemble(hipStream_t st, const AsmJobDev *jobs, int n_jobs, int max_blocks, const double *xyz, const int32_t *track, int n_points,
                      int32_t *rows, unsigned char *keep, int32_t *blk, int32_t *counts, AsmResDev *res);
+
+// ------------------------------------------------------------------------------------------------ SfM map (tri_kernels.hip)
+#define SFD2_TRI_WG 256               // verification: matches of one (pair, chunk) block; also the flat kernels' block
+#define SFD2_TRI_WAVE 64              // triangulation: one wave owns one track; lanes = hypotheses of a pass
+#define SFD2_TRI_MAX_POINTS 4         // points per track (passes over a component's leftover observations)
+#define SFD2_TRI_ST_RANGE 1           // verification / tracks status: an index beyond its table
+#define SFD2_TRI_ST_NOT_CONVERGED 2   // tracks: the hooking rounds reached their ceiling
+#define SFD2_TRI_ST_SHORT 1           // triangulation, per track: fewer than two observations
+#define SFD2_TRI_ST_NONFINITE 2       //   a refinement left the finite numbers (the point is dropped)
+struct TriViewDev {
+    double R[9], t[3], C[3];          // x_cam = R X + t, C = -R^T t
+    PoseCam cam;
+};
+struct TriPairDev {
+    double E[9];                      // x_j^T E x_i = 0 in normalised coordinates
+    double thr_i, thr_j;              // max_error / mean focal of either image
+    int64_t moff, kp_i, kp_j;         // first match of the pair; first key point of either image
+    int32_t n, n_i, n_j, blk0;        // matches, key points of either image, first block of the pair
+};
+struct TriConfDev {
+    double tan_create, cos_min_angle, max_reproj;
+    uint64_t seed;
+    int32_t lm_iters, pad;
+};
+void launch_tri_normalise(hipStream_t st, const TriViewDev *views, int n_views, const int64_t *offsets, const float *kp, int64_t n, double2 *xn);
+void launch_tri_verify(hipStream_t st, const TriPairDev *pairs, int n_pairs, const int32_t *blk_pair, int n_blocks, const double2 *xn,
+                       int32_t *matches, int32_t *blk_cnt, int32_t *pair_cnt, int32_t *pair_status, int min_inliers);
+void launch_tri_cc_init(hipStream_t st, int32_t *parent, int64_t n, int32_t *words);
+void launch_tri_cc_round(hipStream_t st, const int32_t *edges, int64_t n_edges, int32_t *parent, int64_t n, int32_t *words);
+void launch_tri_cc_flags(hipStream_t st, const int32_t *sorted_labels, int64_t n, int32_t *keep, int32_t *head);
+void launch_tri_cc_scatter(hipStream_t st, const int32_t *sorted_labels, const int32_t *sorted_nodes, int64_t n, const int32_t *keep,
+                           const int32_t *head, const int32_t *pos, const int32_t *tid, int32_t *track_offsets, int32_t *track_nodes, int32_t *totals);
+void launch_tri_iota(hipStream_t st, int32_t *p, int64_t n);
+void launch_tri_obs_prep(hipStream_t st, const TriViewDev *views, const int32_t *obs_view, const float *obs_xy, int64_t n, double2 *px, double2 *xn);
+void launch_tri_tracks(hipStream_t st, const TriViewDev *views, const TriConfDev &conf, const int64_t *offsets, const int64_t *labels,
+                       const int32_t *order, int n_tracks, const int32_t *obs_view, const double2 *px, const double2 *xn, signed char *obs_point,
+                       unsigned char *obs_tmp, double *xyz, double *err, int32_t *n_obs, int32_t *status);
