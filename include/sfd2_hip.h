@@ -85,7 +85,7 @@ typedef struct {
     int64_t n_candidates; /* N0 after NMS + threshold + border of the last extract          */
 } sfd2_timings;
 
-int sfd2_version(void);   /* 100 = rounds 1-4; 105 adds sfd2_extract_record_async, sfd2_desc_pack and host outputs with SFD2_FLAG_ASYNC; 106 adds sfd2_get_margin_status; 107 adds sfd2_get_relax_status (option "c3b_plain"); 108 adds sfd2_get_option, sfd2_device_pci_bus_id, SFD2_FLAG_DESC_STORE64; 109 adds the baseline JPEG decoder (sfd2_jpeg_*); 112 adds the SfM map (sfd2_verify_matches_batch, sfd2_build_tracks, sfd2_triangulate_tracks) */
+int sfd2_version(void);   /* 100 = rounds 1-4; 105 adds sfd2_extract_record_async, sfd2_desc_pack and host outputs with SFD2_FLAG_ASYNC; 106 adds sfd2_get_margin_status; 107 adds sfd2_get_relax_status (option "c3b_plain"); 108 adds sfd2_get_option, sfd2_device_pci_bus_id, SFD2_FLAG_DESC_STORE64; 109 adds the baseline JPEG decoder (sfd2_jpeg_*); 112 adds the SfM map (sfd2_verify_matches_batch, sfd2_build_tracks, sfd2_triangulate_tracks); 113 adds the pair selection (sfd2_pairs_retrieval, sfd2_pairs_covisibility, sfd2_pairs_poses) */
 const char *sfd2_last_error(void);
 
 int sfd2_ctx_create(int device, sfd2_ctx **out);
@@ -665,6 +665,41 @@ typedef struct {
 int sfd2_triangulate_tracks(sfd2_ctx *ctx, const sfd2_tri_view *views, int n_views, const int64_t *track_offsets, const int64_t *track_labels,
                             int n_tracks, const int32_t *obs_view, const float *obs_xy, const sfd2_tri_conf *conf, double *xyz, double *error,
                             int32_t *n_obs, int8_t *obs_point, int32_t *track_status, int flags);
+
+/* ------------------------------------------------------------------------------------------------ pair selection
+ * The image pairs the stages above are run on: hloc/pairs_from_retrieval.py (query-db pairs by global-descriptor similarity),
+ * hloc/pairs_from_covisibility.py (db-db pairs by shared 3D points) and hloc/pairs_from_poses.py (pairs by distance under a
+ * rotation gate).  All three are "the k best of n scored candidates per row" under ONE total order: the better score first, then
+ * the smaller candidate index.  A row's result depends on the inputs only -- not on tiling, split count, batch or scheduling.
+ * Conventions of the SfM-map section: concatenated arrays plus offsets (host memory unless said otherwise), the calls run on
+ * sfd2_get_stream() and synchronise before they return, and return -1 with sfd2_last_error() set on a bad argument or non-finite
+ * input.  1 <= k <= SFD2_PAIRS_MAX_K (sfd2_pairs_poses, whose lists are per image and not per strip of rows: <=
+ * SFD2_PAIRS_POSES_MAX_K).  Rows are best first; slots a row does not fill hold index -1. */
+#define SFD2_PAIRS_MAX_K 256
+#define SFD2_PAIRS_POSES_MAX_K 1024
+#define SFD2_PAIRS_FLAG_GLOBAL_COUNTERS 1   /* covisibility: counters in global scratch even where they would fit LDS           */
+#define SFD2_PAIRS_FLAG_CENTRES 2           /* poses: positions are the camera centres -R^T t (see sfd2_pairs_poses)            */
+#define SFD2_PAIRS_SPLITS(n) ((n) << 8)     /* retrieval: flags bits 8..15 = number of db splits (0: chosen by the call)         */
+/* query[nq][d] . db[nd][d]^T in fp32 (f32-input MFMA: an fmaf chain over ascending element index, so a similarity has the same
+ * bits whatever the batch or the split count) and per query the k most similar db rows: idx[nq][k], sim[nq][k] (host).  Replaces
+ * the einsum + topk of pairs_from_retrieval.py:60-61.  inputs_on_device: query and db are host (0) or device (1) pointers.  Any
+ * d, nq, nd >= 1; k > nd is an error, as torch.topk raises.  The split count is clamped to the number of 128-row db tiles. */
+int sfd2_pairs_retrieval(sfd2_ctx *ctx, const float *query, int nq, const float *db, int nd, int d, int k, int inputs_on_device,
+                         int32_t *idx, float *sim, int flags);
+/* The map as two CSRs: obs_offsets[n_images + 1] / obs_point = per image the point-table row of every key point that has a 3D
+ * point; track_offsets[n_points + 1] / track_image = per point the image index of every track element.  Duplicates on either side
+ * are counted, as the loops of pairs_from_covisibility.py:20-24 count them; the image itself is excluded.  Per image the k other
+ * images with the largest counts > 0: idx[n_images][k], count[n_images][k], n_found[n_images] (<= k; 0: no covisibility). */
+int sfd2_pairs_covisibility(sfd2_ctx *ctx, const int64_t *obs_offsets, const int32_t *obs_point, int n_images,
+                            const int64_t *track_offsets, const int32_t *track_image, int n_points, int k, int32_t *idx,
+                            int32_t *count, int32_t *n_found, int flags);
+/* qvec[n][4] (w x y z, used as stored: COLMAP's qvec2rotmat does not normalise) and tvec[n][3], world to camera, fp64 throughout.
+ * Per pair dist = |p_i - p_j| and dR = deg(acos(clip((tr(R_i^T R_j) - 1) / 2, -1, 1))); a candidate is valid when
+ * dR < rotation_threshold_deg and j != i; per image the k nearest valid ones, nearest first: idx[n][k], dist[n][k] (unfilled:
+ * infinity), n_found[n].  The position p is -R t, which is what pairs_from_poses.py:25-26 computes (it multiplies before it
+ * transposes); with SFD2_PAIRS_FLAG_CENTRES it is the camera centre -R^T t.  k >= n is no error: a row has at most n - 1 entries. */
+int sfd2_pairs_poses(sfd2_ctx *ctx, const double *qvec, const double *tvec, int n, int k, double rotation_threshold_deg,
+                     int32_t *idx, double *dist, int32_t *n_found, int flags);
 
 #ifdef __cplusplus
 }

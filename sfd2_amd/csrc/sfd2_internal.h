@@ -794,3 +794,16 @@ void launch_tri_obs_prep(hipStream_t st, const TriViewDev *views, const int32_t 
 void launch_tri_tracks(hipStream_t st, const TriViewDev *views, const TriConfDev &conf, const int64_t *offsets, const int64_t *labels,
                        const int32_t *order, int n_tracks, const int32_t *obs_view, const double2 *px, const double2 *xn, signed char *obs_point,
                        unsigned char *obs_tmp, double *xyz, double *err, int32_t *n_obs, int32_t *status);
+
+// ------------------------------------------------------------------------------------------------ pair selection (pairs_kernels.hip)
+#define SFD2_PAIRS_COVIS_LDS_IMAGES 39936   // covisibility counters stay in LDS up to this many images (156 KB of the 160), else a global row per workgroup
+size_t pairs_retrieval_lds(int k);
+int pairs_retrieval_tiles(int nd);          // db tiles: the unit the split count divides
+int pairs_retrieval_strips(int nq);         // query strips: blocks along x
+hipError_t launch_pairs_finite(hipStream_t st, const float *a, size_t na, const float *b, size_t nb, int *flag);
+hipError_t launch_pairs_retrieval(hipStream_t st, const float *query, int nq, const float *db, int nd, int d, int k, int splits, float *part_s,
+                                  int *part_i, int32_t *idx, float *sim);
+hipError_t launch_pairs_covis(hipStream_t st, const int64_t *obs_off, const int32_t *obs_point, int n_images, const int64_t *trk_off,
+                              const int32_t *trk_img, int k, int global_counters, int blocks, int *scratch, int32_t *idx, int32_t *cnt, int32_t *n_found);
+hipError_t launch_pairs_poses(hipStream_t st, const double *qvec, const double *tvec, int n, int k, double thr_deg, int centres, double *rc,
+                              int32_t *idx, double *dist, int32_t *n_found);
