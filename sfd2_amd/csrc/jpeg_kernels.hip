@@ -10,7 +10,7 @@
 //                       predictor at every lane's start: the sums since the lane's restart interval began)
 //   jpeg_write_kernel   decodes once more from the agreed starts and writes the coefficients; checks block counts, interval ends, sync
 //   jpeg_idct_kernel    libjpeg's accurate integer IDCT (jidctint.c, "islow": 13-bit constants, two passes, range limit around 128) with
-//                       the 16-bit saturation of libjpeg-turbo's SIMD version
+//                       the 16-bit arithmetic of libjpeg-turbo's SIMD version (wrapping sums, saturating packs, the DC-only shortcut)
 //   jpeg_color_kernel   libjpeg's "fancy" chroma upsampling (h2v1 / h2v2 triangle filters, replicated edges) and YCbCr -> RGB with its
 //                       16-bit fixed-point tables; writes RGBX
 // Safety: every read of the bit buffer is clamped to its words, every coefficient write to block < total_blocks; an anomaly sets a
@@ -349,11 +349,14 @@ __global__ __launch_bounds__(kSyncWG) void jpeg_write_kernel(const unsigned char
 // ---------------------------------------------------------------------------------------------------- IDCT (jidctint.c, islow)
 constexpr int kIdctBlocks = 32;    // 8 threads per block
 
-// The arithmetic of libjpeg-turbo's SIMD "islow" (what PIL runs on x86-64): the dequantised coefficient is the low 16 bits of coef * quantval,
-// pass 1's outputs are saturated to 16 bits and the samples to [0, 255] around 128.  Where nothing saturates -- every valid 8-bit stream
-// short of extreme quantisation -- this is jidctint.c's C arithmetic exactly; where something does (noise at quality 100, corrupted
-// coefficients) the C version's wrapping range-limit table and the SIMD saturation differ, and the SIMD one is the reference here.
+// The arithmetic of libjpeg-turbo's SIMD "islow" (what PIL runs on x86-64), pinned against PIL's output on blocks of one to four
+// coefficients under 16-bit quantisation tables (tests/test_gpu_jpeg_crafted.py): the dequantised coefficient is the low 16 bits of
+// coef * quantval; the sums in0 +- in4, in7 + in3 and in5 + in1 of both passes are 16-bit word additions that wrap; pass 1's outputs are
+// saturated to 16 bits and the samples to [0, 255] around 128; and a block whose rows 1-7 hold no coefficient skips pass 1 for a 16-bit
+// shift of row 0, which wraps where the full pass would saturate.  Where nothing leaves 16 bits -- every valid 8-bit stream short of
+// extreme quantisation -- this is jidctint.c's C arithmetic exactly.
 __device__ inline int sat16(int x) { return x < -32768 ? -32768 : x > 32767 ? 32767 : x; }
+__device__ inline int wrap16(int x) { return (int)(short)x; }
 
 __device__ inline unsigned char idct_limit(int x)
 {
@@ -383,8 +386,8 @@ __device__ inline void idct8(const int *in, int *out, int shift)
     int tmp3 = z1 + z2 * FIX_0_765366865;
     z2 = in[0];
     z3 = in[4];
-    int tmp0 = (z2 + z3) * (1 << 13);
-    int tmp1 = (z2 - z3) * (1 << 13);
+    int tmp0 = wrap16(z2 + z3) * (1 << 13);
+    int tmp1 = wrap16(z2 - z3) * (1 << 13);
     const int tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
     tmp0 = in[7];
     tmp1 = in[5];
@@ -392,8 +395,8 @@ __device__ inline void idct8(const int *in, int *out, int shift)
     tmp3 = in[1];
     z1 = tmp0 + tmp3;
     z2 = tmp1 + tmp2;
-    z3 = tmp0 + tmp2;
-    int z4 = tmp1 + tmp3;
+    z3 = wrap16(tmp0 + tmp2);
+    int z4 = wrap16(tmp1 + tmp3);
     const int z5 = (z3 + z4) * FIX_1_175875602;
     tmp0 = tmp0 * FIX_0_298631336;
     tmp1 = tmp1 * FIX_2_053119869;
@@ -435,9 +438,16 @@ __global__ __launch_bounds__(kIdctBlocks * 8) void jpeg_idct_kernel(const unsign
         const short *cb = coef + (int64_t)b * 64;
         const uint16_t *q = tabs->q[c];
         int x[8], y[8];
-        for (int r = 0; r < 8; ++r) x[r] = (int)(short)((int)cb[r * 8 + t] * (int)q[r * 8 + t]);
-        idct8(x, y, 13 - 2);
-        for (int r = 0; r < 8; ++r) ws[lb][r * 8 + t] = sat16(y[r]);
+        int ac = 0;                                        // any coefficient in rows 1-7 of the block (its 8 threads share a wave)
+        for (int r = 1; r < 8; ++r) ac |= cb[r * 8 + t];
+        for (int m = 1; m < 8; m <<= 1) ac |= __shfl_xor(ac, m, 8);
+        for (int r = 0; r < 8; ++r) x[r] = wrap16((int)cb[r * 8 + t] * (int)q[r * 8 + t]);
+        if (ac) {
+            idct8(x, y, 13 - 2);
+            for (int r = 0; r < 8; ++r) ws[lb][r * 8 + t] = sat16(y[r]);
+        } else {
+            for (int r = 0; r < 8; ++r) ws[lb][r * 8 + t] = wrap16(x[0] * 4);
+        }
     }
     __syncthreads();
     if (!active) return;

@@ -109,6 +109,8 @@ int parse(const uint8_t *d, int64_t n, sfd2_jpeg_info *info, Hdr *hd)
             if (P != 8) return reject(info, SFD2_JPEG_PRECISION, "sample precision is not 8 bits");
             if (info->height == 0) return reject(info, SFD2_JPEG_PROCESS, "height defined by DNL");
             if (info->width == 0 || nf == 0) return reject(info, SFD2_JPEG_MALFORMED, "empty frame");
+            if (info->width > 65500 || info->height > 65500)       // libjpeg's JPEG_MAX_DIMENSION: the CPU decoders refuse these
+                return reject(info, SFD2_JPEG_MALFORMED, "frame wider or taller than 65500");
         } else if (m == 0xC3 || m == 0xC5 || m == 0xC7) {
             return reject(info, SFD2_JPEG_PROCESS, "lossless or hierarchical JPEG");
         } else if (m >= 0xC9 && m <= 0xCF) {           // SOF9-SOF15 and DAC (0xCC)
@@ -146,7 +148,7 @@ int parse(const uint8_t *d, int64_t n, sfd2_jpeg_info *info, Hdr *hd)
             if (sl < 2) return reject(info, SFD2_JPEG_MALFORMED, "short DRI");
             info->restart_interval = be16(s);
         } else if (m == 0xE0) {
-            if (sl >= 5 && !memcmp(s, "JFIF\0", 5)) jfif = true;
+            if (sl >= 14 && !memcmp(s, "JFIF\0", 5)) jfif = true;    // libjpeg: only with the 14 data bytes of a JFIF header
         } else if (m == 0xEE) {
             if (sl >= 12 && !memcmp(s, "Adobe", 5)) adobe = s[11];
         } else if ((m >= 0xE1 && m <= 0xEF) || m == 0xFE) {

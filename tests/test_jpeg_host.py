@@ -1,10 +1,12 @@
 """CPU tests of the host side of the baseline JPEG decoder: sfd2_jpeg_parse (sizes, sampling, restart intervals, the reason of every
-refusal, truncations and byte flips that never crash it), sfd2_jpeg_prepare, and ImageDataset(decoder="hip").load."""
+refusal, truncations and byte flips that never crash it), sfd2_jpeg_prepare, and ImageDataset(decoder="hip").load; then the crafted
+files of tests/jpeg_ref.py: the transcoder against PIL, the verdict tables, colour-space detection and the dimension cap."""
 import io
 
 import numpy as np
 import pytest
 
+import jpeg_ref as jr
 from sfd2_amd import jpeg
 
 
@@ -152,3 +154,126 @@ def test_dataset_hip_items(tmp_path):
             assert a.get("jpeg") is None and a["fallback"] and np.array_equal(a["image"], b["image"])
     with pytest.raises(ValueError):
         el.ImageDataset(tmp_path, conf, decoder="nvjpeg")
+
+
+# ------------------------------------------------------------------------------------------------ crafted files (tests/jpeg_ref.py)
+
+def _cases(*families):
+    return [(name, mode) for fam in families for name, (modes, _) in fam.items() for mode in modes]
+
+
+def _build(name, mode, src):
+    for fam in (jr.MUST_SUPPORT, jr.TRANSCODED_SAME, jr.SAME_OR_REFUSED):
+        if name in fam:
+            return fam[name][1](src)
+    raise KeyError(name)
+
+
+@pytest.mark.parametrize("size", [(40, 24), (33, 17)], ids=["40x24", "33x17"])
+@pytest.mark.parametrize("mode", jr.ALL)
+def test_transcoder_keeps_pil_pixels(mode, size):
+    """The reference inside its own conditions: every way the transcoder recodes a PIL file (table ids, table shapes, restart intervals,
+    padding, an extra byte) decodes in PIL to the source's pixels, the coefficients read back equal, and jpeg.parse takes the file."""
+    src = jr.base(mode, *size)
+    want = jr.pil_pixels(src)
+    blocks = jr.decode_scan(jr.read(src))
+    n = 0
+    for name, m in _cases(jr.TRANSCODED_SAME, jr.SAME_OR_REFUSED):
+        if m != mode:
+            continue
+        data = _build(name, mode, src)
+        assert np.array_equal(jr.pil_pixels(data), want), name
+        if name in jr.TRANSCODED_SAME:
+            assert jr.decode_scan(jr.read(data)) == blocks, name
+        info = jpeg.parse(data)
+        assert info.supported, (name, jpeg.reason(info))
+        n += 1
+    assert n >= 14
+
+
+def test_huffman_tables_from_counts_and_lengths():
+    """optimal_table (T.81 K.2): a valid prefix code of at most 16 bits that holds every counted symbol, shorter codes for more frequent
+    symbols, also for 256 symbols with Fibonacci-like counts (which need the length limit); flat_table: one length."""
+    rs = np.random.RandomState(2)
+    for counts in ({s: int(c) for s, c in enumerate(rs.randint(1, 1000, 200))}, {0: 5}, {3: 1, 250: 1},
+                   {s: int(1.5 ** min(s, 60)) for s in range(256)}):
+        bits, vals = jr.optimal_table(counts)
+        enc = jr.huff_codes(bits, vals)
+        assert sorted(vals) == sorted(counts) and sum(bits) == len(vals) and max(l for _, l in enc.values()) <= 16
+        assert sum(2.0 ** -l for _, l in enc.values()) < 1.0                    # (the all-ones code point stays free)
+        if max(l for _, l in enc.values()) < 16:                                # (no length was limited: more frequent, never longer)
+            assert all(enc[a][1] <= enc[b][1] for a in counts for b in counts if counts[a] > counts[b])
+    bits, vals = jr.flat_table(range(12), 9)
+    assert bits[8] == 12 and sum(bits) == 12 and {l for _, l in jr.huff_codes(bits, vals).values()} == {9}
+
+
+@pytest.mark.parametrize("name,mode", _cases(jr.MUST_SUPPORT), ids=lambda v: str(v))
+def test_verdict_must_support(name, mode):
+    """Every crafted header variant: PIL decodes it to the source's pixels, and jpeg.parse calls it supported with the geometry the
+    headers state."""
+    src = jr.base(mode)
+    data = _build(name, mode, src)
+    assert np.array_equal(jr.pil_pixels(data), jr.pil_pixels(src))
+    info = jpeg.parse(data)
+    assert info.supported == 1 and info.reason == 0, jpeg.reason(info)
+    g = jr.geometry(data)
+    for k in ("width", "height", "n_components", "mcus_x", "mcus_y", "n_blocks", "restart_interval", "n_intervals"):
+        assert getattr(info, k) == g[k], (k, getattr(info, k), g[k])
+    nc = g["n_components"]
+    assert list(info.h_samp)[:nc] == g["h_samp"] and list(info.v_samp)[:nc] == g["v_samp"]
+    assert data[info.scan_end] == 0xFF and info.scan_begin < info.scan_end
+
+
+@pytest.mark.parametrize("name", list(jr.MUST_REFUSE))
+def test_verdict_must_refuse(name):
+    """Files PIL refuses or decodes to other pixels than the YCbCr decode of the same scan: jpeg.parse refuses them, with the reason."""
+    why, fn = jr.MUST_REFUSE[name]
+    data = fn()
+    assert jr.pil_is_ycbcr(data) is not True
+    info = jpeg.parse(data)
+    assert not info.supported and jpeg.reason(info) == why, jpeg.reason(info)
+
+
+def test_colour_space_follows_pil():
+    """Component ids x JFIF, Adobe transforms x JFIF, and APP0 segments that start with JFIF\\0 but are shorter than a JFIF header: where
+    PIL does not decode the file as YCbCr (other pixels than the untouched file's, or no image at all), parse refuses with "colour
+    space"; everywhere else the file is supported.  libjpeg counts a JFIF marker only from 14 data bytes on."""
+    cases = jr.colour_cases()
+    assert len(cases) == 8 + 6 + 9
+    other = set()
+    for name, data in cases.items():
+        ycc = jr.pil_is_ycbcr(data)
+        info = jpeg.parse(data)
+        if ycc:
+            assert info.supported, (name, jpeg.reason(info))
+        else:
+            other.add(name)
+            assert not info.supported and jpeg.reason(info) == "colour space", (name, jpeg.reason(info))
+    assert other == {"idsR-G-B-nojfif", "adobe0-nojfif"} | {f"rgb-ids-jfif{n}" for n in range(5, 14)}, other
+
+
+def test_dimension_cap_follows_pil():
+    """libjpeg refuses frames wider or taller than 65500: a file PIL raises on is refused by parse (the driver then fails the same way
+    through its CPU decoder), and 65500 itself is taken."""
+    for mode in ("420", "grey"):
+        for kw in (dict(width=65501), dict(width=65535), dict(height=65501), dict(height=65535)):
+            data = jr.write(jr.set_sof(jr.read(jr.base(mode)), **kw))
+            with pytest.raises(OSError):
+                jr.pil_pixels(data)
+            info = jpeg.parse(data)
+            assert not info.supported and jpeg.reason(info) == "malformed", (mode, kw)
+    for w, h in ((65500, 1), (1, 65500)):
+        data = jr.base("420", w, h)
+        info = jpeg.parse(data)
+        assert jr.pil_pixels(data).shape == (h, w, 3) and info.supported and (info.width, info.height) == (w, h)
+
+
+@pytest.mark.parametrize("edit", list(jr.QUANT_EDITS))
+def test_extreme_quantisation_tables_are_supported(edit):
+    """16-bit tables scaled x3 / x40 / x257 and 8-bit tables of all 255 / all 1: PIL decodes them, parse takes them."""
+    for mode in jr.ALL:
+        for kind in ("noise", "primaries"):
+            data = jr.write(jr.QUANT_EDITS[edit](jr.read(jr.base(mode, 40, 24, kind))))
+            assert jr.pil_pixels(data).shape == (24, 40, 3)
+            info = jpeg.parse(data)
+            assert info.supported, (mode, kind, jpeg.reason(info))
