@@ -316,7 +316,13 @@ int sfd2_debug_activation(sfd2_ctx *ctx, const char *name, float *out, int64_t c
 /* Nearest-neighbour matcher.  d0 [n0 x dim], d1 [n1 x dim] (dtype/layout as given).
  * matches0 [n0] int64 (-1 = no match); scores0 [n0] fp32 (hloc: (sim+1)/2 or 0;
  * itloc: raw row maximum).  Replaces NearestNeighbor._forward
- * (hloc/matchers/nearest_neighbor.py:38-57) and Matcher.forward (it_loc/matcher.py:91-119). */
+ * (hloc/matchers/nearest_neighbor.py:38-57) and Matcher.forward (it_loc/matcher.py:91-119).
+ * Ratio modes (hloc ratio_threshold > 0, SFD2_MATCH_ITLOC_NNR) compare the best similarity s1 of a row (column) with the
+ * second best s2, counted with multiplicity: a duplicated maximum has s2 == s1 and passes no ratio below 1.  A direction
+ * with ONE candidate (n1 == 1 for the rows, n0 == 1 for the columns) has no second best, where the reference's topk(2)
+ * raises: here s2 = -inf, so d1 = 2 (1 - s2) = +inf and that direction's ratio test passes -- hloc: d0 <= r^2 inf,
+ * it_loc: sqrt(d0) / (inf + 1e-8) = 0 <= ratio; the distance threshold and the other direction decide as usual.
+ * n1 == 0: every row -1 with score 0. */
 int sfd2_match(sfd2_ctx *ctx, const void *d0, int n0, const void *d1, int n1, int dim,
                int dtype, int layout, int on_device, const sfd2_match_conf *conf,
                int64_t *matches0, float *scores0, int out_on_device);

@@ -28,6 +28,16 @@ typedef const __attribute__((address_space(1))) void gbl_void_t;
 // 5.6 VALU instructions per MFMA in the mutual modes (7.5 with forward ids) instead of a second GEMM.  Packing perturbs a
 // similarity by <= 2^-15 relative (8 id bits, reverse; 2^-16 forward), below the fp16-operand error (1.5e-4); values equal
 // after truncation -- exact ties included -- go to the lower index, as torch's argmax.
+// EXCEPTION, negative maxima: "the larger code wins the max" holds for positive values only.  For a negative similarity a larger
+// mantissa is a SMALLER value, so among NEGATIVE maxima that are equal after truncation the order of the ids is reversed: the
+// reverse direction names the HIGHEST tied query of its strip, the forward direction with ids the highest tied candidate tile
+// of a split (inside a tile the column scan still takes the first, and splits merge by value, first split first: where every
+// split is one tile -- a single pair of up to 256 candidates -- the forward direction keeps the rule).  The reported partner's
+// similarity equals the maximum either way, the mutual pairs stay a partial bijection and the scores are unchanged; only WHICH of several bit-equal rows is named differs
+// from torch.  It needs a whole row or column of negative similarities, i.e. sets of a few descriptors (the label matcher's
+// small segments); seen with duplicated queries against 1 to 70 candidates and with a candidate copied 32 rows further among
+// 300 (tests/test_gpu_match_top2.py).  A sign-aware code would cost one VALU per value on the full-tile path, a bias through the
+// accumulators' C input would coarsen the truncation of every positive similarity: left as it is.
 #ifdef SFD2_MQ_NO_TSWZ   /* the A side of the A/B: the forward transposition as before */
 #define MQ_TSWZ(q_) 0
 #else
@@ -100,6 +110,7 @@ void match_mutual_kernel(const MatchJob2 *__restrict__ jobs, int splits, int qbl
     // reverse id = 255 - (query index within the block's 256): bits 7:6 = 3 - wave, 5 = 1 - t, 4:3 = 3 - (r >> 2), 2 = 1 - lhi,
     // 1:0 = 3 - (r & 3) (row of a 32 x 32 tile = 8 (r >> 2) + 4 lhi + (r & 3)).  The larger code wins the max, so among values
     // equal after truncation -- exact ties included: duplicated descriptors -- the LOWER query index wins, as torch's argmax
+    // (positive values; negative ones: file header)
     const unsigned int wb = (3u - (unsigned)wave) << 6;
     const unsigned int cb[2] = {wb | 0x20u | ((1u - (unsigned)lhi) << 2), wb | ((1u - (unsigned)lhi) << 2)};
     // the block's reverse table: one packed maximum per candidate of this split
