@@ -229,14 +229,7 @@ extern "C" int sfd2_get_timings(sfd2_ctx *c, sfd2_timings *out)
 }
 
 // ------------------------------------------------------------------------------------------ range status (include/sfd2_hip.h)
-static const int kRsGroup[SFD2_RS_COUNT] = {AE_CONV1A, AE_CONV1B, AE_CONV2A, AE_CONV2B, AE_CONV3A, AE_TRUNK, AE_T1_0, AE_T1_1, AE_T1_2,
-                                            AE_T2_0, AE_T2_1, AE_T2_2, AE_TRUNK, AE_TRUNK, AE_TRUNK, AE_PA0, AE_DA0};
-extern "C" const char *sfd2_range_tensor_name(int i)
-{
-    static const char *names[SFD2_RS_COUNT] = {"conv1a", "conv1b", "conv2a", "conv2b", "conv3a", "conv3b", "conv4.0.t1", "conv4.1.t1", "conv4.2.t1",
-                                               "conv4.0.t2", "conv4.1.t2", "conv4.2.t2", "conv4.0", "conv4.1", "conv4.2", "convPa.0", "convDa.0"};
-    return (i >= 0 && i < SFD2_RS_COUNT) ? names[i] : "";
-}
+extern "C" const char *sfd2_range_tensor_name(int i) { return (i >= 0 && i < SFD2_RS_COUNT) ? kTensor[i].range : ""; }   // (a tensor's slot is its id: sfd2_ctx.h)
 
 // the running words and the device-side history behind them in one read: [SFD2_RS_COUNT][SFD2_RANGE_SUB] then [SFD2_RS_COUNT]
 static int fetch_range_words(sfd2_ctx *c, unsigned int *raw /* SFD2_RS_COUNT * (SFD2_RANGE_SUB + 1) */, bool clear)
@@ -263,7 +256,7 @@ int read_range_status(sfd2_ctx *c, sfd2_range_status *out, int reset)
         const bool sat = m >= sat_bits || c->range_hist[t] >= SFD2_C_SAT;
         if (!(f >= c->range_hist[t])) f = c->range_hist[t];                   // (a NaN pattern stays visible)
         if (reset) c->range_hist[t] = 0.0f;
-        const int e = c->act_exp[kRsGroup[t]];
+        const int e = c->act_exp[kTensor[t].group];
         out->max_stored[t] = f;
         out->max_value[t] = std::ldexp(f, -e);
         out->exponent[t] = e;

@@ -172,7 +172,7 @@ extern "C" int sfd2_extract(sfd2_ctx *c, const void *img, int img_on_device, int
     if (plan.skip_pb) {
         ProfScope ps(c, "convPb+heads+heatmap", "pb_heads_heat_kernel", 2.0 * c->H8 * c->W8 * 65 * 256,
                      (double)c->H8 * c->W8 * 512 + (double)H * W * 4);
-        launch_pb_heads_heat(c->stream, c->pa_cur, c->H8, c->W8, c->pb.w.as<half_t>(), c->pb.cout_pad, c->pb.scale.as<float>(),
+        launch_pb_heads_heat(c->stream, act_view(c, plan, T_PA).as<half_t>(), c->H8, c->W8, c->pb.w.as<half_t>(), c->pb.cout_pad, c->pb.scale.as<float>(),
                              c->pb.shift.as<float>(), (flags & SFD2_FLAG_NO_STABILITY) ? nullptr : c->sta.as<float>(), c->H4, c->W4,
                              H, W, c->heat.as<float>(), c->counters.as<unsigned int>(), SFD2_COUNTER_BYTES / 4);
         c->counters_clean = pb_heads_heat_clears(c->H8, c->W8, SFD2_COUNTER_BYTES / 4);
@@ -216,7 +216,7 @@ extern "C" int sfd2_extract(sfd2_ctx *c, const void *img, int img_on_device, int
                                      c->counters.as<unsigned int>() + 1, sel_cap, c->da3_sparse.as<float>(), c->zero_page.as<half_t>());
             }
             // convDb (1x1) on the compact [sel_cap x 4] "image" with the mode's generic kernel, then the sampler on its compact output
-            if (convf(c, StrictConv{}, "convDb", c->fdb, c->da3_sparse, rows32, 32, c->db_sparse, rows32, 32, 0)) return -1;
+            if (convf_at(c, StrictConv{}, "convDb", c->fdb, c->da3_sparse, rows32, 32, c->db_sparse, rows32, 32, 0)) return -1;
             ProfScope ps(c, "sample_desc", "sample_desc_kernel", 0.0, (double)sel_cap * 128 * 4 * 5);
             launch_sample_desc(c->stream, c->db_sparse.as<float>(), c->H4, c->W4, H, W, c->kpts_cur, c->counters.as<unsigned int>() + 1,
                                sel_cap, desc_dst, 1);
@@ -224,7 +224,7 @@ extern "C" int sfd2_extract(sfd2_ctx *c, const void *img, int img_on_device, int
             HIPCHECK(c->da3_sparse.ensure((size_t)sel_cap * 4 * 256 * sizeof(half_t)));
             {
                 ProfScope ps(c, "convDa.3", "sparse_da3_kernel", 2.0 * 4 * sel_cap * 256.0 * 256.0 * 9, (double)sel_cap * (16 * 512 + 4 * 512) + 2.0 * 256 * 256 * 9);
-                launch_sparse_da3(c->stream, c->da0_cur, c->H4, c->W4, H, W, c->da3.w.as<half_t>(), c->da3.wsl.as<half_t>(), c->da3.cout_pad, c->da3.scale.as<float>(),
+                launch_sparse_da3(c->stream, act_view(c, plan, T_DA0).as<half_t>(), c->H4, c->W4, H, W, c->da3.w.as<half_t>(), c->da3.wsl.as<half_t>(), c->da3.cout_pad, c->da3.scale.as<float>(),
                                   c->da3.shift.as<float>(), 0, c->kpts_cur, c->counters.as<unsigned int>() + 1, sel_cap,
                                   c->da3_sparse.as<half_t>(), c->zero_page.as<half_t>());
             }
@@ -233,7 +233,7 @@ extern "C" int sfd2_extract(sfd2_ctx *c, const void *img, int img_on_device, int
                              c->db.shift.as<float>(), c->kpts_cur, c->counters.as<unsigned int>() + 1, sel_cap, desc_dst, 1);
         } else if (plan.sparse_desc) {
             ProfScope ps(c, "desc_head", "desc_head_kernel", 2.0 * 4 * sel_cap * 128 * 256, (double)sel_cap * (4 * 512 + 512));
-            launch_desc_head(c->stream, c->da_cur, c->H4, c->W4, H, W, c->db.w.as<half_t>(), c->db.cout_pad, c->db.scale.as<float>(),
+            launch_desc_head(c->stream, act_view(c, plan, T_DA).as<half_t>(), c->H4, c->W4, H, W, c->db.w.as<half_t>(), c->db.cout_pad, c->db.scale.as<float>(),
                              c->db.shift.as<float>(), c->kpts_cur, c->counters.as<unsigned int>() + 1, sel_cap, desc_dst);
         } else {
             ProfScope ps(c, "sample_desc", "sample_desc_kernel", 0.0, (double)sel_cap * 128 * 4 * 5);
@@ -335,8 +335,7 @@ extern "C" int sfd2_extract_multiscale(sfd2_ctx *c, const void *img, int img_on_
         nh[l] = scales[l] == 1.0 ? H : (int)((double)H * scales[l]);    // int(H * s), :122-123
         nw[l] = scales[l] == 1.0 ? W : (int)((double)W * scales[l]);
         if (nh[l] < 8 || nw[l] < 8) return fail("sfd2_extract_multiscale: a pyramid level is smaller than 8x8");
-        const size_t P1 = (size_t)nh[l] * nw[l];
-        const size_t cc = std::min(std::max<size_t>(65536, P1 / 8), P1);   // ensure_workspace's candidate capacity
+        const size_t cc = cand_capacity((size_t)nh[l] * nw[l]);
         cap[l] = top_k > 0 ? (int)std::min<size_t>((size_t)top_k, cc) : (int)cc;
         off[l] = cap_total;
         cap_total += cap[l];
@@ -609,8 +608,7 @@ static int heat_to_device(sfd2_ctx *c, const float *heat, int H, int W)
     const size_t bytes = (size_t)H * W * sizeof(float);
     HIPCHECK(c->heat.ensure(bytes));
     HIPCHECK(hipMemcpyAsync(c->heat.p, heat, bytes, hipMemcpyHostToDevice, c->stream));
-    size_t cap = std::max<size_t>(65536, (size_t)H * W / 8);
-    cap = std::min(cap, (size_t)H * W);
+    const size_t cap = cand_capacity((size_t)H * W);
     c->cand_cap = (int)cap;
     HIPCHECK(c->cand.ensure(cap * 8));
     HIPCHECK(c->bnd.ensure(cap * 8));
@@ -694,9 +692,10 @@ extern "C" int sfd2_debug_activation(sfd2_ctx *c, const char *name, float *out, 
 {
     if (!c || !name) return fail("sfd2_debug_activation: null argument");
     HIPCHECK(hipSetDevice(c->device));
-    auto it = c->acts.find(name);
-    if (it == c->acts.end()) return fail(std::string("unknown activation: ") + name);
-    const ActInfo &a = it->second;
+    int id = 0;
+    while (id < T_ALL && !(c->acts[id].known && std::strcmp(kTensor[id].act, name) == 0)) ++id;
+    if (id == T_ALL) return fail(std::string("unknown activation: ") + name);
+    const ActInfo &a = c->acts[id];
     if (!a.p || a.absent) return fail(std::string("activation not materialised on this path: ") + name);
     if (ch) *ch = a.c;
     if (h) *h = a.h;

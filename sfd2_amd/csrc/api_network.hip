@@ -69,19 +69,20 @@ PassPlan plan_pass(const sfd2_ctx *c, PassEntry entry, int H, int W, int top_k, 
         p.chp = p.ch || (p.comp_rb && c->opt_comp_det);
         // The records every stored tensor leaves its producer with, and its readers take (but conv3b with "c3b_plain": a3a_in).  "rb_inner": t1 (2) and
         // t2 (1, 2) plain fp16; "comp_rb" = 0: the ResBlocks' tensors all plain fp16.  The last block's output keeps its units for compensated heads.
-        p.rec.a1b = s6 ? Rec::Half6 : Rec::Unit8;
-        p.rec.a2a = Rec::Unit8;
-        p.rec.a2b = b6 ? Rec::Half6 : Rec::Unit8;
-        p.rec.a3a = p3a ? Rec::None : a6 ? Rec::Half6 : Rec::Unit8;
-        p.a3a_in = p3b ? Rec::None : p.rec.a3a;
-        p.rec.a3b = tr1 ? Rec::Resid8 : Rec::Unit8;
+        p.rec[T_CONV1A] = Rec::Unit8;
+        p.rec[T_CONV1B] = s6 ? Rec::Half6 : Rec::Unit8;
+        p.rec[T_CONV2A] = Rec::Unit8;
+        p.rec[T_CONV2B] = b6 ? Rec::Half6 : Rec::Unit8;
+        p.rec[T_CONV3A] = p3a ? Rec::None : a6 ? Rec::Half6 : Rec::Unit8;
+        p.a3a_in = p3b ? Rec::None : p.rec[T_CONV3A];
+        p.rec[T_CONV3B] = tr1 ? Rec::Resid8 : Rec::Unit8;
         for (int b = 0; b < 3 && p.comp_rb; ++b) {
-            p.rec.t1[b] = p.rb_inner >= 2 ? Rec::None : Rec::Unit8;
-            p.rec.t2[b] = p.rb_inner >= 1 ? Rec::None : Rec::Unit8;
-            p.rec.ro[b] = (tr1 && (b < 2 || !p.chp)) ? Rec::Resid8 : Rec::Unit8;
+            p.rec[T_T1_0 + b] = p.rb_inner >= 2 ? Rec::None : Rec::Unit8;
+            p.rec[T_T2_0 + b] = p.rb_inner >= 1 ? Rec::None : Rec::Unit8;
+            p.rec[T_OUT_0 + b] = (tr1 && (b < 2 || !p.chp)) ? Rec::Resid8 : Rec::Unit8;
         }
-        p.rec.pa0 = p.chp ? Rec::Unit8 : Rec::None;
-        p.rec.da0 = p.ch ? Rec::Unit8 : Rec::None;
+        p.rec[T_PA0] = p.chp ? Rec::Unit8 : Rec::None;
+        p.rec[T_DA0] = p.ch ? Rec::Unit8 : Rec::None;
     }
     p.branches = c->opt_branches;
     if (entry == PASS_EXTRACT) {
@@ -114,24 +115,27 @@ PassPlan plan_pass(const sfd2_ctx *c, PassEntry entry, int H, int W, int top_k, 
         // Infinity Cache and a layer mostly reads what the previous one just wrote (measured: ResBlocks 400 -> 344 us;
         // four slots measure the same as three).  A ResBlock's output overwrites its own t1 (dead once conv3 starts), the
         // next block's t1 takes the slot of the previous input.
-        p.slot = {0, 1 /* spans slots 1-2 */, 0, 1, 2, {0, 2, 0} /* x = slot 2, 0, 2 */, {1, 1, 1}, {0, 2, 0} /* -> final x = slot 0 */,
-                  1, 1 /* behind convPa.0 */, 2, 1 /* convDa.3 runs after convPb has consumed slot 1 */, p.branches ? 4 : 3};
+        static const int slots[T_COUNT] = {-1 /* conv1a: its own buffer */, 0, 1 /* spans slots 1-2 */, 0, 1, 2, 0, 2, 0 /* t1; x = slot 2, 0, 2 */, 1, 1, 1 /* t2 */,
+                                           0, 2, 0 /* -> final x = slot 0 */, 1, 2 /* convDa.0 */, 1 /* convPa.3: behind convPa.0 */, 1 /* convDa.3 runs after convPb has consumed slot 1 */};
+        for (int id = 0; id < T_COUNT; ++id) p.at[id].slot = slots[id];
+        p.n_slots = p.branches ? 4 : 3;
         if (p.rb23) {
             // rb23_c_kernel reads t1 (with the halo rows of neighbouring tiles) while other tiles already write the block's
             // output: the output cannot take t1's slot.  No t2 in HBM on this path, so three slots still do.
-            p.slot.t1[1] = 0; p.slot.t1[2] = 1;    // x = slot 2, 1, 2
-            p.slot.ro[0] = 1; p.slot.ro[2] = 0;    // -> final x = slot 0
+            p.at[T_T1_0 + 1].slot = 0; p.at[T_T1_0 + 2].slot = 1;    // x = slot 2, 1, 2
+            p.at[T_OUT_0].slot = 1; p.at[T_OUT_0 + 2].slot = 0;      // -> final x = slot 0
         }
-        if (p.branches) p.slot.da = 3;   // the two head branches run concurrently: no slot is shared between them
+        if (p.branches) p.at[T_DA].slot = 3;   // the two head branches run concurrently: no slot is shared between them
         // convPb fused into the detector-head kernel: convPa.3's output must outlive the network pass, so convDa.3
         // writes over the backbone output instead (slot 0) -- ConvSta, its last reader, then runs before the heads
-        if (p.skip_pb) p.slot.da = 0;
+        if (p.skip_pb) p.at[T_DA].slot = 0;
         const size_t P2 = (size_t)H2 * W2, P4 = (size_t)H4 * W4, P8 = (size_t)down2(H4) * down2(W4);
         size_t S = std::max(P2 * 64 * 2, P4 * 256 * 2);
         S = std::max(S, (P2 * 128 * 2 + 1) / 2);
         S = std::max(S, 2 * (P8 * 256 * 2 + 256));
         if (p.comp) S *= 2;   // hi plane + corr plane per tensor (the corr plane follows the hi plane inside the slot)
-        p.slot.bytes = (S + 255) & ~(size_t)255;
+        p.slot_bytes = (S + 255) & ~(size_t)255;
+        p.at[T_PA].off = (P8 * 256 * 2 * (p.comp ? 2 : 1) + 255) & ~(size_t)255;   // behind convPa.0's output (its corr plane too with "comp_heads")
     }
     p.x3_pp = x3 && c->opt_x3_pp;
     p.x3_fast = p.x3_pp && !det;     // (the parity entry point: every tensor as fp32 for sfd2_debug_activation)
@@ -193,82 +197,39 @@ int ensure_workspace(sfd2_ctx *c, const PassPlan &p, int H, int W)
     c->H4 = down2(c->H2); c->W4 = down2(c->W2);
     c->H8 = down2(c->H4); c->W8 = down2(c->W4);
     const size_t P1 = (size_t)H * W, P2 = (size_t)c->H2 * c->W2, P4 = (size_t)c->H4 * c->W4, P8 = (size_t)c->H8 * c->W8;
-    const size_t hb = sizeof(half_t);
-    const bool comp = p.comp;
+    const size_t Pl[4] = {P1, P2, P4, P8}, hb = sizeof(half_t);
     const bool layers = !p.f32 && !p.alias;      // private fp16 buffer per activation
-    // SFD2_PREC_F16C: every backbone activation is a hi plane followed by its corr plane (same geometry)
-    const size_t bb = comp ? 2 * hb : hb;
-    if (!p.f32 && !p.fused_stem) HIPCHECK(c->a1a.ensure(P1 * 64 * bb));
-    if (p.alias) HIPCHECK(c->arena.ensure(p.slot.n * p.slot.bytes));
-    if (layers) {
-        HIPCHECK(c->a1b.ensure(P2 * 64 * bb));
-        HIPCHECK(c->a2a.ensure(P2 * 128 * bb));
-        HIPCHECK(c->a2b.ensure(P4 * 128 * bb));
-        HIPCHECK(c->a3a.ensure(P4 * 256 * bb));
-        HIPCHECK(c->a3b.ensure(P4 * 256 * bb));
-        for (int b = 0; b < 3; ++b) {
-            if (!p.rb_fused) {
-                HIPCHECK(c->rt1[b].ensure(P4 * 256 * bb));
-                HIPCHECK(c->rt2[b].ensure(P4 * 256 * bb));
-            }
-            HIPCHECK(c->ro[b].ensure(P4 * 256 * bb));
-        }
-        HIPCHECK(c->pa0_o.ensure(P8 * 256 * bb));   // (corr planes too with option "comp_heads")
-        HIPCHECK(c->pa_o.ensure(P8 * 256 * hb));
-        HIPCHECK(c->da0_o.ensure(P4 * 256 * bb));
-        HIPCHECK(c->da_o.ensure(P4 * 256 * hb));
+    // not stored on the fp16 family's path at hand: conv1a's output inside the fused stem, t1 / t2 inside resblock_kernel
+    auto on_chip = [&](int id) { return id == T_CONV1A ? p.fused_stem : (id >= T_T1_0 && id < T_OUT_0 && p.rb_fused); };
+    for (int id = 0; id < T_COUNT; ++id) {
+        const size_t n = Pl[kTensor[id].level] * kTensor[id].ch;
+        // SFD2_PREC_F16C: a hi plane followed by its corr plane (same geometry; convPa.0's and convDa.0's for option "comp_heads"), none behind convPa.3's and convDa.3's outputs
+        if (p.f32) HIPCHECK(c->act32[id].ensure(n * sizeof(float)));
+        else if ((layers || id == T_CONV1A) && !on_chip(id)) HIPCHECK(c->act16[id].ensure(n * ((p.comp && id < T_PA) ? 2 * hb : hb)));
     }
+    if (p.alias) HIPCHECK(c->arena.ensure(p.n_slots * p.slot_bytes));
     HIPCHECK(c->logits.ensure(P8 * 128 * sizeof(float)));
     HIPCHECK(c->draw.ensure(P4 * 128 * sizeof(float)));
     HIPCHECK(c->sta.ensure(P4 * 3 * sizeof(float)));
     HIPCHECK(c->score.ensure(P8 * 64 * sizeof(float)));
     HIPCHECK(c->heat.ensure(P1 * sizeof(float)));
-    size_t cap = std::max<size_t>(65536, P1 / 8);
-    cap = std::min(cap, P1);
+    const size_t cap = cand_capacity(P1);
     c->cand_cap = (int)cap;
     HIPCHECK(c->cand.ensure(cap * 8));
     HIPCHECK(c->bnd.ensure(cap * 8));
     HIPCHECK(c->counters.ensure(SFD2_COUNTER_BYTES));
-    c->acts.clear();
-    auto reg = [&](const char *nm, const void *ptr, int is_f32, int planar, int ch, int pitch, int h, int w, Rec rec = Rec::None) -> ActInfo & {
-        ActInfo ai{ptr, is_f32, planar, ch, pitch, h, w, rec};
-        if (!is_f32) {      // the fp16 family stores its tensors times 2^act_exp (sfd2_ctx.h): sfd2_debug_activation divides it out
-            static const struct { const char *name; int group; } gmap[] = {
-                {"conv1a", AE_CONV1A}, {"bn1b", AE_CONV1B}, {"conv2a", AE_CONV2A}, {"bn2b", AE_CONV2B}, {"conv3a", AE_CONV3A},
-                {"bn3b", AE_TRUNK}, {"conv4.0", AE_TRUNK}, {"conv4.1", AE_TRUNK}, {"conv4.2", AE_TRUNK},
-                {"conv4.0.bn1", AE_T1_0}, {"conv4.1.bn1", AE_T1_1}, {"conv4.2.bn1", AE_T1_2},
-                {"conv4.0.bn2", AE_T2_0}, {"conv4.1.bn2", AE_T2_1}, {"conv4.2.bn2", AE_T2_2}, {"convPa.0", AE_PA0}, {"convDa.0", AE_DA0}};
-            for (const auto &g : gmap)
-                if (std::strcmp(nm, g.name) == 0) ai.exp2 = c->act_exp[g.group];
-        }
-        return c->acts[nm] = ai;
+    for (ActInfo &a : c->acts) a.known = false;
+    auto reg = [&](int id, const void *ptr, int is_f32, int planar, int pitch, Rec rec = Rec::None) -> ActInfo & {
+        const TensorRow &t = kTensor[id];      // (the fp16 family stores its tensors times 2^act_exp, sfd2_ctx.h: sfd2_debug_activation divides it out)
+        return c->acts[id] = ActInfo{true, ptr, is_f32, planar, t.ch, pitch, act_h(c, id), act_w(c, id), rec, (!is_f32 && t.group >= 0) ? c->act_exp[t.group] : 0};
     };
-    static const char *n1[3] = {"conv4.0.bn1", "conv4.1.bn1", "conv4.2.bn1"};
-    static const char *n2[3] = {"conv4.0.bn2", "conv4.1.bn2", "conv4.2.bn2"};
-    static const char *n3[3] = {"conv4.0", "conv4.1", "conv4.2"};
-    reg("convPb", c->logits.p, 1, 0, 65, 128, c->H8, c->W8);
-    reg("convDb", c->draw.p, 1, 0, 128, 128, c->H4, c->W4);
-    reg("ConvSta", c->sta.p, 1, 1, 3, 0, c->H4, c->W4);
+    reg(T_PB, c->logits.p, 1, 0, 128);
+    reg(T_DB, c->draw.p, 1, 0, 128);
+    reg(T_STA, c->sta.p, 1, 1, 0);
     if (p.f32) {
-        const size_t fb = sizeof(float);
-        HIPCHECK(c->g1a.ensure(P1 * 64 * fb));
-        HIPCHECK(c->g1b.ensure(P2 * 64 * fb));
-        HIPCHECK(c->g2a.ensure(P2 * 128 * fb));
-        HIPCHECK(c->g2b.ensure(P4 * 128 * fb));
-        HIPCHECK(c->g3a.ensure(P4 * 256 * fb));
-        HIPCHECK(c->g3b.ensure(P4 * 256 * fb));
-        for (int b = 0; b < 3; ++b) {
-            HIPCHECK(c->grt1[b].ensure(P4 * 256 * fb));
-            HIPCHECK(c->grt2[b].ensure(P4 * 256 * fb));
-            HIPCHECK(c->gro[b].ensure(P4 * 256 * fb));
-        }
-        HIPCHECK(c->gpa0_o.ensure(P8 * 256 * fb));
-        HIPCHECK(c->gpa_o.ensure(P8 * 256 * fb));
-        HIPCHECK(c->gda0_o.ensure(P4 * 256 * fb));
-        HIPCHECK(c->gda_o.ensure(P4 * 256 * fb));
         // SFD2_PREC_F16X3 (none of this with "x3_pp" = 0): the scratch planes for the largest input split in front of its layer, each hand-off buffer for the largest output routed into it
         if (p.sparse_x3 && !p.desc16 && p.sl[SL_DA0].out != X3_DA0) return fail("f16x3: the sparse descriptor head needs convDa.0 on a three-pass kernel (planes out)");
-        const size_t Pl[4] = {P1, P2, P4, P8}, pb = 2 * hb;
+        const size_t pb = 2 * hb;
         size_t scratch = 0, chain[2] = {p.x3_stem ? std::max(P2 * 64, P4 * 256) : 0, 0}, da0 = p.desc16 ? P4 * 256 : 0;
         for (int i = 0; i < SL_COUNT; ++i) {
             const StrictConv &s = p.sl[i];
@@ -284,51 +245,21 @@ int ensure_workspace(sfd2_ctx *c, const PassPlan &p, int H, int W)
         for (int k = 0; k < 3 && p.x3_rb; ++k) HIPCHECK(c->x3_rb_planes[k].ensure(P4 * 256 * pb));
         HIPCHECK(c->x3_da0_planes.ensure(da0 * pb));
         if (ensure_strict_filters(c, p)) return -1;
+    } else if (!layers) return 0;   // throughput path: intermediates live in aliased arena slots and are not readable
+    for (int id = 0; id < T_COUNT; ++id) {
         // throughput path of SFD2_PREC_F16X3: from the stem to convDa.0 the tensors exist as hi / lo' planes only; the fp32 buffers are
         // written for the last ResBlock's output and convPa.3's.  sfd2_debug_activation must say so instead of handing back what an
         // earlier sfd2_det left in them
-        const bool gone = p.x3_fast;
-        reg("conv1a", c->g1a.p, 1, 0, 64, 64, H, W).absent = gone;
-        reg("bn1b", c->g1b.p, 1, 0, 64, 64, c->H2, c->W2).absent = gone;
-        reg("conv2a", c->g2a.p, 1, 0, 128, 128, c->H2, c->W2).absent = gone;
-        reg("bn2b", c->g2b.p, 1, 0, 128, 128, c->H4, c->W4).absent = gone;
-        reg("conv3a", c->g3a.p, 1, 0, 256, 256, c->H4, c->W4).absent = gone;
-        reg("bn3b", c->g3b.p, 1, 0, 256, 256, c->H4, c->W4).absent = gone;
-        for (int b = 0; b < 3; ++b) {
-            reg(n1[b], c->grt1[b].p, 1, 0, 256, 256, c->H4, c->W4).absent = gone;
-            reg(n2[b], c->grt2[b].p, 1, 0, 256, 256, c->H4, c->W4).absent = gone;
-            reg(n3[b], c->gro[b].p, 1, 0, 256, 256, c->H4, c->W4).absent = gone && b < 2;
-        }
-        reg("convPa.0", c->gpa0_o.p, 1, 0, 256, 256, c->H8, c->W8).absent = gone;
-        reg("convPa", c->gpa_o.p, 1, 0, 256, 256, c->H8, c->W8);
-        reg("convDa.0", c->gda0_o.p, 1, 0, 256, 256, c->H4, c->W4).absent = gone;
-        reg("convDa", c->gda_o.p, 1, 0, 256, 256, c->H4, c->W4).absent = gone;
-        return 0;
+        if (p.f32) reg(id, c->act32[id].p, 1, 0, kTensor[id].ch).absent = p.x3_fast && id != T_OUT_0 + 2 && id != T_PA;
+        // (SFD2_PREC_F16C: each tensor with the corr records the plan has its producer write; the head branches' tensors as their hi planes)
+        else if (!on_chip(id)) reg(id, c->act16[id].p, 0, 0, kTensor[id].ch, id < T_PA0 ? p.rec[id] : Rec::None).absent = p.rb23 && id >= T_T2_0 && id < T_OUT_0;   // (t2 stays on chip in rb23_c_kernel)
     }
-    if (!layers) return 0;   // throughput path: intermediates live in aliased arena slots and are not readable
-    // (SFD2_PREC_F16C: each tensor with the corr records the plan has its producer write; the head branches' tensors as their hi planes)
-    if (!p.fused_stem) reg("conv1a", c->a1a.p, 0, 0, 64, 64, H, W, comp ? Rec::Unit8 : Rec::None);
-    reg("bn1b", c->a1b.p, 0, 0, 64, 64, c->H2, c->W2, p.rec.a1b);
-    reg("conv2a", c->a2a.p, 0, 0, 128, 128, c->H2, c->W2, p.rec.a2a);
-    reg("bn2b", c->a2b.p, 0, 0, 128, 128, c->H4, c->W4, p.rec.a2b);
-    reg("conv3a", c->a3a.p, 0, 0, 256, 256, c->H4, c->W4, p.rec.a3a);
-    reg("bn3b", c->a3b.p, 0, 0, 256, 256, c->H4, c->W4, p.rec.a3b);
-    for (int b = 0; b < 3; ++b) {
-        if (!p.rb_fused) {
-            reg(n1[b], c->rt1[b].p, 0, 0, 256, 256, c->H4, c->W4, p.rec.t1[b]);
-            reg(n2[b], c->rt2[b].p, 0, 0, 256, 256, c->H4, c->W4, p.rec.t2[b]).absent = p.rb23;   // (t2 stays on chip in rb23_c_kernel)
-        }
-        reg(n3[b], c->ro[b].p, 0, 0, 256, 256, c->H4, c->W4, p.rec.ro[b]);
-    }
-    reg("convPa.0", c->pa0_o.p, 0, 0, 256, 256, c->H8, c->W8);
-    reg("convPa", c->pa_o.p, 0, 0, 256, 256, c->H8, c->W8);
-    reg("convDa.0", c->da0_o.p, 0, 0, 256, 256, c->H4, c->W4);
-    reg("convDa", c->da_o.p, 0, 0, 256, 256, c->H4, c->W4);
     return 0;
 }
 
-static void conv(sfd2_ctx *c, const char *name, const ConvW &L, const DevPtr &in, int H, int W, const DevPtr &out,
-                 int Ho, int Wo, int relu, const half_t *res = nullptr, int out_f32 = 0, const float *scale_override = nullptr)
+// one plain fp16 layer on buffers given by hand
+static void conv_at(sfd2_ctx *c, const char *name, const ConvW &L, const DevPtr &in, int H, int W, const DevPtr &out,
+                    int Ho, int Wo, int relu, const half_t *res = nullptr, int out_f32 = 0, const float *scale_override = nullptr)
 {
     char kn[48];
     const float *scale = scale_override ? scale_override : L.scale.as<float>();
@@ -353,6 +284,12 @@ static void conv(sfd2_ctx *c, const char *name, const ConvW &L, const DevPtr &in
                       L.shift.as<float>(), L.cout_pad, L.ks, L.stride, relu, res, out.p, out_f32, Ho, Wo,
                       c->zero_page.as<half_t>());
 }
+// ... from tensor `in` to tensor `out` (+ the skip connection `res`): buffers and geometry by id (act_view, kTensor)
+static void conv(sfd2_ctx *c, const PassPlan &p, const char *name, const ConvW &L, int in, int out, int relu, int res = T_NONE, int out_f32 = 0)
+{
+    conv_at(c, name, L, act_view(c, p, in), act_h(c, in), act_w(c, in), act_view(c, p, out), act_h(c, out), act_w(c, out), relu,
+            res != T_NONE ? act_view(c, p, res).as<half_t>() : nullptr, out_f32);
+}
 
 // the range-status slot of a stored tensor of the compensated mode (sfd2_internal.h), null when nothing is recorded
 static unsigned int *range_slot(sfd2_ctx *c, int id)
@@ -369,13 +306,15 @@ static PPFilters pp_filters(const PassPlan &p, const ConvW &L, Rec in, Rec out)
     if (in == Rec::Unit8 && (out == Rec::Half6 || (out == Rec::Unit8 && p.fp6_filters && L.wc6.p && L.sa6.p))) return {L.wc6.as<half_t>(), L.sa6.as<float>(), true};
     return {L.wc.as<half_t>(), L.shift.as<float>(), false};
 }
-// SFD2_PREC_F16C: one compensated layer.  A compensated tensor = hi plane followed by its corr plane; in / out say in which format the two
-// tensors carry their records (a plain-fp16 consumer just reads the hi plane, Rec::None)
-static void convc(sfd2_ctx *c, const PassPlan &p, const char *name, const ConvW &L, const DevPtr &in, int H, int W, const DevPtr &out,
-                  int Ho, int Wo, int relu, Rec rin, Rec rout, const DevPtr *res = nullptr, int rs_id = -1 /* SFD2_RS_*: the output's range-status slot */,
-                  bool s2d_out = false /* option "s2d": the output stored space-to-depth */)
+// SFD2_PREC_F16C: one compensated layer from tensor `in` to tensor `out` (+ the skip connection `res_id`).  A compensated tensor = hi plane followed by its
+// corr plane; the plan says in which format each carries its records (a plain-fp16 consumer just reads the hi plane, Rec::None); rin: conv3b's override
+static void convc(sfd2_ctx *c, const PassPlan &p, const char *name, const ConvW &L, int in_id, int out_id, int relu, int res_id = T_NONE,
+                  bool s2d_out = false /* option "s2d": the output stored space-to-depth */, const Rec *rin_override = nullptr)
 {
-    unsigned int *rs = range_slot(c, rs_id);
+    const DevPtr in = act_view(c, p, in_id), out = act_view(c, p, out_id), resv = res_id != T_NONE ? act_view(c, p, res_id) : DevPtr{}, *res = res_id != T_NONE ? &resv : nullptr;
+    const int H = act_h(c, in_id), W = act_w(c, in_id), Ho = act_h(c, out_id), Wo = act_w(c, out_id);
+    const Rec rin = rin_override ? *rin_override : p.rec[in_id], rout = p.rec[out_id];
+    unsigned int *rs = range_slot(c, out_id < SFD2_RS_COUNT ? out_id : -1);
     char kn[48];
     const double px = (double)Ho * Wo;
     const double flops = 2.0 * px * L.cout * L.cin * L.ks * L.ks;
@@ -436,8 +375,8 @@ static void convc(sfd2_ctx *c, const PassPlan &p, const char *name, const ConvW 
 static X3Pair planes_of(const DevBuf &b, size_t n) { return {b.as<half_t>(), b.as<half_t>() + n}; }
 static const DevBuf &plane_buf(const sfd2_ctx *c, X3Out o) { return o == X3_CHAIN_A ? c->x3_chain[0] : o == X3_CHAIN_B ? c->x3_chain[1] : o == X3_RB ? c->x3_rb_planes[0] : c->x3_da0_planes; }
 
-int convf(sfd2_ctx *c, const StrictConv &s, const char *name, const ConvW &L, const DevPtr &in, int H, int W, const DevPtr &out,
-          int Ho, int Wo, int relu, const float *res, X3Pair *planes)
+int convf_at(sfd2_ctx *c, const StrictConv &s, const char *name, const ConvW &L, const DevPtr &in, int H, int W, const DevPtr &out,
+             int Ho, int Wo, int relu, const float *res, X3Pair *planes)
 {
     char kn[64];
     const bool x3 = c->precision == SFD2_PREC_F16X3;
@@ -479,6 +418,13 @@ int convf(sfd2_ctx *c, const StrictConv &s, const char *name, const ConvW &L, co
     return 0;
 }
 
+// strict layer `sl` from tensor `in` to tensor `out` (+ the skip connection `res`)
+static int convf(sfd2_ctx *c, const PassPlan &p, int sl, const char *name, int in, int out, int relu, int res = T_NONE, X3Pair *planes = nullptr)
+{
+    return convf_at(c, p.sl[sl], name, strict_layer(c, sl), act_view(c, p, in), act_h(c, in), act_w(c, in), act_view(c, p, out), act_h(c, out), act_w(c, out), relu,
+                    res != T_NONE ? act_view(c, p, res).as<float>() : nullptr, planes);
+}
+
 // strict mode: identical layer sequence on fp32 activations (conv_f32_kernels.hip)
 static int run_network_f32(sfd2_ctx *c, const PassPlan &p, const float *img_dev, int normalise)
 {
@@ -497,18 +443,15 @@ static int run_network_f32(sfd2_ctx *c, const PassPlan &p, const float *img_dev,
     {
         ProfScope ps(c, "conv1a", "conv1a_f32_kernel", 2.0 * P1 * 64 * 27, P1 * (12 + 256));
         launch_conv1a_f32(st, img_dev, H, W, normalise, c->f1a.w.as<float>(), c->f1a.scale.as<float>(),
-                          c->f1a.shift.as<float>(), c->g1a.as<float>());
+                          c->f1a.shift.as<float>(), c->act32[T_CONV1A].as<float>());
     }
-    if (convf(c, p.sl[SL_C1B], "conv1b", c->f1b, c->g1a, H, W, c->g1b, H2, W2, 1)) return -1;
+    if (convf(c, p, SL_C1B, "conv1b", T_CONV1A, T_CONV1B, 1)) return -1;
     }
-    if (convf(c, p.sl[SL_C2A], "conv2a", c->f2a, c->g1b, H2, W2, c->g2a, H2, W2, 1, nullptr, &pl)) return -1;
-    if (convf(c, p.sl[SL_C2B], "conv2b", c->f2b, c->g2a, H2, W2, c->g2b, H4, W4, 1, nullptr, &pl)) return -1;
-    if (convf(c, p.sl[SL_C3A], "conv3a", c->f3a, c->g2b, H4, W4, c->g3a, H4, W4, 1, nullptr, &pl)) return -1;
-    if (convf(c, p.sl[SL_C3B], "conv3b", c->f3b, c->g3a, H4, W4, c->g3b, H4, W4, 1, nullptr, &pl)) return -1;
-    const DevPtr *x = &c->g3b;
-    static const char *nm1[3] = {"conv4.0.conv1", "conv4.1.conv1", "conv4.2.conv1"};
-    static const char *nm2[3] = {"conv4.0.conv2", "conv4.1.conv2", "conv4.2.conv2"};
-    static const char *nm3[3] = {"conv4.0.conv3", "conv4.1.conv3", "conv4.2.conv3"};
+    if (convf(c, p, SL_C2A, "conv2a", T_CONV1B, T_CONV2A, 1, T_NONE, &pl)) return -1;
+    if (convf(c, p, SL_C2B, "conv2b", T_CONV2A, T_CONV2B, 1, T_NONE, &pl)) return -1;
+    if (convf(c, p, SL_C3A, "conv3a", T_CONV2B, T_CONV3A, 1, T_NONE, &pl)) return -1;
+    if (convf(c, p, SL_C3B, "conv3b", T_CONV3A, T_CONV3B, 1, T_NONE, &pl)) return -1;
+    int x = T_CONV3B;      // the tensor in front of the next ResBlock / the heads
     if (p.x3_rb) {
         // ResBlocks of SFD2_PREC_F16X3 on the throughput path: every tensor of a block lives as hi / lo' planes (the input is split
         // once in front of the first block).  conv1 and conv3 on the streaming three-pass 1x1 kernel (filters = the fp16 set's
@@ -520,68 +463,65 @@ static int run_network_f32(sfd2_ctx *c, const PassPlan &p, const float *img_dev,
         half_t *uh = c->x3_rb_planes[2].as<half_t>(), *ul = uh + nin;
         if (p.sl[SL_C3B].out != X3_RB) {      // conv3b on the generic kernel
             ProfScope ps(c, "conv3b planes", "x3_split_planes", 0.0, 12.0 * nin);
-            launch_x3_split_planes(st, x->as<float>(), nin, xh, xl);
+            launch_x3_split_planes(st, c->act32[x].as<float>(), nin, xh, xl);
         }
         for (int b = 0; b < 3; ++b) {
             {
-                ProfScope ps(c, nm1[b], "conv1x1_c256<x3>", 2.0 * P4 * 256.0 * 256.0, P4 * 256.0 * 8);
+                ProfScope ps(c, rb_layer_name(b, 1), "conv1x1_c256<x3>", 2.0 * P4 * 256.0 * 256.0, P4 * 256.0 * 8);
                 launch_conv1x1_c256_x3(st, xh, xl, H4 * W4, c->rb1[b].wfh.as<half_t>(), c->rb1[b].wfl.as<half_t>(), c->frb1[b].scale.as<float>(),
                                        c->frb1[b].shift.as<float>(), 1, nullptr, nullptr, nullptr, th, tl, c->zero_page.as<half_t>());
             }
             {
-                ProfScope ps(c, nm2[b], "gconv_c_kernel<x3>", 2.0 * P4 * 256 * 72, P4 * 256 * 8);
+                ProfScope ps(c, rb_layer_name(b, 2), "gconv_c_kernel<x3>", 2.0 * P4 * 256 * 72, P4 * 256 * 8);
                 launch_gconv_c(st, th, tl, H4, W4, c->rb2[b].w.as<half_t>(), c->rb2[b].wlk.p, c->frb2[b].scale.as<float>(),
                                c->frb2[b].shift.as<float>(), uh, ul, -1, 0, H4);
             }
             {
-                ProfScope ps(c, nm3[b], "conv1x1_c256<x3>+res", 2.0 * P4 * 256.0 * 256.0, P4 * 256.0 * (b == 2 ? 16 : 12));
+                ProfScope ps(c, rb_layer_name(b, 3), "conv1x1_c256<x3>+res", 2.0 * P4 * 256.0 * 256.0, P4 * 256.0 * (b == 2 ? 16 : 12));
                 launch_conv1x1_c256_x3(st, uh, ul, H4 * W4, c->rb3[b].wfh.as<half_t>(), c->rb3[b].wfl.as<half_t>(), c->frb3[b].scale.as<float>(),
-                                       c->frb3[b].shift.as<float>(), 1, xh, xl, b == 2 ? c->gro[b].as<float>() : nullptr, xh, xl,
+                                       c->frb3[b].shift.as<float>(), 1, xh, xl, b == 2 ? c->act32[T_OUT_0 + b].as<float>() : nullptr, xh, xl,
                                        c->zero_page.as<half_t>());
             }
         }
-        x = &c->gro[2];
+        x = T_OUT_0 + 2;
         pl = {xh, xl};
     }
     for (int b = 0; b < (p.x3_rb ? 0 : 3); ++b) {
-        if (convf(c, p.sl[SL_RB1 + b], nm1[b], c->frb1[b], *x, H4, W4, c->grt1[b], H4, W4, 1)) return -1;
+        float *t1 = c->act32[T_T1_0 + b].as<float>(), *t2 = c->act32[T_T2_0 + b].as<float>();
+        if (convf(c, p, SL_RB1 + b, rb_layer_name(b, 1), x, T_T1_0 + b, 1)) return -1;
         {
             if (c->precision == SFD2_PREC_F16X3) {
-                ProfScope ps(c, nm2[b], "gconv_x3_kernel", 2.0 * P4 * 256 * 72, P4 * 256 * 8);
-                launch_gconv_x3(st, c->grt1[b].as<float>(), H4, W4, c->frb2[b].wx3.p, c->frb2[b].scale.as<float>(),
-                                c->frb2[b].shift.as<float>(), c->grt2[b].as<float>());
+                ProfScope ps(c, rb_layer_name(b, 2), "gconv_x3_kernel", 2.0 * P4 * 256 * 72, P4 * 256 * 8);
+                launch_gconv_x3(st, t1, H4, W4, c->frb2[b].wx3.p, c->frb2[b].scale.as<float>(), c->frb2[b].shift.as<float>(), t2);
             } else {
-                ProfScope ps(c, nm2[b], "gconv_f32_kernel", 2.0 * P4 * 256 * 72, P4 * 256 * 8);
-                launch_gconv_f32(st, c->grt1[b].as<float>(), H4, W4, c->frb2[b].w.as<float>(), c->frb2[b].scale.as<float>(),
-                                 c->frb2[b].shift.as<float>(), c->grt2[b].as<float>());
+                ProfScope ps(c, rb_layer_name(b, 2), "gconv_f32_kernel", 2.0 * P4 * 256 * 72, P4 * 256 * 8);
+                launch_gconv_f32(st, t1, H4, W4, c->frb2[b].w.as<float>(), c->frb2[b].scale.as<float>(), c->frb2[b].shift.as<float>(), t2);
             }
         }
-        if (convf(c, p.sl[SL_RB3 + b], nm3[b], c->frb3[b], c->grt2[b], H4, W4, c->gro[b], H4, W4, 1, x->as<float>())) return -1;
-        x = &c->gro[b];
+        if (convf(c, p, SL_RB3 + b, rb_layer_name(b, 3), T_T2_0 + b, T_OUT_0 + b, 1, x)) return -1;
+        x = T_OUT_0 + b;
     }
     // (throughput path: both head branches read the backbone output's planes; convPa.0 leaves its own output as planes for convPa.3)
     const X3Pair backbone = pl;
-    if (convf(c, p.sl[SL_PA0], "convPa.0", c->fpa0, *x, H4, W4, c->gpa0_o, H8, W8, 1, nullptr, &pl)) return -1;
-    if (convf(c, p.sl[SL_PA3], "convPa.3", c->fpa3, c->gpa0_o, H8, W8, c->gpa_o, H8, W8, 0, nullptr, &pl)) return -1;
-    if (convf(c, p.sl[SL_PB], "convPb", c->fpb, c->gpa_o, H8, W8, c->logits, H8, W8, 0)) return -1;
+    if (convf(c, p, SL_PA0, "convPa.0", x, T_PA0, 1, T_NONE, &pl)) return -1;
+    if (convf(c, p, SL_PA3, "convPa.3", T_PA0, T_PA, 0, T_NONE, &pl)) return -1;
+    if (convf(c, p, SL_PB, "convPb", T_PA, T_PB, 0)) return -1;
     pl = backbone;
     // Option "x3_desc16": the descriptor branch leaves this mode's arithmetic here -- convDa.0 as ONE fp16 pass (conv3x3_pp) over the backbone output's hi
     // plane, at the network's own scale (scale_rawin), its output (times 2^act_exp[AE_DA0], what convDa.3's folded constants expect) in the buffer
-    // the planes would have taken; sfd2_extract then runs the fp16 sparse head on it.  The detector branch above is untouched.
+    // the planes would have taken (act_view); sfd2_extract then runs the fp16 sparse head on it.  The detector branch above is untouched.
     if (p.desc16) {
-        DevPtr in, out;
+        DevPtr in;
         in.p = backbone.hi;
-        out.p = c->x3_da0_planes.p;
-        conv(c, "convDa.0", c->da0, in, H4, W4, out, H4, W4, 1, nullptr, 0, c->da0.scale_rawin.as<float>());
-        c->da0_cur = c->x3_da0_planes.as<half_t>();
-    } else if (convf(c, p.sl[SL_DA0], "convDa.0", c->fda0, *x, H4, W4, c->gda0_o, H4, W4, 1, nullptr, &pl)) return -1;
+        conv_at(c, "convDa.0", c->da0, in, H4, W4, act_view(c, p, T_DA0), H4, W4, 1, nullptr, 0, c->da0.scale_rawin.as<float>());
+    } else if (convf(c, p, SL_DA0, "convDa.0", x, T_DA0, 1, T_NONE, &pl)) return -1;
     if (!p.skip_da3) {      // (otherwise sfd2_extract's sparse descriptor head runs them on the sampled corners: on convDa.0's planes, or in fp16 with "x3_desc16")
-        if (convf(c, p.sl[SL_DA3], "convDa.3", c->fda3, c->gda0_o, H4, W4, c->gda_o, H4, W4, 0, nullptr, &pl)) return -1;
-        if (convf(c, p.sl[SL_DB], "convDb", c->fdb, c->gda_o, H4, W4, c->draw, H4, W4, 0)) return -1;
+        if (convf(c, p, SL_DA3, "convDa.3", T_DA0, T_DA, 0, T_NONE, &pl)) return -1;
+        if (convf(c, p, SL_DB, "convDb", T_DA, T_DB, 0)) return -1;
     }
     if (c->has_sta) {
         ProfScope ps(c, "ConvSta", "convsta_f32_kernel", 2.0 * P4 * 3 * 256, P4 * (1024 + 12));
-        launch_convsta_f32(st, x->as<float>(), H4 * W4, c->sta_w.as<float>(), c->sta_b.as<float>(), c->sta.as<float>());
+        launch_convsta_f32(st, c->act32[x].as<float>(), H4 * W4, c->sta_w.as<float>(), c->sta_b.as<float>(), c->sta.as<float>());
     }
     if (!p.skip_head) {
         ProfScope ps(c, "detector_head", "detector_head_kernel", 0.0, P8 * (65 * 4 + 256));
@@ -601,45 +541,33 @@ int run_network(sfd2_ctx *c, const PassPlan &p, const float *img_dev, int normal
     hipStream_t st = c->stream;
     const int H = c->H, W = c->W, H2 = c->H2, W2 = c->W2, H4 = c->H4, W4 = c->W4, H8 = c->H8, W8 = c->W8;
     const double P1 = (double)H * W, P4 = (double)H4 * W4, P8 = (double)H8 * W8;
-    // Activation placement (plan_pass): one buffer per activation, or the arena slots of the throughput path
-    DevPtr a1b = c->a1b, a2a = c->a2a, a2b = c->a2b, a3a = c->a3a, a3b = c->a3b, pa0_o = c->pa0_o, pa_o = c->pa_o,
-           da0_o = c->da0_o, da_o = c->da_o;   // non-owning views
-    DevPtr t1v[3] = {c->rt1[0], c->rt1[1], c->rt1[2]}, t2v[3] = {c->rt2[0], c->rt2[1], c->rt2[2]},
-           rov[3] = {c->ro[0], c->ro[1], c->ro[2]};
-    if (alias) {
-        const size_t P8s = (size_t)H8 * W8, S = p.slot.bytes;
-        char *base = c->arena.as<char>();
-        auto slot = [&](int i, size_t off = 0) { DevPtr v; v.p = base + (size_t)i * S + off; v.cap = 0; return v; };
-        a1b = slot(p.slot.a1b); a2a = slot(p.slot.a2a); a2b = slot(p.slot.a2b); a3a = slot(p.slot.a3a); a3b = slot(p.slot.a3b);
-        for (int b = 0; b < 3; ++b) { t1v[b] = slot(p.slot.t1[b]); t2v[b] = slot(p.slot.t2[b]); rov[b] = slot(p.slot.ro[b]); }
-        pa0_o = slot(p.slot.pa0); pa_o = slot(p.slot.pa, (P8s * 256 * 2 * (comp ? 2 : 1) + 255) & ~(size_t)255);   // (convPa.0's corr plane with "comp_heads")
-        da0_o = slot(p.slot.da0); da_o = slot(p.slot.da);
-    }
-    const DevPtr *x = &a3b;
-    static const char *nm1[3] = {"conv4.0.conv1", "conv4.1.conv1", "conv4.2.conv1"};
-    static const char *nm2[3] = {"conv4.0.conv2", "conv4.1.conv2", "conv4.2.conv2"};
-    static const char *nm3[3] = {"conv4.0.conv3", "conv4.1.conv3", "conv4.2.conv3"};
+    auto V = [&](int id) { return act_view(c, p, id); };      // where tensor `id` lives for this pass (plan_pass's placement)
+    int x = T_CONV3B;      // the tensor in front of the next ResBlock / the heads
     // one ResBlock (nets/sfd2.py:25-55) in plain fp16
-    static const char *nmf[3] = {"conv4.0", "conv4.1", "conv4.2"};
     auto rb_f16 = [&](int b) {
-        DevPtr &t1 = t1v[b], &t2 = t2v[b], &ob = rov[b];
+        const int t1 = T_T1_0 + b, t2 = T_T2_0 + b, ob = T_OUT_0 + b;
         if (p.rb_fused) {
-            ProfScope ps(c, nmf[b], "resblock_kernel", 2.0 * P4 * 256 * (256 + 72 + 256), P4 * 256 * 4);
-            launch_resblock(st, x->as<half_t>(), H4, W4, c->rb1[b].wrm.as<half_t>(), c->rb1[b].scale.as<float>(),
+            const int o = alias ? t1 : ob;   // the fused kernel must not write over its own input: with the arena the output takes t1's slot
+            ProfScope ps(c, kTensor[ob].act, "resblock_kernel", 2.0 * P4 * 256 * (256 + 72 + 256), P4 * 256 * 4);
+            launch_resblock(st, V(x).as<half_t>(), H4, W4, c->rb1[b].wrm.as<half_t>(), c->rb1[b].scale.as<float>(),
                             c->rb1[b].shift.as<float>(), c->rb2[b].wgc.as<half_t>(), c->rb2[b].scale.as<float>(),
                             c->rb2[b].shift.as<float>(), c->rb3[b].wrm.as<half_t>(), c->rb3[b].scale.as<float>(),
-                            c->rb3[b].shift.as<float>(), alias ? t1.as<half_t>() : ob.as<half_t>(), c->zero_page.as<half_t>());
-            x = alias ? &t1 : &ob;   // the fused kernel must not write over its own input: with the arena the output takes t1's slot
+                            c->rb3[b].shift.as<float>(), V(o).as<half_t>(), c->zero_page.as<half_t>());
+            x = o;
             return;
         }
-        conv(c, nm1[b], c->rb1[b], *x, H4, W4, t1, H4, W4, 1);
+        conv(c, p, rb_layer_name(b, 1), c->rb1[b], x, t1, 1);
         {
-            ProfScope ps(c, nm2[b], "gconv3x3_g8_kernel", 2.0 * P4 * 256 * 72, P4 * 256 * 4);
-            launch_gconv3x3_g8(st, t1.as<half_t>(), H4, W4, c->rb2[b].w.as<half_t>(),
-                               c->rb2[b].scale.as<float>(), c->rb2[b].shift.as<float>(), t2.as<half_t>());
+            ProfScope ps(c, rb_layer_name(b, 2), "gconv3x3_g8_kernel", 2.0 * P4 * 256 * 72, P4 * 256 * 4);
+            launch_gconv3x3_g8(st, V(t1).as<half_t>(), H4, W4, c->rb2[b].w.as<half_t>(),
+                               c->rb2[b].scale.as<float>(), c->rb2[b].shift.as<float>(), V(t2).as<half_t>());
         }
-        conv(c, nm3[b], c->rb3[b], t2, H4, W4, ob, H4, W4, 1, x->as<half_t>());
-        x = &ob;
+        conv(c, p, rb_layer_name(b, 3), c->rb3[b], t2, ob, 1, x);
+        x = ob;
+    };
+    auto conv_sta = [&]() {
+        ProfScope ps(c, "ConvSta", "convsta_kernel", 2.0 * P4 * 3 * 256, P4 * (512 + 12));
+        launch_convsta(c->cur_stream, V(x).as<half_t>(), H4 * W4, c->sta_w16.as<float>(), c->sta_b.as<float>(), c->sta.as<float>());
     };
     if (comp) {
         // SFD2_PREC_F16C backbone: every activation carries a corr plane, every layer adds the fp8 correction terms (the formats: plan_pass)
@@ -647,32 +575,33 @@ int run_network(sfd2_ctx *c, const PassPlan &p, const float *img_dev, int normal
             ProfScope ps(c, "conv1a+conv1b", "fused_stem_c_kernel", 2.0 * P1 * 64 * 27 + 2.0 * (double)H2 * W2 * 64 * 576,
                          P1 * 12 + (double)H2 * W2 * 256);
             launch_fused_stem_c(st, img_dev, H, W, normalise, c->c1a.wc.as<half_t>(), c->c1a.scale.as<float>(),
-                                c->c1a.shift.as<float>(), p.rec.a1b == Rec::Half6 ? c->w1b_stem_c6.p : c->w1b_stem_c.p, c->c1b.scale.as<float>(),
-                                c->c1b.shift.as<float>(), a1b.as<half_t>(), corr_of(a1b, (size_t)H2 * W2, 64), H2, W2, c->c1b.sbyte,
-                                c->range_stat.as<unsigned int>(), p.rec.a1b);
+                                c->c1a.shift.as<float>(), p.rec[T_CONV1B] == Rec::Half6 ? c->w1b_stem_c6.p : c->w1b_stem_c.p, c->c1b.scale.as<float>(),
+                                c->c1b.shift.as<float>(), V(T_CONV1B).as<half_t>(), corr_of(V(T_CONV1B), (size_t)H2 * W2, 64), H2, W2, c->c1b.sbyte,
+                                c->range_stat.as<unsigned int>(), p.rec[T_CONV1B]);
         } else {
             {
                 ProfScope ps(c, "conv1a", "conv1a_c_kernel", 2.0 * P1 * 64 * 27, P1 * (12 + 256));
                 launch_conv1a_c(st, img_dev, H, W, normalise, c->c1a.wc.as<half_t>(), c->c1a.scale.as<float>(),
-                                c->c1a.shift.as<float>(), c->a1a.as<half_t>(), corr_of(c->a1a, (size_t)H * W, 64), range_slot(c, SFD2_RS_CONV1A));
+                                c->c1a.shift.as<float>(), V(T_CONV1A).as<half_t>(), corr_of(V(T_CONV1A), (size_t)H * W, 64), range_slot(c, T_CONV1A));
             }
-            convc(c, p, "conv1b", c->c1b, c->a1a, H, W, a1b, H2, W2, 1, Rec::Unit8, p.rec.a1b, nullptr, SFD2_RS_CONV1B);
+            convc(c, p, "conv1b", c->c1b, T_CONV1A, T_CONV1B, 1);
         }
-        convc(c, p, "conv2a", c->c2a, a1b, H2, W2, a2a, H2, W2, 1, p.rec.a1b, p.rec.a2a, nullptr, SFD2_RS_CONV2A, p.a2a_s2d);
+        convc(c, p, "conv2a", c->c2a, T_CONV1B, T_CONV2A, 1, T_NONE, p.a2a_s2d);
         if (p.a2a_s2d) {
             const ConvW &L = c->c2b;
             ProfScope ps(c, "conv2b", "conv2b_s2d_kernel", 2.0 * P4 * L.cout * L.cin * 9, 4.0 * ((double)H2 * W2 * L.cin + (double)L.cout * L.cin * 9) + P4 * L.cout_pad * 4.0);
-            launch_conv2b_s2d(st, a2a.as<half_t>(), corr_of(a2a, (size_t)H2 * W2, L.cin), H4, W4, L.wc.as<half_t>(), L.scale.as<float>(), L.shift.as<float>(), 1,
-                              a2b.as<half_t>(), corr_of(a2b, (size_t)H4 * W4, L.cout_pad), c->zero_page.as<half_t>(), L.sbyte, range_slot(c, SFD2_RS_CONV2B), p.rec.a2b);
+            launch_conv2b_s2d(st, V(T_CONV2A).as<half_t>(), corr_of(V(T_CONV2A), (size_t)H2 * W2, L.cin), H4, W4, L.wc.as<half_t>(), L.scale.as<float>(), L.shift.as<float>(), 1,
+                              V(T_CONV2B).as<half_t>(), corr_of(V(T_CONV2B), (size_t)H4 * W4, L.cout_pad), c->zero_page.as<half_t>(), L.sbyte, range_slot(c, T_CONV2B), p.rec[T_CONV2B]);
         } else
-        convc(c, p, "conv2b", c->c2b, a2a, H2, W2, a2b, H4, W4, 1, p.rec.a2a, p.rec.a2b, nullptr, SFD2_RS_CONV2B);
-        convc(c, p, "conv3a", c->c3a, a2b, H4, W4, a3a, H4, W4, 1, p.rec.a2b, p.rec.a3a, nullptr, SFD2_RS_CONV3A);
-        convc(c, p, "conv3b", c->c3b, a3a, H4, W4, a3b, H4, W4, 1, p.a3a_in, p.rec.a3b, nullptr, SFD2_RS_CONV3B);
+        convc(c, p, "conv2b", c->c2b, T_CONV2A, T_CONV2B, 1);
+        convc(c, p, "conv3a", c->c3a, T_CONV2B, T_CONV3A, 1);
+        convc(c, p, "conv3b", c->c3b, T_CONV3A, T_CONV3B, 1, T_NONE, false, &p.a3a_in);
         for (int b = 0; b < 3; ++b) {  // ResBlock (nets/sfd2.py:25-55)
             if (!p.comp_rb) { rb_f16(b); continue; }   // option "comp_rb" = 0: this block in plain fp16 on the hi planes
-            DevPtr &t1 = t1v[b], &t2 = t2v[b], &ob = rov[b];
+            const int t1i = T_T1_0 + b, t2i = T_T2_0 + b, obi = T_OUT_0 + b;
+            const DevPtr xv = V(x), t1 = V(t1i), t2 = V(t2i), ob = V(obi);
             // the records of the block's input, t1, t2 and output (plan_pass)
-            const Rec x_rec = b == 0 ? p.rec.a3b : p.rec.ro[b - 1], t1_rec = p.rec.t1[b], t2_rec = p.rec.t2[b], o_rec = p.rec.ro[b];
+            const Rec x_rec = p.rec[x], t1_rec = p.rec[t1i], t2_rec = p.rec[t2i], o_rec = p.rec[obi];
             if (p.rb_inner) {
                 // Option "rb_inner": the tensors INSIDE the block as plain fp16 (1: t2, 2: t1 and t2).  These kernels are bound
                 // by HBM bytes, a plain tensor is half of a compensated one; the filters stay compensated (over a plain input the
@@ -682,46 +611,46 @@ int run_network(sfd2_ctx *c, const PassPlan &p, const float *img_dev, int normal
                 const bool t1p = t1_rec == Rec::None;
                 if (t1p) {
                     const bool x_r1 = x_rec == Rec::Resid8;
-                    ProfScope ps(c, nm1[b], "conv1x1_c256<comp,plain out>", 2.0 * P4 * 256.0 * 256.0, P4 * 256.0 * (x_r1 ? 5 : 6));
-                    launch_conv1x1_c256_c(st, x->as<half_t>(), corr_of(*x, PP, 256), (int)PP, L1.wfh.as<half_t>(), x_r1 ? L1.wfr.as<half_t>() : L1.wfc.as<half_t>(),
+                    ProfScope ps(c, rb_layer_name(b, 1), "conv1x1_c256<comp,plain out>", 2.0 * P4 * 256.0 * 256.0, P4 * 256.0 * (x_r1 ? 5 : 6));
+                    launch_conv1x1_c256_c(st, xv.as<half_t>(), corr_of(xv, PP, 256), (int)PP, L1.wfh.as<half_t>(), x_r1 ? L1.wfr.as<half_t>() : L1.wfc.as<half_t>(),
                                           L1.scale.as<float>(), L1.shift.as<float>(), 1, nullptr, nullptr, t1.as<half_t>(), nullptr,
-                                          c->zero_page.as<half_t>(), L1.sbyte, range_slot(c, SFD2_RS_T1_0 + b), x_rec, t1_rec);
+                                          c->zero_page.as<half_t>(), L1.sbyte, range_slot(c, t1i), x_rec, t1_rec);
                 } else {
-                    convc(c, p, nm1[b], L1, *x, H4, W4, t1, H4, W4, 1, x_rec, t1_rec, nullptr, SFD2_RS_T1_0 + b);
+                    convc(c, p, rb_layer_name(b, 1), L1, x, t1i, 1);
                 }
                 if (p.rb23) {
-                    ProfScope ps(c, nm3[b], "rb23_c_kernel", 2.0 * P4 * 256 * 72 + 2.0 * P4 * 256.0 * 256.0,
+                    ProfScope ps(c, rb_layer_name(b, 3), "rb23_c_kernel", 2.0 * P4 * 256 * 72 + 2.0 * P4 * 256.0 * 256.0,
                                  P4 * 256.0 * (10 - (x_rec == Rec::Resid8) - (o_rec == Rec::Resid8)));
                     launch_rb23_c(st, t1.as<half_t>(), H4, W4, L2.w.as<half_t>(), L2.wlk.as<half_t>(), L2.scale.as<float>(), L2.shift.as<float>(),
-                                  L3.wfh.as<half_t>(), L3.wfl.as<half_t>(), L3.scale.as<float>(), L3.shift.as<float>(), x->as<half_t>(),
-                                  corr_of(*x, PP, 256), ob.as<half_t>(), corr_of(ob, PP, 256), c->zero_page.as<half_t>(),
-                                  range_slot(c, SFD2_RS_T2_0 + b), range_slot(c, SFD2_RS_OUT_0 + b), x_rec, o_rec, L3.wf8l.as<half_t>(), L3.sbyte);
-                    x = &ob;
+                                  L3.wfh.as<half_t>(), L3.wfl.as<half_t>(), L3.scale.as<float>(), L3.shift.as<float>(), xv.as<half_t>(),
+                                  corr_of(xv, PP, 256), ob.as<half_t>(), corr_of(ob, PP, 256), c->zero_page.as<half_t>(),
+                                  range_slot(c, t2i), range_slot(c, obi), x_rec, o_rec, L3.wf8l.as<half_t>(), L3.sbyte);
+                    x = obi;
                     continue;
                 }
                 {
-                    ProfScope ps(c, nm2[b], t1p ? "gconv_c_kernel<plain>" : "gconv_c_kernel<plain out>", 2.0 * P4 * 256 * 72, P4 * 256 * (t1p ? 4 : 6));
+                    ProfScope ps(c, rb_layer_name(b, 2), t1p ? "gconv_c_kernel<plain>" : "gconv_c_kernel<plain out>", 2.0 * P4 * 256 * 72, P4 * 256 * (t1p ? 4 : 6));
                     launch_gconv_c(st, t1.as<half_t>(), t1p ? nullptr : corr_of(t1, PP, 256), H4, W4, L2.w.as<half_t>(),
                                    t1p ? L2.wlk.p : L2.wc.p, L2.scale.as<float>(), L2.shift.as<float>(), t2.as<half_t>(), nullptr, L2.sbyte, 0, H4,
-                                   range_slot(c, SFD2_RS_T2_0 + b));
+                                   range_slot(c, t2i));
                 }
                 {
-                    ProfScope ps(c, nm3[b], "conv1x1_c256<comp,plain in>+res", 2.0 * P4 * 256.0 * 256.0, P4 * 256.0 * 10);
+                    ProfScope ps(c, rb_layer_name(b, 3), "conv1x1_c256<comp,plain in>+res", 2.0 * P4 * 256.0 * 256.0, P4 * 256.0 * 10);
                     launch_conv1x1_c256_c(st, t2.as<half_t>(), nullptr, (int)PP, L3.wfh.as<half_t>(), L3.wfl.as<half_t>(), L3.scale.as<float>(),
-                                          L3.shift.as<float>(), 1, x->as<half_t>(), corr_of(*x, PP, 256), ob.as<half_t>(), corr_of(ob, PP, 256),
-                                          c->zero_page.as<half_t>(), L3.sbyte, range_slot(c, SFD2_RS_OUT_0 + b), t2_rec, o_rec);
+                                          L3.shift.as<float>(), 1, xv.as<half_t>(), corr_of(xv, PP, 256), ob.as<half_t>(), corr_of(ob, PP, 256),
+                                          c->zero_page.as<half_t>(), L3.sbyte, range_slot(c, obi), t2_rec, o_rec);
                 }
             } else {
-                convc(c, p, nm1[b], c->rb1[b], *x, H4, W4, t1, H4, W4, 1, x_rec, t1_rec, nullptr, SFD2_RS_T1_0 + b);
+                convc(c, p, rb_layer_name(b, 1), c->rb1[b], x, t1i, 1);
                 {
-                    ProfScope ps(c, nm2[b], "gconv_c_kernel", 2.0 * P4 * 256 * 72, P4 * 256 * 8);
+                    ProfScope ps(c, rb_layer_name(b, 2), "gconv_c_kernel", 2.0 * P4 * 256 * 72, P4 * 256 * 8);
                     launch_gconv_c(st, t1.as<half_t>(), corr_of(t1, (size_t)H4 * W4, 256), H4, W4, c->rb2[b].w.as<half_t>(),
                                    c->rb2[b].wc.p, c->rb2[b].scale.as<float>(), c->rb2[b].shift.as<float>(), t2.as<half_t>(),
-                                   corr_of(t2, (size_t)H4 * W4, 256), c->rb2[b].sbyte, 0, H4, range_slot(c, SFD2_RS_T2_0 + b));
+                                   corr_of(t2, (size_t)H4 * W4, 256), c->rb2[b].sbyte, 0, H4, range_slot(c, t2i));
                 }
-                convc(c, p, nm3[b], c->rb3[b], t2, H4, W4, ob, H4, W4, 1, t2_rec, o_rec, x, SFD2_RS_OUT_0 + b);
+                convc(c, p, rb_layer_name(b, 3), c->rb3[b], t2i, obi, 1, x);
             }
-            x = &ob;
+            x = obi;
         }
     } else {
     if (p.fused_stem) {
@@ -729,19 +658,19 @@ int run_network(sfd2_ctx *c, const PassPlan &p, const float *img_dev, int normal
                      P1 * 12 + (double)H2 * W2 * 128);
         launch_fused_stem(st, img_dev, H, W, normalise, c->c1a.w.as<half_t>(), c->c1a.scale.as<float>(),
                           c->c1a.shift.as<float>(), c->w1b_fused.as<half_t>(), c->c1b.scale.as<float>(),
-                          c->c1b.shift.as<float>(), a1b.as<half_t>(), H2, W2);
+                          c->c1b.shift.as<float>(), V(T_CONV1B).as<half_t>(), H2, W2);
     } else {
         {
             ProfScope ps(c, "conv1a", "conv1a_kernel", 2.0 * P1 * 64 * 27, P1 * (12 + 128));
             launch_conv1a(st, img_dev, H, W, normalise, c->c1a.w.as<half_t>(), c->c1a.scale.as<float>(),
-                          c->c1a.shift.as<float>(), c->a1a.as<half_t>());
+                          c->c1a.shift.as<float>(), V(T_CONV1A).as<half_t>());
         }
-        conv(c, "conv1b", c->c1b, c->a1a, H, W, a1b, H2, W2, 1);
+        conv(c, p, "conv1b", c->c1b, T_CONV1A, T_CONV1B, 1);
     }
-    conv(c, "conv2a", c->c2a, a1b, H2, W2, a2a, H2, W2, 1);
-    conv(c, "conv2b", c->c2b, a2a, H2, W2, a2b, H4, W4, 1);
-    conv(c, "conv3a", c->c3a, a2b, H4, W4, a3a, H4, W4, 1);
-    conv(c, "conv3b", c->c3b, a3a, H4, W4, a3b, H4, W4, 1);
+    conv(c, p, "conv2a", c->c2a, T_CONV1B, T_CONV2A, 1);
+    conv(c, p, "conv2b", c->c2b, T_CONV2A, T_CONV2B, 1);
+    conv(c, p, "conv3a", c->c3a, T_CONV2B, T_CONV3A, 1);
+    conv(c, p, "conv3b", c->c3b, T_CONV3A, T_CONV3B, 1);
     for (int b = 0; b < 3; ++b) rb_f16(b);
     }
     // The two head branches read the backbone output and nothing of each other (nets/sfd2.py:328-342).  The detector
@@ -760,10 +689,7 @@ int run_network(sfd2_ctx *c, const PassPlan &p, const float *img_dev, int normal
             HIPCHECK(hipStreamWaitEvent(c->side_stream, c->ev_fork, 0));
             c->cur_stream = c->side_stream;
         }
-        {
-            ProfScope ps(c, "ConvSta", "convsta_kernel", 2.0 * P4 * 3 * 256, P4 * (512 + 12));
-            launch_convsta(c->cur_stream, x->as<half_t>(), H4 * W4, c->sta_w16.as<float>(), c->sta_b.as<float>(), c->sta.as<float>());
-        }
+        conv_sta();
         if (sta_side) {
             HIPCHECK(hipEventRecord(c->ev_join, c->side_stream));
             c->cur_stream = st;
@@ -776,14 +702,13 @@ int run_network(sfd2_ctx *c, const PassPlan &p, const float *img_dev, int normal
         c->cur_stream = c->side_stream;
     }
     if (p.chp) {      // options "comp_heads" / "comp_det" (plan_pass)
-        convc(c, p, "convPa.0", c->pa0, *x, H4, W4, pa0_o, H8, W8, 1, p.rec.ro[2], p.rec.pa0, nullptr, SFD2_RS_PA0);
-        convc(c, p, "convPa.3", c->pa3, pa0_o, H8, W8, pa_o, H8, W8, 0, p.rec.pa0, Rec::None);
+        convc(c, p, "convPa.0", c->pa0, x, T_PA0, 1);
+        convc(c, p, "convPa.3", c->pa3, T_PA0, T_PA, 0);
     } else {
-        conv(c, "convPa.0", c->pa0, *x, H4, W4, pa0_o, H8, W8, 1);
-        conv(c, "convPa.3", c->pa3, pa0_o, H8, W8, pa_o, H8, W8, 0);
+        conv(c, p, "convPa.0", c->pa0, x, T_PA0, 1);
+        conv(c, p, "convPa.3", c->pa3, T_PA0, T_PA, 0);
     }
-    c->pa_cur = pa_o.as<half_t>();
-    if (!p.skip_pb) conv(c, "convPb", c->pb, pa_o, H8, W8, c->logits, H8, W8, 0, nullptr, 1);
+    if (!p.skip_pb) conv(c, p, "convPb", c->pb, T_PA, T_PB, 0, T_NONE, 1);
     if (!p.skip_head) {
         ProfScope ps(c, "detector_head", "detector_head_kernel", 0.0, P8 * (65 * 4 + 256));
         launch_detector_head(c->cur_stream, c->logits.as<float>(), 128, H8, W8, c->score.as<float>());
@@ -793,19 +718,14 @@ int run_network(sfd2_ctx *c, const PassPlan &p, const float *img_dev, int normal
         c->cur_stream = st;
     }
     if (p.ch) {
-        convc(c, p, "convDa.0", c->da0, *x, H4, W4, da0_o, H4, W4, 1, p.rec.ro[2], p.rec.da0, nullptr, SFD2_RS_DA0);
-        convc(c, p, "convDa.3", c->da3, da0_o, H4, W4, da_o, H4, W4, 0, p.rec.da0, Rec::None);
+        convc(c, p, "convDa.0", c->da0, x, T_DA0, 1);
+        convc(c, p, "convDa.3", c->da3, T_DA0, T_DA, 0);
     } else {
-        conv(c, "convDa.0", c->da0, *x, H4, W4, da0_o, H4, W4, 1);
-        if (!p.skip_da3) conv(c, "convDa.3", c->da3, da0_o, H4, W4, da_o, H4, W4, 0);
+        conv(c, p, "convDa.0", c->da0, x, T_DA0, 1);
+        if (!p.skip_da3) conv(c, p, "convDa.3", c->da3, T_DA0, T_DA, 0);
     }
-    c->da_cur = da_o.as<half_t>();
-    c->da0_cur = da0_o.as<half_t>();
-    if (!p.skip_db) conv(c, "convDb", c->db, da_o, H4, W4, c->draw, H4, W4, 0, nullptr, 1);
-    if (c->has_sta && !p.sta_early) {
-        ProfScope ps(c, "ConvSta", "convsta_kernel", 2.0 * P4 * 3 * 256, P4 * (512 + 12));
-        launch_convsta(st, x->as<half_t>(), H4 * W4, c->sta_w16.as<float>(), c->sta_b.as<float>(), c->sta.as<float>());
-    }
+    if (!p.skip_db) conv(c, p, "convDb", c->db, T_DA, T_DB, 0, T_NONE, 1);
+    if (c->has_sta && !p.sta_early) conv_sta();
     if (fork || sta_side) HIPCHECK(hipStreamWaitEvent(st, c->ev_join, 0));
     HIPCHECK(hipGetLastError());
     if (c->net_error) { c->net_error = 0; return -1; }      // (a layer helper recorded an error: sfd2_last_error has its text)

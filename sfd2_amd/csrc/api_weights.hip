@@ -1,5 +1,6 @@
 // libsfd2hip: BatchNorm folding and filter packing (sfd2_load_weights).
 #include "sfd2_ctx.h"
+#include <map>
 
 // ------------------------------------------------------------------------------------------ weights
 struct TView {
@@ -705,18 +706,8 @@ static int calibrate_impl(sfd2_ctx *c, const float *img, int on_device, int H, i
     if (rc) return -1;
     HIPCHECK(c->range_scratch.ensure(AE_COUNT * sizeof(unsigned int)));
     HIPCHECK(hipMemsetAsync(c->range_scratch.p, 0, AE_COUNT * sizeof(unsigned int), c->stream));
-    static const struct { const char *name; int group; } tens[] = {
-        {"conv1a", AE_CONV1A}, {"bn1b", AE_CONV1B}, {"conv2a", AE_CONV2A}, {"bn2b", AE_CONV2B}, {"conv3a", AE_CONV3A},
-        {"bn3b", AE_TRUNK}, {"conv4.0", AE_TRUNK}, {"conv4.1", AE_TRUNK}, {"conv4.2", AE_TRUNK},
-        {"conv4.0.bn1", AE_T1_0}, {"conv4.1.bn1", AE_T1_1}, {"conv4.2.bn1", AE_T1_2},
-        {"conv4.0.bn2", AE_T2_0}, {"conv4.1.bn2", AE_T2_1}, {"conv4.2.bn2", AE_T2_2}, {"convPa.0", AE_PA0}, {"convDa.0", AE_DA0}};
-    for (const auto &t : tens) {
-        auto it = c->acts.find(t.name);
-        if (it == c->acts.end() || !it->second.f32 || it->second.planar || it->second.pitch != it->second.c)
-            return fail(std::string("sfd2_calibrate_range: activation not available: ") + t.name);
-        launch_absmax_f32(c->stream, reinterpret_cast<const float *>(it->second.p), (size_t)it->second.c * it->second.h * it->second.w,
-                          c->range_scratch.as<unsigned int>() + t.group);
-    }
+    for (int id = 0; id < SFD2_RS_COUNT; ++id)      // every tensor with an exponent group, in the fp32 buffer the pass above left it in
+        launch_absmax_f32(c->stream, c->act32[id].as<float>(), (size_t)kTensor[id].ch * act_h(c, id) * act_w(c, id), c->range_scratch.as<unsigned int>() + kTensor[id].group);
     HIPCHECK(hipGetLastError());
     float mx[AE_COUNT];
     HIPCHECK(hipMemcpyAsync(mx, c->range_scratch.p, sizeof(mx), hipMemcpyDeviceToHost, c->stream));
@@ -878,11 +869,9 @@ static void release_probe_workspace(sfd2_ctx *c)
 {
     // the probe's fp32 parity workspace (every activation in its own fp32 buffer) is of no use to a throughput context: give it back
     // (a context that runs SFD2_PREC_F32 / F16X3 allocates what its own geometry needs on its first call)
-    DevBuf *f32ws[] = {&c->g1a, &c->g1b, &c->g2a, &c->g2b, &c->g3a, &c->g3b, &c->gpa0_o, &c->gpa_o, &c->gda0_o, &c->gda_o};
     (void)hipStreamSynchronize(c->stream);
-    for (DevBuf *b : f32ws) b->release();
-    for (int b = 0; b < 3; ++b) { c->grt1[b].release(); c->grt2[b].release(); c->gro[b].release(); }
-    c->acts.clear();            // (they named those buffers)
+    for (DevBuf &b : c->act32) b.release();
+    for (ActInfo &a : c->acts) a.known = false;            // (they named those buffers)
 }
 
 // The self-check belongs to SFD2_PREC_F16C: a context in another precision does not pay for it at load -- it runs when the

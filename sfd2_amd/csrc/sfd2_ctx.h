@@ -15,7 +15,6 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <map>
 #include <string>
 #include <vector>
 
@@ -104,7 +103,33 @@ struct ConvW {                 // one folded + packed layer
 enum { AE_CONV1A, AE_CONV1B, AE_CONV2A, AE_CONV2B, AE_CONV3A, AE_TRUNK /* conv3b's and every ResBlock's output: one skip path */,
        AE_T1_0, AE_T1_1, AE_T1_2, AE_T2_0, AE_T2_1, AE_T2_2, AE_PA0, AE_DA0, AE_COUNT };
 
-struct ActInfo { const void *p; int f32; int planar; int c, pitch, h, w; Rec rec = Rec::None; /* f16c: the format of the corr records (their plane follows the hi plane) */ int exp2 = 0; /* stored = value * 2^exp2 (activation exponents of the fp16 family) */ bool absent = false; /* stays on chip on the path taken */ };
+// A stored activation tensor has ONE identity: its id.  The id indexes the context's buffers (act16 / act32), the pass plan's records and arena placement,
+// the registered activations, and -- for the first SFD2_RS_COUNT ids, in sfd2_internal.h's order -- is the tensor's range-status slot.  convPa.3's and
+// convDa.3's outputs have no slot and no exponent group; the three head outputs behind T_COUNT live in buffers of their own (logits, draw, sta).
+enum Tensor { T_CONV1A, T_CONV1B, T_CONV2A, T_CONV2B, T_CONV3A, T_CONV3B, T_T1_0, T_T2_0 = T_T1_0 + 3, T_OUT_0 = T_T2_0 + 3, T_PA0 = T_OUT_0 + 3, T_DA0,
+              T_PA, T_DA, T_COUNT, T_PB = T_COUNT, T_DB, T_STA, T_ALL, T_NONE = -1 };
+struct TensorRow { const char *act /* sfd2_debug_activation */, *range /* sfd2_range_tensor_name */; int level /* 0: H x W ... 3: 1/8 */, ch, group /* AE_*, -1: none */; };
+inline constexpr TensorRow kTensor[] = {
+    {"conv1a", "conv1a", 0, 64, AE_CONV1A}, {"bn1b", "conv1b", 1, 64, AE_CONV1B}, {"conv2a", "conv2a", 1, 128, AE_CONV2A},
+    {"bn2b", "conv2b", 2, 128, AE_CONV2B}, {"conv3a", "conv3a", 2, 256, AE_CONV3A}, {"bn3b", "conv3b", 2, 256, AE_TRUNK},
+    {"conv4.0.bn1", "conv4.0.t1", 2, 256, AE_T1_0}, {"conv4.1.bn1", "conv4.1.t1", 2, 256, AE_T1_1}, {"conv4.2.bn1", "conv4.2.t1", 2, 256, AE_T1_2},
+    {"conv4.0.bn2", "conv4.0.t2", 2, 256, AE_T2_0}, {"conv4.1.bn2", "conv4.1.t2", 2, 256, AE_T2_1}, {"conv4.2.bn2", "conv4.2.t2", 2, 256, AE_T2_2},
+    {"conv4.0", "conv4.0", 2, 256, AE_TRUNK}, {"conv4.1", "conv4.1", 2, 256, AE_TRUNK}, {"conv4.2", "conv4.2", 2, 256, AE_TRUNK},
+    {"convPa.0", "convPa.0", 3, 256, AE_PA0}, {"convDa.0", "convDa.0", 2, 256, AE_DA0}, {"convPa", "", 3, 256, -1}, {"convDa", "", 2, 256, -1},
+    {"convPb", "", 3, 65, -1}, {"convDb", "", 2, 128, -1}, {"ConvSta", "", 2, 3, -1}};
+static_assert(sizeof(kTensor) == T_ALL * sizeof(TensorRow), "one row per tensor id");
+static_assert(T_PA == SFD2_RS_COUNT, "the ids with a range-status slot come first (SFD2_RS_COUNT == SFD2_RANGE_TENSORS: api_core.hip)");
+static_assert(T_CONV1A == SFD2_RS_CONV1A && T_CONV1B == SFD2_RS_CONV1B && T_CONV2A == SFD2_RS_CONV2A && T_CONV2B == SFD2_RS_CONV2B && T_CONV3A == SFD2_RS_CONV3A &&
+              T_CONV3B == SFD2_RS_CONV3B && T_T1_0 == SFD2_RS_T1_0 && T_T1_0 + 2 == SFD2_RS_T1_2 && T_T2_0 == SFD2_RS_T2_0 && T_T2_0 + 2 == SFD2_RS_T2_2 &&
+              T_OUT_0 == SFD2_RS_OUT_0 && T_OUT_0 + 2 == SFD2_RS_OUT_2 && T_PA0 == SFD2_RS_PA0 && T_DA0 == SFD2_RS_DA0, "a tensor's range-status slot is its id");
+// the profile-row name of a ResBlock layer: "conv4.<b>.conv<k>" (k = 1, 2, 3)
+inline const char *rb_layer_name(int b, int k)
+{
+    static const char *n[3][3] = {{"conv4.0.conv1", "conv4.0.conv2", "conv4.0.conv3"}, {"conv4.1.conv1", "conv4.1.conv2", "conv4.1.conv3"}, {"conv4.2.conv1", "conv4.2.conv2", "conv4.2.conv3"}};
+    return n[b][k - 1];
+}
+
+struct ActInfo { bool known = false; /* registered by the last ensure_workspace */ const void *p; int f32; int planar; int c, pitch, h, w; Rec rec = Rec::None; /* f16c: the format of the corr records (their plane follows the hi plane) */ int exp2 = 0; /* stored = value * 2^exp2 (activation exponents of the fp16 family) */ bool absent = false; /* stays on chip on the path taken */ };
 
 // Scratch of the JPEG decoder (api_jpeg.hip).  Its own allocations, not DevBufs: growing them must not bump g_alloc_gen, which would
 // drop the captured graphs of the network (api_graph.hip) that never read these buffers.
@@ -169,7 +194,6 @@ struct sfd2_ctx {
     DevBuf x3_rb_planes[3];            // a ResBlock's input (X3_RB), conv1's and the grouped conv's outputs
     int opt_fuse_post = 1;             // sfd2_set_option "fuse_post": heads -> heat map -> NMS in one kernel on the extract path
     int opt_sparse_desc = 1;           // sfd2_set_option "sparse_desc": extract path runs convDb on the sampled corner pixels only
-    const half_t *da0_cur = nullptr;   // convDa.0 output of the last fp16 network pass
     DevBuf da3_sparse;                 // [sel_cap][4][256] fp16: convDa.3 on the sampled corner pixels
     int opt_fp6_acts = 1;              // sfd2_set_option "fp6_acts": the corr records of the three tensors only conv3x3_pp<comp> reads (conv1b's, conv2b's,
                                        // conv3a's output) as block-scaled fp6 half-records, their consumers' corr MFMAs fp6 x fp6 (33.5 cycles instead of 66)
@@ -204,8 +228,6 @@ struct sfd2_ctx {
     DevBuf db_sparse;                  // [sel_cap][4][128] fp32: convDb on the sampled corners (f16x3)
     int opt_sparse_da3 = 1;            // sfd2_set_option "sparse_da3": with the sparse descriptor head, convDa.3 on the sampled corners only
     int opt_fuse_pb = 1;               // sfd2_set_option "fuse_pb": convPb inside the fused detector-head / heat-map kernel
-    const half_t *pa_cur = nullptr;    // convPa.3 output of the last fp16 network pass
-    const half_t *da_cur = nullptr;    // convDa.3 output of the last fp16 network pass
     int opt_comp_rb = 1;               // sfd2_set_option "comp_rb": SFD2_PREC_F16C compensates the ResBlocks too (0: fused fp16 ResBlock kernel)
     int opt_rb_inner = 2;              // sfd2_set_option "rb_inner": SFD2_PREC_F16C ResBlocks, 1 = t2 (the grouped conv's output) stored as plain
                                        // fp16, 2 (default) = t1 and t2, 0 = both compensated; the filters stay compensated either way
@@ -239,11 +261,11 @@ struct sfd2_ctx {
     // strict fp32 mode
     int precision = SFD2_PREC_F16;
     ConvW f1a, f1b, f2a, f2b, f3a, f3b, frb1[3], frb2[3], frb3[3], fpa0, fpa3, fda0, fda3, fpb, fdb;
-    DevBuf g1a, g1b, g2a, g2b, g3a, g3b, grt1[3], grt2[3], gro[3], gpa0_o, gpa_o, gda0_o, gda_o;   // fp32 NHWC activations
+    DevBuf act32[T_COUNT];             // fp32 NHWC activations, by tensor id
     // geometry of the current workspace
     int H = 0, W = 0, H2 = 0, W2 = 0, H4 = 0, W4 = 0, H8 = 0, W8 = 0;
-    // activations (NHWC fp16 unless noted)
-    DevBuf img, a1a, a1b, a2a, a2b, a3a, a3b, rt1[3], rt2[3], ro[3], pa0_o, pa_o, da0_o, da_o;
+    // activations (NHWC fp16 unless noted), by tensor id
+    DevBuf img, act16[T_COUNT];
     DevBuf logits /*f32 [P8][128]*/, draw /*f32 [P4][128]*/, sta /*f32 [3][P4]*/, score /*f32*/, heat /*f32*/;
     DevBuf stab /*f32 [H][W]*/, desc_nchw, tmp_f32;
     // selection
@@ -267,7 +289,7 @@ struct sfd2_ctx {
     // matcher
     DevBuf m_stage, m_hi0, m_lo0, m_hi1, m_lo1, m_part_f, m_part_i, m_red, m_jobs, m_fins, m_out_m, m_out_s, m_rkeys;
     sfd2_timings tim = {};
-    std::map<std::string, ActInfo> acts;
+    ActInfo acts[T_ALL] = {};          // by tensor id; sfd2_debug_activation searches kTensor's names
     // per-launch profiling (sfd2_set_profiling)
     int prof_max_steps = 0, prof_step = 0, prof_slot = 0;
     std::vector<hipEvent_t> prof_ev;          // [max_steps][PROF_SLOTS][2]
@@ -364,15 +386,17 @@ struct PassPlan {
     bool comp_rb = false;                    // SFD2_PREC_F16C: compensated ResBlocks (otherwise plain fp16 on the hi planes)
     int rb_inner = 0;                        // ... "rb_inner" in effect; rb23: 2 with ResBlock.conv2 + conv3 in rb23_c_kernel (t2 stays on chip)
     bool rb23 = false, generic_c = false, no_rf_c = false, fp6_filters = false;
-    // SFD2_PREC_F16C: the corr records of every stored tensor from conv1b's output to convPa.0's / convDa.0's (Rec::None in other modes)
-    struct { Rec a1b, a2a, a2b, a3a, a3b, t1[3], t2[3], ro[3], pa0, da0; } rec = {};
+    // SFD2_PREC_F16C: the corr records of every stored tensor from conv1a's output to convPa.0's / convDa.0's (Rec::None in other modes)
+    Rec rec[T_COUNT] = {};
     Rec a3a_in = Rec::None;                  // a3a as conv3b reads it: None with "c3b_plain", also where conv3a still stores Half6 (SFD2_C3A_KEEP_CORR)
     bool a2a_s2d = false;                    // "s2d": conv2a's output stored space-to-depth, conv2b on conv2b_s2d_kernel
     bool ch = false, chp = false;            // compensated head branches ("comp_heads"); compensated detector branch ("comp_heads" or "comp_det")
     bool branches = false, sta_early = false, sta_side = false;   // detector branch on the side stream; ConvSta before the heads / on the side stream
     bool skip_head = false, skip_pb = false, skip_db = false, skip_da3 = false;   // layers left to sfd2_extract's post-processing
     bool sparse_desc = false, sparse_da3 = false, sparse_x3 = false;           // its sparse descriptor head: fp16, fp16 with convDa.3, f16x3
-    struct { int a1b, a2a, a2b, a3a, a3b, t1[3], t2[3], ro[3], pa0, pa, da0, da, n; size_t bytes; } slot = {};   // alias: each tensor's arena slot, slots in all, bytes per slot
+    struct { int slot = -1; size_t off = 0; } at[T_COUNT];   // alias: each tensor's arena slot (-1: its own buffer) and its byte offset inside the slot
+    int n_slots = 0;                         // ... slots in all, bytes per slot
+    size_t slot_bytes = 0;
     bool x3_pp = false, x3_fast = false;     // f16x3: 3x3 layers on the three-pass kernels ("x3_pp"); the throughput path's plane hand-offs
     bool x3_stem = false, x3_rb = false;     // ... the fused three-pass stem (planes in X3_CHAIN_A); ResBlocks on the planes
     bool desc16 = false;                     // "x3_desc16": the descriptor branch in fp16 on the backbone's hi plane
@@ -381,9 +405,23 @@ struct PassPlan {
 PassPlan plan_pass(const sfd2_ctx *c, PassEntry entry, int H, int W, int top_k = 0, bool desc = false);
 int ensure_workspace(sfd2_ctx *c, const PassPlan &p, int H, int W);   // allocates every buffer the pass touches and makes the filter forms it reads
 int run_network(sfd2_ctx *c, const PassPlan &p, const float *img_dev, int normalise);   // launches only
-// one layer of the strict family.  planes: in, the input's planes where s.planes_in; out, the output's (null pair: it went to the fp32 tensor)
-int convf(sfd2_ctx *c, const StrictConv &s, const char *name, const ConvW &L, const DevPtr &in, int H, int W, const DevPtr &out, int Ho, int Wo,
-          int relu, const float *res = nullptr, X3Pair *planes = nullptr);
+// Where a tensor lives for the pass at hand (a non-owning view): the fp32 buffer on the strict family (convDa.0 with "x3_desc16": the fp16 output in the
+// plane buffer), the arena slot on the throughput path, the fp16 buffer otherwise; the head outputs in their own buffers
+inline DevPtr act_view(const sfd2_ctx *c, const PassPlan &p, int id)
+{
+    if (id >= T_COUNT) return id == T_PB ? c->logits : id == T_DB ? c->draw : c->sta;
+    if (p.f32) return (id == T_DA0 && p.desc16) ? c->x3_da0_planes : c->act32[id];
+    if (!p.alias || p.at[id].slot < 0) return c->act16[id];
+    DevPtr v;
+    v.p = c->arena.as<char>() + (size_t)p.at[id].slot * p.slot_bytes + p.at[id].off;
+    return v;
+}
+inline int act_h(const sfd2_ctx *c, int id) { const int h[4] = {c->H, c->H2, c->H4, c->H8}; return h[kTensor[id].level]; }
+inline int act_w(const sfd2_ctx *c, int id) { const int w[4] = {c->W, c->W2, c->W4, c->W8}; return w[kTensor[id].level]; }
+inline size_t cand_capacity(size_t P1) { return std::min(std::max<size_t>(65536, P1 / 8), P1); }   // candidates the selection keeps for an image of P1 pixels
+// one layer of the strict family on buffers given by hand (sfd2_extract's sparse head).  planes: in, the input's planes where s.planes_in; out, the output's (null pair: it went to the fp32 tensor)
+int convf_at(sfd2_ctx *c, const StrictConv &s, const char *name, const ConvW &L, const DevPtr &in, int H, int W, const DevPtr &out, int Ho, int Wo,
+             int relu, const float *res = nullptr, X3Pair *planes = nullptr);
 // api_weights.hip
 int ensure_strict_filters(sfd2_ctx *c, const PassPlan &p);   // SFD2_PREC_F16X3: the split filter forms (ConvW::wx3, wx3p, wsl) the plan's kernels read
 // api_extract.hip

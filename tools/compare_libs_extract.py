@@ -3,7 +3,9 @@
 kernel variant that claims the same operations in the same order -- and screen the second for run-to-run differences.
     python tools/compare_libs_extract.py default build/variants/libX.so [--precision f16c] [--runs 6] [--labels]
 (a library may carry environment switches for its worker: default@SFD2_AB_OPTS=s2d=0).  --labels: the launch sequence too -- the
-(stage, kernel) rows of layer_timings() of one profiled extract per size -- for a change of the dispatch that claims the same kernels."""
+(stage, kernel) rows of layer_timings() of one profiled extract per size -- for a change of the dispatch that claims the same kernels.
+--activations: instead, what sfd2_debug_activation returns for every registered name (the array, or the error text) after one det and after
+one extract at 96x128 and 133x211 -- for a change of the workspace that claims the same readable tensors."""
 import argparse
 import itertools
 import os
@@ -15,6 +17,9 @@ import numpy as np
 
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 SIZES = [(1200, 1600), (1063, 1600), (480, 640), (133, 211), (96, 128), (1600, 1200)]
+ACT_SIZES = [(96, 128), (133, 211)]
+ACT_NAMES = ["conv1a", "bn1b", "conv2a", "bn2b", "conv3a", "bn3b"] + [f"conv4.{b}{s}" for s in (".bn1", ".bn2", "") for b in range(3)] + \
+    ["convPa.0", "convDa.0", "convPa", "convDa", "convPb", "convDb", "ConvSta"]
 WORKER = r'''
 import sys, os, numpy as np
 sys.path.insert(0, %r)
@@ -28,7 +33,19 @@ m = ResSegNetV2(outdim=128, require_stability=True, precision=sys.argv[3]).eval(
 for kv in filter(None, os.environ.get("SFD2_AB_OPTS", "").split("+")):
     m.context.set_option(kv.split("=")[0], int(kv.split("=")[1]))
 out = {}
-for (h, w) in %r:
+def activations(tag):
+    for n in %r:
+        try:
+            out[tag + "/" + n] = m.context.debug_activation(n)
+        except Exception as e:
+            out[tag + "/" + n] = np.array("error: " + str(e))
+for (h, w) in (%r if sys.argv[6] == "1" else []):
+    x = synth.make_image(h, w, 7 + h).astype(np.float32)
+    m.det(x[None])
+    activations(f"{h}x{w}/det")
+    extract_resnet_return(m, x[None], conf_th=0.001, topK=4096, scales=[1.0])
+    activations(f"{h}x{w}/extract")
+for (h, w) in (%r if sys.argv[6] != "1" else []):
     x = synth.make_image(h, w, 7 + h).astype(np.float32)
     first = None
     for r in range(int(sys.argv[4])):
@@ -48,7 +65,7 @@ for (h, w) in %r:
         assert len(out[f"{h}x{w}/labels"]) > 0, "no launches profiled"
         m.context.set_profiling(0)
 np.savez(sys.argv[2], **out)
-''' % (os.path.abspath(ROOT), SIZES)
+''' % (os.path.abspath(ROOT), ACT_NAMES, ACT_SIZES, SIZES)
 
 
 def split_spec(spec):
@@ -65,13 +82,14 @@ ap.add_argument("libs", nargs=2)
 ap.add_argument("--precision", default="f16c")
 ap.add_argument("--runs", type=int, default=6)
 ap.add_argument("--labels", action="store_true")
+ap.add_argument("--activations", action="store_true")
 args = ap.parse_args()
 res = []
 with tempfile.TemporaryDirectory() as td:
     for i, spec in enumerate(args.libs):
         lib, env = split_spec(spec)
         f = os.path.join(td, f"o{i}.npz")
-        r = subprocess.run([sys.executable, "-c", WORKER, lib, f, args.precision, str(args.runs), str(int(args.labels))], env=env, capture_output=True, text=True)
+        r = subprocess.run([sys.executable, "-c", WORKER, lib, f, args.precision, str(args.runs), str(int(args.labels)), str(int(args.activations))], env=env, capture_output=True, text=True)
         sys.stdout.write(r.stdout)
         if r.returncode != 0:
             sys.stderr.write(r.stderr[-3000:])
@@ -81,7 +99,11 @@ bad = 0
 for k in sorted(res[0]):
     a, b = res[0][k], res[1][k]
     same = a.shape == b.shape and np.array_equal(a, b)
-    if not same and k.endswith("/labels"):
+    if (a.ndim == 0 and a.dtype.kind == "U") or (b.ndim == 0 and b.dtype.kind == "U"):      # --activations: an error text on either side
+        if not same:
+            bad += 1
+            print(f"DIFFERENT {k}: {a if a.ndim == 0 else a.shape} | {b if b.ndim == 0 else b.shape}")
+    elif not same and k.endswith("/labels"):
         bad += 1
         print(f"DIFFERENT {k}:\n  " + "\n  ".join(f"{x!s:60} {y!s}" for x, y in itertools.zip_longest(a, b)))
     elif not same:
