@@ -296,7 +296,10 @@ int sfd2_nms_fast(sfd2_ctx *ctx, const float *heat, int H, int W, float conf_th,
 /* Stage entry points (parity tests; each is the device kernel the pipeline uses). */
 /* simple_nms(scores, 4) (nets/extractor.py:20-35): heat [H][W] -> nms [H][W] */
 int sfd2_simple_nms(sfd2_ctx *ctx, const float *heat, int H, int W, int radius, float *nms_out);
-/* NMS + threshold + border + sort + top-K (nets/extractor.py:157-183,322-326) */
+/* NMS + threshold + border + sort + top-K (nets/extractor.py:157-183,322-326).  conf_th must be >= 0 and not NaN, here
+ * and in every extract call (an error otherwise): candidates are the scores > conf_th, ordered by their float bits, which
+ * is the order of the values only for non-negative scores.  More candidates than min(max(65536, H*W/8), H*W) is the
+ * "candidate buffer overflow" error; the context stays usable.  At most cap_out rows are written. */
 int sfd2_select_keypoints(sfd2_ctx *ctx, const float *heat, int H, int W, float conf_th,
                           int radius, int border, int top_k,
                           float *kpts_xy, float *scores, int64_t cap_out, int *n_out);

@@ -101,6 +101,8 @@ static int run_selection(sfd2_ctx *c, const float *heat_dev, int H, int W, float
     if (Hb <= 0) Hb = H;
     if (Wb <= 0) Wb = W;
     if (radius < 0 || radius > 4) return fail("nms radius must be in [0,4] (reference uses 4)");
+    // candidate keys are the raw float bits of scores > conf_th: a negative score would sort above every positive one
+    if (!(conf_th >= 0.0f)) return fail("conf_th must be >= 0 and not NaN (got " + std::to_string(conf_th) + ")");
     const int sel_cap = top_k > 0 ? std::min(top_k, c->cand_cap) : c->cand_cap;
     c->last_sel_cap = sel_cap;
     HIPCHECK(c->sel.ensure((size_t)sel_cap * 8));
