@@ -85,7 +85,7 @@ typedef struct {
     int64_t n_candidates; /* N0 after NMS + threshold + border of the last extract          */
 } sfd2_timings;
 
-int sfd2_version(void);   /* 100 = rounds 1-4; 105 adds sfd2_extract_record_async, sfd2_desc_pack and host outputs with SFD2_FLAG_ASYNC; 106 adds sfd2_get_margin_status; 107 adds sfd2_get_relax_status (option "c3b_plain"); 108 adds sfd2_get_option, sfd2_device_pci_bus_id, SFD2_FLAG_DESC_STORE64; 109 adds the baseline JPEG decoder (sfd2_jpeg_*); 112 adds the SfM map (sfd2_verify_matches_batch, sfd2_build_tracks, sfd2_triangulate_tracks); 113 adds the pair selection (sfd2_pairs_retrieval, sfd2_pairs_covisibility, sfd2_pairs_poses) */
+int sfd2_version(void);   /* 100 = rounds 1-4; 105 adds sfd2_extract_record_async, sfd2_desc_pack and host outputs with SFD2_FLAG_ASYNC; 106 adds sfd2_get_margin_status; 107 adds sfd2_get_relax_status (option "c3b_plain"); 108 adds sfd2_get_option, sfd2_device_pci_bus_id, SFD2_FLAG_DESC_STORE64; 109 adds the baseline JPEG decoder (sfd2_jpeg_*); 112 adds the SfM map (sfd2_verify_matches_batch, sfd2_build_tracks, sfd2_triangulate_tracks); 113 adds the pair selection (sfd2_pairs_retrieval, sfd2_pairs_covisibility, sfd2_pairs_poses); 114 adds sfd2_covis_clusters */
 const char *sfd2_last_error(void);
 
 int sfd2_ctx_create(int device, sfd2_ctx **out);
@@ -709,6 +709,30 @@ int sfd2_pairs_covisibility(sfd2_ctx *ctx, const int64_t *obs_offsets, const int
  * transposes); with SFD2_PAIRS_FLAG_CENTRES it is the camera centre -R^T t.  k >= n is no error: a row has at most n - 1 entries. */
 int sfd2_pairs_poses(sfd2_ctx *ctx, const double *qvec, const double *tvec, int n, int k, double rotation_threshold_deg,
                      int32_t *idx, double *dist, int32_t *n_found, int flags);
+
+/* ------------------------------------------------------------------------------------------------ covisibility clustering
+ * it_loc/localize_cv2.py:87-117 do_covisibility_clustering for many queries in one call, over the two CSRs of
+ * sfd2_pairs_covisibility (the conventions of the pair-selection section hold: host arrays, the call runs on sfd2_get_stream(),
+ * synchronises before it returns, and returns -1 with sfd2_last_error() set on a bad argument, writing nothing).  Query q lists the
+ * images frames[frame_offsets[q] .. frame_offsets[q + 1]) in retrieval order: at most SFD2_CLUSTER_MAX_FRAMES of them, each an
+ * index in [0, n_images), none twice (drop repeats before the call: the reference's visited set skips them).
+ *   - There is an edge i -> j when image j occurs in the track of a point that image i observes.  The rule is directed: j need not
+ *     observe the point itself.
+ *   - The list is walked in order; a frame not yet visited opens a cluster that takes every not-yet-visited frame OF THE LIST
+ *     reachable from it over those edges (paths run through frames of the list only).
+ *   - The clusters are ordered by size, largest first; equal sizes keep their order of creation (Python's sorted(key=len,
+ *     reverse=True) is stable), and creation order is the order of each cluster's earliest list position.
+ * cluster[p] is the rank of list position p's cluster in that order, n_clusters[q] the number of clusters (0 for an empty query).
+ * Deviation: the order of the members INSIDE a cluster is not part of the result (the reference's is whatever set.pop() yields);
+ * callers list them by ascending list position.  Integer and bit operations only: a query's output does not depend on the batch,
+ * its order, the grid or the flag.  The image -> list-position table sits in LDS up to SFD2_CLUSTER_LDS_IMAGES images, beyond that
+ * (or with the flag) in a row of global scratch per workgroup. */
+#define SFD2_CLUSTER_MAX_FRAMES 256
+#define SFD2_CLUSTER_LDS_IMAGES 65536
+#define SFD2_CLUSTER_FLAG_GLOBAL_SLOTS 1   /* image -> list-position table in global scratch even where it fits LDS             */
+int sfd2_covis_clusters(sfd2_ctx *ctx, const int64_t *obs_offsets, const int32_t *obs_point, int n_images,
+                        const int64_t *track_offsets, const int32_t *track_image, int n_points, const int64_t *frame_offsets,
+                        const int32_t *frames, int nq, int32_t *cluster, int32_t *n_clusters, int flags);
 
 #ifdef __cplusplus
 }

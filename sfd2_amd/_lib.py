@@ -143,6 +143,7 @@ TRI_MAX_POINTS = 4
 TRI_ST_RANGE, TRI_ST_NOT_CONVERGED = 1, 2
 PAIRS_MAX_K, PAIRS_POSES_MAX_K = 256, 1024
 PAIRS_FLAG_GLOBAL_COUNTERS, PAIRS_FLAG_CENTRES = 1, 2
+CLUSTER_MAX_FRAMES, CLUSTER_LDS_IMAGES, CLUSTER_FLAG_GLOBAL_SLOTS = 256, 65536, 1   # SFD2_CLUSTER_*
 
 
 def pairs_splits(n):
@@ -161,7 +162,7 @@ EXPORTS = [
     "sfd2_extract_record_async", "sfd2_desc_pack", "sfd2_get_margin_status", "sfd2_get_relax_status", "sfd2_get_option", "sfd2_device_pci_bus_id",
     "sfd2_jpeg_parse", "sfd2_jpeg_prepare", "sfd2_jpeg_decode", "sfd2_absolute_pose_batch", "sfd2_pose_refine_batch",
     "sfd2_assemble_2d3d", "sfd2_verify_matches_batch", "sfd2_build_tracks", "sfd2_triangulate_tracks",
-    "sfd2_pairs_retrieval", "sfd2_pairs_covisibility", "sfd2_pairs_poses",
+    "sfd2_pairs_retrieval", "sfd2_pairs_covisibility", "sfd2_pairs_poses", "sfd2_covis_clusters",
 ]
 
 _lib = None
@@ -255,10 +256,11 @@ def load():
     lib.sfd2_pairs_retrieval.argtypes = [vp, vp, ci, vp, ci, ci, ci, ci, vp, vp, ci]
     lib.sfd2_pairs_covisibility.argtypes = [vp, vp, vp, ci, vp, vp, ci, ci, vp, vp, vp, ci]
     lib.sfd2_pairs_poses.argtypes = [vp, vp, vp, ci, ci, cd, vp, vp, vp, ci]
+    lib.sfd2_covis_clusters.argtypes = [vp, vp, vp, ci, vp, vp, ci, vp, vp, ci, vp, vp, ci]
     for name in EXPORTS:
         getattr(lib, name)  # raises AttributeError if the .so lacks a declared symbol
-    if lib.sfd2_version() < 113:
-        raise RuntimeError(f"{LIB_PATH} is version {lib.sfd2_version()}, this binding needs >= 113 (rebuild: __graft_entry__.build())")
+    if lib.sfd2_version() < 114:
+        raise RuntimeError(f"{LIB_PATH} is version {lib.sfd2_version()}, this binding needs >= 114 (rebuild: __graft_entry__.build())")
     _lib = lib
     return lib
 

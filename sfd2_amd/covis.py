@@ -74,6 +74,7 @@ class MapIndex:
         self._rows, self._dev_rows = {}, {}
         self.device = None
         self._dev_xyz = self._dev_track = None
+        self._csr = None
 
     # ------------------------------------------------------------------------------------------------ tables
     def point_rows(self, ids):
@@ -113,6 +114,58 @@ class MapIndex:
         if self._dev_xyz is None:
             raise RuntimeError("MapIndex.to_device() has not been called")
         return _lib.PointTable(self._dev_xyz.data_ptr(), self._dev_track.data_ptr(), len(self.point_ids), 0)
+
+    # ------------------------------------------------------------------------------------------------ clustering
+    def csr(self):
+        """(image id -> image index, obs_offsets, obs_point, track_offsets, track_image): the two CSRs of sfd2_pairs_covisibility /
+        sfd2_covis_clusters (sfd2_amd.pairs.covisibility_csr), built on first use and kept."""
+        if self._csr is None:
+            from .pairs import covisibility_csr
+            ids, oo, op, to, ti = covisibility_csr(self.images, self.points3D)
+            self._csr = ({iid: i for i, iid in enumerate(ids)}, oo, op, to, ti)
+        return self._csr
+
+    def cluster_lists(self, frame_ids_per_query):
+        """The host part of clusters(): per query the ids with repeats dropped (the first occurrence stays, which is what the
+        reference's visited set does), and the concatenated form sfd2_covis_clusters takes: frame_offsets int64 [nq + 1], frames
+        int32 (image indices of csr()).  An id the map does not hold is a KeyError, as in the reference."""
+        index = self.csr()[0]
+        lists = [list(dict.fromkeys(int(f) for f in frame_ids)) for frame_ids in frame_ids_per_query]
+        off = np.zeros(len(lists) + 1, dtype=np.int64)
+        np.cumsum([len(li) for li in lists], out=off[1:])
+        frames = np.array([index[f] for li in lists for f in li], dtype=np.int32)
+        return lists, off, frames
+
+    @staticmethod
+    def clusters_from_ranks(lists, frame_offsets, cluster, n_clusters):
+        """Per query the list of clusters (lists of image ids): cluster[p] is position p's cluster, members by ascending position."""
+        out = []
+        for q, li in enumerate(lists):
+            cl = [[] for _ in range(int(n_clusters[q]))]
+            for f, c in zip(li, cluster[frame_offsets[q]:frame_offsets[q + 1]]):
+                cl[int(c)].append(f)
+            out.append(cl)
+        return out
+
+    def clusters(self, frame_ids_per_query, device=0, global_slots=False):
+        """do_covisibility_clustering (it_loc/localize_cv2.py:87-117) for many queries in ONE sfd2_covis_clusters call:
+        frame_ids_per_query[q] is query q's retrieved image ids in retrieval order.  Returns per query the reference's list of lists
+        of image ids: largest cluster first, equal sizes in order of creation; members by ascending list position (the reference's
+        member order is set.pop()'s).  At most _lib.CLUSTER_MAX_FRAMES distinct ids per query.  global_slots forces the path of maps
+        too large for the LDS table."""
+        from . import _lib
+        lists, off, frames = self.cluster_lists(frame_ids_per_query)
+        if not lists:
+            return []
+        _, oo, op, to, ti = self.csr()
+        cluster = np.empty(len(frames), dtype=np.int32)
+        n_clusters = np.empty(len(lists), dtype=np.int32)
+        ctx = _lib.default_context(device)
+        _lib.check(ctx.lib.sfd2_covis_clusters(ctx.h, oo.ctypes.data, op.ctypes.data if len(op) else None, len(oo) - 1, to.ctypes.data,
+                                               ti.ctypes.data if len(ti) else None, len(to) - 1, off.ctypes.data,
+                                               frames.ctypes.data if len(frames) else None, len(lists), cluster.ctypes.data if len(frames) else None,
+                                               n_clusters.ctypes.data, _lib.CLUSTER_FLAG_GLOBAL_SLOTS if global_slots else 0))
+        return self.clusters_from_ranks(lists, off, cluster, n_clusters)
 
     # ------------------------------------------------------------------------------------------------ selections
     def _observed(self, frame_id, ref_3Dpoints):

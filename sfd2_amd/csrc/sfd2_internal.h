@@ -807,3 +807,10 @@ hipError_t launch_pairs_covis(hipStream_t st, const int64_t *obs_off, const int3
                               const int32_t *trk_img, int k, int global_counters, int blocks, int *scratch, int32_t *idx, int32_t *cnt, int32_t *n_found);
 hipError_t launch_pairs_poses(hipStream_t st, const double *qvec, const double *tvec, int n, int k, double thr_deg, int centres, double *rc,
                               int32_t *idx, double *dist, int32_t *n_found);
+
+// ------------------------------------------------------------------------------------------------ covisibility clustering (cluster_kernels.hip)
+// the image -> list-position table (16 bits per image) stays in LDS up to SFD2_CLUSTER_LDS_IMAGES images (128 KB beside the 12 KB of
+// adjacency bits and per-frame words), else it is a row of global scratch per workgroup that arrives filled with 0xffff
+hipError_t launch_covis_clusters(hipStream_t st, const int64_t *obs_off, const int32_t *obs_point, int n_images, const int64_t *trk_off,
+                                 const int32_t *trk_img, const int64_t *frame_off, const int32_t *frames, int nq, int global_slots, int blocks,
+                                 uint16_t *scratch, int32_t *cluster, int32_t *n_clusters);

@@ -118,6 +118,50 @@ class StoreMatcher:
                 out[i] = np.ones((n0,), dtype=int) * -1
         return out
 
+    def _match_on_device(self, map_index, desc_q, image_ids, seq, conf, keep):
+        """One sfd2_match_batch of a query against image_ids, queued on the context's stream with the result left in HBM.  Returns
+        (matches0 device tensor [rows][n0] or None, [(image id, row of matches0 or -1)], n0); keep collects what must outlive the
+        launch."""
+        import ctypes
+        import torch
+        from . import _lib
+        if isinstance(desc_q, str):
+            qp, n0 = self.sets.get(desc_q, seq)
+            qs = _lib.DescSet(qp, n0, _lib.DT_F16, _lib.LAYOUT_ND, 1, None, 0, 0)
+        else:
+            a = np.ascontiguousarray(desc_q)
+            if a.dtype not in (np.float64, np.float32):
+                a = a.astype(np.float64)
+            keep.append(a)
+            n0 = a.shape[0]
+            qs = _lib.DescSet(a.ctypes.data, n0, _lib.DT_F64 if a.dtype == np.float64 else _lib.DT_F32, _lib.LAYOUT_ND, 0, None, 0, 0)
+        images, sets, rows = [], [], []
+        for image_id in image_ids:
+            im = map_index.images[image_id]
+            ids = np.asarray(im.point3D_ids)
+            r = np.flatnonzero(ids != -1).astype(np.int32)
+            if ids.size == 0 or len(r) <= 3:
+                images.append((image_id, -1))
+                continue
+            p, n1 = self.sets.get(im.name, seq)
+            if ids.size != n1:
+                raise ValueError(f"{im.name}: {ids.size} point ids for {n1} key points")
+            images.append((image_id, len(sets)))
+            sets.append((p, n1))
+            rows.append(r)
+        m = None
+        if sets and n0 > 0:
+            db = (_lib.DescSet * len(sets))(*[_lib.DescSet(p, n1, _lib.DT_F16, _lib.LAYOUT_ND, 1, r.ctypes.data, len(r), 0)
+                                              for (p, n1), r in zip(sets, rows)])
+            m = torch.empty((len(sets), n0), dtype=torch.int64, device=map_index.device)
+            sc = torch.empty((len(sets), n0), dtype=torch.float32, device=map_index.device)
+            keep += [rows, db, sc, qs]
+            _lib.check(self.ctx.lib.sfd2_match_batch(self.ctx.h, ctypes.byref(qs), db, len(sets), 128, ctypes.byref(conf), m.data_ptr(),
+                                                     sc.data_ptr(), 1, _lib.FLAG_ASYNC))
+        else:
+            images = [(i, -1) for i, _ in images]
+        return m, images, n0
+
     def match_assemble(self, map_index, queries):
         """Matching and 2D-3D assembly on the device for a batch of queries: per query one sfd2_match_batch whose result stays in
         HBM, then ONE sfd2_assemble_2d3d for all of them behind it on the same stream.  map_index: sfd2_amd.covis.MapIndex;
@@ -126,9 +170,6 @@ class StoreMatcher:
         3 or fewer key points that have a 3D point never reaches the matcher (localize_cv2.py:537-538) and takes part as an image
         without matches, so image_idx indexes image_ids.  Returns per query what assemble_2d3d returns; equal to match() followed
         by match_cluster_2D."""
-        import ctypes
-        import torch
-        from . import _lib
         if map_index.device is None:
             map_index.to_device(self.ctx.device)
         seq = self._seq
@@ -137,45 +178,36 @@ class StoreMatcher:
         conf = self.matcher._conf()
         keep, jobs = [], []
         for q in queries:
-            desc_q = q["desc_q"]
-            if isinstance(desc_q, str):
-                qp, n0 = self.sets.get(desc_q, seq)
-                qs = _lib.DescSet(qp, n0, _lib.DT_F16, _lib.LAYOUT_ND, 1, None, 0, 0)
-            else:
-                a = np.ascontiguousarray(desc_q)
-                if a.dtype not in (np.float64, np.float32):
-                    a = a.astype(np.float64)
-                keep.append(a)
-                n0 = a.shape[0]
-                qs = _lib.DescSet(a.ctypes.data, n0, _lib.DT_F64 if a.dtype == np.float64 else _lib.DT_F32, _lib.LAYOUT_ND, 0, None, 0, 0)
-            images, sets, rows = [], [], []
-            for image_id in q["image_ids"]:
-                im = map_index.images[image_id]
-                ids = np.asarray(im.point3D_ids)
-                r = np.flatnonzero(ids != -1).astype(np.int32)
-                if ids.size == 0 or len(r) <= 3:
-                    images.append((image_id, -1))
-                    continue
-                p, n1 = self.sets.get(im.name, seq)
-                if ids.size != n1:
-                    raise ValueError(f"{im.name}: {ids.size} point ids for {n1} key points")
-                images.append((image_id, len(sets)))
-                sets.append((p, n1))
-                rows.append(r)
-            m = None
-            if sets and n0 > 0:
-                db = (_lib.DescSet * len(sets))(*[_lib.DescSet(p, n1, _lib.DT_F16, _lib.LAYOUT_ND, 1, r.ctypes.data, len(r), 0)
-                                                  for (p, n1), r in zip(sets, rows)])
-                m = torch.empty((len(sets), n0), dtype=torch.int64, device=map_index.device)
-                sc = torch.empty((len(sets), n0), dtype=torch.float32, device=map_index.device)
-                keep += [rows, db, sc, qs]
-                _lib.check(self.ctx.lib.sfd2_match_batch(self.ctx.h, ctypes.byref(qs), db, len(sets), 128, ctypes.byref(conf), m.data_ptr(),
-                                                         sc.data_ptr(), 1, _lib.FLAG_ASYNC))
-            else:
-                images = [(i, -1) for i, _ in images]
+            m, images, _ = self._match_on_device(map_index, q["desc_q"], q["image_ids"], seq, conf, keep)
             jobs.append(dict(matches0=m, images=images, kpq=q["kpq"], scores=q.get("scores"), obs_th=q.get("obs_th", 0), gate=q.get("gate"),
                              capacity=q.get("capacity")))
         return assemble_2d3d(self.ctx, map_index, jobs)
+
+    def match_assemble_clusters(self, map_index, queries):
+        """match_assemble for the cluster stage: queries are dicts with desc_q, kpq, clusters (a list of lists of image ids) and obs_th.
+        Per query ONE sfd2_match_batch over the union of its clusters' images, each image once, and then ONE sfd2_assemble_2d3d for
+        all clusters of all queries: a job per cluster whose images point into that query's shared matches0.  No gate, no scores.
+        Returns per query a list over its clusters of what assemble_2d3d returns, plus 'image_ids'.  The library takes at most
+        65535 jobs per call: callers bound their rounds (sfd2_amd.localizer.ROUND)."""
+        if map_index.device is None:
+            map_index.to_device(self.ctx.device)
+        seq = self._seq
+        self._seq += 1
+        self.sets.completed_seq = seq - 1          # every earlier call has synchronised
+        conf = self.matcher._conf()
+        keep, jobs, spans = [], [], []
+        for q in queries:
+            union = list(dict.fromkeys(i for cl in q["clusters"] for i in cl))
+            m, images, _ = self._match_on_device(map_index, q["desc_q"], union, seq, conf, keep)
+            row = dict(images)
+            spans.append((len(jobs), len(q["clusters"])))
+            for cl in q["clusters"]:
+                jobs.append(dict(matches0=m, images=[(i, row[i]) for i in cl], kpq=q["kpq"], scores=None, obs_th=q.get("obs_th", 0), gate=None,
+                                 image_ids=list(cl)))
+        res = assemble_2d3d(self.ctx, map_index, jobs)
+        for r, j in zip(res, jobs):
+            r["image_ids"] = j["image_ids"]
+        return [res[o:o + n] for o, n in spans]
 
     def close(self):
         self.sets.close()
@@ -368,6 +400,50 @@ class Covis:
             refiner=self.refiner)
 
 
+class Stage1:
+    """What the cluster stage needs to run from image ids instead of matches computed beforehand -- the Covis idea applied to stage 1:
+    map_index (sfd2_amd.covis.MapIndex), matcher and feature_file as Covis takes them.  With a StoreMatcher (anything with its
+    match_assemble_clusters) a round's clusters are matched and assembled on the device; a callable matcher (qname, db_names,
+    point3D_ids_list) -> matches0 per image keeps the host loop of match_cluster_2D."""
+
+    def __init__(self, map_index, matcher, feature_file):
+        self.map_index, self.matcher, self.feature_file = map_index, matcher, feature_file
+        self.on_device = hasattr(matcher, "match_assemble_clusters")
+
+    def assemble(self, requests):
+        """requests: a list of (qname, kpq, cluster_ids, obs_th).  Returns per request the list over its clusters of
+        (cluster_info, mp3d, mkpq, mp3d_ids, q_ids) as match_cluster_2D returns them; cluster_info holds 'qids' and 'mp_3d_ids' per
+        database image, rebuilt from the job's per-image segments.  An image without key points has no entry (match_cluster_2D:
+        ids.size == 0 -> continue); one with <= 3 key points that have a 3D point has an empty one."""
+        mi = self.map_index
+        res = self.matcher.match_assemble_clusters(mi, [dict(desc_q=qname, kpq=kpq, clusters=cluster_ids, obs_th=obs_th)
+                                                        for qname, kpq, cluster_ids, obs_th in requests])
+        out = []
+        for per_query in res:
+            prepared = []
+            for r in per_query:
+                ids3d = mi.point_ids[r["point_row"]]
+                q_ids = r["query_idx"].copy()
+                info, o = {}, 0
+                for image_id, n in zip(r["image_ids"], r["image_counts"]):
+                    im = mi.images[image_id]
+                    if np.asarray(im.point3D_ids).size == 0:
+                        continue
+                    info[im.name] = {"qids": q_ids[o:o + n], "mp_3d_ids": ids3d[o:o + n]}
+                    o += int(n)
+                prepared.append((info, r["points3D"].copy(), r["points2D"].copy(), ids3d, q_ids))
+            out.append(prepared)
+        return out
+
+
+def do_covisibility_clustering(frame_ids, all_images, points3D, device=0):
+    """it_loc/localize_cv2.py:87-117 for one list of retrieved image ids, on the device (sfd2_covis_clusters): the clusters, largest
+    first, equal sizes in order of creation.  Members are listed by ascending list position; the reference's member order is
+    whatever set.pop() yields.  For many queries build one sfd2_amd.covis.MapIndex and call its clusters()."""
+    from .covis import MapIndex
+    return MapIndex(all_images, points3D).clusters([frame_ids], device=device)[0]
+
+
 def _assemble(matcher, map_index, feature_file, jobs):
     """jobs: dicts with qname, kpq, score_q, db_ids, obs_th, gate.  matcher: a StoreMatcher or anything else with its match_assemble (device: one match launch per query, one
     sfd2_assemble_2d3d for all of them) or a callable (qname, db_names, point3D_ids_list) -> matches0 per image (then the host loop
@@ -481,18 +557,34 @@ def pose_refinement_covisibility(qname, cfg, feature_file, db_frame_id, map_inde
                                               refiner=refiner, ref_3Dpoints=ref_3Dpoints)[0]
 
 
-def _cluster_steps(kpq, clusters, camera, thresh, inlier_th, points3D, obs_th, qname, covis):
+def _cluster_steps(kpq, clusters, camera, thresh, inlier_th, points3D, obs_th, qname, covis, cluster_ids=None, stage1=None):
     """pose_from_clusters as a coroutine: yields ('estimate', problems) once and ('covis', request) at most once per visit of a call
-    site, receives the results; returns what pose_from_clusters returns.  localize_queries drives many of these in rounds."""
+    site, receives the results; returns what pose_from_clusters returns.  localize_queries drives many of these in rounds.  With
+    cluster_ids (lists of image ids of stage1.map_index) instead of clusters the correspondences come from stage1: a device stage
+    first yields ('assemble', request); a callable matcher is asked per cluster and match_cluster_2D runs here."""
     n_q = len(kpq)
-    first = clusters[0][0][0]
+    if cluster_ids is not None:
+        if stage1 is None:
+            raise ValueError("cluster_ids need a stage1 (sfd2_amd.localize.Stage1)")
+        images = stage1.map_index.images
+        first = images[cluster_ids[0][0]]
+    else:
+        first = clusters[0][0][0]
     best_results = {"tvec": None, "qvec": None, "num_inliers": 0, "single_num_inliers": 0, "db_id": -1, "order": -1, "qname": qname,
                     "optimize": False, "dbname": first.name, "ret_source": "", "inliers": []}
-    prepared = []
-    for cl in clusters:
-        info, mp3d, mkpq, mp3d_ids, q_ids = match_cluster_2D(kpq, [m for _, m in cl], [im.point3D_ids for im, _ in cl], points3D,
-                                                             obs_th=obs_th, db_names=[im.name for im, _ in cl])
-        prepared.append((info, mp3d, mkpq, mp3d_ids, q_ids))
+    if cluster_ids is not None and stage1.on_device:
+        prepared = yield ("assemble", (qname, kpq, cluster_ids, obs_th))
+    else:
+        if cluster_ids is not None:
+            clusters = []
+            for cl in cluster_ids:
+                ims = [images[i] for i in cl]
+                clusters.append(list(zip(ims, stage1.matcher(qname, [im.name for im in ims], [np.asarray(im.point3D_ids) for im in ims]))))
+        prepared = []
+        for cl in clusters:
+            info, mp3d, mkpq, mp3d_ids, q_ids = match_cluster_2D(kpq, [m for _, m in cl], [im.point3D_ids for im, _ in cl], points3D,
+                                                                 obs_th=obs_th, db_names=[im.name for im, _ in cl])
+            prepared.append((info, mp3d, mkpq, mp3d_ids, q_ids))
     live = [i for i, p in enumerate(prepared) if p[1].shape[0] >= 8]
     rets = dict(zip(live, (yield ("estimate", [(prepared[i][2], prepared[i][1], camera, thresh) for i in live])) if live else []))
     last = None
@@ -536,7 +628,7 @@ def _cluster_steps(kpq, clusters, camera, thresh, inlier_th, points3D, obs_th, q
     return first.qvec, first.tvec, -1, best_results
 
 
-def _drive(gens, estimator, covis):
+def _drive(gens, estimator, covis, stage1=None):
     """Runs the coroutines of _cluster_steps in rounds: the pending requests of one kind go out in one call."""
     results = [None] * len(gens)
     pending = {}
@@ -547,6 +639,10 @@ def _drive(gens, estimator, covis):
             results[i] = e.value
     while pending:
         answers = {}
+        asm = [i for i in sorted(pending) if pending[i][0] == "assemble"]
+        if asm:
+            for i, r in zip(asm, stage1.assemble([pending[i][1] for i in asm])):
+                answers[i] = r
         est = [i for i in sorted(pending) if pending[i][0] == "estimate"]
         if est:
             flat = [p for i in est for p in pending[i][1]]
@@ -570,7 +666,8 @@ def _drive(gens, estimator, covis):
     return results
 
 
-def pose_from_clusters(kpq, clusters, camera, thresh, inlier_th=50, *, points3D, obs_th=3, qname=None, estimator=None, covis=None, **ransac):
+def pose_from_clusters(kpq, clusters, camera, thresh, inlier_th=50, *, points3D, obs_th=3, qname=None, estimator=None, covis=None,
+                       cluster_ids=None, stage1=None, **ransac):
     """The initialisation loop of it_loc/localize_cv2.py:653-1273 pose_from_cluster_with_matcher, on matches already computed.
     clusters: a list over the retrieved clusters, each a list of (db_image, matches0) pairs (db_image with
     .name, .qvec, .tvec, .point3D_ids as read_write_model returns them; matches0 from StoreMatcher.match / feature_matching_batch).
@@ -585,17 +682,25 @@ def pose_from_clusters(kpq, clusters, camera, thresh, inlier_th=50, *, points3D,
     covis: None is do_covisility_opt=False.  A Covis replays the two call sites of pose_refinement_covisibility: after a successful
     cluster (:981-1014) the pose is refined from the cluster's best database image -- a failed refinement goes on to the next
     cluster, a successful one returns its pose and num_inliers -- and on the fallback path (:1139-1265) the kept pose is refined
-    and returned with 0 whether or not the refinement succeeded.  qname then names the query's set in covis.feature_file."""
+    and returned with 0 whether or not the refinement succeeded.  qname then names the query's set in covis.feature_file.
+
+    cluster_ids + stage1 (a Stage1) replace clusters (pass None): lists of image ids, matched and assembled by the stage."""
     if estimator is None:
         estimator = _default_estimator(ransac)
-    return _drive([_cluster_steps(kpq, clusters, camera, thresh, inlier_th, points3D, obs_th, qname, covis)], estimator, covis)[0]
+    return _drive([_cluster_steps(kpq, clusters, camera, thresh, inlier_th, points3D, obs_th, qname, covis, cluster_ids, stage1)], estimator,
+                  covis, stage1)[0]
 
 
-def localize_queries(queries, thresh, inlier_th=50, *, points3D, obs_th=3, estimator=None, covis=None, **ransac):
+def localize_queries(queries, thresh, inlier_th=50, *, points3D, obs_th=3, estimator=None, covis=None, stage1=None, **ransac):
     """pose_from_clusters for many queries in rounds: queries is a list of dicts with kpq, clusters, camera and qname.  Stage 1 of
     all queries is one estimator call; then every covisibility refinement pending in a round is one match / assemble / estimate /
-    refine call each, until no query is pending.  Every result equals the per-query call's exactly."""
+    refine call each, until no query is pending.  Every result equals the per-query call's exactly.
+
+    A query may give cluster_ids (a list of lists of image ids) instead of clusters; stage1 (a Stage1) then matches the query named
+    qname against them.  On the device that is, for all such queries together, one sfd2_match_batch per query over the union of its
+    clusters' images and ONE sfd2_assemble_2d3d with a job per cluster, before the one estimator call."""
     if estimator is None:
         estimator = _default_estimator(ransac)
-    gens = [_cluster_steps(q["kpq"], q["clusters"], q["camera"], thresh, inlier_th, points3D, obs_th, q.get("qname"), covis) for q in queries]
-    return _drive(gens, estimator, covis)
+    gens = [_cluster_steps(q["kpq"], q.get("clusters"), q["camera"], thresh, inlier_th, points3D, obs_th, q.get("qname"), covis,
+                           q.get("cluster_ids"), stage1) for q in queries]
+    return _drive(gens, estimator, covis, stage1)

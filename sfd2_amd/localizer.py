@@ -1,0 +1,262 @@
+"""it_loc/localizer.py on the device: reads a query list with intrinsics, a retrieval file, a COLMAP model and a feature store, and
+writes the poses a user submits to the benchmark.  `python -m sfd2_amd.localizer` takes the reference's arguments (names and
+defaults of it_loc/localizer.py:394-427) plus --device and --stage1, and writes the reference's four files under the reference's
+names: <stem>.txt (name qvec tvec), <stem>.txt.failed, <stem>.log (qname dbname num_inliers order) and <stem>_full.log, where
+<stem> = save_root/{features}_{matcher}_{init_type}_{ransac_thresh:.0f}_{inlier_thresh:d} + 'all' ('vis' and a slice{N}_ prefix
+for --dataset ecmu) + _o{obs}op{frames}{opt_type}th{opt}r{radius}i{iters} with --do_covisible_opt.
+
+The steps: retrieved names -> image ids (a name the model does not hold is warned about and dropped); --init_type sng makes one
+cluster per retrieved image, clu clusters them by covisibility (MapIndex.clusters: ONE sfd2_covis_clusters call for all queries);
+localize.localize_queries over the queries in rounds of ROUND; --stage1 device matches and assembles the clusters on the device
+(localize.Stage1), host is the loop of match_cluster_2D on matches brought to the host; --do_covisible_opt adds localize.Covis.
+
+Deviations from the reference:
+  * a query absent from the retrieval file, or none of whose retrieved images is in the model, is skipped with a warning, listed in
+    .failed and gets no pose line (the reference reuses the previous query's candidates, and raises on the first query);
+  * no plots (--image_dir, --db_imglist_fn, --only_gt are accepted and unused; --image_dir and --save_root default to None and
+    outputs/localizer, not to the author's directories), no per-cluster log_info in _full.log; matching
+    always happens here (--with_match is the only mode);
+  * the wall times of the summary lines are this run's: clustering time and a round's time, divided by their numbers of queries;
+  * the members of a clu cluster come in retrieval order, the reference's in set.pop() order;
+  * a --dataset without a naming rule is an error before anything runs (the reference fails when it writes the poses);
+  * --init_type clu takes at most 256 distinct retrieved images per query (SFD2_CLUSTER_MAX_FRAMES, the kernel's bit matrix);
+    more is an error of MapIndex.clusters.  The reference has no limit; its scripts retrieve 10 to 50."""
+import argparse
+import logging
+import os
+import os.path as osp
+import time
+from pathlib import Path
+
+import numpy as np
+
+from . import colmap_io, feature_io, parsers
+from .covis import MapIndex, compute_pose_error
+
+ROUND = 32                      # queries per localize_queries call: bounds the matches, jobs and outputs alive at once
+ERROR_THS = ((0.25, 2), (0.5, 5), (5, 10))       # (metres, degrees) of the three success counters
+DATASETS_LAST_PART = ('aachen', 'aachen_v1.1')
+
+
+def make_parser():
+    parser = argparse.ArgumentParser()
+    parser.add_argument('--image_dir', type=str, default=None)
+    parser.add_argument('--dataset', type=str, required=True)
+    parser.add_argument('--db_imglist_fn', type=str, required=True)
+    parser.add_argument('--reference_sfm', type=Path, required=True)
+    parser.add_argument('--queries', type=Path, required=True)
+    parser.add_argument('--features', type=Path, required=True)
+    parser.add_argument('--ransac_thresh', type=float, default=12)
+    parser.add_argument('--covisibility_frame', type=int, default=50)
+    parser.add_argument('--with_match', action='store_true')
+    parser.add_argument('--do_covisible_opt', action='store_true')
+    parser.add_argument('--init_type', type=str, default='clu', choices=['sng', 'clu'])
+    parser.add_argument('--opt_type', type=str, default='cluster')
+    parser.add_argument('--matcher_method', type=str, default="NNM")
+    parser.add_argument('--inlier_thresh', type=int, default=50)
+    parser.add_argument('--obs_thresh', type=float, default=3)
+    parser.add_argument('--opt_thresh', type=float, default=12)
+    parser.add_argument('--radius', type=int, default=20)
+    parser.add_argument('--iters', type=int, default=1)
+    parser.add_argument('--save_root', type=str, default="outputs/localizer")
+    parser.add_argument('--retrieval', type=Path, default=None)
+    parser.add_argument('--gt_pose_fn', type=str, default=None)
+    parser.add_argument('--only_gt', type=int, default=0)
+    parser.add_argument('--slice', type=int, default=2)
+    parser.add_argument('--device', type=int, default=0)
+    parser.add_argument('--stage1', type=str, default='device', choices=['device', 'host'])
+    return parser
+
+
+def output_stem(args, ecmu=False):
+    """save_root/<name> of the four output files; the pieces are those of it_loc/localizer.py:45-64 and :224-251."""
+    feat = Path(args.features).name.split(".")[0]
+    name = f"{feat}_{args.matcher_method}_{args.init_type}_{args.ransac_thresh:.0f}_{args.inlier_thresh:d}"
+    if ecmu:
+        name = f"slice{args.slice:d}_{name}"
+    name += 'vis' if ecmu else 'all'
+    if args.do_covisible_opt:
+        name += f"_o{int(args.obs_thresh)}op{int(args.covisibility_frame)}{args.opt_type}th{int(args.opt_thresh)}r{args.radius}"
+        name += f"i{int(args.iters)}" if args.iters > 0 else ""
+    return osp.join(args.save_root, name)
+
+
+def result_name(dataset, qname, ecmu=False):
+    """The name of a pose line: the last path part, two parts for robotcar (rear/img_id)."""
+    if dataset in DATASETS_LAST_PART or (ecmu and dataset == 'ecmu'):
+        return qname.split('/')[-1]
+    if dataset == 'robotcar':
+        return qname.split('/')[-2] + "/" + qname.split('/')[-1]
+    raise ValueError(f"dataset {dataset!r} has no naming rule for the pose file (aachen, aachen_v1.1, robotcar, ecmu)")
+
+
+def read_gt_poses(path):
+    """name (last path part) -> (qvec, tvec) of a `name qw qx qy qz tx ty tz` file; {} without one."""
+    if path is None:
+        return {}
+    poses = {}
+    for line in Path(path).read_text().splitlines():
+        name, *numbers = line.strip().split(' ')
+        v = np.array(numbers, dtype=float)
+        poses[name.split('/')[-1]] = (v[:4], v[4:])
+    return poses
+
+
+def summary_line(counts, time_coarse, time_full, error=None):
+    """One line of _full.log.  counts: dict with failed, total, top1 and, for the ground-truth part, hits (per threshold pair of
+    ERROR_THS) and with_gt; error: (q_error, t_error) of a query that has a ground-truth pose."""
+    line = f"All {counts['failed']:d}/{counts['total']:d} failed cases top@1:{counts['top1'] / counts['total']:.2f}, " \
+           f"time[cs/fn]: {time_coarse:.2f}/{time_full:.2f}"
+    if error is not None:
+        line += f", q_error:{error[0]:.2f} t_error:{error[1]:.2f} " + "/".join(f"{n:d}" for n in counts['hits'] + [counts['with_gt']])
+    return line
+
+
+def candidate_ids(qname, retrievals, name_to_id):
+    """The ids of a query's retrieved images in retrieval order, or None when the query is not in the retrieval file."""
+    if qname not in retrievals:
+        return None
+    ids = []
+    for c in retrievals[qname]:
+        if c not in name_to_id:
+            logging.warning(f'Image {c} was retrieved but not in database')
+            continue
+        ids.append(name_to_id[c])
+    return ids
+
+
+def write_outputs(stem, dataset, order, poses, failed_cases, all_logs, full_log_info, ecmu=False):
+    """<stem>.txt.failed, <stem>.txt, <stem>.log and <stem>_full.log as it_loc/localizer.py:175-200 writes them."""
+    results = stem + '.txt'
+    with open(f'{results}.failed', 'w') as f:
+        for v in failed_cases:
+            f.write(v + "\n")
+    with open(results, 'w') as f:
+        for q in order:
+            if q not in poses:
+                continue
+            f.write(' '.join([result_name(dataset, q, ecmu)] + [str(v) for pose_part in poses[q] for v in pose_part]) + '\n')
+    with open(stem + '.log', 'w') as f:
+        for v in all_logs:
+            f.write(f"{v['qname']} {v['dbname']} {int(v['num_inliers']):d} {int(v['order']):d}\n")
+    with open(stem + '_full.log', 'w') as f:
+        f.write(full_log_info)
+
+
+def run(args, estimator=None, refiner=None, matcher=None, clusterer=None, features=None, ecmu=False):
+    """The reference's run(args).  estimator / refiner replace pose.absolute_pose_estimation_batch / pose.pose_refinement_batch
+    (their problem lists); matcher replaces the device matcher by a callable (qname, db_names, point3D_ids_list) -> matches0 per
+    image, which keeps the host loop for either --stage1; clusterer replaces MapIndex.clusters (lists of ids per query -> clusters
+    per query); features is an already open feature store (a mapping name -> keypoints / scores / descriptors) used instead of
+    opening args.features, which then only names the output.  With matcher, estimator, refiner (and clusterer for clu) given nothing
+    touches a GPU.  Returns the stem of the files written."""
+    from . import localize
+    result_name(args.dataset, 'a/b', ecmu)                    # an unknown dataset fails here, not after the run
+    gt_poses = read_gt_poses(args.gt_pose_fn)
+    retrievals = parsers.read_retrieval_results(args.retrieval)
+    stem = output_stem(args, ecmu)
+    os.makedirs(args.save_root, exist_ok=True)
+    print("save_fn: ", stem + '.log')
+    queries = parsers.query_cameras(args.queries)
+    _, db_images, points3D = colmap_io.read_model(str(args.reference_sfm))
+    mi = MapIndex(db_images, points3D)
+    feature_file = features if features is not None else feature_io.open_store(str(args.features), 'r')
+    store_matcher = None
+    if matcher is None:
+        from .matcher import Matcher, confs
+        store_matcher = matcher = localize.StoreMatcher(Matcher(confs[args.matcher_method]).eval().cuda(args.device), feature_file)
+    try:
+        logging.info('Starting localization...')
+        failed_cases, todo = [], []
+        for qname, cam in queries:
+            ids = candidate_ids(qname, retrievals, mi.name_to_id)
+            if not ids:
+                logging.warning(f'Query {qname} ' + ('is not in the retrieval file' if ids is None else 'has no retrieved image in the model') + ': skipped')
+                failed_cases.append(qname)
+                continue
+            todo.append((qname, cam, ids))
+        time_start = time.time()
+        if args.init_type == 'sng':
+            cluster_ids = [[[i] for i in ids] for _, _, ids in todo]
+        else:
+            lists = [ids for _, _, ids in todo]
+            cluster_ids = (clusterer(lists) if clusterer is not None else mi.clusters(lists, device=args.device)) if lists else []
+        time_coarse = (time.time() - time_start) / max(len(todo), 1)
+        on_device = args.stage1 == 'device'
+        stage1 = localize.Stage1(mi, matcher, feature_file)
+        covis = None
+        if args.do_covisible_opt:
+            covis = localize.Covis(mi, matcher, feature_file, opt_type=args.opt_type, covisibility_frame=args.covisibility_frame, iters=args.iters,
+                                   radius=args.radius, obs_th=args.obs_thresh, opt_th=args.opt_thresh, estimator=estimator, refiner=refiner)
+        poses, all_logs, summary = {}, [], []
+        counts = dict(failed=0, total=0, top1=0, hits=[0] * len(ERROR_THS), with_gt=0)
+        for r0 in range(0, len(todo), ROUND):
+            t0 = time.time()
+            batch = []
+            for (qname, cam, ids), cl in zip(todo[r0:r0 + ROUND], cluster_ids[r0:r0 + ROUND]):
+                q = dict(kpq=feature_file[qname]['keypoints'].__array__(), camera=cam, qname=qname)
+                if on_device:
+                    q["cluster_ids"] = cl
+                else:
+                    q["clusters"] = host_clusters(matcher, mi, qname, cl)
+                batch.append(q)
+            out = localize.localize_queries(batch, args.ransac_thresh, inlier_th=args.inlier_thresh, points3D=points3D, obs_th=args.obs_thresh,
+                                            estimator=estimator, covis=covis, stage1=stage1)
+            time_full = (time.time() - t0) / len(batch)
+            for q, (qvec, tvec, n_inliers, logs) in zip(batch, out):
+                qname = q["qname"]
+                all_logs.append(logs)
+                poses[qname] = (qvec, tvec)
+                counts['total'] += 1
+                counts['top1'] += logs['order'] == 1
+                if n_inliers == 0:                                 # the reference's rule: -1 (the first image's pose) is not listed
+                    failed_cases.append(qname)
+                    counts['failed'] += 1
+                error = None
+                gt = gt_poses.get(qname.split('/')[-1])
+                if gt is not None:
+                    error = compute_pose_error(qvec, tvec, gt[0], gt[1])[:2]
+                    counts['with_gt'] += 1
+                    for i, (t_max, q_max) in enumerate(ERROR_THS):
+                        counts['hits'][i] += error[1] <= t_max and error[0] <= q_max
+                summary.append(summary_line(counts, time_coarse, time_full, error))
+                print(summary[-1])
+        full_log_info = ''.join(line + "\n" for line in summary)
+        logging.info(f'Localized {len(poses)} / {len(queries)} images.')
+        logging.info(f'Writing poses to {stem}.txt...')
+        write_outputs(stem, args.dataset, [q for q, _ in queries], poses, failed_cases, all_logs, full_log_info, ecmu)
+        logging.info('Done!')
+    finally:
+        if store_matcher is not None:
+            store_matcher.close()
+        if features is None:
+            feature_file.close()
+    return stem
+
+
+def host_clusters(matcher, map_index, qname, cluster_ids):
+    """--stage1 host: the query matched against the union of its clusters' images, each image once (StoreMatcher.match brings the
+    matches to the host; a callable is simply called), handed out as the (db_image, matches0) pairs pose_from_clusters takes."""
+    union = list(dict.fromkeys(i for cl in cluster_ids for i in cl))
+    ims = [map_index.images[i] for i in union]
+    ids_list = [np.asarray(im.point3D_ids) for im in ims]
+    names = [im.name for im in ims]
+    ml = matcher.match(qname, names, ids_list) if hasattr(matcher, "match") else matcher(qname, names, ids_list)
+    by_id = dict(zip(union, ml))
+    return [[(map_index.images[i], by_id[i]) for i in cl] for cl in cluster_ids]
+
+
+def run_ecmu(args, **kw):
+    """The reference's run_ecmu(args): run() with the slice{N}_ prefix, the 'vis' tag and the ecmu naming rule."""
+    return run(args, ecmu=True, **kw)
+
+
+def main(argv=None):
+    args = make_parser().parse_args(argv)
+    if args.dataset == 'ecmu':
+        return run_ecmu(args=args)
+    return run(args=args)
+
+
+if __name__ == '__main__':
+    main()

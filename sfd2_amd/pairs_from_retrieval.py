@@ -9,24 +9,7 @@ from pathlib import Path
 import numpy as np
 
 from . import colmap_io, feature_io, pairs as P
-
-
-def parse_image_lists_with_intrinsics(paths):
-    """hloc/utils/parsers.py:7-25: the names (first column) of every list file the glob matches, with the rest of each line."""
-    paths = Path(paths)
-    files = list(Path(paths.parent).glob(paths.name))
-    assert len(files) > 0
-    results = []
-    for lfile in files:
-        with open(lfile, 'r') as f:
-            raw_data = f.readlines()
-        logging.info(f'Importing {len(raw_data)} queries in {lfile.name}')
-        for data in raw_data:
-            data = data.strip('\n').split(' ')
-            name, camera_model, width, height = data[:4]
-            results.append((name, (camera_model, int(width), int(height), np.array(data[4:], float))))
-    assert len(results) > 0
-    return results
+from .parsers import parse_image_lists_with_intrinsics
 
 
 def select_names(h5_names, prefix, list_path, model, what):
