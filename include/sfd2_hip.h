@@ -85,7 +85,7 @@ typedef struct {
     int64_t n_candidates; /* N0 after NMS + threshold + border of the last extract          */
 } sfd2_timings;
 
-int sfd2_version(void);   /* 100 = rounds 1-4; 105 adds sfd2_extract_record_async, sfd2_desc_pack and host outputs with SFD2_FLAG_ASYNC; 106 adds sfd2_get_margin_status; 107 adds sfd2_get_relax_status (option "c3b_plain"); 108 adds sfd2_get_option, sfd2_device_pci_bus_id, SFD2_FLAG_DESC_STORE64; 109 adds the baseline JPEG decoder (sfd2_jpeg_*); 112 adds the SfM map (sfd2_verify_matches_batch, sfd2_build_tracks, sfd2_triangulate_tracks); 113 adds the pair selection (sfd2_pairs_retrieval, sfd2_pairs_covisibility, sfd2_pairs_poses); 114 adds sfd2_covis_clusters */
+int sfd2_version(void);   /* 100 = rounds 1-4; 105 adds sfd2_extract_record_async, sfd2_desc_pack and host outputs with SFD2_FLAG_ASYNC; 106 adds sfd2_get_margin_status; 107 adds sfd2_get_relax_status (option "c3b_plain"); 108 adds sfd2_get_option, sfd2_device_pci_bus_id, SFD2_FLAG_DESC_STORE64; 109 adds the baseline JPEG decoder (sfd2_jpeg_*); 112 adds the SfM map (sfd2_verify_matches_batch, sfd2_build_tracks, sfd2_triangulate_tracks); 113 adds the pair selection (sfd2_pairs_retrieval, sfd2_pairs_covisibility, sfd2_pairs_poses); 114 adds sfd2_covis_clusters; 115 adds sfd2_covis_frames */
 const char *sfd2_last_error(void);
 
 int sfd2_ctx_create(int device, sfd2_ctx **out);
@@ -733,6 +733,76 @@ int sfd2_pairs_poses(sfd2_ctx *ctx, const double *qvec, const double *tvec, int 
 int sfd2_covis_clusters(sfd2_ctx *ctx, const int64_t *obs_offsets, const int32_t *obs_point, int n_images,
                         const int64_t *track_offsets, const int32_t *track_image, int n_points, const int64_t *frame_offsets,
                         const int32_t *frames, int nq, int32_t *cluster, int32_t *n_clusters, int flags);
+
+/* ------------------------------------------------------------------------------------------------ covisible frame selection
+ * it_loc/localize_cv2.py:120-169 get_covisibility_frames (SFD2_FRAMES_OBS) and :172-233 get_covisibility_frames_by_pose
+ * (SFD2_FRAMES_POS) for many tasks in one call.  The map is the two CSRs of sfd2_covis_clusters plus
+ *   - the SEEN CSR: seen_offsets[n_points + 1] / seen_image = per point the distinct images whose key points hold the point,
+ *     ascending: the de-duplicated inverse of obs.  The reference takes connectivity from the tracks and the count from
+ *     np.isin(points, image.point3D_ids); the two differ when a track lists an image that does not observe the point, or an image
+ *     lists a point twice;
+ *   - excluded[n_images]: one byte per image, set when its name holds "left" or "right" (POS only; may be NULL without POS tasks);
+ *   - qvec[n_images][4] (w x y z), tvec[n_images][3]: the images' poses, fp64 (may be NULL when no task has a pose);
+ *   - n_obs, n_track, n_seen: the lengths of obs_point, track_image, seen_image, which the offsets must end at.
+ * Image indices must ascend with the image ids (ties are broken by index where the reference breaks them by id).  With
+ * inputs_on_device every map array is a device pointer and nothing of the map is uploaded: the call reads the three offset ends
+ * back and the kernel range-checks every index it follows.  Tasks, ref_offsets / ref_points and the outputs are host arrays.
+ *
+ * A task: frame (image index), kind, covisibility_frame (cf, 0 = no limit), obs_th, q_th (POS), has_pose with qvec / tvec (POS needs
+ * one), use_ref.  V, the task's point rows, is the frame's obs segment, or with use_ref ref_points[ref_offsets[i] .. ref_offsets[i + 1])
+ * (the reference's ref_3Dpoints; repeats count, as the reference counts them).
+ *   connected  every image in the track of any row of V -- the frame itself too; the track length is not tested here.
+ *   count(d)   the entries of V with track length >= obs_th (track_offsets, duplicates counted) whose seen list holds d.
+ *   pose error against an image's pose, fp64, compute_pose_error's formulas: both quaternions normalised, the centres -R^T t,
+ *              t_error = |C_pred - C_d|, q_error = 2 acos(min(1, |q . q_d|)) in degrees.
+ * OBS: the connected frames are walked by larger count first, then smaller index.  With a pose a frame is set aside when
+ * q_error >= 30, t_error >= 30 or count <= 30; the others are taken until cf are (cf = 0: all).  If at most 3 were taken, the
+ * frames set aside before the walk ended are appended in order, stopping after the append that brings the length to >= cf.
+ * POS: excluded images leave connected.  The frames with q_error <= q_th come by ascending t_error, up to cf; cf = 0 ends here.
+ * If fewer than cf, the list is filled by (larger count, smaller index) from the frames not yet taken, up to cf.
+ *
+ * idx[n_tasks][cap]: image indices in result order, -1 beyond n_out[i].  status[i]:
+ *   0  the row is the reference's result;
+ *   1  a decision lay inside a rounding band -- the row is empty, n_out 0, and the caller must decide on the host:
+ *        a q_error within 1e-9 + min(1e-13 / sin(q_error / 2), 1e-5) degrees of its threshold (the second term is what acos does
+ *        to a rounding of the dot product near 1), for any connected frame of a task with a pose;
+ *        OBS: a t_error within 1e-9 (1 + |C_pred| + |C_d|) of 30;
+ *        POS: two neighbours in t_error order among the first cf + 1 (cf = 0: all) closer than 1e-9 (1 + 2 |C_pred| + t_error), the
+ *        farther one's t_error (|C_d| <= |C_pred| + t_error: the band above without a second look at the pose) -- numpy's default
+ *        argsort is not stable, a tie has no defined order;
+ *        a non-finite value in the task's pose, an image's pose or an error;
+ *   2  capacity, same consequence: more than cap results, or more than SFD2_FRAMES_MAX_CANDIDATES connected frames.
+ * Counts and the (count, index) order are integer and exact.  A task's outputs do not depend on the batch, its order, the grid
+ * or the flag.  The counters sit in LDS up to SFD2_FRAMES_LDS_IMAGES images, beyond that (or with the flag) in a row of global
+ * scratch per workgroup.  Returns -1 with sfd2_last_error() set, writing nothing, on a bad argument: an index out of range in any
+ * host array, negative sizes, cap < 1, offsets that do not end at the stated sizes; and, after the launch, when the kernel's range
+ * check met a bad index in a device-resident map (no output array is written then either). */
+#define SFD2_FRAMES_OBS 0
+#define SFD2_FRAMES_POS 1
+#define SFD2_FRAMES_MAX_CANDIDATES 4096
+#define SFD2_FRAMES_LDS_IMAGES 16384
+#define SFD2_FRAMES_FLAG_GLOBAL_COUNTERS 1   /* counters in global scratch even where they fit LDS                              */
+typedef struct {
+    const int64_t *obs_offsets;     /* [n_images + 1]                                                                      */
+    const int32_t *obs_point;       /* [n_obs] point rows                                                                  */
+    const int64_t *track_offsets;   /* [n_points + 1]                                                                      */
+    const int32_t *track_image;     /* [n_track] image indices, duplicates kept                                            */
+    const int64_t *seen_offsets;    /* [n_points + 1]                                                                      */
+    const int32_t *seen_image;      /* [n_seen] image indices, distinct and ascending per point                            */
+    const uint8_t *excluded;        /* [n_images] or NULL                                                                  */
+    const double *qvec, *tvec;      /* [n_images][4], [n_images][3] or NULL                                                */
+    int64_t n_obs, n_track, n_seen;
+    int32_t n_images, n_points;
+    int32_t inputs_on_device, reserved;
+} sfd2_frames_map;
+typedef struct {
+    int32_t frame, kind, covisibility_frame, obs_th;
+    int32_t has_pose, use_ref;
+    double q_th;
+    double qvec[4], tvec[3];        /* world to camera, qvec = (w, x, y, z)                                                */
+} sfd2_frames_task;
+int sfd2_covis_frames(sfd2_ctx *ctx, const sfd2_frames_map *map, const sfd2_frames_task *tasks, int n_tasks, const int64_t *ref_offsets,
+                      const int32_t *ref_points, int cap, int32_t *idx, int32_t *n_out, int32_t *status, int flags);
 
 #ifdef __cplusplus
 }

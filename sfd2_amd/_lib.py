@@ -144,6 +144,24 @@ TRI_ST_RANGE, TRI_ST_NOT_CONVERGED = 1, 2
 PAIRS_MAX_K, PAIRS_POSES_MAX_K = 256, 1024
 PAIRS_FLAG_GLOBAL_COUNTERS, PAIRS_FLAG_CENTRES = 1, 2
 CLUSTER_MAX_FRAMES, CLUSTER_LDS_IMAGES, CLUSTER_FLAG_GLOBAL_SLOTS = 256, 65536, 1   # SFD2_CLUSTER_*
+FRAMES_OBS, FRAMES_POS = 0, 1                                                       # SFD2_FRAMES_*
+FRAMES_MAX_CANDIDATES, FRAMES_LDS_IMAGES, FRAMES_FLAG_GLOBAL_COUNTERS = 4096, 16384, 1
+
+
+class FramesMap(ctypes.Structure):
+    """sfd2_frames_map (include/sfd2_hip.h)."""
+    _fields_ = [("obs_offsets", ctypes.c_void_p), ("obs_point", ctypes.c_void_p), ("track_offsets", ctypes.c_void_p),
+                ("track_image", ctypes.c_void_p), ("seen_offsets", ctypes.c_void_p), ("seen_image", ctypes.c_void_p),
+                ("excluded", ctypes.c_void_p), ("qvec", ctypes.c_void_p), ("tvec", ctypes.c_void_p), ("n_obs", ctypes.c_int64),
+                ("n_track", ctypes.c_int64), ("n_seen", ctypes.c_int64), ("n_images", ctypes.c_int32), ("n_points", ctypes.c_int32),
+                ("inputs_on_device", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class FramesTask(ctypes.Structure):
+    """sfd2_frames_task (include/sfd2_hip.h)."""
+    _fields_ = [("frame", ctypes.c_int32), ("kind", ctypes.c_int32), ("covisibility_frame", ctypes.c_int32), ("obs_th", ctypes.c_int32),
+                ("has_pose", ctypes.c_int32), ("use_ref", ctypes.c_int32), ("q_th", ctypes.c_double), ("qvec", ctypes.c_double * 4),
+                ("tvec", ctypes.c_double * 3)]
 
 
 def pairs_splits(n):
@@ -163,6 +181,7 @@ EXPORTS = [
     "sfd2_jpeg_parse", "sfd2_jpeg_prepare", "sfd2_jpeg_decode", "sfd2_absolute_pose_batch", "sfd2_pose_refine_batch",
     "sfd2_assemble_2d3d", "sfd2_verify_matches_batch", "sfd2_build_tracks", "sfd2_triangulate_tracks",
     "sfd2_pairs_retrieval", "sfd2_pairs_covisibility", "sfd2_pairs_poses", "sfd2_covis_clusters",
+    "sfd2_covis_frames",
 ]
 
 _lib = None
@@ -257,10 +276,11 @@ def load():
     lib.sfd2_pairs_covisibility.argtypes = [vp, vp, vp, ci, vp, vp, ci, ci, vp, vp, vp, ci]
     lib.sfd2_pairs_poses.argtypes = [vp, vp, vp, ci, ci, cd, vp, vp, vp, ci]
     lib.sfd2_covis_clusters.argtypes = [vp, vp, vp, ci, vp, vp, ci, vp, vp, ci, vp, vp, ci]
+    lib.sfd2_covis_frames.argtypes = [vp, ctypes.POINTER(FramesMap), ctypes.POINTER(FramesTask), ci, vp, vp, ci, vp, vp, vp, ci]
     for name in EXPORTS:
         getattr(lib, name)  # raises AttributeError if the .so lacks a declared symbol
-    if lib.sfd2_version() < 114:
-        raise RuntimeError(f"{LIB_PATH} is version {lib.sfd2_version()}, this binding needs >= 114 (rebuild: __graft_entry__.build())")
+    if lib.sfd2_version() < 115:
+        raise RuntimeError(f"{LIB_PATH} is version {lib.sfd2_version()}, this binding needs >= 115 (rebuild: __graft_entry__.build())")
     _lib = lib
     return lib
 

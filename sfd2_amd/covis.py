@@ -1,6 +1,8 @@
 """The map side of the localiser's covisibility stage (it_loc/localize_cv2.py:120-233 and the helpers of it_loc/common.py it uses):
-a dense index over COLMAP's images / points3D dicts, the two covisible-frame selections, vectorised on the host, and the device
-buffers sfd2_assemble_2d3d reads (point table, per-image key point -> point row tables)."""
+a dense index over COLMAP's images / points3D dicts, the two covisible-frame selections, vectorised on the host and batched on the
+device (sfd2_covis_frames), and the device buffers sfd2_assemble_2d3d reads (point table, per-image key point -> point row tables)."""
+import math
+
 import numpy as np
 
 from .pose import CAMERA_MODELS
@@ -75,6 +77,8 @@ class MapIndex:
         self.device = None
         self._dev_xyz = self._dev_track = None
         self._csr = None
+        self._frames = self._dev_frames = None
+        self.frames_tasks = self.frames_host = 0      # tasks covisible_frames_batch has seen / decided with the host functions
 
     # ------------------------------------------------------------------------------------------------ tables
     def point_rows(self, ids):
@@ -97,6 +101,7 @@ class MapIndex:
         self._dev_xyz = torch.from_numpy(self.xyz if self.xyz.size else np.zeros((1, 3))).to(self.device)
         self._dev_track = torch.from_numpy(self.track_len if self.track_len.size else np.zeros(1, np.int32)).to(self.device)
         self._dev_rows = {}
+        self._dev_frames = None                       # the CSRs of frames_csr() follow on first use (covisible_frames_batch)
         return self
 
     def device_rows(self, image_id):
@@ -166,6 +171,145 @@ class MapIndex:
                                                frames.ctypes.data if len(frames) else None, len(lists), cluster.ctypes.data if len(frames) else None,
                                                n_clusters.ctypes.data, _lib.CLUSTER_FLAG_GLOBAL_SLOTS if global_slots else 0))
         return self.clusters_from_ranks(lists, off, cluster, n_clusters)
+
+    # ------------------------------------------------------------------------------------------------ selections on the device
+    def frames_csr(self):
+        """What sfd2_covis_frames reads of the map, built on first use and kept: a dict with ids (image ids ascending: index order is
+        id order, so that ties by index are the reference's ties by id), index (id -> image index), the CSRs of csr() over that
+        order (obs_offsets, obs_point, track_offsets, track_image), the seen CSR (seen_offsets, seen_image: per point the distinct
+        images whose point3D_ids hold it, ascending), excluded (uint8: the name holds 'left' or 'right'), qvec [n, 4], tvec [n, 3]."""
+        if self._frames is None:
+            ids = sorted(self.images)
+            if ids == list(self.images):
+                _, oo, op, to, ti = self.csr()
+            else:
+                from .pairs import covisibility_csr
+                _, oo, op, to, ti = covisibility_csr({i: self.images[i] for i in ids}, self.points3D)
+            n, P = len(ids), len(self.point_ids)
+            pairs = np.unique(op.astype(np.int64) * n + np.repeat(np.arange(n, dtype=np.int64), np.diff(oo)))
+            so = np.zeros(P + 1, dtype=np.int64)
+            np.cumsum(np.bincount(pairs // n, minlength=P), out=so[1:])
+            names = [self.images[i].name for i in ids]
+            self._frames = dict(
+                ids=np.array(ids, dtype=np.int64), index={iid: i for i, iid in enumerate(ids)}, obs_offsets=oo, obs_point=op, track_offsets=to,
+                track_image=ti, seen_offsets=so, seen_image=np.ascontiguousarray((pairs % n).astype(np.int32)),
+                excluded=np.array([nm.find("left") >= 0 or nm.find("right") >= 0 for nm in names], dtype=np.uint8),
+                qvec=np.ascontiguousarray(np.array([self.images[i].qvec for i in ids], dtype=np.float64).reshape(n, 4)),
+                tvec=np.ascontiguousarray(np.array([self.images[i].tvec for i in ids], dtype=np.float64).reshape(n, 3)))
+        return self._frames
+
+    _FRAMES_ARRAYS = ("obs_offsets", "obs_point", "track_offsets", "track_image", "seen_offsets", "seen_image", "excluded", "qvec", "tvec")
+
+    def _frames_map(self):
+        """(sfd2_frames_map, what must outlive the call): device pointers once to_device() was called -- the arrays are uploaded on
+        first use and stay -- else host pointers."""
+        from . import _lib
+        fc = self.frames_csr()
+        if self.device is not None:
+            if self._dev_frames is None:
+                import torch
+                self._dev_frames = {k: torch.from_numpy(fc[k] if fc[k].size else np.zeros(1, fc[k].dtype)).to(self.device) for k in self._FRAMES_ARRAYS}
+            src, at = self._dev_frames, (lambda a: a.data_ptr())
+        else:
+            src, at = fc, (lambda a: a.ctypes.data if a.size else None)
+        m = _lib.FramesMap(*[at(src[k]) for k in self._FRAMES_ARRAYS], len(fc["obs_point"]), len(fc["track_image"]), len(fc["seen_image"]),
+                           len(fc["ids"]), len(self.point_ids), 1 if self.device is not None else 0, 0)
+        return m, src
+
+    def covisible_frames_batch(self, tasks, kind="obs", covisibility_frame=50, obs_th=0, q_th=5, ref_3Dpoints=None, device=0,
+                               global_counters=False, cap=None, lib=None):
+        """covisible_frames (kind 'obs') / covisible_frames_by_pose ('pos') for many tasks in ONE sfd2_covis_frames call.  tasks: dicts
+        with frame_id and qvec / tvec (None or absent: no pose; 'pos' needs one), which may also hold kind, covisibility_frame,
+        obs_th, q_th and ref_3Dpoints to override the arguments.  Returns per task the list of image ids the host function returns.
+
+        The library reports per task whether its row is the host's result (status 0), whether a decision lay inside a rounding band
+        (1) or whether a capacity was exceeded (2: more than cap results -- the default cap cannot overflow -- or more than
+        _lib.FRAMES_MAX_CANDIDATES connected frames); every task whose status is not 0 is decided by the host function here, and so
+        is every task with covisibility_frame 1, 2 or 3, where the reference's `<= 3 frames` fall-back appends to a list that is
+        already full: those never reach the library.  A ref_3Dpoints id the map does not hold goes to the host function as well,
+        which raises the reference's KeyError.  With the map on the device (to_device()) the CSRs are uploaded on first use and
+        stay; otherwise the call takes host arrays and uploads them itself.  lib: a stand-in for the library (tests)."""
+        from . import _lib
+        tasks = list(tasks)
+        if not tasks:
+            return []
+        fc = self.frames_csr()
+        n_images = len(fc["ids"])
+        spec, out = [], [None] * len(tasks)
+
+        def host(s):
+            if s["kind"] == "obs":
+                return self.covisible_frames(s["frame_id"], covisibility_frame=s["cf"], ref_3Dpoints=s["ref"], obs_th=s["obs_th"], pred_qvec=s["qvec"],
+                                             pred_tvec=s["tvec"])
+            return self.covisible_frames_by_pose(s["frame_id"], s["qvec"], s["tvec"], covisibility_frame=s["cf"], q_th=s["q_th"], obs_th=s["obs_th"],
+                                                 ref_3Dpoints=s["ref"])
+        live, rows_list = [], []
+        for i, t in enumerate(tasks):
+            s = dict(frame_id=t["frame_id"], kind=t.get("kind", kind), cf=int(t.get("covisibility_frame", covisibility_frame)),
+                     obs_th=t.get("obs_th", obs_th), q_th=t.get("q_th", q_th), qvec=t.get("qvec"), tvec=t.get("tvec"),
+                     ref=t.get("ref_3Dpoints", ref_3Dpoints))
+            if s["kind"] not in ("obs", "pos"):
+                raise ValueError(f"kind {s['kind']!r}: 'obs' or 'pos'")
+            spec.append(s)
+            rows = None
+            if s["ref"] is not None:
+                ids = np.asarray(s["ref"], dtype=np.int64).reshape(-1)
+                rows = self.point_rows(ids[ids != -1])
+            posed = s["qvec"] is not None and s["tvec"] is not None
+            if 1 <= s["cf"] <= 3 or s["cf"] < 0 or s["frame_id"] not in fc["index"] or (rows is not None and (rows < 0).any()) or \
+                    (s["kind"] == "pos" and not posed):
+                out[i] = host(s)
+                continue
+            live.append(i)
+            rows_list.append(rows)
+        self.frames_tasks += len(tasks)
+        self.frames_host += len(tasks) - len(live)
+        if not live:
+            return out
+        arr = (_lib.FramesTask * len(live))()
+        ref_off = np.zeros(len(live) + 1, dtype=np.int64)
+        for j, (i, rows) in enumerate(zip(live, rows_list)):
+            s, a = spec[i], arr[j]
+            a.frame, a.kind, a.covisibility_frame = fc["index"][s["frame_id"]], _lib.FRAMES_POS if s["kind"] == "pos" else _lib.FRAMES_OBS, s["cf"]
+            a.obs_th = int(min(max(math.ceil(s["obs_th"]), -2 ** 31), 2 ** 31 - 1))      # track_len >= obs_th over integers
+            a.q_th = float(s["q_th"])
+            a.has_pose = 1 if (s["qvec"] is not None and s["tvec"] is not None) else 0
+            if a.has_pose:
+                qv, tv = np.asarray(s["qvec"], dtype=np.float64).reshape(4), np.asarray(s["tvec"], dtype=np.float64).reshape(3)
+                for k in range(4):
+                    a.qvec[k] = qv[k]
+                for k in range(3):
+                    a.tvec[k] = tv[k]
+            a.use_ref = 0 if rows is None else 1
+            ref_off[j + 1] = ref_off[j] + (0 if rows is None else len(rows))
+        any_ref = any(r is not None for r in rows_list)
+        ref_pts = np.ascontiguousarray(np.concatenate([r for r in rows_list if r is not None]).astype(np.int32)) if any_ref else np.zeros(0, np.int32)
+        if cap is None:
+            cap = max(max(spec[i]["cf"], 4) if spec[i]["cf"] > 0 else min(n_images, _lib.FRAMES_MAX_CANDIDATES) for i in live)
+        cap = int(cap)
+        fmap, keep = self._frames_map()
+        idx = np.empty((len(live), max(cap, 1)), dtype=np.int32)
+        n_out = np.empty(len(live), dtype=np.int32)
+        status = np.empty(len(live), dtype=np.int32)
+        h = None
+        if lib is None:
+            ctx = _lib.default_context(self.device.index if self.device is not None else device)
+            lib, h = ctx.lib, ctx.h
+        import ctypes
+        rc = lib.sfd2_covis_frames(h, ctypes.byref(fmap), arr, len(live), ref_off.ctypes.data if any_ref else None,
+                                   ref_pts.ctypes.data if len(ref_pts) else None, cap, idx.ctypes.data, n_out.ctypes.data, status.ctypes.data,
+                                   _lib.FRAMES_FLAG_GLOBAL_COUNTERS if global_counters else 0)
+        del keep
+        if rc != 0:
+            raise RuntimeError("libsfd2hip: " + _lib.load().sfd2_last_error().decode("utf-8", "replace"))
+        ids = fc["ids"]
+        for j, i in enumerate(live):
+            if status[j] != 0:
+                self.frames_host += 1
+                out[i] = host(spec[i])
+            else:
+                out[i] = [int(v) for v in ids[idx[j, :n_out[j]]]]
+        return out
 
     # ------------------------------------------------------------------------------------------------ selections
     def _observed(self, frame_id, ref_3Dpoints):

@@ -282,7 +282,7 @@ struct sfd2_ctx {
     JpegBuf asm_in, asm_ws, asm_out;    // sfd2_assemble_2d3d (api_assemble.hip): descriptors and host inputs, per-(image, key point) work, host-bound outputs
     JpegBuf pose_in, pose_ws, pose_out; // sfd2_absolute_pose_batch / sfd2_pose_refine_batch (api_pose.hip): inputs, per-point work, results
     JpegBuf tri_in, tri_ws;             // sfd2_verify_matches_batch / sfd2_build_tracks / sfd2_triangulate_tracks (api_triangulate.hip): inputs, work and results
-    JpegBuf pairs_in, pairs_ws;         // sfd2_pairs_retrieval / _covisibility / _poses (api_pairs.hip) and sfd2_covis_clusters (api_cluster.hip, with its own copy of grow() / Carve as every api_*.hip has): uploaded inputs, partial lists / counters / slot rows and results
+    JpegBuf pairs_in, pairs_ws;         // sfd2_pairs_retrieval / _covisibility / _poses (api_pairs.hip) and sfd2_covis_clusters / sfd2_covis_frames (api_cluster.hip, api_frames.hip, with their own copies of grow() / Carve as every api_*.hip has): uploaded inputs, partial lists / counters / slot rows and results
     DevBuf img_scaled, ms_kp, ms_sc, ms_de, ms_keys, ms_sorted, ms_cnt;
     unsigned int ms_cand_seen[8] = {};
     int ms_cand_cap[8] = {};

@@ -814,3 +814,27 @@ hipError_t launch_pairs_poses(hipStream_t st, const double *qvec, const double *
 hipError_t launch_covis_clusters(hipStream_t st, const int64_t *obs_off, const int32_t *obs_point, int n_images, const int64_t *trk_off,
                                  const int32_t *trk_img, const int64_t *frame_off, const int32_t *frames, int nq, int global_slots, int blocks,
                                  uint16_t *scratch, int32_t *cluster, int32_t *n_clusters);
+
+// ------------------------------------------------------------------------------------------------ covisible frame selection (frames_kernels.hip)
+#define FRAMES_MAX_CANDIDATES 4096   // SFD2_FRAMES_MAX_CANDIDATES: slots of the sort arrays in LDS (12 bytes each)
+#define FRAMES_KIND_POS 1            // SFD2_FRAMES_POS
+struct FramesMapDev {                // sfd2_frames_map with device pointers
+    const int64_t *obs_off;
+    const int32_t *obs_point;
+    const int64_t *trk_off;
+    const int32_t *trk_img;
+    const int64_t *seen_off;
+    const int32_t *seen_img;
+    const uint8_t *excluded;
+    const double *qvec, *tvec;
+    int64_t n_obs, n_track, n_seen;
+    int n_images, n_points;
+};
+struct FramesTaskDev {               // the layout of sfd2_frames_task (api_frames.hip asserts it)
+    int32_t frame, kind, covisibility_frame, obs_th, has_pose, use_ref;
+    double q_th, qvec[4], tvec[3];
+};
+// scratch: per workgroup a row of n_images ints (the touched list) and, with global_counters, n_images zeroed words behind it (the
+// counters; the LDS path takes 4 bytes per image beside the 50 KB of sort arrays).  out: (n_out, status) per task, then idx[n_tasks][cap]
+hipError_t launch_covis_frames(hipStream_t st, const FramesMapDev &map, const FramesTaskDev *tasks, int n_tasks, const int64_t *ref_off,
+                               const int32_t *ref_points, int cap, int global_counters, int blocks, int *scratch, int32_t *out);

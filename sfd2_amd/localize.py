@@ -381,15 +381,16 @@ class Covis:
     """The settings of the covisibility stage (the `--do_covisible_opt` arguments of the reference's localiser) and what it runs
     on: map_index (sfd2_amd.covis.MapIndex), matcher and feature_file as pose_refinement_covisibility takes them.  opt_type must
     hold 'clu' (both call sites of localize_cv2.py test it), 'obs' or 'pos' for the frame selection and 'ref' for the refinement,
-    e.g. 'clurefobs' (Aachen: 50 frames, radius 30), 'clurefpos' (RobotCar: 20, 20)."""
+    e.g. 'clurefobs' (Aachen: 50 frames, radius 30), 'clurefpos' (RobotCar: 20, 20).  frames: 'host' or 'device', where a round's
+    frame selections run (pose_refinement_covisibility_batch)."""
 
     def __init__(self, map_index, matcher, feature_file, opt_type="clurefobs", covisibility_frame=50, iters=1, radius=20, obs_th=3,
-                 opt_th=12, estimator=None, refiner=None):
+                 opt_th=12, estimator=None, refiner=None, frames="host"):
         if opt_type.find("clu") < 0:
             raise ValueError(f"opt_type {opt_type!r}: the covisibility stage runs for the 'clu' types only")
         self.map_index, self.matcher, self.feature_file = map_index, matcher, feature_file
         self.opt_type, self.covisibility_frame, self.iters, self.radius = opt_type, covisibility_frame, iters, radius
-        self.obs_th, self.opt_th, self.estimator, self.refiner = obs_th, opt_th, estimator, refiner
+        self.obs_th, self.opt_th, self.estimator, self.refiner, self.frames = obs_th, opt_th, estimator, refiner, frames
 
     def refine(self, requests):
         """requests: a list of (qname, camera, db_frame_id, thresh, qvec, tvec); one batched run of the stage."""
@@ -397,7 +398,7 @@ class Covis:
             [dict(qname=q, cfg=cam, db_frame_id=f, thresh=th, qvec=qv, tvec=tv) for q, cam, f, th, qv, tv in requests],
             self.feature_file, self.map_index, self.matcher, covisibility_frame=self.covisibility_frame, iters=self.iters,
             obs_th=self.obs_th, opt_th=self.opt_th, radius=self.radius, opt_type=self.opt_type, estimator=self.estimator,
-            refiner=self.refiner)
+            refiner=self.refiner, frames=self.frames)
 
 
 class Stage1:
@@ -463,24 +464,36 @@ def _assemble(matcher, map_index, feature_file, jobs):
 
 
 def pose_refinement_covisibility_batch(tasks, feature_file, map_index, matcher, covisibility_frame=50, iters=1, obs_th=3, opt_th=12,
-                                       radius=20, opt_type="ref", estimator=None, refiner=None, ref_3Dpoints=None):
+                                       radius=20, opt_type="ref", estimator=None, refiner=None, ref_3Dpoints=None, frames="host"):
     """pose_refinement_covisibility for many queries at once: tasks are dicts with qname, cfg, db_frame_id, thresh, qvec, tvec.  One
     match / assemble call, one estimator call and one refiner call per iteration for all of them; each result equals the single
-    call's (the device calls are batch-independent)."""
+    call's (the device calls are batch-independent).  frames: 'host' selects every task's covisible frames with
+    MapIndex.covisible_frames / _by_pose, 'device' with ONE MapIndex.covisible_frames_batch call (sfd2_covis_frames) for all tasks;
+    the lists are the same."""
     estimator = estimator or _default_estimator({})
     refiner = refiner or _default_refiner
-    jobs = []
+    if frames not in ("host", "device"):
+        raise ValueError(f"frames {frames!r}: 'host' or 'device'")
     for t in tasks:
         if t["qvec"] is None or t["tvec"] is None:
             raise ValueError("pose_refinement_covisibility needs the pose to refine (qvec, tvec)")
-        if opt_type.find("obs") >= 0:
+    if tasks and opt_type.find("obs") < 0 and opt_type.find("pos") < 0:
+        raise ValueError(f"opt_type {opt_type!r} names no method for getting reference images ('obs' or 'pos')")
+    selected = None
+    if frames == "device" and tasks:
+        selected = map_index.covisible_frames_batch(
+            [dict(frame_id=t["db_frame_id"], qvec=t["qvec"], tvec=t["tvec"]) for t in tasks], kind="obs" if opt_type.find("obs") >= 0 else "pos",
+            covisibility_frame=covisibility_frame, obs_th=obs_th, q_th=10, ref_3Dpoints=ref_3Dpoints)
+    jobs = []
+    for i, t in enumerate(tasks):
+        if selected is not None:
+            db_ids = selected[i]
+        elif opt_type.find("obs") >= 0:
             db_ids = map_index.covisible_frames(t["db_frame_id"], covisibility_frame=covisibility_frame, ref_3Dpoints=ref_3Dpoints,
                                                 obs_th=obs_th, pred_qvec=t["qvec"], pred_tvec=t["tvec"])
-        elif opt_type.find("pos") >= 0:
+        else:
             db_ids = map_index.covisible_frames_by_pose(t["db_frame_id"], t["qvec"], t["tvec"], covisibility_frame=covisibility_frame,
                                                         ref_3Dpoints=ref_3Dpoints, q_th=10, t_th=10, obs_th=obs_th)
-        else:
-            raise ValueError(f"opt_type {opt_type!r} names no method for getting reference images ('obs' or 'pos')")
         f = feature_file[t["qname"]]
         jobs.append(dict(qname=t["qname"], kpq=f["keypoints"].__array__(), score_q=f["scores"].__array__(), db_ids=db_ids, obs_th=obs_th,
                          gate=(t["qvec"], t["tvec"], t["cfg"], radius)))

@@ -1,6 +1,6 @@
 """it_loc/localizer.py on the device: reads a query list with intrinsics, a retrieval file, a COLMAP model and a feature store, and
 writes the poses a user submits to the benchmark.  `python -m sfd2_amd.localizer` takes the reference's arguments (names and
-defaults of it_loc/localizer.py:394-427) plus --device and --stage1, and writes the reference's four files under the reference's
+defaults of it_loc/localizer.py:394-427) plus --device, --stage1 and --frames, and writes the reference's four files under the reference's
 names: <stem>.txt (name qvec tvec), <stem>.txt.failed, <stem>.log (qname dbname num_inliers order) and <stem>_full.log, where
 <stem> = save_root/{features}_{matcher}_{init_type}_{ransac_thresh:.0f}_{inlier_thresh:d} + 'all' ('vis' and a slice{N}_ prefix
 for --dataset ecmu) + _o{obs}op{frames}{opt_type}th{opt}r{radius}i{iters} with --do_covisible_opt.
@@ -8,7 +8,9 @@ for --dataset ecmu) + _o{obs}op{frames}{opt_type}th{opt}r{radius}i{iters} with -
 The steps: retrieved names -> image ids (a name the model does not hold is warned about and dropped); --init_type sng makes one
 cluster per retrieved image, clu clusters them by covisibility (MapIndex.clusters: ONE sfd2_covis_clusters call for all queries);
 localize.localize_queries over the queries in rounds of ROUND; --stage1 device matches and assembles the clusters on the device
-(localize.Stage1), host is the loop of match_cluster_2D on matches brought to the host; --do_covisible_opt adds localize.Covis.
+(localize.Stage1), host is the loop of match_cluster_2D on matches brought to the host; --do_covisible_opt adds localize.Covis,
+whose frame selections --frames device makes in one sfd2_covis_frames call per round over the map resident on the device (host: the
+Python functions; a callable matcher, which leaves the map on the host, keeps host).  The pose files of the two are identical.
 
 Deviations from the reference:
   * a query absent from the retrieval file, or none of whose retrieved images is in the model, is skipped with a warning, listed in
@@ -34,6 +36,7 @@ from . import colmap_io, feature_io, parsers
 from .covis import MapIndex, compute_pose_error
 
 ROUND = 32                      # queries per localize_queries call: bounds the matches, jobs and outputs alive at once
+FRAMES_DEFAULT = 'device'       # where --do_covisible_opt selects its frames: faster in every measured run
 ERROR_THS = ((0.25, 2), (0.5, 5), (5, 10))       # (metres, degrees) of the three success counters
 DATASETS_LAST_PART = ('aachen', 'aachen_v1.1')
 
@@ -65,6 +68,7 @@ def make_parser():
     parser.add_argument('--slice', type=int, default=2)
     parser.add_argument('--device', type=int, default=0)
     parser.add_argument('--stage1', type=str, default='device', choices=['device', 'host'])
+    parser.add_argument('--frames', type=str, default=FRAMES_DEFAULT, choices=['device', 'host'])
     return parser
 
 
@@ -186,8 +190,14 @@ def run(args, estimator=None, refiner=None, matcher=None, clusterer=None, featur
         stage1 = localize.Stage1(mi, matcher, feature_file)
         covis = None
         if args.do_covisible_opt:
+            frames = getattr(args, 'frames', FRAMES_DEFAULT)
+            if frames == 'device' and store_matcher is None:
+                frames = 'host'                                    # a callable matcher: nothing puts the map on the device
+            if frames == 'device' and mi.device is None:
+                mi.to_device(args.device)
             covis = localize.Covis(mi, matcher, feature_file, opt_type=args.opt_type, covisibility_frame=args.covisibility_frame, iters=args.iters,
-                                   radius=args.radius, obs_th=args.obs_thresh, opt_th=args.opt_thresh, estimator=estimator, refiner=refiner)
+                                   radius=args.radius, obs_th=args.obs_thresh, opt_th=args.opt_thresh, estimator=estimator, refiner=refiner,
+                                   frames=frames)
         poses, all_logs, summary = {}, [], []
         counts = dict(failed=0, total=0, top1=0, hits=[0] * len(ERROR_THS), with_gt=0)
         for r0 in range(0, len(todo), ROUND):

@@ -4,7 +4,11 @@ retrieved database images of about --keypoints key points per query (default 50 
   * queries/s of run() for --stage1 host (the earlier stage 1: matches to the host, match_cluster_2D per cluster) and device, for
     --init_type sng and clu, with and without --do_covisible_opt; every combination --runs times, alternating; a --stage1 device window is
     --device-repeat calls of the command, so that it lasts seconds;
-  * the share of a covisibility run spent in MapIndex.covisible_frames (still host code);
+  * the two --do_covisible_opt rows with --stage1 device also with --frames device (key suffix _frames): the frame selection as one
+    sfd2_covis_frames call per round; per run the share of the time spent in the host functions MapIndex.covisible_frames / _by_pose
+    and the share of the selections the host functions decided (the fallbacks of the status protocol);
+  * sfd2_covis_frames alone: 1 000 obs tasks, 50 frames each, in one call on the map of --big-images images resident on the device,
+    against MapIndex.covisible_frames per task;
   * sfd2_covis_clusters (MapIndex.clusters, one call, upload included) against a plain Python search, on the scene's map and on a
     map of --big-images images, there with the image table in LDS and in global scratch.
 Wall clock around calls that end in a device synchronise.  Writes one JSON document (default profiles/localizer_bench.json).
@@ -113,30 +117,48 @@ def main():
         finally:
             spent["t"] += time.perf_counter() - t0
     covis.MapIndex.covisible_frames = timed_frames
+    inner_batch = covis.MapIndex.covisible_frames_batch
+    routed = {"tasks": 0, "host": 0}
+
+    def counted_batch(self, *args, **kw):
+        before = (self.frames_tasks, self.frames_host)
+        try:
+            return inner_batch(self, *args, **kw)
+        finally:
+            routed["tasks"] += self.frames_tasks - before[0]
+            routed["host"] += self.frames_host - before[1]
+    covis.MapIndex.covisible_frames_batch = counted_batch
     with tempfile.TemporaryDirectory() as root:
         base = write_files(root, cam, store, images, points3D, queries)
-        combos = [(s1, it, cv) for it in ("sng", "clu") for cv in (False, True) for s1 in ("host", "device")]
+        combos = [(s1, it, cv, fr) for it in ("sng", "clu") for cv in (False, True) for s1 in ("host", "device")
+                  for fr in (("host", "device") if cv and s1 == "device" else ("host",))]
         outputs = {}
         for rep in range(a.runs + 1):                              # repetition 0 warms up: code objects, resident sets, buffers
-            for s1, it, cv in combos:
-                argv = base + ["--stage1", s1, "--init_type", it] + (["--do_covisible_opt"] if cv else [])
+            for s1, it, cv, fr in combos:
+                argv = base + ["--stage1", s1, "--init_type", it, "--frames", fr] + (["--do_covisible_opt"] if cv else [])
                 spent["t"] = 0.0
+                routed["tasks"] = routed["host"] = 0
                 inner_runs = a.device_repeat if s1 == "device" else 1          # a timed window of seconds, not of a fraction of one
                 t0 = time.perf_counter()
                 with contextlib.redirect_stdout(io.StringIO()):
                     for _ in range(inner_runs):
                         stem = localizer.main(argv)
                 dt = (time.perf_counter() - t0) / inner_runs
-                key = f"{it}_{'covis' if cv else 'plain'}_{s1}"
+                key = f"{it}_{'covis' if cv else 'plain'}_{s1}" + ("_frames" if fr == "device" else "")
+                print(f"rep {rep} {key}: {dt:.2f} s per run", file=sys.stderr, flush=True)
                 txt = open(stem + ".txt").read()
-                assert outputs.setdefault((it, cv), txt) == txt, f"{key}: the pose file differs between --stage1 host and device"
+                assert outputs.setdefault((it, cv), txt) == txt, f"{key}: the pose file differs between the --stage1 / --frames settings"
                 if rep:
                     e = res["run"].setdefault(key, {"queries_per_s": [], "covisible_frames_share": [], "window_s": []})
                     e["window_s"].append(dt * inner_runs)
                     e["queries_per_s"].append(len(queries) / dt)
                     e["covisible_frames_share"].append(spent["t"] / (dt * inner_runs) if cv else 0.0)
+                    if fr == "device":
+                        e.setdefault("host_fallback_share", []).append(routed["host"] / max(routed["tasks"], 1))
+                        e["selections_per_run"] = routed["tasks"] // inner_runs
                     e["localised"] = len(txt.splitlines()) - len(open(stem + ".txt.failed").read().splitlines())
     covis.MapIndex.covisible_frames = inner
+    covis.MapIndex.covisible_frames_batch = inner_batch
     # ---- the clustering alone
     rs = np.random.RandomState(5)
     clu = {}
@@ -166,6 +188,28 @@ def main():
         e["clusters_per_query"] = float(np.mean([len(g) for g in got]))
         clu[label] = e
     res["covis_clusters"] = clu
+    # ---- the frame selection alone: the big map resident on the device, 1 000 obs tasks of 50 frames in one call
+    print("covis_frames", file=sys.stderr, flush=True)
+    mi = mi.to_device(0)                                           # the last map of the loop above: big_map
+    ids = np.array(list(mi.images))
+    tasks = [dict(frame_id=int(f)) for f in ids[rs.randint(0, len(ids), 1000)]]
+    e = {"n_images": len(ids), "tasks": len(tasks), "covisibility_frame": 50, "call_ms": []}
+    for rep in range(a.runs + 1):
+        before = mi.frames_host
+        t0 = time.perf_counter()
+        got = mi.covisible_frames_batch(tasks, kind="obs", covisibility_frame=50, obs_th=3)
+        if rep:
+            e["call_ms"].append((time.perf_counter() - t0) * 1e3)
+        e["host_fallbacks"] = mi.frames_host - before
+    n_py = 20
+    t0 = time.perf_counter()
+    want = [mi.covisible_frames(t["frame_id"], covisibility_frame=50, obs_th=3) for t in tasks[:n_py]]
+    e["host_ms_per_task"] = (time.perf_counter() - t0) * 1e3 / n_py
+    e["device_ms_per_task"] = [v / len(tasks) for v in e["call_ms"]]
+    assert got[:n_py] == [[int(v) for v in w] for w in want]
+    e["frames_per_task"] = float(np.mean([len(g) for g in got]))
+    res["covis_frames"] = e
+    res["frames_default"] = localizer.FRAMES_DEFAULT
     res["lds_table_bound_images"] = _lib.CLUSTER_LDS_IMAGES
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as fh:
