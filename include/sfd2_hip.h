@@ -645,7 +645,7 @@ typedef struct {
  * pair_views[2p + 1] with matches[match_offsets[p] .. match_offsets[p + 1])[2] = (key point in the first, key point in the second),
  * host, IN/OUT.  A match survives when its point-to-epipolar-line distance in normalised coordinates is <= max_error_px / mean focal
  * in both images; a pair with fewer than min_num_inliers survivors loses all.  Rejected entries become (-1, -1); entries that come
- * in negative stay rejected.  pair_counts[p]: the survivors before the min_num_inliers rule; pair_status[p]: 0 or 1 = an index
+ * in negative stay rejected, and a pair of a view with itself loses all.  pair_counts[p]: the survivors before the min_num_inliers rule; pair_status[p]: 0 or 1 = an index
  * beyond the image's key points (the call then returns -1).  flags: 0. */
 int sfd2_verify_matches_batch(sfd2_ctx *ctx, const sfd2_tri_view *views, int n_views, const int64_t *kp_offsets, const float *keypoints,
                               const int32_t *pair_views, const int64_t *match_offsets, int n_pairs, int32_t *matches,
@@ -670,7 +670,8 @@ typedef struct {
  * observations of one view must be consecutive, as sfd2_build_tracks' ascending nodes are) and obs_xy (key point as stored, the call
  * adds +0.5); track_labels[t] keys the random draws.  Up to SFD2_TRI_MAX_POINTS points per track, slot s = t * SFD2_TRI_MAX_POINTS +
  * pass: xyz[s][3], error[s] (mean reprojection error, pixels), n_obs[s] (0: no point); obs_point[o]: the pass that took observation
- * o, or -1; track_status[t]: 0, 1 = fewer than two observations, 2 = a refinement left the finite numbers.  flags: 0. */
+ * o, or -1; track_status[t]: 0, 1 = fewer than two observations, 2 = a refinement left the finite numbers.  A track that returns to
+ * a view after leaving it is refused (-1, the error names the observation); the views of a track may come in any order.  flags: 0. */
 int sfd2_triangulate_tracks(sfd2_ctx *ctx, const sfd2_tri_view *views, int n_views, const int64_t *track_offsets, const int64_t *track_labels,
                             int n_tracks, const int32_t *obs_view, const float *obs_xy, const sfd2_tri_conf *conf, double *xyz, double *error,
                             int32_t *n_obs, int8_t *obs_point, int32_t *track_status, int flags);

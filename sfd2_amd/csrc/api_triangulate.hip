@@ -119,6 +119,8 @@ extern "C" int sfd2_verify_matches_batch(sfd2_ctx *c, const sfd2_tri_view *views
             d.E[3 + b] = t[2] * R[b] - t[0] * R[6 + b];
             d.E[6 + b] = t[0] * R[3 + b] - t[1] * R[b];
         }
+        if (i == j) memset(d.E, 0, sizeof(d.E));             // an image with itself: E = 0 (every distance NaN, all rejected), not the
+                                                             // rounding residue of R R^T - 1
         d.thr_i = max_error_px / mf[i];
         d.thr_j = max_error_px / mf[j];
         d.moff = match_offsets[p];
@@ -274,6 +276,17 @@ extern "C" int sfd2_triangulate_tracks(sfd2_ctx *c, const sfd2_tri_view *views, 
     for (int64_t o = 0; o < O; ++o)
         if (obs_view[o] < 0 || obs_view[o] >= n_views) return fail(F + "observation " + std::to_string(o) + ": view index out of range");
     if (!all_finite_f(obs_xy, 2 * O)) return fail(F + "non-finite observations");
+    {   // the one-per-image rule looks at neighbours only: a track must not come back to a view it has left
+        std::vector<int32_t> run_of(n_views, -1);            // the last track that opened a run of this view
+        for (int t = 0; t < n_tracks; ++t)
+            for (int64_t o = track_offsets[t]; o < track_offsets[t + 1]; ++o) {
+                if (o > track_offsets[t] && obs_view[o] == obs_view[o - 1]) continue;
+                if (run_of[obs_view[o]] == t)
+                    return fail(F + "observation " + std::to_string(o) + ": its track returns to view " + std::to_string(obs_view[o]) +
+                                " after leaving it (the observations of one view must be consecutive)");
+                run_of[obs_view[o]] = t;
+            }
+    }
     std::vector<TriViewDev> vd;
     std::vector<double> mf;
     std::string why;

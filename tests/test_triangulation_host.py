@@ -1,6 +1,7 @@
 """The SfM map, the parts that need no GPU: sfd2_amd.colmap_io against a model the reference's read_write_model.py wrote
 (tests/golden/tri_model, tests/golden/gen_tri_goldens.py), no CPU fallback in sfd2_amd.triangulation, the numpy restatement of
-tests/tri_ref.py against the scene's ground truth (it is the yardstick of tests/test_gpu_triangulation.py), and the new kernels'
+tests/tri_ref.py against the scene's ground truth (it is the yardstick of tests/test_gpu_triangulation.py), the designed inputs of
+tests/test_gpu_triangulation_edges.py held to their band caps and class counts by the restatement alone, and the new kernels'
 resource metadata and instruction vocabulary."""
 import functools
 import os
@@ -178,6 +179,120 @@ def test_restatement_map_supports_the_localisation_bound():
         rot, pos = np.degrees(pr.rot_angle(qv, q["qvec"])), np.linalg.norm(pr.centre(qv, tv) - pr.centre(q["qvec"], q["tvec"])) / depth
         print(f"query: {len(X)} correspondences, rotation {rot:.4f} deg, centre {100 * pos:.4f} % of the median depth")
         assert rot <= 0.05 and pos <= 0.0025                 # half the bound the GPU test asserts
+
+
+# ---------------------------------------------------------------------------------------------------------------- designed inputs
+@pytest.mark.parametrize("name", sorted(tr.LONG_SCENES))
+def test_long_track_scenes_meet_their_classes(name):
+    """The committed seeds keep the restatement inside the band cap and give the GPU test its classes of unbanded tracks."""
+    sc, tri = tr.track_scene(name), tr.long_ref(name)
+    got = tr.track_classes(sc, tri)
+    print(f"{name}: {got}, lengths {np.diff(sc['t_off']).tolist()}, points per pass {(tri['n_obs'] > 0).sum(0).tolist()}")
+    assert got["banded"] <= tr.LONG_BAND_CAP * got["tracks"]
+    for k, least in tr.LONG_CLASSES[name].items():
+        assert got[k] >= least, (k, got[k])
+    assert (np.diff(sc["t_nodes"]) > 0)[np.setdiff1d(np.arange(len(sc["t_nodes"]) - 1), sc["t_off"][1:-1] - 1)].all()   # nodes ascend inside a track
+    # an outlier is an outlier: no point of the restatement holds one
+    assert (tri["obs_point"][sc["truth"] < 0] == -1).all()
+
+
+def test_rule_tracks_take_their_designed_paths(monkeypatch):
+    """The hand-built tracks of the one-per-image rule: nothing banded, and the restatement does with them what they were built for."""
+    made = []
+    refine = tr._Track.refine
+    monkeypatch.setattr(tr._Track, "refine", lambda self, p, X, iters=200: (made.append((self.n, p)), refine(self, p, X, iters))[1])
+    tr.rule_ref.cache_clear()
+    rt, plain, off, nodes, tri, loff, lnodes, late = tr.rule_ref()
+    tr.rule_ref.cache_clear()                                 # (computed under the patch: not for the other tests)
+    assert not tri["banded"].any() and not late["banded"].any()
+    for name in ("dup_mid", "dup_first"):
+        t = plain.index(name)
+        seg = tri["obs_point"][off[t]:off[t + 1]]
+        lower, higher = rt["at"][name]["lower"], rt["at"][name]["higher"]
+        a, b = rt["t_nodes"][rt["t_off"][rt["names"].index(name)]:][[lower, higher]]
+        assert rt["L"].node_view[a] == rt["L"].node_view[b] and np.concatenate(rt["L"].kp)[a].tobytes() == np.concatenate(rt["L"].kp)[b].tobytes()
+        assert seg[lower] == 0 and seg[higher] == -1 and (np.delete(seg, higher) == 0).all() and list(tri["n_obs"][t]) == [9, 0, 0, 0]
+    for name in ("narrow", "narrow_far", "narrow_far_long"):
+        t = plain.index(name)
+        assert (tri["n_obs"][t] == 0).all() and (tri["obs_point"][off[t]:off[t + 1]] == -1).all()
+    # 'narrow' never makes a point; 'narrow_far' and 'narrow_far_long' make one (of the five observations at the end) and drop it
+    assert (4, 0) not in made and (5, 0) in made and made.count((75, 0)) == 1
+    assert tri["n_obs"][plain.index("plain"), 0] == 9
+    t = plain.index("plain_long")                             # its point's observations all lie past index 64
+    assert tri["n_obs"][t, 0] == 9 and (tri["obs_point"][off[t]:off[t + 1]][:70] == -1).all() and (tri["obs_point"][off[t] + 70:off[t + 1]] == 0).all()
+    at, seg = rt["at"]["late"], late["obs_point"]
+    assert seg[at["a_near"]] == 0 and seg[at["a_far"]] != 0 and seg[at["b_near"]] == 0 and seg[at["b_far"]] != 0
+    assert seg[at["c_held"]] == 0 and seg[at["c_other"]] != 0 and late["n_obs"][0, 0] == 9
+    # b joins in the completion only: with a filter bound that leaves it out the point has 8 observations
+    only = tr.triangulate_ref(rt["L"], loff, lnodes, create_max_angle_error=tr.RULE_LATE["create_max_angle_error"], filter_max_reproj_error=1.2)
+    assert only["n_obs"][0, 0] == 8 and only["obs_point"][at["b_near"]] == -1
+
+
+@pytest.mark.parametrize("g", tr.GRID, ids=lambda g: "-".join(str(v) for v in g))
+def test_option_grid_stays_inside_the_band_cap(g):
+    tri = tr.grid_ref(g)
+    print(f"grid {g}: {int(tri['banded'].sum())} of {len(tri['banded'])} tracks banded, points per pass {(tri['n_obs'] > 0).sum(0).tolist()}")
+    assert tri["banded"].mean() <= tr.GRID_BAND_CAP
+    assert (tri["n_obs"][:, 0] > 0).sum() >= 6
+
+
+@pytest.mark.parametrize("seed", tr.SEEDS)
+def test_seed_and_label_cases_stay_inside_the_band_cap(seed):
+    sc, off, nodes = tr.short_tracks()
+    assert ((np.diff(off) >= 12) & (np.diff(off) <= 64)).sum() >= 6
+    for label in tr.LABELS:
+        tri = tr.seed_ref(seed, label)
+        print(f"seed {seed} label {label}: {int(tri['banded'].sum())} of {len(tri['banded'])} tracks banded")
+        assert tri["banded"].mean() <= tr.GRID_BAND_CAP, label
+
+
+def test_seed_and_label_cases_depend_on_all_64_bits():
+    """The committed values make the draws matter: restated with the seed or the labels cut to 32 bits, unbanded tracks take other
+    observations, so a device that truncates either cannot pass tests/test_gpu_triangulation_edges.py."""
+    sc, off, nodes = tr.short_tracks()
+    for seed, label, kw in ((1, tr.LABELS[2], dict(label_mask=0xFFFFFFFF)), (tr.SEEDS[2], tr.LABELS[2], dict(label_mask=0xFFFFFFFF)),
+                            (tr.SEEDS[2], tr.LABELS[0], dict(seed_mask=0xFFFFFFFF)), (tr.SEEDS[3], tr.LABELS[1], dict(seed_mask=0xFFFFFFFF))):
+        tri, cut = tr.seed_ref(seed, label), tr.seed_ref(seed, label, **kw)
+        clear = np.repeat(~tri["banded"], np.diff(off))
+        changed = int((cut["obs_point"] != tri["obs_point"])[clear].sum())
+        print(f"seed {seed} label {label} {kw}: {changed} observations of unbanded tracks change")
+        assert changed > 0
+
+
+def test_seam_pairs_are_what_they_claim():
+    sp = tr.seam_scene()
+    L = sp["L"]
+    m, off, counts, banded, _ = tr.verify_ref(L, sp["pair_matches"], min_num_inliers=0)
+    assert not banded.any()
+    assert sorted(int(n) for n in np.diff(off)[:8]) == [0, 1, 255, 256, 257, 512, 513, 700]
+    for p, (name, (i, j, rows), truth) in enumerate(zip(sp["names"], sp["pair_matches"], sp["truth"])):
+        kept = m[off[p]:off[p + 1], 0] >= 0
+        assert np.array_equal(kept, truth) and counts[p] == truth.sum(), name
+        if len(rows) > 1 and name.startswith("n"):
+            assert not truth[[r for r in (0, 255, 256, 511, 512, len(rows) - 1) if r < len(rows)]].any(), name
+    by = dict(zip(sp["names"], range(len(sp["names"]))))
+    assert not sp["truth"][by["self"]].any() and sp["pair_matches"][by["self"]][0] == sp["pair_matches"][by["self"]][1]
+    i, j, _ = sp["pair_matches"][by["reversed_last_block"]]
+    assert i > j and sp["truth"][by["reversed_last_block"]][:512].all() and not sp["truth"][by["reversed_last_block"]][512:].all()
+    for name, n in (("exactly_min", tr.SEAM_MIN_INLIERS), ("one_short", tr.SEAM_MIN_INLIERS - 1)):
+        t = sp["truth"][by[name]]
+        assert t.sum() == n and t[:256].any() and t[256:512].any() and t[512:].any()
+    dropped = tr.verify_ref(L, sp["pair_matches"], min_num_inliers=tr.SEAM_MIN_INLIERS)
+    assert (dropped[0][off[by["exactly_min"]]:off[by["exactly_min"] + 1], 0] >= 0).sum() == tr.SEAM_MIN_INLIERS
+    assert (dropped[0][off[by["one_short"]]:off[by["one_short"] + 1]] == -1).all() and np.array_equal(dropped[2], counts)
+    # empty images at the front, in the middle and at the end; their non-empty neighbours are matched at key points 0 and n - 1
+    assert [len(sp["keypoints"][i]) for i in tr.SEAM_EMPTY] == [0, 0, 0] and tr.SEAM_EMPTY == (min(sp["images"]), 6, max(sp["images"]))
+    used = {i: set() for i in sp["images"]}
+    for i, j, rows in sp["pair_matches"]:
+        used[i] |= set(rows[:, 0].tolist())
+        used[j] |= set(rows[:, 1].tolist())
+    for i in (2, 5, 7, 9):
+        assert {0, len(sp["keypoints"][i]) - 1} <= used[i], i
+    assert {sp["cameras"][sp["images"][i].camera_id]["model"] for i in sp["images"] if len(sp["keypoints"][i])} == set(tr.MODELS)
+    i, j, rows = sp["pair_matches"][by["corners"]]
+    corner = {(0.0, 0.0), (639.0, 0.0), (0.0, 479.0), (639.0, 479.0)}
+    assert corner <= {tuple(k) for k in sp["keypoints"][i][rows[:, 0]].tolist()} and corner <= {tuple(k) for k in sp["keypoints"][j][rows[:, 1]].tolist()}
+    assert {sp["cameras"][sp["images"][v].camera_id]["model"] for v in (i, j)} == {"SIMPLE_RADIAL", "OPENCV"}
 
 
 def test_tri_kernels_compile_without_private_segment_or_spills(tmp_path):

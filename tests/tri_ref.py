@@ -6,6 +6,8 @@ The restatement also says which of its decisions were close: a comparison whose 
 is `banded`.  For the verification that is per match; for the triangulation a track is banded when a banded comparison could have
 changed its result (an observation's error against a threshold for the winning pose, a hypothesis whose support could reach the
 winner's once its banded comparisons flip, a triangulation angle at its bound)."""
+import functools
+
 import numpy as np
 
 import pose_ref as pr
@@ -143,6 +145,275 @@ def make_scene(seed=0, n_images=12, n_points=900, n_clutter=100, window=4, p_vis
             "match_truth": match_truth, "X": X, "n_points": n_points, "joiners": joiners, "weak_pairs": sorted(weak), "queries": queries}
 
 
+# ------------------------------------------------------------------------------------------------------------------ designed tracks
+ARC_TARGET = np.array([0.0, 0.0, 10.0])
+# (true points merged into the track, every stride-th image): 36 images give 12 to 181 observations per track
+TRACKS_36 = ((1, 1), (1, 1), (1, 2), (1, 3), (2, 2), (3, 2), (2, 3), (2, 1), (3, 1), (4, 1), (5, 1), (4, 1), (5, 1))
+TRACKS_80 = ((1, 1), (1, 1), (1, 1), (2, 1), (2, 1), (2, 1))
+
+
+def arc_cameras(n_images, radius=10.0, arc_deg=90.0):
+    """Cameras of the four models in turn on an arc in the x-z plane around ARC_TARGET (`radius` units away), all looking at it."""
+    cameras = {m + 1: Cam(id=m + 1, **pr.camera(MODELS[m])) for m in range(4)}
+    images = {}
+    for i in range(n_images):
+        th = np.radians(arc_deg) * (i / max(n_images - 1, 1) - 0.5)
+        c = ARC_TARGET + radius * np.array([np.sin(th), 0.03 * np.sin(1.3 * i), -np.cos(th)])
+        q, t = _look_at(c, ARC_TARGET.copy(), 0.04 * np.sin(0.8 * i))
+        images[i + 1] = Img(i + 1, q, t, i % 4 + 1, f"arc/img{i:03d}.jpg")
+    return cameras, images
+
+
+def make_track_scene(seed=0, n_images=36, tracks=TRACKS_36, noise_px=0.15, n_outliers=3, outlier_px=60.0, gap=0.9):
+    """Tracks for sfd2_triangulate_tracks directly, without verification.  Track t merges k true points and is seen in every
+    stride-th image of arc_cameras(n_images), so it holds k observations per image: the points sit `gap` units apart in y, across the
+    camera motion (more than 2 degrees apart from every view, so no observation of one supports another); every observation is the
+    projection plus noise_px of Gaussian noise, and n_outliers more per track lie further than outlier_px from every true projection
+    of their track in their image.  The key-point tables hold the observations image by image, so a track's nodes ascend and its
+    label is its first node, as sfd2_build_tracks gives them.
+    Returns {'cameras', 'images', 'keypoints', 'L', 't_off', 't_nodes', 'k' [T], 'X' (per track [k, 3]), 'truth' [O]: the true point
+    of an observation or -1}."""
+    rs = np.random.RandomState(seed)
+    cameras, images = arc_cameras(n_images)
+    ids = sorted(images)
+    per_image = {i: [] for i in ids}                          # (track, true point or -1, pixel)
+    Xs = []
+    for t, (k, stride) in enumerate(tracks):
+        base = ARC_TARGET + np.array([rs.uniform(-1.2, 1.2), rs.uniform(-0.5, 0.5), rs.uniform(-1.2, 1.2)])
+        X = np.stack([base + np.array([rs.uniform(-0.3, 0.3), gap * (j - 0.5 * (k - 1)), rs.uniform(-0.3, 0.3)]) for j in range(k)])
+        Xs.append(X)
+        seen = ids[(t % stride)::stride]
+        proj = {}
+        for i in seen:
+            px, z = pr.project(cameras[images[i].camera_id], images[i].qvec, images[i].tvec, X)
+            assert (z > 0).all() and (px > 8).all() and (px[:, 0] < 632).all() and (px[:, 1] < 472).all(), (t, i)
+            proj[i] = px
+            for j in range(k):
+                per_image[i].append((t, j, px[j] + noise_px * rs.standard_normal(2)))
+        for _ in range(n_outliers):
+            i = seen[int(rs.randint(len(seen)))]
+            while True:
+                p = np.array([rs.uniform(8, 632), rs.uniform(8, 472)])
+                if np.linalg.norm(proj[i] - p, axis=1).min() > outlier_px:
+                    break
+            rows = [r for r, e in enumerate(per_image[i]) if e[0] == t]
+            per_image[i].insert(rows[int(rs.randint(len(rows)))], (t, -1, p))   # somewhere inside the track's run of that image
+    keypoints = {i: (np.array([e[2] for e in per_image[i]]).reshape(-1, 2) - 0.5).astype(np.float32) for i in ids}
+    L = Layout(cameras, images, keypoints)
+    nodes = [[] for _ in tracks]
+    truth = [[] for _ in tracks]
+    for v, i in enumerate(ids):
+        for r, (t, j, _) in enumerate(per_image[i]):
+            nodes[t].append(int(L.off[v]) + r)
+            truth[t].append(j)
+    t_off = np.concatenate([[0], np.cumsum([len(n) for n in nodes])]).astype(np.int64)
+    return {"cameras": cameras, "images": images, "keypoints": keypoints, "L": L, "t_off": t_off, "t_nodes": np.concatenate(nodes).astype(np.int32),
+            "k": np.array([k for k, _ in tracks]), "X": Xs, "truth": np.concatenate(truth)}
+
+
+def sub_tracks(t_off, t_nodes, which):
+    """(offsets, nodes) of the tracks `which` alone, in that order."""
+    seg = [np.asarray(t_nodes[t_off[t]:t_off[t + 1]]) for t in which]
+    return np.concatenate([[0], np.cumsum([len(s) for s in seg])]).astype(np.int64), np.concatenate(seg) if seg else np.zeros(0, np.int32)
+
+
+def track_classes(sc, tri):
+    """The classes the long-track tests need, counted over the unbanded tracks of a make_track_scene: longer than 64 and than 128
+    observations, a point in pass 3, k = 5 with four points and every observation of the fifth true point left free, 12 to 64
+    observations."""
+    t_off, k = sc["t_off"], sc["k"]
+    n = np.diff(t_off)
+    clear = ~tri["banded"]
+    fifth = np.zeros(len(n), bool)
+    for t in np.nonzero(k == 5)[0]:
+        truth, point = sc["truth"][t_off[t]:t_off[t + 1]], tri["obs_point"][t_off[t]:t_off[t + 1]]
+        fifth[t] = (tri["n_obs"][t] > 0).all() and any((point[truth == j] == -1).all() for j in range(5))
+    return {"tracks": len(n), "banded": int((~clear).sum()), "gt64": int((clear & (n > 64)).sum()), "gt128": int((clear & (n > 128)).sum()),
+            "pass3": int((clear & (tri["n_obs"][:, MAX_POINTS - 1] > 0)).sum()), "k5_fifth_free": int((clear & fifth).sum()),
+            "n12to64": int((clear & (n >= 12) & (n <= 64)).sum())}
+
+
+def layout_from_tracks(cameras, images, tracks):
+    """tracks: per track the observations [(image id, pixel [2] in the COLMAP frame)] in the order they are to be passed.  The
+    key-point table of an image holds its observations track by track.  Returns (keypoints, Layout, t_off, t_nodes)."""
+    ids = sorted(images)
+    per_image = {i: [] for i in ids}
+    where = []
+    for obs in tracks:
+        where.append([])
+        for i, p in obs:
+            where[-1].append((i, len(per_image[i])))
+            per_image[i].append(np.asarray(p, float))
+    keypoints = {i: (np.array(per_image[i]).reshape(-1, 2) - 0.5).astype(np.float32) for i in ids}
+    L = Layout(cameras, images, keypoints)
+    nodes = [[int(L.off[L.index[i]]) + r for i, r in w] for w in where]
+    t_off = np.concatenate([[0], np.cumsum([len(n) for n in nodes])]).astype(np.int64)
+    return keypoints, L, t_off, np.concatenate(nodes).astype(np.int32)
+
+
+RULE_VIEWS = (3, 7, 11, 15, 19, 23, 27, 31, 35)
+RULE_LONG_LABELS = {"narrow_far_long": 1, "plain_long": 1}   # labels under which one of the track's 64 draws is a pair that makes its point
+RULE_LATE = dict(create_max_angle_error=0.1, filter_max_reproj_error=4.0)   # 0.1 deg is 1.4 px at these focal lengths
+
+
+def make_rule_tracks(n_images=36):
+    """Hand-built tracks on the views of make_track_scene(n_images=36) for the one-per-image rule; 0.05 px of noise except where designed.
+      'dup_mid', 'dup_first'  one true point in RULE_VIEWS, the observation of view 19 / view 3 listed twice, bit for bit;
+      'plain'                 one true point, nothing special (the unaffected neighbour);
+      'narrow'                a point 100 units away seen by views 17-20: every pair of views subtends less than 1 degree;
+      'narrow_far'            the same plus view 33 with an observation 14 px off: the pair with it is a valid hypothesis that all
+                              five support, the refinement then puts it 11 px out, the filter frees it, and the four left subtend
+                              less than min_tri_angle, so the point is dropped after it was made;
+      'narrow_far_long'       'narrow_far' behind 70 stray key points of view 1, so the point's observations lie beyond index 64 and its
+                              hypothesis is drawn (RULE_LONG_LABELS picks a draw that finds it);
+      'plain_long'            a true point in RULE_VIEWS behind the same 70 stray key points: every pair of views that gives the point its
+                              triangulation angle lies beyond index 64;
+      'late'                  (for RULE_LATE) view 11 holds two observations 0.9 and 0.3 px off (both support; the closer one, the
+                              second, must be taken), view 23 two at -3.2 and -2.4 px (outside the creation bound, inside the filter's:
+                              the view joins in the completion only, with the second), view 31 an exact one and one 2.5 px off (the
+                              point holds the view already: nothing of it joins in the completion).
+    Returns {'cameras', 'images', 'keypoints', 'L', 't_off', 't_nodes', 'names', 'at': name -> {role: observation index in the track}}."""
+    rs = np.random.RandomState(5)
+    cameras, images = arc_cameras(n_images)
+
+    def seen(X, views, dy=None):
+        out = []
+        for i in views:
+            px, z = pr.project(cameras[images[i].camera_id], images[i].qvec, images[i].tvec, X[None])
+            assert z[0] > 0
+            out.append((i, px[0] + 0.05 * rs.standard_normal(2) + np.array([0.0, 0.0 if dy is None else dy.get(i, 0.0)])))
+        return out
+
+    names, tracks, at = [], [], {}
+    for name, view, X in (("dup_mid", 19, ARC_TARGET + [0.3, 0.2, -0.4]), ("dup_first", 3, ARC_TARGET + [-0.5, -0.3, 0.6])):
+        obs = seen(np.asarray(X), RULE_VIEWS)
+        k = RULE_VIEWS.index(view)
+        obs.insert(k + 1, (view, obs[k][1].copy()))
+        names.append(name), tracks.append(obs)
+        at[name] = {"lower": k, "higher": k + 1}
+    names.append("plain"), tracks.append(seen(ARC_TARGET + [0.1, -0.4, 0.2], RULE_VIEWS))
+    far = ARC_TARGET + [0.0, 0.0, 90.0]
+    names.append("narrow"), tracks.append(seen(far, (17, 18, 19, 20)))
+    names.append("narrow_far"), tracks.append(seen(far, (17, 18, 19, 20, 33), {33: 14.0}))
+    # 70 stray key points of view 1 in front (none within 60 px of the two points they precede): what follows sits past a wave
+    near = ARC_TARGET + [0.4, 0.1, -0.3]
+    keep_off = pr.project(cameras[images[1].camera_id], images[1].qvec, images[1].tvec, np.stack([far, near]))[0]
+    stray = []
+    while len(stray) < 70:
+        p = np.array([rs.uniform(8, 632), rs.uniform(8, 472)])
+        if np.linalg.norm(keep_off - p, axis=1).min() > 60:
+            stray.append((1, p))
+    names.append("narrow_far_long"), tracks.append(stray + seen(far, (17, 18, 19, 20, 33), {33: 14.0}))
+    names.append("plain_long"), tracks.append(stray + seen(near, RULE_VIEWS))
+    X = ARC_TARGET + [-0.2, 0.3, 0.3]
+    obs, roles = [], {}
+    for i, p in seen(X, RULE_VIEWS):
+        extra = {11: (("a_far", 0.9), ("a_near", 0.3)), 23: (("b_far", -3.2), ("b_near", -2.4)), 31: (("c_held", 0.0), ("c_other", 2.5))}.get(i)
+        if extra is None:
+            obs.append((i, p))
+            continue
+        for role, dy in extra:
+            roles[role] = len(obs)
+            obs.append((i, p + [0.0, dy]))
+    names.append("late"), tracks.append(obs)
+    at["late"] = roles
+    keypoints, L, t_off, t_nodes = layout_from_tracks(cameras, images, tracks)
+    labels = [RULE_LONG_LABELS.get(n, int(t_nodes[t_off[t]])) for t, n in enumerate(names)]
+    return {"cameras": cameras, "images": images, "keypoints": keypoints, "L": L, "t_off": t_off, "t_nodes": t_nodes, "names": names, "at": at,
+            "labels": labels}
+
+
+# ------------------------------------------------------------------------------------------------------------------ designed pairs
+SEAM_EMPTY = (1, 6, 10)
+SEAM_MIN_INLIERS = 15
+
+
+def make_seam_pairs(seed=0, max_error=DEFAULTS["max_error"]):
+    """Hand-built pairs for the verification at its block seams (a block is 256 matches) on ten arc cameras of which images 1, 6 and
+    10 (front, middle, end of the table) have no key points.  A true match is the exact projection of a point into both images; a
+    false one has its second key point moved across the epipolar line by 3.5 to 8 thresholds.  Every pair brings its own key points,
+    appended to its images' tables in pair order.
+    Returns {'cameras', 'images', 'keypoints', 'L', 'pair_matches', 'truth' (per pair, bool; False also for the rows that are no
+    match), 'names'}."""
+    rs = np.random.RandomState(seed)
+    cameras, images = arc_cameras(10)
+    kps = {i: [] for i in images}
+    cam = (lambda i: cameras[images[i].camera_id])
+    R = {i: pr.qvec2rotmat(images[i].qvec) for i in images}
+
+    def moved(i, j, pi, pj):                                 # pj across the epipolar line of pi
+        Rr = R[j] @ R[i].T
+        t = images[j].tvec - Rr @ images[i].tvec
+        E = np.array([[0, -t[2], t[1]], [t[2], 0, -t[0]], [-t[1], t[0], 0]]) @ Rr
+        line = E @ np.append(pr.undistort(cam(i), pi[None])[0], 1.0)
+        n = line[:2] / np.linalg.norm(line[:2])
+        xj = pr.undistort(cam(j), pj[None])[0] + rs.choice([-1.0, 1.0]) * rs.uniform(3.5, 8.0) * max_error / pr.mean_focal(cam(j)) * n
+        fx, fy, cx, cy = pr._opencv(cam(j))[:4]
+        ud, vd = pr.distort(cam(j), xj[0], xj[1])
+        return np.array([fx * ud + cx, fy * vd + cy])
+
+    def add(i, j, n, false_at, points=None):
+        rows = np.zeros((n, 2), np.int32)
+        truth = np.ones(n, bool)
+        for r in range(n):
+            if points is None:
+                X = ARC_TARGET + np.array([rs.uniform(-2, 2), rs.uniform(-1.5, 1.5), rs.uniform(-2, 2)])
+            else:
+                X = points[r]
+            pi, zi = pr.project(cam(i), images[i].qvec, images[i].tvec, X[None])
+            pj, zj = pr.project(cam(j), images[j].qvec, images[j].tvec, X[None])
+            assert zi[0] > 0 and zj[0] > 0
+            pi, pj = pi[0], pj[0]
+            if r in false_at:
+                pj, truth[r] = moved(i, j, pi, pj), False
+            rows[r, 0] = len(kps[i])
+            kps[i].append(pi)
+            rows[r, 1] = len(kps[j])
+            kps[j].append(pj)
+        return rows, truth
+
+    def seams(n):
+        return {r for r in (0, 255, 256, 511, 512, n - 1) if 0 <= r < n and n > 1} | set(rs.choice(n, n // 20, replace=False).tolist() if n > 40 else [])
+
+    def back(i, corners, depth):                              # the points that image i sees at these stored key points
+        xn = pr.undistort(cam(i), np.asarray(corners, float) + 0.5)
+        return (np.concatenate([xn, np.ones((len(xn), 1))], 1) * depth - images[i].tvec) @ R[i]
+
+    names, pairs, truths = [], [], []
+
+    def pair(name, i, j, rows, truth):
+        names.append(name), pairs.append((i, j, rows)), truths.append(truth)
+
+    for name, i, j, n in (("n700", 2, 3, 700), ("n0", 3, 4, 0), ("n1", 4, 5, 1), ("n255", 5, 7, 255), ("n256", 7, 8, 256), ("n257", 8, 9, 257),
+                          ("n512", 2, 5, 512), ("n513", 3, 7, 513)):
+        pair(name, i, j, *add(i, j, n, seams(n)))
+    pair("reversed_last_block", 9, 2, *add(9, 2, 600, set(range(520, 600, 2))))            # listed as (j, i), j > i
+    rows, truth = add(4, 4, 20, set())                        # an image with itself: no epipolar geometry, every match is rejected
+    rows[10:, 1] = rows[10:, 0]                               # (half of them a key point against itself)
+    pair("self", 4, 4, rows, np.zeros(20, bool))
+    rows, truth = add(5, 9, 40, {3, 17})
+    rows[8], truth[8] = rows[7], truth[7]                     # a match listed twice
+    rows[20], rows[21] = (-1, 5), (5, -1)
+    truth[20] = truth[21] = False
+    pair("twice_and_negative", 5, 9, rows, truth)
+    corners = [(0, 0), (639, 0), (0, 479), (639, 479)]
+    a, ta = add(7, 8, 5, {4}, back(7, corners + [(639, 479)], 10.0))                       # SIMPLE_RADIAL corners into OPENCV
+    b, tb = add(8, 7, 5, {4}, back(8, corners + [(0, 0)], 10.0))                           # OPENCV corners into SIMPLE_RADIAL
+    for i, rows, last in ((7, a, (639, 479)), (8, b, (0, 0))):                             # the corner itself, not its round trip
+        for r, c in zip(rows[:, 0], corners + [last]):
+            kps[i][r] = np.asarray(c, float) + 0.5
+    pair("corners", 7, 8, np.concatenate([a, b[:, ::-1]]), np.concatenate([ta, tb]))
+    spread = [10, 100, 200, 250, 255, 256, 300, 400, 500, 511, 512, 550, 580, 590, 599]
+    assert len(spread) == SEAM_MIN_INLIERS
+    pair("exactly_min", 2, 9, *add(2, 9, 600, set(range(600)) - set(spread)))
+    pair("one_short", 2, 9, *add(2, 9, 600, set(range(600)) - set(spread[:-1])))
+    keypoints = {i: (np.array(kps[i]).reshape(-1, 2) - 0.5).astype(np.float32) for i in images}
+    for i in SEAM_EMPTY:
+        assert len(keypoints[i]) == 0
+    return {"cameras": cameras, "images": images, "keypoints": keypoints, "L": Layout(cameras, images, keypoints), "pair_matches": pairs,
+            "truth": truths, "names": names}
+
+
 # ------------------------------------------------------------------------------------------------------------------ shared layout
 class Layout:
     """Views in ascending image id, the key-point table concatenated in that order, every key point normalised through its camera."""
@@ -171,6 +442,8 @@ def verify_ref(L, pair_matches, max_error=DEFAULTS["max_error"], min_num_inliers
         R = L.R[b] @ L.R[a].T
         t = L.t[b] - R @ L.t[a]
         E = np.array([[0, -t[2], t[1]], [t[2], 0, -t[0]], [-t[1], t[0], 0]]) @ R
+        if a == b:
+            E = np.zeros((3, 3))                              # an image with itself has no epipolar geometry: every distance is NaN
         m = np.asarray(m).reshape(-1, 2)
         xi = np.concatenate([L.xn[L.off[a] + m[:, 0]], np.ones((len(m), 1))], 1)
         xj = np.concatenate([L.xn[L.off[b] + m[:, 1]], np.ones((len(m), 1))], 1)
@@ -179,8 +452,9 @@ def verify_ref(L, pair_matches, max_error=DEFAULTS["max_error"], min_num_inliers
             dj = np.abs((xj * lj).sum(1)) / np.hypot(lj[:, 0], lj[:, 1])
             di = np.abs((xi * li).sum(1)) / np.hypot(li[:, 0], li[:, 1])
         ti, tj = max_error / pr.mean_focal(L.cams[a]), max_error / pr.mean_focal(L.cams[b])
-        ok = (di <= ti) & (dj <= tj)
-        near = (np.abs(di - ti) <= BAND * ti) | (np.abs(dj - tj) <= BAND * tj)
+        live = (m >= 0).all(1)                                # a row with a negative end is no match: it leaves as (-1, -1), uncounted
+        ok = (di <= ti) & (dj <= tj) & live
+        near = ((np.abs(di - ti) <= BAND * ti) | (np.abs(dj - tj) <= BAND * tj)) & live
         n_sure, n_max = int((ok & ~near).sum()), int((ok | near).sum())
         sure.append(True if n_sure >= min_num_inliers else (False if n_max < min_num_inliers else None))
         o = np.where(ok[:, None], m, -1).astype(np.int32)
@@ -356,8 +630,9 @@ def _hypothesis(T, L, oa, ob, cos_min):
 
 
 def triangulate_ref(L, track_offsets, track_nodes, min_tri_angle=DEFAULTS["min_tri_angle"], create_max_angle_error=DEFAULTS["create_max_angle_error"],
-                    filter_max_reproj_error=DEFAULTS["filter_max_reproj_error"], seed=DEFAULTS["seed"]):
-    """Returns {'xyz' [T, 4, 3], 'error' [T, 4], 'n_obs' [T, 4], 'obs_point' int8 [O], 'banded' bool [T]}."""
+                    filter_max_reproj_error=DEFAULTS["filter_max_reproj_error"], seed=DEFAULTS["seed"], labels=None):
+    """labels: the tracks' labels (64-bit, they key the draws); None = each track's first node, as sfd2_build_tracks labels them.
+    Returns {'xyz' [T, 4, 3], 'error' [T, 4], 'n_obs' [T, 4], 'obs_point' int8 [O], 'banded' bool [T]}."""
     Tn = len(track_offsets) - 1
     out = {"xyz": np.zeros((Tn, MAX_POINTS, 3)), "error": np.zeros((Tn, MAX_POINTS)), "n_obs": np.zeros((Tn, MAX_POINTS), np.int32),
            "obs_point": np.full(len(track_nodes), -1, np.int8), "banded": np.zeros(Tn, bool)}
@@ -365,7 +640,7 @@ def triangulate_ref(L, track_offsets, track_nodes, min_tri_angle=DEFAULTS["min_t
     for t in range(Tn):
         lo, hi = int(track_offsets[t]), int(track_offsets[t + 1])
         T = _Track(L, np.asarray(track_nodes[lo:hi], dtype=np.int64))
-        key = mix64((seed & M64) ^ mix64(int(track_nodes[lo])))
+        key = mix64((seed & M64) ^ mix64(int(track_nodes[lo] if labels is None else labels[t]) & M64))
         banded = False
         for p in range(MAX_POINTS):
             free = [o for o in range(T.n) if T.point[o] == -1]
@@ -476,3 +751,73 @@ def truth_figures(scene, L, track_offsets, track_nodes, tri):
             depth = (L.R[v] @ scene["X"][k] + L.t[v])[2]
             errs.append(np.linalg.norm(tri["xyz"][t, p] - scene["X"][k]) / depth)
     return len(got & want) / max(len(want), 1), mixed / max(n_out, 1), float(np.median(errs)) if errs else np.inf
+
+
+# ------------------------------------------------------------------------------------------------------------------ committed cases
+# The scenes, option values, seeds and labels of tests/test_gpu_triangulation_edges.py, with their restatement results cached here so
+# that the GPU tests and the CPU guards of tests/test_triangulation_host.py compute each once per run.  The seeds of the scenes were
+# chosen so that the restatement meets LONG_CLASSES inside the band cap; the guards hold them to it.
+LONG_SCENES = {"arc36": dict(seed=0), "arc80": dict(seed=10, n_images=80, tracks=TRACKS_80)}
+LONG_BAND_CAP, GRID_BAND_CAP = 0.10, 0.15
+LONG_CLASSES = {"arc36": dict(gt64=4, gt128=2, pass3=2, k5_fifth_free=1, n12to64=6), "arc80": dict(gt64=4, gt128=2)}
+# (min_tri_angle, create_max_angle_error, filter_max_reproj_error): the defaults, one option at a time, two corners
+GRID = ((1.5, 2.0, 4.0), (0.0, 2.0, 4.0), (5.0, 2.0, 4.0), (19.0, 2.0, 4.0), (1.5, 0.5, 4.0), (1.5, 1.0, 4.0), (1.5, 2.0, 1.0), (1.5, 2.0, 12.0),
+        (0.0, 1.0, 12.0), (19.0, 0.5, 1.0))
+SEEDS = (0, 1, 2 ** 63 + 5, -1)
+LABELS = (7, 2 ** 31 - 2, 2 ** 40 + 3)
+LABEL_STRIDE = 3                      # track t of a case carries label + LABEL_STRIDE * t
+
+
+@functools.lru_cache(maxsize=None)
+def track_scene(name):
+    return make_track_scene(**LONG_SCENES[name])
+
+
+@functools.lru_cache(maxsize=None)
+def long_ref(name):
+    sc = track_scene(name)
+    return triangulate_ref(sc["L"], sc["t_off"], sc["t_nodes"])
+
+
+@functools.lru_cache(maxsize=None)
+def short_tracks():
+    """The tracks of arc36 of at most 80 observations (k = 1, 2 and 3; all but one draw their hypotheses): the option grid and the
+    seed / label cases run on these, a second per restatement."""
+    sc = track_scene("arc36")
+    which = [t for t in range(len(sc["k"])) if sc["t_off"][t + 1] - sc["t_off"][t] <= 80]
+    return (sc,) + sub_tracks(sc["t_off"], sc["t_nodes"], which)
+
+
+@functools.lru_cache(maxsize=None)
+def grid_ref(g):
+    sc, off, nodes = short_tracks()
+    return triangulate_ref(sc["L"], off, nodes, min_tri_angle=g[0], create_max_angle_error=g[1], filter_max_reproj_error=g[2])
+
+
+def case_labels(label, n):
+    return [label + LABEL_STRIDE * t for t in range(n)]
+
+
+@functools.lru_cache(maxsize=None)
+def seed_ref(seed, label, seed_mask=M64, label_mask=M64):
+    """The restatement of short_tracks() under a seed and labels; the masks restate it as a 32-bit truncation would have it."""
+    sc, off, nodes = short_tracks()
+    return triangulate_ref(sc["L"], off, nodes, seed=seed & seed_mask, labels=[v & label_mask for v in case_labels(label, len(off) - 1)])
+
+
+@functools.lru_cache(maxsize=None)
+def rule_ref():
+    """(make_rule_tracks(), names of the tracks run at the defaults (labels: rt['labels']), their offsets and nodes and restatement, the
+    same of 'late' under RULE_LATE)."""
+    rt = make_rule_tracks()
+    plain = [n for n in rt["names"] if n != "late"]
+    off, nodes = sub_tracks(rt["t_off"], rt["t_nodes"], [rt["names"].index(n) for n in plain])
+    loff, lnodes = sub_tracks(rt["t_off"], rt["t_nodes"], [rt["names"].index("late")])
+    labels = [rt["labels"][rt["names"].index(n)] for n in plain]
+    return (rt, plain, off, nodes, triangulate_ref(rt["L"], off, nodes, labels=labels), loff, lnodes,
+            triangulate_ref(rt["L"], loff, lnodes, **RULE_LATE))
+
+
+@functools.lru_cache(maxsize=None)
+def seam_scene():
+    return make_seam_pairs()
