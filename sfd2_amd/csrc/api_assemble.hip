@@ -1,22 +1,10 @@
 // libsfd2hip: sfd2_assemble_2d3d -- checks and packs the jobs, the four launches of assemble_kernels.hip on the context's stream,
 // results back.  The job and image descriptors (and host-side key points / scores) go up in one copy.
 #include "sfd2_ctx.h"
+#include "api_scratch.h"
 #include "pose_camera.h"
 
 namespace {
-
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-hipError_t grow(JpegBuf &b, size_t bytes)
-{
-    if (bytes <= b.cap) return hipSuccess;
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.cap = 0;
-    hipError_t e = hipMalloc(&b.p, bytes);
-    if (e == hipSuccess) b.cap = bytes;
-    return e;
-}
 
 constexpr size_t kRowBytes = 16 + 24 + 4 + 4 + 4 + 4;     // one output row over the six arrays
 
@@ -32,7 +20,8 @@ extern "C" int sfd2_assemble_2d3d(sfd2_ctx *c, const sfd2_point_table *map, sfd2
     if (n_jobs == 0) return 0;
     // ---- checks and the layout of the three device blocks
     std::vector<AsmJobDev> jd(n_jobs);
-    size_t n_img = 0, ws_elems = 0, blk_elems = 0, host_in = 0, out_rows = 0;
+    size_t n_img = 0, ws_elems = 0, blk_elems = 0, out_rows = 0;
+    Carve host_in;                                             // the host key points and scores, as the packing loop below carves them
     int max_blocks = 0;
     for (int j = 0; j < n_jobs; ++j) {
         sfd2_assemble_job &J = jobs[j];
@@ -81,29 +70,32 @@ extern "C" int sfd2_assemble_2d3d(sfd2_ctx *c, const sfd2_point_table *map, sfd2
         blk_elems += (size_t)J.k * d.nchunk;
         n_img += (size_t)J.k;
         max_blocks = std::max(max_blocks, J.k * d.nchunk);
-        if (!J.inputs_on_device) host_in += align256((size_t)J.n * 8) + (J.scores ? align256((size_t)J.n * 4) : 0);
+        if (!J.inputs_on_device) host_in.take((size_t)J.n * 8);
+        if (!J.inputs_on_device && J.scores) host_in.take((size_t)J.n * 4);
         if (!out_on_device) out_rows += (size_t)J.capacity;
     }
     HIPCHECK(hipSetDevice(c->device));
     // in: jobs | images | host key points and scores;  ws: rows | keep | block counts | image counts | results;  out: the rows of host-bound jobs
-    const size_t o_img = align256(sizeof(AsmJobDev) * n_jobs), o_hin = o_img + align256(sizeof(AsmImgDev) * std::max<size_t>(n_img, 1));
-    const size_t in_bytes = o_hin + host_in;
-    const size_t o_keep = align256(4 * std::max<size_t>(ws_elems, 1)), o_blk = o_keep + align256(std::max<size_t>(ws_elems, 1));
-    const size_t o_cnt = o_blk + align256(4 * std::max<size_t>(blk_elems, 1)), o_res = o_cnt + align256(4 * std::max<size_t>(n_img, 1));
-    const size_t ws_bytes = o_res + align256(sizeof(AsmResDev) * n_jobs);
+    Carve ci, cw;
+    const size_t o_job = ci.take(sizeof(AsmJobDev) * n_jobs), o_img = ci.take(sizeof(AsmImgDev) * n_img), o_hin = ci.off;
+    const size_t in_bytes = o_hin + host_in.off;
+    const size_t o_rows = cw.take(4 * ws_elems), o_keep = cw.take(ws_elems), o_blk = cw.take(4 * blk_elems), o_cnt = cw.take(4 * n_img),
+                 o_res = cw.take(sizeof(AsmResDev) * n_jobs);
     HIPCHECK(grow(c->asm_in, in_bytes));       // (hipFree waits for the device: an earlier call's kernels have finished with the old block)
-    HIPCHECK(grow(c->asm_ws, ws_bytes));
+    HIPCHECK(grow(c->asm_ws, cw.off));
+    // six arrays per job, each at most 255 bytes of padding -- or, of a job with capacity 0, one 256-byte slot: 6 * 256 per job covers both
     if (!out_on_device) HIPCHECK(grow(c->asm_out, std::max<size_t>(out_rows, 1) * kRowBytes + 6 * 256 * (size_t)n_jobs));
     char *in = c->asm_in.as<char>(), *ws = c->asm_ws.as<char>(), *out = c->asm_out.as<char>();
     std::vector<char> stage(in_bytes, 0);
     {
-        AsmImgDev *im = reinterpret_cast<AsmImgDev *>(stage.data() + o_img);
-        size_t hin = o_hin, ii = 0, oo = 0;
+        AsmImgDev *im = at<AsmImgDev>(stage.data(), o_img);
+        Carve hin{o_hin}, oo;
+        size_t ii = 0;
         for (int j = 0; j < n_jobs; ++j) {
             const sfd2_assemble_job &J = jobs[j];
             AsmJobDev &d = jd[j];
             d.matches0 = reinterpret_cast<const long long *>(J.matches0);
-            d.imgs = reinterpret_cast<const AsmImgDev *>(in + o_img) + ii;
+            d.imgs = at<const AsmImgDev>(in, o_img) + ii;
             for (int i = 0; i < J.k; ++i, ++ii) {
                 im[ii].tab = J.images[i].point_rows;
                 im[ii].n1 = J.images[i].n1;
@@ -113,37 +105,36 @@ extern "C" int sfd2_assemble_2d3d(sfd2_ctx *c, const sfd2_point_table *map, sfd2
                 d.kpq = J.keypoints;
                 d.scores = J.scores;
             } else {
-                if (J.n) memcpy(stage.data() + hin, J.keypoints, (size_t)J.n * 8);
-                d.kpq = reinterpret_cast<const float *>(in + hin);
-                hin += align256((size_t)J.n * 8);
+                const size_t o_kp = hin.take((size_t)J.n * 8);
+                if (J.n) memcpy(stage.data() + o_kp, J.keypoints, (size_t)J.n * 8);
+                d.kpq = at<const float>(in, o_kp);
                 if (J.scores) {
-                    if (J.n) memcpy(stage.data() + hin, J.scores, (size_t)J.n * 4);
-                    d.scores = reinterpret_cast<const float *>(in + hin);
-                    hin += align256((size_t)J.n * 4);
+                    const size_t o_sc = hin.take((size_t)J.n * 4);
+                    if (J.n) memcpy(stage.data() + o_sc, J.scores, (size_t)J.n * 4);
+                    d.scores = at<const float>(in, o_sc);
                 }
             }
             if (out_on_device) {
                 d.p2 = J.points2D; d.p3 = J.points3D; d.prow = J.point_row; d.qidx = J.query_idx; d.iidx = J.image_idx; d.score = J.score;
             } else {
                 const size_t cap = (size_t)J.capacity;
-                d.p2 = reinterpret_cast<double *>(out + oo); oo += align256(16 * cap);
-                d.p3 = reinterpret_cast<double *>(out + oo); oo += align256(24 * cap);
-                d.prow = reinterpret_cast<int32_t *>(out + oo); oo += align256(4 * cap);
-                d.qidx = reinterpret_cast<int32_t *>(out + oo); oo += align256(4 * cap);
-                d.iidx = reinterpret_cast<int32_t *>(out + oo); oo += align256(4 * cap);
-                d.score = reinterpret_cast<float *>(out + oo); oo += align256(4 * cap);
+                d.p2 = at<double>(out, oo.take(16 * cap));
+                d.p3 = at<double>(out, oo.take(24 * cap));
+                d.prow = at<int32_t>(out, oo.take(4 * cap));
+                d.qidx = at<int32_t>(out, oo.take(4 * cap));
+                d.iidx = at<int32_t>(out, oo.take(4 * cap));
+                d.score = at<float>(out, oo.take(4 * cap));
             }
         }
-        memcpy(stage.data(), jd.data(), sizeof(AsmJobDev) * n_jobs);
+        memcpy(stage.data() + o_job, jd.data(), sizeof(AsmJobDev) * n_jobs);
     }
     HIPCHECK(hipMemcpyAsync(in, stage.data(), in_bytes, hipMemcpyHostToDevice, c->stream));
-    AsmResDev *res = reinterpret_cast<AsmResDev *>(ws + o_res);
+    AsmResDev *res = at<AsmResDev>(ws, o_res);
     HIPCHECK(hipMemsetAsync(res, 0, sizeof(AsmResDev) * n_jobs, c->stream));
     {
         ProfScope ps(c, "assemble_2d3d", "assemble_resolve+flag+scan+scatter", 0.0, (double)ws_elems * 18.0);
-        launch_assemble(c->stream, reinterpret_cast<const AsmJobDev *>(in), n_jobs, max_blocks, map->xyz, map->track_len, map->n_points,
-                        reinterpret_cast<int32_t *>(ws), reinterpret_cast<unsigned char *>(ws + o_keep), reinterpret_cast<int32_t *>(ws + o_blk),
-                        reinterpret_cast<int32_t *>(ws + o_cnt), res);
+        launch_assemble(c->stream, at<const AsmJobDev>(in, o_job), n_jobs, max_blocks, map->xyz, map->track_len, map->n_points, at<int32_t>(ws, o_rows),
+                        at<unsigned char>(ws, o_keep), at<int32_t>(ws, o_blk), at<int32_t>(ws, o_cnt), res);
     }
     HIPCHECK(hipGetLastError());
     std::vector<AsmResDev> r(n_jobs);

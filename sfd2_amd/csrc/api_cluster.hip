@@ -1,39 +1,9 @@
 // libsfd2hip: sfd2_covis_clusters -- checks the inputs (every index the kernel follows is bounds-checked here, before anything is
 // uploaded or written), uploads the map and the query lists, one launch of cluster_kernels.hip on the context's stream, results back.
 #include "sfd2_ctx.h"
+#include "api_scratch.h"
 
 namespace {
-
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-hipError_t grow(JpegBuf &b, size_t bytes)
-{
-    if (bytes <= b.cap) return hipSuccess;
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.cap = 0;
-    hipError_t e = hipMalloc(&b.p, bytes);
-    if (e == hipSuccess) b.cap = bytes;
-    return e;
-}
-
-struct Carve {                        // offsets into one block, 256-byte aligned
-    size_t off = 0;
-    size_t take(size_t bytes)
-    {
-        const size_t o = off;
-        off += align256(std::max<size_t>(bytes, 1));
-        return o;
-    }
-};
-
-bool monotone(const int64_t *o, int64_t n)
-{
-    if (o[0] != 0) return false;
-    for (int64_t i = 0; i < n; ++i)
-        if (o[i + 1] < o[i]) return false;
-    return true;
-}
 
 }  // namespace
 
@@ -50,10 +20,8 @@ extern "C" int sfd2_covis_clusters(sfd2_ctx *c, const int64_t *obs_offsets, cons
     if (!monotone(frame_offsets, nq)) return fail(F + "frame_offsets must start at 0 and not decrease");
     const int64_t O = obs_offsets[n_images], T = track_offsets[n_points], N = frame_offsets[nq];
     if ((O > 0 && !obs_point) || (T > 0 && !track_image) || (N > 0 && (!frames || !cluster))) return fail(F + "null argument");
-    for (int64_t o = 0; o < O; ++o)
-        if (obs_point[o] < 0 || obs_point[o] >= n_points) return fail(F + "observation " + std::to_string(o) + ": point row out of range");
-    for (int64_t t = 0; t < T; ++t)
-        if (track_image[t] < 0 || track_image[t] >= n_images) return fail(F + "track element " + std::to_string(t) + ": image index out of range");
+    if (const int64_t o = first_outside(obs_point, O, n_points); o < O) return fail(F + "observation " + std::to_string(o) + ": point row out of range");
+    if (const int64_t t = first_outside(track_image, T, n_images); t < T) return fail(F + "track element " + std::to_string(t) + ": image index out of range");
     {
         std::vector<int32_t> seen((size_t)n_images, -1);           // the query that listed the image last
         for (int q = 0; q < nq; ++q) {
@@ -89,10 +57,9 @@ extern "C" int sfd2_covis_clusters(sfd2_ctx *c, const int64_t *obs_offsets, cons
     if (global) HIPCHECK(hipMemsetAsync(dw + o_scr, 0xff, 2 * (size_t)blocks * n_images, c->stream));
     {
         ProfScope ps(c, "covis_clusters", global ? "covis_cluster<global>" : "covis_cluster<lds>", 0.0, 4.0 * (double)(O + T + N));
-        HIPCHECK(launch_covis_clusters(c->stream, reinterpret_cast<const int64_t *>(di + o_oo), reinterpret_cast<const int32_t *>(di + o_op), n_images,
-                                       reinterpret_cast<const int64_t *>(di + o_to), reinterpret_cast<const int32_t *>(di + o_ti),
-                                       reinterpret_cast<const int64_t *>(di + o_fo), reinterpret_cast<const int32_t *>(di + o_fr), nq, global, blocks,
-                                       reinterpret_cast<uint16_t *>(dw + o_scr), reinterpret_cast<int32_t *>(dw + o_cl), reinterpret_cast<int32_t *>(dw + o_n)));
+        HIPCHECK(launch_covis_clusters(c->stream, at<const int64_t>(di, o_oo), at<const int32_t>(di, o_op), n_images, at<const int64_t>(di, o_to),
+                                       at<const int32_t>(di, o_ti), at<const int64_t>(di, o_fo), at<const int32_t>(di, o_fr), nq, global, blocks,
+                                       at<uint16_t>(dw, o_scr), at<int32_t>(dw, o_cl), at<int32_t>(dw, o_n)));
     }
     if (N) HIPCHECK(hipMemcpyAsync(cluster, dw + o_cl, 4 * (size_t)N, hipMemcpyDeviceToHost, c->stream));
     HIPCHECK(hipMemcpyAsync(n_clusters, dw + o_n, 4 * (size_t)nq, hipMemcpyDeviceToHost, c->stream));

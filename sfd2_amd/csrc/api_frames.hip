@@ -3,46 +3,9 @@
 // back and compared with the stated sizes, and the kernel range-checks what it reads), uploads the tasks, one launch of
 // frames_kernels.hip on the context's stream, results back.
 #include "sfd2_ctx.h"
+#include "api_scratch.h"
 
 namespace {
-
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-hipError_t grow(JpegBuf &b, size_t bytes)
-{
-    if (bytes <= b.cap) return hipSuccess;
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.cap = 0;
-    hipError_t e = hipMalloc(&b.p, bytes);
-    if (e == hipSuccess) b.cap = bytes;
-    return e;
-}
-
-struct Carve {                        // offsets into one block, 256-byte aligned
-    size_t off = 0;
-    size_t take(size_t bytes)
-    {
-        const size_t o = off;
-        off += align256(std::max<size_t>(bytes, 1));
-        return o;
-    }
-};
-
-bool monotone(const int64_t *o, int64_t n)
-{
-    if (o[0] != 0) return false;
-    for (int64_t i = 0; i < n; ++i)
-        if (o[i + 1] < o[i]) return false;
-    return true;
-}
-
-bool in_range(const int32_t *a, int64_t n, int hi)
-{
-    for (int64_t i = 0; i < n; ++i)
-        if (a[i] < 0 || a[i] >= hi) return false;
-    return true;
-}
 
 static_assert(sizeof(FramesTaskDev) == sizeof(sfd2_frames_task) && offsetof(FramesTaskDev, q_th) == offsetof(sfd2_frames_task, q_th) &&
                   offsetof(FramesTaskDev, tvec) == offsetof(sfd2_frames_task, tvec),
@@ -144,19 +107,18 @@ extern "C" int sfd2_covis_frames(sfd2_ctx *c, const sfd2_frames_map *map, const 
         if (map->excluded) HIPCHECK(hipMemcpyAsync(di + o_ex, map->excluded, (size_t)n_images, hipMemcpyHostToDevice, c->stream));
         if (map->qvec) HIPCHECK(hipMemcpyAsync(di + o_qv, map->qvec, 32 * (size_t)n_images, hipMemcpyHostToDevice, c->stream));
         if (map->tvec) HIPCHECK(hipMemcpyAsync(di + o_tv, map->tvec, 24 * (size_t)n_images, hipMemcpyHostToDevice, c->stream));
-        dm.obs_off = reinterpret_cast<const int64_t *>(di + o_oo), dm.obs_point = reinterpret_cast<const int32_t *>(di + o_op);
-        dm.trk_off = reinterpret_cast<const int64_t *>(di + o_to), dm.trk_img = reinterpret_cast<const int32_t *>(di + o_ti);
-        dm.seen_off = reinterpret_cast<const int64_t *>(di + o_so), dm.seen_img = reinterpret_cast<const int32_t *>(di + o_si);
-        dm.excluded = reinterpret_cast<const uint8_t *>(di + o_ex);
-        dm.qvec = reinterpret_cast<const double *>(di + o_qv), dm.tvec = reinterpret_cast<const double *>(di + o_tv);
+        dm.obs_off = at<const int64_t>(di, o_oo), dm.obs_point = at<const int32_t>(di, o_op);
+        dm.trk_off = at<const int64_t>(di, o_to), dm.trk_img = at<const int32_t>(di, o_ti);
+        dm.seen_off = at<const int64_t>(di, o_so), dm.seen_img = at<const int32_t>(di, o_si);
+        dm.excluded = at<const uint8_t>(di, o_ex);
+        dm.qvec = at<const double>(di, o_qv), dm.tvec = at<const double>(di, o_tv);
     }
     HIPCHECK(hipMemsetAsync(dw + o_out, 0xff, 4 * n_res, c->stream));           // slots a row does not fill hold -1
     if (global) HIPCHECK(hipMemsetAsync(dw + o_scr, 0, 4 * scr, c->stream));
     {
         ProfScope ps(c, "covis_frames", global ? "covis_frames<global>" : "covis_frames<lds>", 0.0, 0.0);
-        HIPCHECK(launch_covis_frames(c->stream, dm, reinterpret_cast<const FramesTaskDev *>(di + o_tk), n_tasks, reinterpret_cast<const int64_t *>(di + o_ro),
-                                     reinterpret_cast<const int32_t *>(di + o_rp), cap, global, blocks, reinterpret_cast<int *>(dw + o_scr),
-                                     reinterpret_cast<int32_t *>(dw + o_out)));
+        HIPCHECK(launch_covis_frames(c->stream, dm, at<const FramesTaskDev>(di, o_tk), n_tasks, at<const int64_t>(di, o_ro), at<const int32_t>(di, o_rp), cap,
+                                     global, blocks, at<int>(dw, o_scr), at<int32_t>(dw, o_out)));
     }
     // into a buffer of the call's own first: the caller's arrays stay untouched when a copy or the kernel fails
     std::vector<int32_t> h(n_res);

@@ -3,7 +3,7 @@
 
 namespace {
 
-hipError_t grow(JpegBuf &b, size_t bytes, sfd2_ctx *c, bool &synced)
+hipError_t grow(ScratchBuf &b, size_t bytes, sfd2_ctx *c, bool &synced)
 {
     if (bytes <= b.cap) return hipSuccess;
     if (!synced) {                                  // queued decodes may still use the old buffer

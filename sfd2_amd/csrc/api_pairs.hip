@@ -1,39 +1,9 @@
 // libsfd2hip: sfd2_pairs_retrieval / sfd2_pairs_covisibility / sfd2_pairs_poses -- checks the inputs (every index a kernel follows is
 // bounds-checked here), uploads them, the launches of pairs_kernels.hip on the context's stream, results back.
 #include "sfd2_ctx.h"
+#include "api_scratch.h"
 
 namespace {
-
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-hipError_t grow(JpegBuf &b, size_t bytes)
-{
-    if (bytes <= b.cap) return hipSuccess;
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.cap = 0;
-    hipError_t e = hipMalloc(&b.p, bytes);
-    if (e == hipSuccess) b.cap = bytes;
-    return e;
-}
-
-struct Carve {                        // offsets into one block, 256-byte aligned
-    size_t off = 0;
-    size_t take(size_t bytes)
-    {
-        const size_t o = off;
-        off += align256(std::max<size_t>(bytes, 1));
-        return o;
-    }
-};
-
-bool monotone(const int64_t *o, int64_t n)
-{
-    if (o[0] != 0) return false;
-    for (int64_t i = 0; i < n; ++i)
-        if (o[i + 1] < o[i]) return false;
-    return true;
-}
 
 bool k_ok(int k, int most = SFD2_PAIRS_MAX_K) { return k >= 1 && k <= most; }
 
@@ -68,15 +38,15 @@ extern "C" int sfd2_pairs_retrieval(sfd2_ctx *c, const float *query, int nq, con
     if (!inputs_on_device) {
         HIPCHECK(hipMemcpyAsync(di + o_q, query, 4 * na, hipMemcpyHostToDevice, c->stream));
         HIPCHECK(hipMemcpyAsync(di + o_db, db, 4 * nb, hipMemcpyHostToDevice, c->stream));
-        dq = reinterpret_cast<const float *>(di + o_q);
-        dd = reinterpret_cast<const float *>(di + o_db);
+        dq = at<const float>(di, o_q);
+        dd = at<const float>(di, o_db);
     }
     HIPCHECK(hipMemsetAsync(dw + o_flag, 0, 4, c->stream));
     {
         ProfScope ps(c, "pairs_retrieval", "pairs_finite+retrieval+merge", 2.0 * (double)nq * nd * d, 4.0 * (double)(na + nb));
-        HIPCHECK(launch_pairs_finite(c->stream, dq, na, dd, nb, reinterpret_cast<int *>(dw + o_flag)));
-        HIPCHECK(launch_pairs_retrieval(c->stream, dq, nq, dd, nd, d, k, splits, reinterpret_cast<float *>(dw + o_ps), reinterpret_cast<int *>(dw + o_pi),
-                                        reinterpret_cast<int32_t *>(dw + o_idx), reinterpret_cast<float *>(dw + o_sim)));
+        HIPCHECK(launch_pairs_finite(c->stream, dq, na, dd, nb, at<int>(dw, o_flag)));
+        HIPCHECK(launch_pairs_retrieval(c->stream, dq, nq, dd, nd, d, k, splits, at<float>(dw, o_ps), at<int>(dw, o_pi), at<int32_t>(dw, o_idx),
+                                        at<float>(dw, o_sim)));
     }
     int bad = 0;
     HIPCHECK(hipMemcpyAsync(&bad, dw + o_flag, 4, hipMemcpyDeviceToHost, c->stream));
@@ -100,10 +70,8 @@ extern "C" int sfd2_pairs_covisibility(sfd2_ctx *c, const int64_t *obs_offsets, 
     if (!monotone(track_offsets, n_points)) return fail(F + "track_offsets must start at 0 and not decrease");
     const int64_t O = obs_offsets[n_images], T = track_offsets[n_points];
     if ((O > 0 && !obs_point) || (T > 0 && !track_image)) return fail(F + "null argument");
-    for (int64_t o = 0; o < O; ++o)
-        if (obs_point[o] < 0 || obs_point[o] >= n_points) return fail(F + "observation " + std::to_string(o) + ": point row out of range");
-    for (int64_t t = 0; t < T; ++t)
-        if (track_image[t] < 0 || track_image[t] >= n_images) return fail(F + "track element " + std::to_string(t) + ": image index out of range");
+    if (const int64_t o = first_outside(obs_point, O, n_points); o < O) return fail(F + "observation " + std::to_string(o) + ": point row out of range");
+    if (const int64_t t = first_outside(track_image, T, n_images); t < T) return fail(F + "track element " + std::to_string(t) + ": image index out of range");
     const int global = (flags & SFD2_PAIRS_FLAG_GLOBAL_COUNTERS) || n_images > SFD2_PAIRS_COVIS_LDS_IMAGES;
     const int blocks = std::min(n_images, global ? 512 : 2048);
     HIPCHECK(hipSetDevice(c->device));
@@ -122,10 +90,9 @@ extern "C" int sfd2_pairs_covisibility(sfd2_ctx *c, const int64_t *obs_offsets, 
     if (T) HIPCHECK(hipMemcpyAsync(di + o_ti, track_image, 4 * (size_t)T, hipMemcpyHostToDevice, c->stream));
     {
         ProfScope ps(c, "pairs_covisibility", global ? "pairs_covis<global>" : "pairs_covis<lds>", 0.0, 4.0 * (double)(O + T));
-        HIPCHECK(launch_pairs_covis(c->stream, reinterpret_cast<const int64_t *>(di + o_oo), reinterpret_cast<const int32_t *>(di + o_op), n_images,
-                                    reinterpret_cast<const int64_t *>(di + o_to), reinterpret_cast<const int32_t *>(di + o_ti), k, global, blocks,
-                                    reinterpret_cast<int *>(dw + o_scr), reinterpret_cast<int32_t *>(dw + o_idx), reinterpret_cast<int32_t *>(dw + o_cnt),
-                                    reinterpret_cast<int32_t *>(dw + o_n)));
+        HIPCHECK(launch_pairs_covis(c->stream, at<const int64_t>(di, o_oo), at<const int32_t>(di, o_op), n_images, at<const int64_t>(di, o_to),
+                                    at<const int32_t>(di, o_ti), k, global, blocks, at<int>(dw, o_scr), at<int32_t>(dw, o_idx), at<int32_t>(dw, o_cnt),
+                                    at<int32_t>(dw, o_n)));
     }
     HIPCHECK(hipMemcpyAsync(idx, dw + o_idx, 4 * (size_t)n_images * k, hipMemcpyDeviceToHost, c->stream));
     HIPCHECK(hipMemcpyAsync(count, dw + o_cnt, 4 * (size_t)n_images * k, hipMemcpyDeviceToHost, c->stream));
@@ -144,10 +111,8 @@ extern "C" int sfd2_pairs_poses(sfd2_ctx *c, const double *qvec, const double *t
     if (flags & ~SFD2_PAIRS_FLAG_CENTRES) return fail(F + "unknown flags");
     if ((int64_t)n * k > 0x7fffffffLL) return fail(F + "n * k must stay below 2^31");
     if (std::isnan(rotation_threshold_deg)) return fail(F + "rotation_threshold_deg is not a number");
-    for (int64_t i = 0; i < 4 * (int64_t)n; ++i)
-        if (!std::isfinite(qvec[i])) return fail(F + "non-finite qvec");
-    for (int64_t i = 0; i < 3 * (int64_t)n; ++i)
-        if (!std::isfinite(tvec[i])) return fail(F + "non-finite tvec");
+    if (!all_finite(qvec, 4 * (int64_t)n)) return fail(F + "non-finite qvec");
+    if (!all_finite(tvec, 3 * (int64_t)n)) return fail(F + "non-finite tvec");
     HIPCHECK(hipSetDevice(c->device));
     Carve in, ws;
     const size_t o_q = in.take(32 * (size_t)n), o_t = in.take(24 * (size_t)n);
@@ -160,9 +125,9 @@ extern "C" int sfd2_pairs_poses(sfd2_ctx *c, const double *qvec, const double *t
     HIPCHECK(hipMemcpyAsync(di + o_t, tvec, 24 * (size_t)n, hipMemcpyHostToDevice, c->stream));
     {
         ProfScope ps(c, "pairs_poses", "pairs_pose_prep+pairs_pose", 0.0, 96.0 * (double)n);
-        HIPCHECK(launch_pairs_poses(c->stream, reinterpret_cast<const double *>(di + o_q), reinterpret_cast<const double *>(di + o_t), n, k,
-                                    rotation_threshold_deg, (flags & SFD2_PAIRS_FLAG_CENTRES) ? 1 : 0, reinterpret_cast<double *>(dw + o_rc),
-                                    reinterpret_cast<int32_t *>(dw + o_idx), reinterpret_cast<double *>(dw + o_d), reinterpret_cast<int32_t *>(dw + o_n)));
+        HIPCHECK(launch_pairs_poses(c->stream, at<const double>(di, o_q), at<const double>(di, o_t), n, k, rotation_threshold_deg,
+                                    (flags & SFD2_PAIRS_FLAG_CENTRES) ? 1 : 0, at<double>(dw, o_rc), at<int32_t>(dw, o_idx), at<double>(dw, o_d),
+                                    at<int32_t>(dw, o_n)));
     }
     HIPCHECK(hipMemcpyAsync(idx, dw + o_idx, 4 * (size_t)n * k, hipMemcpyDeviceToHost, c->stream));
     HIPCHECK(hipMemcpyAsync(dist, dw + o_d, 8 * (size_t)n * k, hipMemcpyDeviceToHost, c->stream));

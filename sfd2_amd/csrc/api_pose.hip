@@ -1,5 +1,6 @@
 // libsfd2hip: sfd2_absolute_pose_batch / sfd2_pose_refine_batch -- checks and packs the problems, one launch of pose_kernels.hip.
 #include "sfd2_ctx.h"
+#include "api_scratch.h"
 
 namespace {
 
@@ -19,13 +20,6 @@ const char *model_name(int m)
     case 10: return "THIN_PRISM_FISHEYE";
     default: return "unknown";
     }
-}
-
-bool all_finite(const double *p, int64_t n)
-{
-    for (int64_t i = 0; i < n; ++i)
-        if (!std::isfinite(p[i])) return false;
-    return true;
 }
 
 // COLMAP's camera in the kernels' OPENCV form; false (with the reason) for a model this library does not take
@@ -51,19 +45,6 @@ bool to_cam(const sfd2_pose_problem &p, PoseCam &c, double &mean_focal, std::str
     c.distorted = (c.k1 != 0 || c.k2 != 0 || c.p1 != 0 || c.p2 != 0) ? 1 : 0;
     mean_focal = 0.5 * (c.f[0] + c.f[1]);
     return true;
-}
-
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-hipError_t grow(JpegBuf &b, size_t bytes)
-{
-    if (bytes <= b.cap) return hipSuccess;
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.cap = 0;
-    hipError_t e = hipMalloc(&b.p, bytes);
-    if (e == hipSuccess) b.cap = bytes;
-    return e;
 }
 
 // COLMAP ComputeNumTrials (sample size 3, dyn_num_trials_multiplier 3)
@@ -111,17 +92,16 @@ int run(sfd2_ctx *c, const char *fn, const sfd2_pose_problem *problems, int k, c
     if (k == 0) return 0;
     HIPCHECK(hipSetDevice(c->device));
     const int64_t N = std::max<int64_t>(total, 1);
+    Carve ci, cw, co;
     // inputs: problems | points2D | points3D | mask
-    const size_t o_p2 = align256(sizeof(PoseProbDev) * k), o_p3 = o_p2 + align256(16 * N), o_m = o_p3 + align256(24 * N);
-    const size_t in_bytes = o_m + align256(N);
+    const size_t o_pd = ci.take(sizeof(PoseProbDev) * k), o_p2 = ci.take(16 * N), o_p3 = ci.take(24 * N), o_m = ci.take(N);
     // work: float4 X | float2 x | double2 x | hypotheses;  out: results | mask
-    const size_t o_x2 = align256(16 * N), o_xn = o_x2 + align256(8 * N), o_hyp = o_xn + align256(16 * N);
-    const size_t ws_bytes = o_hyp + sizeof(double) * (size_t)k * SFD2_POSE_WG * 4 * 12;
-    const size_t o_mo = align256(sizeof(PoseResDev) * k), out_bytes = o_mo + align256(N);
+    const size_t o_X = cw.take(16 * N), o_x2 = cw.take(8 * N), o_xn = cw.take(16 * N), o_hyp = cw.take(sizeof(double) * (size_t)k * SFD2_POSE_WG * 4 * 12);
+    const size_t o_res = co.take(sizeof(PoseResDev) * k), o_mo = co.take(N);
     HIPCHECK(hipStreamSynchronize(c->stream));              // earlier pose calls on this stream may still read the buffers
-    HIPCHECK(grow(c->pose_in, in_bytes));
-    HIPCHECK(grow(c->pose_ws, ws_bytes));
-    HIPCHECK(grow(c->pose_out, out_bytes));
+    HIPCHECK(grow(c->pose_in, ci.off));
+    HIPCHECK(grow(c->pose_ws, cw.off));
+    HIPCHECK(grow(c->pose_out, co.off));
     std::vector<double> p2(2 * (size_t)N), p3(3 * (size_t)N);
     std::vector<uint8_t> m(mask_in ? (size_t)N : 0);
     for (int i = 0; i < k; ++i) {
@@ -134,18 +114,16 @@ int run(sfd2_ctx *c, const char *fn, const sfd2_pose_problem *problems, int k, c
             for (int64_t j = 0; j < n; ++j) m[o + j] = mask_in[o + j] ? 1 : 0;
     }
     char *in = c->pose_in.as<char>(), *ws = c->pose_ws.as<char>(), *out = c->pose_out.as<char>();
-    HIPCHECK(hipMemcpyAsync(in, pd.data(), sizeof(PoseProbDev) * k, hipMemcpyHostToDevice, c->stream));
+    HIPCHECK(hipMemcpyAsync(in + o_pd, pd.data(), sizeof(PoseProbDev) * k, hipMemcpyHostToDevice, c->stream));
     HIPCHECK(hipMemcpyAsync(in + o_p2, p2.data(), 16 * total, hipMemcpyHostToDevice, c->stream));
     HIPCHECK(hipMemcpyAsync(in + o_p3, p3.data(), 24 * total, hipMemcpyHostToDevice, c->stream));
     if (mask_in) HIPCHECK(hipMemcpyAsync(in + o_m, m.data(), total, hipMemcpyHostToDevice, c->stream));
-    launch_pose(c->stream, reinterpret_cast<const PoseProbDev *>(in), k, conf, reinterpret_cast<const double *>(in + o_p2),
-                reinterpret_cast<const double *>(in + o_p3), reinterpret_cast<float4 *>(ws), reinterpret_cast<float2 *>(ws + o_x2),
-                reinterpret_cast<double2 *>(ws + o_xn), reinterpret_cast<double *>(ws + o_hyp),
-                reinterpret_cast<const unsigned char *>(in + o_m), reinterpret_cast<unsigned char *>(out + o_mo),
-                reinterpret_cast<PoseResDev *>(out));
+    launch_pose(c->stream, at<const PoseProbDev>(in, o_pd), k, conf, at<const double>(in, o_p2), at<const double>(in, o_p3), at<float4>(ws, o_X),
+                at<float2>(ws, o_x2), at<double2>(ws, o_xn), at<double>(ws, o_hyp), at<const unsigned char>(in, o_m), at<unsigned char>(out, o_mo),
+                at<PoseResDev>(out, o_res));
     HIPCHECK(hipGetLastError());
     std::vector<PoseResDev> r(k);
-    HIPCHECK(hipMemcpyAsync(r.data(), out, sizeof(PoseResDev) * k, hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(hipMemcpyAsync(r.data(), out + o_res, sizeof(PoseResDev) * k, hipMemcpyDeviceToHost, c->stream));
     if (mask_out && total) HIPCHECK(hipMemcpyAsync(mask_out, out + o_mo, total, hipMemcpyDeviceToHost, c->stream));
     HIPCHECK(hipStreamSynchronize(c->stream));
     for (int i = 0; i < k; ++i) {

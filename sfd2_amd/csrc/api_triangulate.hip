@@ -2,47 +2,11 @@
 // tri_kernels.hip on the context's stream, results back.  The sort and the scans of the track compaction are rocPRIM's (a stable
 // radix sort and integer scans: the bytes they give depend on the input alone).
 #include "sfd2_ctx.h"
+#include "api_scratch.h"
 #include "pose_camera.h"
 #include <rocprim/rocprim.hpp>
 
 namespace {
-
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-hipError_t grow(JpegBuf &b, size_t bytes)
-{
-    if (bytes <= b.cap) return hipSuccess;
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.cap = 0;
-    hipError_t e = hipMalloc(&b.p, bytes);
-    if (e == hipSuccess) b.cap = bytes;
-    return e;
-}
-
-struct Carve {                        // offsets into one block, 256-byte aligned
-    size_t off = 0;
-    size_t take(size_t bytes)
-    {
-        const size_t o = off;
-        off += align256(std::max<size_t>(bytes, 1));
-        return o;
-    }
-};
-
-bool all_finite(const double *p, int n)
-{
-    for (int i = 0; i < n; ++i)
-        if (!std::isfinite(p[i])) return false;
-    return true;
-}
-
-bool all_finite_f(const float *p, int64_t n)
-{
-    for (int64_t i = 0; i < n; ++i)
-        if (!std::isfinite(p[i])) return false;
-    return true;
-}
 
 // views -> device form; mean focal lengths on the side
 bool pack_views(const sfd2_tri_view *views, int n, std::vector<TriViewDev> &out, std::vector<double> &mean_focal, std::string &why)
@@ -68,14 +32,6 @@ bool pack_views(const sfd2_tri_view *views, int n, std::vector<TriViewDev> &out,
     return true;
 }
 
-bool monotone(const int64_t *o, int64_t n)
-{
-    if (o[0] != 0) return false;
-    for (int64_t i = 0; i < n; ++i)
-        if (o[i + 1] < o[i]) return false;
-    return true;
-}
-
 }  // namespace
 
 extern "C" int sfd2_verify_matches_batch(sfd2_ctx *c, const sfd2_tri_view *views, int n_views, const int64_t *kp_offsets, const float *keypoints,
@@ -94,7 +50,7 @@ extern "C" int sfd2_verify_matches_batch(sfd2_ctx *c, const sfd2_tri_view *views
     if (!monotone(match_offsets, n_pairs)) return fail(F + "match_offsets must start at 0 and not decrease");
     const int64_t M = match_offsets[n_pairs];
     if (M > 0 && !matches) return fail(F + "null matches");
-    if (!all_finite_f(keypoints, 2 * N)) return fail(F + "non-finite key points");
+    if (!all_finite(keypoints, 2 * N)) return fail(F + "non-finite key points");
     std::vector<TriViewDev> vd;
     std::vector<double> mf;
     std::string why;
@@ -154,11 +110,10 @@ extern "C" int sfd2_verify_matches_batch(sfd2_ctx *c, const sfd2_tri_view *views
     HIPCHECK(hipMemsetAsync(dw + o_ps, 0, 4 * (size_t)n_pairs, c->stream));
     {
         ProfScope ps(c, "verify_matches", "tri_normalise+verify+count+drop", 0.0, 16.0 * (double)N + 48.0 * (double)M);
-        launch_tri_normalise(c->stream, reinterpret_cast<const TriViewDev *>(di + o_v), n_views, reinterpret_cast<const int64_t *>(di + o_off),
-                             reinterpret_cast<const float *>(di + o_kp), N, reinterpret_cast<double2 *>(dw + o_xn));
-        launch_tri_verify(c->stream, reinterpret_cast<const TriPairDev *>(di + o_pd), n_pairs, reinterpret_cast<const int32_t *>(di + o_bp), n_blocks,
-                          reinterpret_cast<const double2 *>(dw + o_xn), reinterpret_cast<int32_t *>(dw + o_m), reinterpret_cast<int32_t *>(dw + o_bc),
-                          reinterpret_cast<int32_t *>(dw + o_pc), reinterpret_cast<int32_t *>(dw + o_ps), min_num_inliers);
+        launch_tri_normalise(c->stream, at<const TriViewDev>(di, o_v), n_views, at<const int64_t>(di, o_off), at<const float>(di, o_kp), N,
+                             at<double2>(dw, o_xn));
+        launch_tri_verify(c->stream, at<const TriPairDev>(di, o_pd), n_pairs, at<const int32_t>(di, o_bp), n_blocks, at<const double2>(dw, o_xn),
+                          at<int32_t>(dw, o_m), at<int32_t>(dw, o_bc), at<int32_t>(dw, o_pc), at<int32_t>(dw, o_ps), min_num_inliers);
     }
     HIPCHECK(hipGetLastError());
     if (M) HIPCHECK(hipMemcpyAsync(matches, dw + o_m, 8 * (size_t)M, hipMemcpyDeviceToHost, c->stream));
@@ -200,7 +155,7 @@ extern "C" int sfd2_build_tracks(sfd2_ctx *c, int64_t n_nodes, const int32_t *ed
     HIPCHECK(hipStreamSynchronize(c->stream));
     HIPCHECK(grow(c->tri_ws, ws.off));
     char *d = c->tri_ws.as<char>();
-    int32_t *par = reinterpret_cast<int32_t *>(d + o_par), *words = reinterpret_cast<int32_t *>(d + o_w);
+    int32_t *par = at<int32_t>(d, o_par), *words = at<int32_t>(d, o_w);
     if (n_edges) HIPCHECK(hipMemcpyAsync(d + o_e, edges, 8 * (size_t)n_edges, hipMemcpyHostToDevice, c->stream));
     HIPCHECK(hipMemsetAsync(words, 0, 16, c->stream));
     launch_tri_iota(c->stream, par, n_nodes);
@@ -211,7 +166,7 @@ extern "C" int sfd2_build_tracks(sfd2_ctx *c, int64_t n_nodes, const int32_t *ed
         ProfScope ps(c, "build_tracks", "tri_cc_hook+jump", 0.0, 0.0);
         for (; rounds < max_rounds && !quiet;) {
             HIPCHECK(hipMemsetAsync(words, 0, 4, c->stream));
-            launch_tri_cc_round(c->stream, reinterpret_cast<const int32_t *>(d + o_e), n_edges, par, n_nodes, words);
+            launch_tri_cc_round(c->stream, at<const int32_t>(d, o_e), n_edges, par, n_nodes, words);
             HIPCHECK(hipMemcpyAsync(w, words, 8, hipMemcpyDeviceToHost, c->stream));
             HIPCHECK(hipStreamSynchronize(c->stream));
             ++rounds;
@@ -229,20 +184,19 @@ extern "C" int sfd2_build_tracks(sfd2_ctx *c, int64_t n_nodes, const int32_t *ed
         status[0] = SFD2_TRI_ST_NOT_CONVERGED;
         return fail(F + "not converged after " + std::to_string(rounds) + " rounds (max_rounds)");
     }
-    int32_t *sl = reinterpret_cast<int32_t *>(d + o_sl), *sn = reinterpret_cast<int32_t *>(d + o_sn), *keep = reinterpret_cast<int32_t *>(d + o_keep),
-            *head = reinterpret_cast<int32_t *>(d + o_head), *pos = reinterpret_cast<int32_t *>(d + o_pos), *tid = reinterpret_cast<int32_t *>(d + o_tid);
+    int32_t *sl = at<int32_t>(d, o_sl), *sn = at<int32_t>(d, o_sn), *keep = at<int32_t>(d, o_keep), *head = at<int32_t>(d, o_head),
+            *pos = at<int32_t>(d, o_pos), *tid = at<int32_t>(d, o_tid);
     {
         ProfScope ps(c, "build_tracks", "tri_cc_sort+scan+scatter", 0.0, 0.0);
-        launch_tri_iota(c->stream, reinterpret_cast<int32_t *>(d + o_iota), n_nodes);
+        launch_tri_iota(c->stream, at<int32_t>(d, o_iota), n_nodes);
         size_t tb = tmp_sort;
-        HIPCHECK(rocprim::radix_sort_pairs(d + o_tmp, tb, par, sl, reinterpret_cast<int32_t *>(d + o_iota), sn, n, 0, (unsigned)bits, c->stream));
+        HIPCHECK(rocprim::radix_sort_pairs(d + o_tmp, tb, par, sl, at<int32_t>(d, o_iota), sn, n, 0, (unsigned)bits, c->stream));
         launch_tri_cc_flags(c->stream, sl, n_nodes, keep, head);
         tb = tmp_scan;
         HIPCHECK(rocprim::exclusive_scan(d + o_tmp, tb, keep, pos, 0, n, rocprim::plus<int32_t>(), c->stream));
         tb = tmp_scan;
         HIPCHECK(rocprim::exclusive_scan(d + o_tmp, tb, head, tid, 0, n, rocprim::plus<int32_t>(), c->stream));
-        launch_tri_cc_scatter(c->stream, sl, sn, n_nodes, keep, head, pos, tid, reinterpret_cast<int32_t *>(d + o_to), reinterpret_cast<int32_t *>(d + o_tn),
-                              words + 2);
+        launch_tri_cc_scatter(c->stream, sl, sn, n_nodes, keep, head, pos, tid, at<int32_t>(d, o_to), at<int32_t>(d, o_tn), words + 2);
     }
     HIPCHECK(hipGetLastError());
     int32_t tot[2] = {0, 0};
@@ -273,9 +227,8 @@ extern "C" int sfd2_triangulate_tracks(sfd2_ctx *c, const sfd2_tri_view *views, 
     if (!monotone(track_offsets, n_tracks)) return fail(F + "track_offsets must start at 0 and not decrease");
     const int64_t O = track_offsets[n_tracks];
     if (O > 0 && (!obs_view || !obs_xy || !obs_point)) return fail(F + "null observations");
-    for (int64_t o = 0; o < O; ++o)
-        if (obs_view[o] < 0 || obs_view[o] >= n_views) return fail(F + "observation " + std::to_string(o) + ": view index out of range");
-    if (!all_finite_f(obs_xy, 2 * O)) return fail(F + "non-finite observations");
+    if (const int64_t o = first_outside(obs_view, O, n_views); o < O) return fail(F + "observation " + std::to_string(o) + ": view index out of range");
+    if (!all_finite(obs_xy, 2 * O)) return fail(F + "non-finite observations");
     {   // the one-per-image rule looks at neighbours only: a track must not come back to a view it has left
         std::vector<int32_t> run_of(n_views, -1);            // the last track that opened a run of this view
         for (int t = 0; t < n_tracks; ++t)
@@ -328,14 +281,12 @@ extern "C" int sfd2_triangulate_tracks(sfd2_ctx *c, const sfd2_tri_view *views, 
     HIPCHECK(hipMemsetAsync(dw + o_xyz, 0, ws.off - o_xyz, c->stream));     // points, errors, counts, status
     {
         ProfScope ps(c, "triangulate_tracks", "tri_obs_prep+tri_track", 0.0, 48.0 * (double)O);
-        launch_tri_obs_prep(c->stream, reinterpret_cast<const TriViewDev *>(di + o_v), reinterpret_cast<const int32_t *>(di + o_ov),
-                            reinterpret_cast<const float *>(di + o_xy), O, reinterpret_cast<double2 *>(dw + o_px), reinterpret_cast<double2 *>(dw + o_xn));
-        launch_tri_tracks(c->stream, reinterpret_cast<const TriViewDev *>(di + o_v), cd, reinterpret_cast<const int64_t *>(di + o_off),
-                          reinterpret_cast<const int64_t *>(di + o_lab), reinterpret_cast<const int32_t *>(di + o_ord), n_tracks,
-                          reinterpret_cast<const int32_t *>(di + o_ov), reinterpret_cast<const double2 *>(dw + o_px),
-                          reinterpret_cast<const double2 *>(dw + o_xn), reinterpret_cast<signed char *>(dw + o_pt),
-                          reinterpret_cast<unsigned char *>(dw + o_tmp), reinterpret_cast<double *>(dw + o_xyz), reinterpret_cast<double *>(dw + o_err),
-                          reinterpret_cast<int32_t *>(dw + o_no), reinterpret_cast<int32_t *>(dw + o_st));
+        launch_tri_obs_prep(c->stream, at<const TriViewDev>(di, o_v), at<const int32_t>(di, o_ov), at<const float>(di, o_xy), O, at<double2>(dw, o_px),
+                            at<double2>(dw, o_xn));
+        launch_tri_tracks(c->stream, at<const TriViewDev>(di, o_v), cd, at<const int64_t>(di, o_off), at<const int64_t>(di, o_lab),
+                          at<const int32_t>(di, o_ord), n_tracks, at<const int32_t>(di, o_ov), at<const double2>(dw, o_px), at<const double2>(dw, o_xn),
+                          at<signed char>(dw, o_pt), at<unsigned char>(dw, o_tmp), at<double>(dw, o_xyz), at<double>(dw, o_err), at<int32_t>(dw, o_no),
+                          at<int32_t>(dw, o_st));
     }
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipMemcpyAsync(xyz, dw + o_xyz, 24 * P, hipMemcpyDeviceToHost, c->stream));

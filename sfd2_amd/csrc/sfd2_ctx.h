@@ -131,23 +131,36 @@ inline const char *rb_layer_name(int b, int k)
 
 struct ActInfo { bool known = false; /* registered by the last ensure_workspace */ const void *p; int f32; int planar; int c, pitch, h, w; Rec rec = Rec::None; /* f16c: the format of the corr records (their plane follows the hi plane) */ int exp2 = 0; /* stored = value * 2^exp2 (activation exponents of the fp16 family) */ bool absent = false; /* stays on chip on the path taken */ };
 
-// Scratch of the JPEG decoder (api_jpeg.hip).  Its own allocations, not DevBufs: growing them must not bump g_alloc_gen, which would
-// drop the captured graphs of the network (api_graph.hip) that never read these buffers.
-struct JpegBuf {
+// A device block that is scratch of one entry point: its own hipMalloc, NOT a DevBuf.  Growing it never bumps g_alloc_gen, so it
+// never drops the captured graphs of the network (api_graph.hip), which never read these blocks.  Users: the JPEG decoder
+// (api_jpeg.hip, with a grow() of its own that synchronises and leaves headroom) and every geometry entry point (api_pose /
+// assemble / triangulate / pairs / cluster / frames .hip), which lay the block out with api_scratch.h's Carve.
+struct ScratchBuf {
     void *p = nullptr;
     size_t cap = 0;
-    JpegBuf() = default;
-    JpegBuf(const JpegBuf &) = delete;
-    JpegBuf &operator=(const JpegBuf &) = delete;
-    ~JpegBuf() { if (p) (void)hipFree(p); }
+    ScratchBuf() = default;
+    ScratchBuf(const ScratchBuf &) = delete;
+    ScratchBuf &operator=(const ScratchBuf &) = delete;
+    ~ScratchBuf() { if (p) (void)hipFree(p); }
     template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
 };
+// at least `bytes`; the old block is freed first (hipFree waits for the device), the contents are not kept
+inline hipError_t grow(ScratchBuf &b, size_t bytes)
+{
+    if (bytes <= b.cap) return hipSuccess;
+    if (b.p) (void)hipFree(b.p);
+    b.p = nullptr;
+    b.cap = 0;
+    hipError_t e = hipMalloc(&b.p, bytes);
+    if (e == hipSuccess) b.cap = bytes;
+    return e;
+}
 struct JpegScratch {
-    JpegBuf in[2];                     // prepared buffers, uploaded through the copy stream (two, so the next upload overlaps this decode)
+    ScratchBuf in[2];                     // prepared buffers, uploaded through the copy stream (two, so the next upload overlaps this decode)
     hipEvent_t ev_copied[2] = {}, ev_free[2] = {};
     int slot = 0;
-    JpegBuf lanes, pre, coef, planes;
-    JpegBuf words;                     // sync flags (SFD2_JPEG_SYNC_LAUNCHES) and the status word
+    ScratchBuf lanes, pre, coef, planes;
+    ScratchBuf words;                     // sync flags (SFD2_JPEG_SYNC_LAUNCHES) and the status word
     ~JpegScratch()
     {
         for (int i = 0; i < 2; ++i) {
@@ -279,10 +292,11 @@ struct sfd2_ctx {
     DevBuf arena;   // aliased activation slots of the throughput path (placed by plan_pass, sized by ensure_workspace)
     DevBuf img_u8_packed;              // SFD2_FLAG_IMG_U8_X: the image as three bytes per pixel (unpack_rgbx_kernel)
     JpegScratch jpeg;                  // sfd2_jpeg_decode
-    JpegBuf asm_in, asm_ws, asm_out;    // sfd2_assemble_2d3d (api_assemble.hip): descriptors and host inputs, per-(image, key point) work, host-bound outputs
-    JpegBuf pose_in, pose_ws, pose_out; // sfd2_absolute_pose_batch / sfd2_pose_refine_batch (api_pose.hip): inputs, per-point work, results
-    JpegBuf tri_in, tri_ws;             // sfd2_verify_matches_batch / sfd2_build_tracks / sfd2_triangulate_tracks (api_triangulate.hip): inputs, work and results
-    JpegBuf pairs_in, pairs_ws;         // sfd2_pairs_retrieval / _covisibility / _poses (api_pairs.hip) and sfd2_covis_clusters / sfd2_covis_frames (api_cluster.hip, api_frames.hip, with their own copies of grow() / Carve as every api_*.hip has): uploaded inputs, partial lists / counters / slot rows and results
+    // scratch of the geometry entry points (ScratchBuf: growing one drops no captured graph; grow() above, layouts by api_scratch.h's Carve)
+    ScratchBuf asm_in, asm_ws, asm_out;     // sfd2_assemble_2d3d (api_assemble.hip): descriptors and host inputs, per-(image, key point) work, host-bound outputs
+    ScratchBuf pose_in, pose_ws, pose_out;  // sfd2_absolute_pose_batch / sfd2_pose_refine_batch (api_pose.hip): inputs, per-point work, results
+    ScratchBuf tri_in, tri_ws;              // sfd2_verify_matches_batch / sfd2_build_tracks / sfd2_triangulate_tracks (api_triangulate.hip): inputs, work and results
+    ScratchBuf pairs_in, pairs_ws;          // sfd2_pairs_retrieval / _covisibility / _poses (api_pairs.hip), sfd2_covis_clusters (api_cluster.hip) and sfd2_covis_frames (api_frames.hip): uploaded inputs, partial lists / counters / slot rows and results
     DevBuf img_scaled, ms_kp, ms_sc, ms_de, ms_keys, ms_sorted, ms_cnt;
     unsigned int ms_cand_seen[8] = {};
     int ms_cand_cap[8] = {};

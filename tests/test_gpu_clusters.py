@@ -92,6 +92,12 @@ def test_isolated_frames_and_one_cluster():
     assert _check(images, points3D, [li])[0] == [li]
 
 
+def test_a_map_without_points():
+    """Three images, no point (obs_point and track_image are empty arrays), one query listing two of them: two clusters of one."""
+    images, points3D = clr.build_map(3, [])
+    assert _check(images, points3D, [[1, 3]])[0] == [[1], [3]]
+
+
 def test_first_and_last_image_empty_frame_outside_partners_and_short_tracks(big):
     images, points3D, comps, mi = big
     n = len(images)

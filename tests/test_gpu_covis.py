@@ -141,6 +141,28 @@ def test_empty_jobs_in_a_batch():
     _equal(mi, b, want)
 
 
+@pytest.mark.parametrize("empty", ["n0_with_scores", "capacity0_k1"])
+@pytest.mark.parametrize("empty_at", [0, 1])
+def test_a_job_with_empty_arrays_beside_a_small_one(empty, empty_at):
+    """Two jobs with host inputs and host outputs: one whose key points AND scores are empty (two empty slots of the packed input),
+    or whose six output arrays have capacity 0, before or after a job of n = 8, k = 2, which is what the host loop gives."""
+    torch, _lib, covis, localize = _mods()
+    w = _world(21, k=2, n=8, all_matched=True, dup=False)
+    mi = covis.MapIndex(w["images"], w["points3D"])
+    want = _host(localize, w, 0, None)
+    assert len(want[3]) > 0
+    if empty == "n0_with_scores":
+        e = dict(matches0=None, images=[(1, -1)], kpq=np.zeros((0, 2), np.float32), scores=np.zeros(0, np.float32), obs_th=0, gate=None)
+    else:
+        e = dict(matches0=None, images=[(1, -1)], kpq=w["kpq"], scores=w["scores"], obs_th=0, gate=None, capacity=0)
+    jobs = [None, None]
+    jobs[empty_at], jobs[1 - empty_at] = e, _job(torch, w, 0, None)
+    res = localize.assemble_2d3d(_ctx(_lib), mi, jobs)
+    assert res[empty_at]["m"] == 0 and res[empty_at]["image_counts"].tolist() == [0]
+    _equal(mi, res[1 - empty_at], want)
+    assert res[1 - empty_at]["score"].tobytes() == w["scores"][res[1 - empty_at]["query_idx"]].tobytes()
+
+
 def test_gate_removes_and_keeps():
     torch, _lib, covis, localize = _mods()
     w = _world(11, k=7, n=1000)

@@ -175,6 +175,23 @@ def test_edges(selection):
     assert lists(mi, idx, n_out) == [[int(v) for v in fr.host_select(mi, t)] for t in far]
 
 
+@pytest.mark.parametrize("ref", [None, []], ids=["own_points", "empty_ref_points"])
+def test_a_host_map_without_points(ref):
+    """Three images, no point: obs_point, track_image and seen_image (and, with use_ref, ref_points) are empty arrays of a host map,
+    each a slot of its own in the uploaded block.  The one task selects nothing, with the restatement's status."""
+    import cluster_ref as clr
+    _lib, covis = _mods()
+    mi = covis.MapIndex(*clr.build_map(3, []))
+    fc = mi.frames_csr()
+    assert len(fc["ids"]) == 3 and len(fc["obs_point"]) == len(fc["track_image"]) == len(fc["seen_image"]) == 0
+    t = dict(frame_id=2, covisibility_frame=50) if ref is None else dict(frame_id=2, covisibility_frame=50, ref_3Dpoints=ref)
+    want, want_status = fr.task_select(mi, t)
+    assert want == [] and want_status == 0
+    for flags in (0, _lib.FRAMES_FLAG_GLOBAL_COUNTERS):
+        rc, idx, n_out, status = raw(mi, [t], flags=flags)
+        assert rc == 0 and n_out.tolist() == [0] and status.tolist() == [want_status] and (idx == -1).all()
+
+
 def test_bands_return_status_1_and_the_batch_the_host_list(selection):
     _lib, covis = _mods()
     images, _ = selection

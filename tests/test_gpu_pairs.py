@@ -155,6 +155,16 @@ def test_covisibility_equals_restatement_on_both_counter_paths(k):
         assert a.tobytes() == b.tobytes()
 
 
+@pytest.mark.parametrize("global_counters", (False, True))
+def test_covisibility_of_a_map_without_points(global_counters):
+    """Three images, no point: obs_point and track_image are empty arrays (null pointers), every n_found is 0."""
+    inc = dict(obs_offsets=np.zeros(4, np.int64), obs_point=np.zeros(0, np.int32), track_offsets=np.zeros(1, np.int64), track_image=np.zeros(0, np.int32))
+    ref = pr.covisibility_ref(inc, 2)
+    idx, cnt, nf = _device_covis(inc, 2, global_counters)
+    assert ref["n_found"].tolist() == [0, 0, 0] and np.array_equal(nf, ref["n_found"])
+    assert np.array_equal(idx, ref["idx"]) and np.array_equal(cnt, ref["count"])
+
+
 def test_covisibility_in_a_permuted_image_order_gives_the_same_pairs_by_name():
     inc = _incidence()
     perm = np.random.RandomState(11).permutation(len(inc["names"]))

@@ -348,3 +348,30 @@ def test_pose_refinement_degenerate_masks():
         r = _pose().pose_refinement(t, q, x, X, mask, cam)
         assert not r["success"]
         assert np.isfinite(r["qvec"]).all() and np.isfinite(r["tvec"]).all()
+
+
+@pytest.mark.parametrize("empty_at", [0, 1])
+def test_an_empty_problem_beside_a_full_one(empty_at):
+    """k = 2, one problem of n = 0 beside one of n = 8 (an empty array takes a slot of the packed input all the same): the empty one
+    fails, the other is what it is alone and what the restatement gives -- estimation and refinement."""
+    P = _pose()
+    cam = pr.camera("PINHOLE")
+    q, t, x, X, _ = pr.scene(np.random.RandomState(72), cam, 8)
+    full = 1 - empty_at
+    probs = [None, None]
+    probs[empty_at], probs[full] = (x[:0], X[:0], cam), (x, X, cam)
+    res = P.absolute_pose_estimation_batch(probs, THRESH)
+    assert not res[empty_at]["success"] and res[empty_at]["num_inliers"] == 0 and len(res[empty_at]["inliers"]) == 0
+    assert np.isfinite(res[empty_at]["qvec"]).all() and np.isfinite(res[empty_at]["tvec"]).all()
+    assert _same(res[full], P.absolute_pose_estimation(x, X, cam, THRESH))
+    ref = pr.absolute_pose_ref(x, X, cam, THRESH)
+    assert not ref["banded"] and ref["success"] and ref["num_inliers"] == 8
+    _agrees(res[full], ref)
+    mask = np.ones(8, bool)
+    probs[empty_at], probs[full] = (t, q, x[:0], X[:0], mask[:0], cam), (t, q, x, X, mask, cam)
+    res = P.pose_refinement_batch(probs)
+    assert not res[empty_at]["success"]
+    alone = P.pose_refinement(t, q, x, X, mask, cam)
+    assert res[full]["success"] and np.array_equal(res[full]["qvec"], alone["qvec"]) and np.array_equal(res[full]["tvec"], alone["tvec"])
+    qr, tr = pr.refine_cauchy(cam, q, t, x, X, mask, iters=1000)
+    assert pr.rot_angle(res[full]["qvec"], qr) <= 1e-6 and np.linalg.norm(res[full]["tvec"] - tr) <= 1e-6 * np.linalg.norm(tr)
