@@ -148,6 +148,193 @@ def make_poses(seed, n=300):
     return q, t
 
 
+# ------------------------------------------------------------------------------------- inputs whose answer is decided (top-k seams)
+# the cases of tests/test_gpu_pairs_topk.py, guarded without a GPU by tests/test_pairs_host.py
+TOPK_EXACT = (70, 600, 16)                                                    # (nq, nd, d) of exact_descriptors(TOPK_EXACT_SEED, ...)
+TOPK_EXACT_SEED = 21
+TOPK_EXACT_KS = (1, 63, 64, 65, 127, 128, 129, 191, 192, 193, 255, 256)
+# (nq, nd, d, k, splits): d = 1 and k = nd; a db row alone in the second tile, d one past a 16-group, everybody selected; d one past
+# a 32-chunk, a row alone in the second query strip; the vector loader below 16 columns with the largest LDS request; the vector
+# loader with a partial second group; 65 tiles over 64 splits
+TOPK_EXACT_SHAPES = ((3, 64, 1, 64, 0), (5, 129, 17, 129, 0), (65, 257, 33, 129, 0), (2, 256, 4, 256, 0), (1, 128, 20, 128, 0),
+                     (130, 8300, 8, 200, 64))
+TOPK_GENERAL = ((11, 70, 300, 64, 256), (12, 65, 257, 33, 129), (15, 130, 1000, 20, 193))       # (seed, nq, nd, d, k) of make_descriptors
+TOPK_ORDER = (17, 600, 64)                                                    # (seed, nd, d): one query, the db rows reordered
+TOPK_ORDER_KS = (64, 65, 256)
+TOPK_DENSE_SEED, TOPK_DENSE_KS = 3, (63, 64, 65, 128, 129, 192, 193, 255, 256)
+TOPK_STAR_SIZES, TOPK_STAR_KS = (63, 64, 65, 127, 128, 129, 255, 256, 257), (64, 128, 256)
+TOPK_ORDERED_N = 300
+TOPK_FIELD_SEED, TOPK_FIELD_N, TOPK_FIELD_KS = 5, 1100, (1024, 1023, 961, 960, 513, 320)
+TOPK_DUP_GROUPS = ([5, 280, 555, 830, 1099], [10, 11], list(range(300, 370)))  # the first: one member in each wave's quarter
+TOPK_LINE_KS = (64, 1024)
+
+
+def exact_descriptors(seed, nq, nd, d):
+    """(query [nq, d], db [nd, d]) fp32 with entries from {-1, 0, 1}: every product and partial sum is a small integer, so every
+    fp32 summation order, fused or not, gives the exact similarity, and nearly every neighbouring pair of a ranking is a tie."""
+    rs = np.random.RandomState(seed)
+    return rs.randint(-1, 2, (nq, d)).astype(np.float32), rs.randint(-1, 2, (nd, d)).astype(np.float32)
+
+
+def reorder_by_similarity(query_row, db, direction):
+    """db with its rows permuted so that the exact similarity to query_row ascends with the row ('ascending'), descends
+    ('descending'), or takes the two halves of the ascending order in turns ('interleaved')."""
+    sim = db.astype(np.float64) @ np.asarray(query_row, dtype=np.float64)
+    order = np.argsort(sim, kind="stable")
+    if direction == "descending":
+        order = order[::-1]
+    elif direction == "interleaved":
+        half = (len(order) + 1) // 2
+        mixed = np.empty_like(order)
+        mixed[0::2], mixed[1::2] = order[:half], order[half:]
+        order = mixed
+    elif direction != "ascending":
+        raise ValueError(direction)
+    return np.ascontiguousarray(db[order])
+
+
+def _csr(obs, tracks):
+    oo = np.concatenate([[0], np.cumsum([len(o) for o in obs])]).astype(np.int64)
+    to = np.concatenate([[0], np.cumsum([len(t) for t in tracks])]).astype(np.int64)
+    cat = lambda parts: np.concatenate([np.asarray(p, dtype=np.int32) for p in parts]).astype(np.int32)  # noqa: E731
+    return {"obs_offsets": oo, "obs_point": cat(obs), "track_offsets": to, "track_image": cat(tracks)}
+
+
+def _csr_of_tracks(n_images, tracks):
+    obs = [[] for _ in range(n_images)]
+    for p, t in enumerate(tracks):
+        for im in t:
+            obs[im].append(p)
+    return _csr(obs, tracks)
+
+
+def dense_incidence(seed, n_images=400, n_points=30000, track=(2, 5)):
+    """A map in which every image shares points with most others: each track is a uniform draw of track[0] .. track[1] distinct
+    images.  The CSR arrays of make_incidence."""
+    rs = np.random.RandomState(seed)
+    tracks = [rs.choice(n_images, rs.randint(track[0], track[1] + 1), replace=False) for _ in range(n_points)]
+    return _csr_of_tracks(n_images, tracks)
+
+
+def star_incidence(sizes):
+    """One hub image per entry m of sizes, sharing exactly one point with each of m partners of its own (no partner serves two
+    hubs, partners share nothing with each other): every count of a hub is 1, its order is index order and its n_found is m.  A hub
+    sits in the middle of its partners' index range.  The CSR arrays plus 'hubs' (the hub's index per entry)."""
+    tracks, hubs, base = [], [], 0
+    for m in sizes:
+        hub = base + m // 2
+        hubs.append(hub)
+        tracks.extend([hub, j] for j in range(base, base + m + 1) if j != hub)
+        base += m + 1
+    out = _csr_of_tracks(base, tracks)
+    out["hubs"] = np.asarray(hubs)
+    return out
+
+
+def ordered_incidence(n, direction):
+    """Image 0 shares j + 1 points ('ascending') or n - j points ('descending') with image j = 1 .. n - 1, and nobody shares anything
+    else: in index order every count of row 0 is a new best, or none is."""
+    if direction not in ("ascending", "descending"):
+        raise ValueError(direction)
+    tracks = []
+    for j in range(1, n):
+        tracks.extend([0, j] for _ in range(j + 1 if direction == "ascending" else n - j))
+    return _csr_of_tracks(n, tracks)
+
+
+def pose_field(seed, n, dup_groups=()):
+    """(qvec [n, 4], tvec [n, 3]): yaw uniform in +-10 degrees (any two images within 20 degrees of each other), centres uniform in
+    a cube of side 40.  dup_groups: index lists whose rows become bit-identical copies, qvec and tvec, of the list's first row."""
+    rs = np.random.RandomState(seed)
+    yaw = np.deg2rad(rs.uniform(-10, 10, n))
+    centres = rs.uniform(-20, 20, (n, 3))
+    q, t = np.zeros((n, 4)), np.zeros((n, 3))
+    for i in range(n):
+        q[i] = [np.cos(yaw[i] / 2), 0.0, 0.0, np.sin(yaw[i] / 2)]
+        t[i] = -qvec2rotmat(q[i]) @ centres[i]
+    for group in dup_groups:
+        q[group[1:]], t[group[1:]] = q[group[0]], t[group[0]]
+    return q, t
+
+
+def pose_line(n, direction):
+    """(qvec, tvec): identity rotations, image 0 at the origin and image j at x = n - j ('decreasing': in index order every image
+    is nearer to image 0 than all before it) or x = j ('increasing').  Neighbouring distances from image 0 differ by 1 in at most n."""
+    if direction not in ("decreasing", "increasing"):
+        raise ValueError(direction)
+    q, t = np.zeros((n, 4)), np.zeros((n, 3))
+    q[:, 0] = 1.0
+    j = np.arange(1, n)
+    t[1:, 0] = -(n - j if direction == "decreasing" else j)       # the position is -R t = -t
+    return q, t
+
+
+def _sequential_topk(scores, k, indices=None):
+    """(profile of insertion_profile, the final list as [(score, index)], best first)."""
+    import bisect
+    scores = np.asarray(scores)
+    indices = np.arange(len(scores)) if indices is None else np.asarray(indices)
+    keys, profile = [], []                                       # keys: (-score, index) ascending = best first
+    for s, i in zip(scores.tolist(), indices.tolist()):
+        key = (-s, i)
+        if len(keys) == k and not key < keys[-1]:
+            continue
+        pos = bisect.bisect_left(keys, key)
+        profile.append((pos // 64, min(len(keys), k - 1) // 64))
+        keys.insert(pos, key)
+        del keys[k:]
+    return profile, [(-a, b) for a, b in keys]
+
+
+def insertion_profile(scores_in_offer_order, k, indices=None):
+    """'Keep the k best, better score first then smaller index', restated as a sequential insertion (indices default to the offer
+    position).  For every accepted candidate (pos // 64, min(len_before, k - 1) // 64): the register of the device's list (entry p in
+    lane p & 63 of register p >> 6) the candidate lands in, and the last register its insertion shifts.  A guard for the tests'
+    inputs, not a reference."""
+    return _sequential_topk(scores_in_offer_order, k, indices)[0]
+
+
+def retrieval_offers(sim_row, splits, k):
+    """The sequences of (scores, indices) that the retrieval kernels offer to pairs_topk_scan for one query row: per split the
+    similarities of its 128-row tiles in row order, then the merge's concatenation of the splits' lists."""
+    nd = len(sim_row)
+    tiles = (nd + 127) // 128
+    splits = max(1, min(splits, tiles, 64))
+    offers, merged_s, merged_i = [], [], []
+    for s in range(splits):
+        c0, c1 = min(nd, (s * tiles // splits) * 128), min(nd, ((s + 1) * tiles // splits) * 128)
+        offers.append((sim_row[c0:c1], np.arange(c0, c1)))
+        kept = _sequential_topk(sim_row[c0:c1], k, np.arange(c0, c1))[1]
+        merged_s.extend(x for x, _ in kept)
+        merged_i.extend(i for _, i in kept)
+    offers.append((np.asarray(merged_s), np.asarray(merged_i, dtype=np.int64)))
+    return offers
+
+
+def poses_offers(dist_row, valid_row, k):
+    """The same for the poses kernel and one image: four waves take a quarter of the images each, then wave 0 is offered the lists
+    of waves 1 to 3 in turn.  Scores are -distance; the merge's three sequences come last."""
+    n = len(dist_row)
+    lists, offers = [], []
+    for w in range(4):
+        j = np.arange(w * n // 4, (w + 1) * n // 4)
+        j = j[valid_row[j]]
+        offers.append((-dist_row[j], j))
+        lists.append(_sequential_topk(-dist_row[j], k, j)[1])
+    for w in range(1, 4):
+        offers.append((np.array([s for s, _ in lists[w]]), np.array([i for _, i in lists[w]], dtype=np.int64)))
+    return offers, lists[0]
+
+
+def profile_of_offers(offers, k, start=()):
+    """The classes insertion_profile reports when the sequences of offers[...] go into one list in turn (start: the list's content
+    before the first), and the number of accepted candidates."""
+    scores = np.concatenate([np.asarray([s for s, _ in start], dtype=np.float64)] + [np.asarray(s, dtype=np.float64) for s, _ in offers])
+    idx = np.concatenate([np.asarray([i for _, i in start], dtype=np.int64)] + [np.asarray(i, dtype=np.int64) for _, i in offers])
+    profile = insertion_profile(scores, k, idx)[len(start):]
+    return set(profile), len(profile)
+
+
 # ---------------------------------------------------------------------------------------------------------------- restatement
 def _rank(score, valid=None):
     """Candidate indices of one row by (score descending, index ascending); invalid ones dropped."""

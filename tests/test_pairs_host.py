@@ -1,6 +1,7 @@
 """The pair selection, the parts that need no GPU: the numpy restatement (tests/pairs_ref.py) against the pair files the reference's
 three scripts wrote (tests/golden/pairs.npz, tests/golden/gen_pairs_goldens.py), the caps on the banded share the GPU tests rely on,
-the CSR builder, the written file's format and the command lines."""
+the CSR builder, the written file's format and the command lines; and the guards of tests/test_gpu_pairs_topk.py: that its generated
+inputs are what they claim, and that its cases insert into, and shift across, every register of the device's top-k list."""
 import os
 
 import numpy as np
@@ -108,6 +109,262 @@ def test_poses_gates():
     assert pr.poses_ref(q, t, 10, 1e-3)["n_found"].max() == 0
     every = pr.poses_ref(q, t, pr.POSES_N - 1, 181.0)
     assert (every["n_found"] == pr.POSES_N - 1).all() and (np.diff(every["dist"], axis=1) >= 0).all()
+
+
+# ------------------------------------------------------------------------------------------- guards of tests/test_gpu_pairs_topk.py
+def _classes(k):
+    """Every (register a candidate lands in, last register its insertion shifts) a list of k entries has."""
+    regs = (k + 63) // 64
+    return {(a, b) for b in range(regs) for a in range(b + 1)}
+
+
+@pytest.mark.parametrize("d", (16, 100))
+def test_exact_descriptors_give_integer_similarities_and_mostly_ties(d):
+    nq, nd, k = 70, 600, 256
+    q, db = pr.exact_descriptors(pr.TOPK_EXACT_SEED, nq, nd, d)
+    assert q.dtype == np.float32 and db.dtype == np.float32 and set(np.unique(q)) == {-1.0, 0.0, 1.0} == set(np.unique(db))
+    ref = pr.retrieval_ref(q, db, k)
+    assert np.array_equal(ref["sim64"], np.rint(ref["sim64"])) and np.abs(ref["sim64"]).max() <= d
+    ties = (np.diff(ref["exact"], axis=1) == 0).mean()
+    distinct = [len(np.unique(r)) for r in ref["sim64"]]
+    print(f"exact descriptors {nq} x {nd} x {d}: equal neighbours among the first {k + 1} {ties:.3f}, distinct values per row {min(distinct)} .. {max(distinct)}")
+    assert ties >= 0.5
+    q2, db2 = pr.exact_descriptors(pr.TOPK_EXACT_SEED, nq, nd, d)
+    assert np.array_equal(q, q2) and np.array_equal(db, db2)
+
+
+@pytest.mark.parametrize("case", range(len(pr.TOPK_GENERAL)))
+def test_general_descriptor_cases_of_the_topk_tests_stay_under_the_band_cap(case):
+    seed, nq, nd, d, k = pr.TOPK_GENERAL[case]
+    ref = pr.retrieval_ref(*pr.make_descriptors(seed, nq, nd, d), k)
+    print(f"retrieval {nq} x {nd} x {d}, k = {k}: banded share {ref['band'].mean():.4f}")
+    assert ref["band"].mean() <= 0.10
+
+
+def test_reordered_db_cases_stay_under_the_band_cap_and_are_ordered():
+    seed, nd, d = pr.TOPK_ORDER
+    q, db = pr.make_descriptors(seed, 1, nd, d)
+    base = np.sort(db.astype(np.float64) @ q[0].astype(np.float64))
+    for direction in ("ascending", "descending", "interleaved"):
+        db2 = pr.reorder_by_similarity(q[0], db, direction)
+        sim = db2.astype(np.float64) @ q[0].astype(np.float64)
+        assert np.array_equal(np.sort(sim), base)
+        if direction == "ascending":
+            assert (np.diff(sim) >= 0).all()
+        elif direction == "descending":
+            assert (np.diff(sim) <= 0).all()
+        else:
+            assert (np.diff(sim[0::2]) >= 0).all() and (np.diff(sim[1::2]) >= 0).all() and sim[0::2].max() <= sim[1::2].min()
+        for k in pr.TOPK_ORDER_KS:
+            share = pr.retrieval_ref(q, db2, k)["band"].mean()
+            print(f"retrieval 1 x {nd} x {d} {direction}, k = {k}: banded share {share:.4f}")
+            assert share <= 0.10
+
+
+def test_retrieval_cases_reach_every_register_and_seam_at_k_256():
+    """Union over what the tile epilogue and the split merge are offered in the k = 256 cases of the GPU tests."""
+    k, seen = 256, set()
+    seed, nq, nd, d, _ = pr.TOPK_GENERAL[0]
+    q, db = pr.make_descriptors(seed, nq, nd, d)
+    sim = (q.astype(np.float64) @ db.astype(np.float64).T).astype(np.float32)
+    for row in range(0, nq, 7):
+        for splits in (1, 2, 3):
+            for offer in pr.retrieval_offers(sim[row], splits, k):
+                seen |= pr.profile_of_offers([offer], k)[0]
+    qe, dbe = pr.exact_descriptors(pr.TOPK_EXACT_SEED, *pr.TOPK_EXACT)
+    sime = qe @ dbe.T
+    for row in range(0, len(qe), 7):
+        for splits in (1, 5):                                        # 5: what the call chooses for 600 db rows
+            for offer in pr.retrieval_offers(sime[row], splits, k):
+                seen |= pr.profile_of_offers([offer], k)[0]
+    seed, nd, d = pr.TOPK_ORDER
+    q, db = pr.make_descriptors(seed, 1, nd, d)
+    for direction in ("ascending", "descending", "interleaved"):
+        db2 = pr.reorder_by_similarity(q[0], db, direction)
+        s = (db2.astype(np.float64) @ q[0].astype(np.float64)).astype(np.float32)
+        assert len(np.unique(s)) == nd                               # fp32 keeps the order strict
+        epilogue = pr.retrieval_offers(s, 1, k)[0]
+        classes, accepted = pr.profile_of_offers([epilogue], k)
+        seen |= classes
+        if direction == "ascending":                                 # every candidate a new best: position 0, the whole list shifts
+            assert accepted == nd and classes == {(0, b) for b in range(4)}
+        if direction == "descending":
+            assert accepted == k and classes == {(b, b) for b in range(4)}
+    assert seen == _classes(k)
+
+
+@pytest.fixture(scope="module")
+def dense_ref():
+    inc = pr.dense_incidence(pr.TOPK_DENSE_SEED)
+    return inc, pr.covisibility_ref(inc, 256)
+
+
+def test_dense_incidence_fills_every_list_with_few_distinct_counts(dense_ref):
+    inc, ref = dense_ref
+    assert len(inc["obs_offsets"]) == 401 and len(inc["track_offsets"]) == 30001
+    lengths = np.diff(inc["track_offsets"])
+    assert lengths.min() == 2 and lengths.max() == 5
+    assert all(len(set(inc["track_image"][a:b].tolist())) == b - a for a, b in zip(inc["track_offsets"][:200], inc["track_offsets"][1:201]))
+    distinct = np.mean([len(np.unique(c[c > 0])) for c in ref["counts"]])
+    print(f"dense incidence: n_found {ref['n_found'].min()} .. {ref['n_found'].max()}, distinct positive counts per row {distinct:.1f}, "
+          f"positions tied with a neighbour {ref['band'].mean():.3f}")
+    assert ref["n_found"].min() == 256 and ref["n_found"].max() == 256
+    assert distinct < 16
+    again = pr.dense_incidence(pr.TOPK_DENSE_SEED)
+    assert all(np.array_equal(inc[key], again[key]) for key in inc)
+
+
+def test_star_and_ordered_incidence_have_the_counts_they_promise():
+    sizes = pr.TOPK_STAR_SIZES
+    inc = pr.star_incidence(sizes)
+    assert len(inc["obs_offsets"]) - 1 == sum(sizes) + len(sizes)
+    for k in pr.TOPK_STAR_KS:
+        ref = pr.covisibility_ref(inc, k)
+        assert ref["n_found"][inc["hubs"]].tolist() == [min(m, k) for m in sizes]
+        others = np.delete(np.arange(len(ref["n_found"])), inc["hubs"])
+        assert (ref["n_found"][others] == 1).all() and (ref["counts"].max() == 1)
+        for hub, m in zip(inc["hubs"], sizes):                       # all ties: the partners in index order, from both sides of the hub
+            row = ref["idx"][hub, :min(m, k)]
+            assert (np.diff(row) > 0).all() and row[0] < hub and (m // 2 >= k or row[-1] > hub)
+    n = pr.TOPK_ORDERED_N
+    for direction in ("ascending", "descending"):
+        c = pr.covisibility_counts(pr.ordered_incidence(n, direction), 0)
+        assert c.tolist() == [0] + [j + 1 if direction == "ascending" else n - j for j in range(1, n)]
+
+
+def test_covisibility_cases_reach_every_register_and_seam_at_k_256(dense_ref):
+    k, seen = 256, set()
+    counts = dense_ref[1]["counts"]
+    for row in range(0, len(counts), 10):
+        j = np.nonzero(counts[row] > 0)[0]
+        seen |= pr.profile_of_offers([(counts[row, j], j)], k)[0]
+    star = pr.star_incidence(pr.TOPK_STAR_SIZES)
+    for hub, m in zip(star["hubs"], pr.TOPK_STAR_SIZES):
+        c = pr.covisibility_counts(star, hub)
+        j = np.nonzero(c > 0)[0]
+        classes, accepted = pr.profile_of_offers([(c[j], j)], k)
+        assert accepted == min(m, k)                                 # all ties: appended until the list is full, then refused
+        seen |= classes
+    n = pr.TOPK_ORDERED_N
+    for direction in ("ascending", "descending"):
+        c = pr.covisibility_counts(pr.ordered_incidence(n, direction), 0)
+        classes, accepted = pr.profile_of_offers([(c[1:], np.arange(1, n))], k)
+        assert accepted == (n - 1 if direction == "ascending" else k)
+        assert classes == ({(0, b) for b in range(4)} if direction == "ascending" else {(b, b) for b in range(4)})
+        seen |= classes
+    assert seen == _classes(k)
+
+
+@pytest.fixture(scope="module")
+def field_refs():
+    n, k = pr.TOPK_FIELD_N, 1024
+    plain = pr.pose_field(pr.TOPK_FIELD_SEED, n)
+    dup = pr.pose_field(pr.TOPK_FIELD_SEED, n, pr.TOPK_DUP_GROUPS)
+    return plain, pr.poses_ref(*plain, k, 30.0), dup, pr.poses_ref(*dup, k + 1, 30.0)
+
+
+def test_pose_field_fills_every_list_and_bands_nothing(field_refs):
+    (q, t), ref, _, _ = field_refs
+    n = pr.TOPK_FIELD_N
+    assert np.allclose(np.linalg.norm(q, axis=1), 1.0) and (q[:, 1:3] == 0).all()
+    yaw = np.rad2deg(2 * np.arctan2(q[:, 3], q[:, 0]))
+    centres = np.stack([-pr.qvec2rotmat(qi).T @ ti for qi, ti in zip(q, t)])
+    assert np.abs(yaw).max() <= 10 and np.abs(centres).max() <= 20 and np.abs(centres).max() > 19
+    print(f"pose field n = {n}: banded positions {int(ref['band'].sum())}, gate-banded pairs {int(ref['rot_band'].sum())}, "
+          f"largest dR {ref['dR'].max():.2f} deg")
+    assert (ref["n_found"] == 1024).all()
+    assert not ref["band"].any() and not ref["rot_band"].any()
+    assert ref["dR"].max() < 20.001
+
+
+def test_pose_field_duplicates_band_exactly_their_own_positions(field_refs):
+    _, _, (q, t), ref1 = field_refs
+    k = 1024
+    for group in pr.TOPK_DUP_GROUPS:
+        assert all(q[j].tobytes() == q[group[0]].tobytes() and t[j].tobytes() == t[group[0]].tobytes() for j in group)
+    assert [j * 4 // pr.TOPK_FIELD_N for j in pr.TOPK_DUP_GROUPS[0]] == [0, 1, 2, 3, 3]      # a member in every wave's quarter
+    ref = pr.poses_ref(q, t, k, 30.0)
+    assert np.array_equal(ref["idx"], ref1["idx"][:, :k])
+    group_of = np.full(len(q), -1)
+    for g, group in enumerate(pr.TOPK_DUP_GROUPS):
+        group_of[group] = g
+    g = group_of[ref1["idx"]]                                        # [n, k + 1]: the group of every ranked candidate, the (k + 1)-th too
+    same_next = (g[:, :-1] == g[:, 1:]) & (g[:, :-1] >= 0)
+    want = same_next[:, :k].copy()
+    want[:, 1:] |= same_next[:, :k - 1]
+    share = ref["band"].mean()
+    print(f"pose field with duplicate groups of {[len(x) for x in pr.TOPK_DUP_GROUPS]}: banded positions {share:.4f}")
+    assert np.array_equal(ref["band"], want)                         # a group member next to another of its group, and nothing else
+    assert 0 < share < 0.10 and not ref["rot_band"].any()
+
+
+def test_pose_line_is_strictly_ordered_from_image_0():
+    n = pr.TOPK_FIELD_N
+    for direction in ("decreasing", "increasing"):
+        q, t = pr.pose_line(n, direction)
+        dist, dR = pr.pose_tables(q, t)
+        step = np.diff(dist[0, 1:])
+        assert (dR == 0).all() and ((step < 0).all() if direction == "decreasing" else (step > 0).all())
+        assert np.abs(step).min() / dist[0].max() > 1e-4             # far above the 1e-9 of the band
+        for k in pr.TOPK_LINE_KS:
+            ref = pr.poses_ref(q, t, k, 30.0)
+            assert not ref["band"][0].any() and ref["n_found"][0] == k
+
+
+def test_poses_cases_reach_every_register_and_seam_at_k_1024(field_refs):
+    """Two models of the offer order.  In index order, as one sequence, the cases produce every class (a, b).  The kernel offers a
+    quarter of the images to each of four waves and then waves 1 to 3's sorted lists to wave 0's: there a list beyond 275 entries
+    grows only by merging, where the j-th entry of a sorted list lands at or behind position j, so some classes cannot occur with
+    1100 images ((0, 15) needs 960 entries in front of a list's first 64).  What the shift's code distinguishes per register c does
+    occur: a candidate landing in c with and without a tail behind it, and a shift through the seam in front of c."""
+    k, seen, in_index_order = 1024, set(), set()
+    regs = k // 64
+    (q, t), ref, _, _ = field_refs
+    valid = ref["dR"] < 30.0
+    np.fill_diagonal(valid, False)
+
+    def offer(dist, ok):
+        offers, start = pr.poses_offers(dist, ok, k)
+        per_wave = [pr.profile_of_offers([o], k) for o in offers[:4]]                 # the four waves' own passes
+        merged = pr.profile_of_offers(offers[4:], k, start)                           # waves 1 to 3 into wave 0's list
+        j = np.nonzero(ok)[0]
+        plain = pr.insertion_profile(-dist[j], k, j)
+        return per_wave, merged, plain
+
+    for row in range(0, pr.TOPK_FIELD_N, 37):
+        per_wave, merged, plain = offer(ref["dist_all"][row], valid[row])
+        seen |= set().union(*(c for c, _ in per_wave)) | merged[0]
+        in_index_order |= set(plain)
+    for direction in ("decreasing", "increasing"):
+        ql, tl = pr.pose_line(pr.TOPK_FIELD_N, direction)
+        per_wave, merged, plain = offer(np.abs(tl[:, 0] - tl[0, 0]), np.arange(len(tl)) != 0)
+        for (classes, accepted), j0 in zip(per_wave, range(4)):
+            assert accepted == (j0 + 1) * len(tl) // 4 - j0 * len(tl) // 4 - (j0 == 0)   # a quarter never fills a list of 1024
+            assert all(a == 0 for a, _ in classes) if direction == "decreasing" else all(a == b for a, b in classes)
+            seen |= classes
+        seen |= merged[0]
+        in_index_order |= set(plain)
+        if direction == "decreasing":                                # every candidate a new best
+            assert len(plain) == len(tl) - 1 and set(plain) == {(0, b) for b in range(regs)}
+    assert in_index_order == _classes(k)
+    print(f"poses k = {k}: classes reached in index order {len(in_index_order)}, in the kernel's offer order {len(seen)} of {len(_classes(k))}")
+    for c in range(regs):
+        assert (c, c) in seen
+        assert c == regs - 1 or any(a == c and b > c for a, b in seen)
+        assert c == 0 or any(a < c <= b for a, b in seen)
+
+
+def test_insertion_profile_is_the_sequential_top_k():
+    rs = np.random.RandomState(0)
+    scores = rs.randint(0, 9, 500)
+    for k in (1, 64, 65, 200):
+        kept = pr._sequential_topk(scores, k)[1]
+        order = np.lexsort((np.arange(500), -scores))[:k]
+        assert [i for _, i in kept] == order.tolist()
+        prof = pr.insertion_profile(scores, k)
+        assert all(0 <= a <= b < (k + 63) // 64 for a, b in prof) and k <= len(prof) <= 500
+    assert pr.insertion_profile(np.arange(200), 130) == [(0, min(i, 129) // 64) for i in range(200)]
+    assert pr.insertion_profile(-np.arange(200), 130) == [(i // 64, i // 64) for i in range(130)]
 
 
 def test_csr_builder_follows_dict_order_and_sorted_point_table():
