@@ -85,7 +85,7 @@ typedef struct {
     int64_t n_candidates; /* N0 after NMS + threshold + border of the last extract          */
 } sfd2_timings;
 
-int sfd2_version(void);   /* 100 = rounds 1-4; 105 adds sfd2_extract_record_async, sfd2_desc_pack and host outputs with SFD2_FLAG_ASYNC; 106 adds sfd2_get_margin_status; 107 adds sfd2_get_relax_status (option "c3b_plain"); 108 adds sfd2_get_option, sfd2_device_pci_bus_id, SFD2_FLAG_DESC_STORE64; 109 adds the baseline JPEG decoder (sfd2_jpeg_*); 112 adds the SfM map (sfd2_verify_matches_batch, sfd2_build_tracks, sfd2_triangulate_tracks); 113 adds the pair selection (sfd2_pairs_retrieval, sfd2_pairs_covisibility, sfd2_pairs_poses); 114 adds sfd2_covis_clusters; 115 adds sfd2_covis_frames */
+int sfd2_version(void);   /* 100 = rounds 1-4; 105 adds sfd2_extract_record_async, sfd2_desc_pack and host outputs with SFD2_FLAG_ASYNC; 106 adds sfd2_get_margin_status; 107 adds sfd2_get_relax_status (option "c3b_plain"); 108 adds sfd2_get_option, sfd2_device_pci_bus_id, SFD2_FLAG_DESC_STORE64; 109 adds the baseline JPEG decoder (sfd2_jpeg_*); 112 adds the SfM map (sfd2_verify_matches_batch, sfd2_build_tracks, sfd2_triangulate_tracks); 113 adds the pair selection (sfd2_pairs_retrieval, sfd2_pairs_covisibility, sfd2_pairs_poses); 114 adds sfd2_covis_clusters; 115 adds sfd2_covis_frames; 116 adds the VLAD global descriptors (sfd2_vlad_assign, sfd2_vlad_aggregate, sfd2_vlad_kmeans) */
 const char *sfd2_last_error(void);
 
 int sfd2_ctx_create(int device, sfd2_ctx **out);
@@ -804,6 +804,48 @@ typedef struct {
 } sfd2_frames_task;
 int sfd2_covis_frames(sfd2_ctx *ctx, const sfd2_frames_map *map, const sfd2_frames_task *tasks, int n_tasks, const int64_t *ref_offsets,
                       const int32_t *ref_points, int cap, int32_t *idx, int32_t *n_out, int32_t *status, int flags);
+
+/* ------------------------------------------------------------------------------------------------ global descriptors (VLAD)
+ * What sfd2_pairs_retrieval ranks by: per image one vector aggregated from its local descriptors (Jegou et al. 2010, with the
+ * intra-normalisation of Arandjelovic & Zisserman 2013) over a k-means vocabulary learnt by Lloyd iterations on the device.  The
+ * project's own choice, not a port: the reference retrieves with NetVLAD / AP-GeM descriptors extracted by another project.
+ * Conventions of the pair-selection section: outputs and offsets are host arrays, inputs_on_device says whether x and centroids
+ * are host (0) or device (1) pointers, the calls run on sfd2_get_stream() and synchronise before they return, and return -1 with
+ * sfd2_last_error() set on a bad argument (before anything is uploaded) or on non-finite input.  Rows and centroids are
+ * SFD2_VLAD_DIM floats; 1 <= k <= SFD2_VLAD_MAX_K, any k.  flags must be 0.  The arithmetic is part of the interface:
+ *   h_j     = 0.5f * (fmaf chain of c_j[e] * c_j[e] over ascending e, from 0)
+ *   dot_j   = fmaf chain of x[e] * c_j[e] over ascending e, from 0 (the f32-input MFMA)
+ *   s_j     = dot_j - h_j, one fp32 subtraction; a row goes to the j of largest s_j, a tie to the smaller j
+ *   V[j][e] = the sum, over the segment's rows i in ascending order with assignment j, of (x[i][e] - c_j[e]): an fp32 subtraction,
+ *             then an fp32 addition (k-means sums x[i][e] itself and counts the rows)
+ *   norms   in fp64 from the fp32 sums, every output component rounded to fp32 once.  INTRA: each centroid's 128 values divided by
+ *           their L2 norm (a zero block stays zero), then the whole vector by its L2 norm; SSR: sign(v) sqrt(|v|) per component,
+ *           then the L2 norm; NONE: the L2 norm only.  A zero vector stays zero: nothing is ever NaN.
+ * A row's or an image's result depends on that row or image and the centroids only -- not on the batch, its order or the grid.
+ * No floating-point atomics. */
+#define SFD2_VLAD_DIM 128
+#define SFD2_VLAD_MAX_K 256
+#define SFD2_VLAD_CHUNK 4096
+#define SFD2_VLAD_NORM_INTRA 0
+#define SFD2_VLAD_NORM_SSR 1
+#define SFD2_VLAD_NORM_NONE 2
+/* x[n][128], centroids[k][128]: assign[n] and, unless NULL, score[n] = s of the chosen centroid.  n >= 1. */
+int sfd2_vlad_assign(sfd2_ctx *ctx, const float *x, int64_t n, const float *centroids, int k, int inputs_on_device,
+                     int32_t *assign, float *score /* or NULL */, int flags);
+/* Image i owns the rows offsets[i] .. offsets[i + 1] - 1 of x (offsets[n_images + 1], from 0, not decreasing; an image may have
+ * any number of rows, 0 included: its vector is zero).  out[n_images][k * 128]; assign, unless NULL, receives offsets[n_images]
+ * assignments.  n_images >= 1. */
+int sfd2_vlad_aggregate(sfd2_ctx *ctx, const float *x, const int64_t *offsets, int n_images, const float *centroids, int k,
+                        int inputs_on_device, int norm, float *out /* [n_images][k * 128] */, int32_t *assign /* or NULL */, int flags);
+/* Lloyd iterations from the k start centroids in centroids[k][128] (always a host array, overwritten with the result); x stays on
+ * the device across the iterations.  An iteration assigns, sums the rows and counts them per centroid within every chunk of
+ * SFD2_VLAD_CHUNK consecutive rows (fp32, row order), adds the chunks' partial sums in ascending chunk order in fp64 and sets
+ * centroid = (float)(sum / count); a centroid without rows keeps its value.  moved[it] is the number of rows whose assignment
+ * differs from the previous iteration's (n for the first); the call stops after the first iteration with moved == 0 or after
+ * max_iters (>= 1).  counts[k]: the rows per centroid under the last iteration's assignment; moved[max_iters], -1 for an iteration
+ * that did not run; *iters_run. */
+int sfd2_vlad_kmeans(sfd2_ctx *ctx, const float *x, int64_t n, int k, int max_iters, int inputs_on_device,
+                     float *centroids /* in: start, out: result */, int64_t *counts, int64_t *moved, int *iters_run, int flags);
 
 #ifdef __cplusplus
 }

@@ -146,6 +146,8 @@ PAIRS_FLAG_GLOBAL_COUNTERS, PAIRS_FLAG_CENTRES = 1, 2
 CLUSTER_MAX_FRAMES, CLUSTER_LDS_IMAGES, CLUSTER_FLAG_GLOBAL_SLOTS = 256, 65536, 1   # SFD2_CLUSTER_*
 FRAMES_OBS, FRAMES_POS = 0, 1                                                       # SFD2_FRAMES_*
 FRAMES_MAX_CANDIDATES, FRAMES_LDS_IMAGES, FRAMES_FLAG_GLOBAL_COUNTERS = 4096, 16384, 1
+VLAD_DIM, VLAD_MAX_K, VLAD_CHUNK = 128, 256, 4096                                   # SFD2_VLAD_*
+VLAD_NORM_INTRA, VLAD_NORM_SSR, VLAD_NORM_NONE = 0, 1, 2
 
 
 class FramesMap(ctypes.Structure):
@@ -181,7 +183,7 @@ EXPORTS = [
     "sfd2_jpeg_parse", "sfd2_jpeg_prepare", "sfd2_jpeg_decode", "sfd2_absolute_pose_batch", "sfd2_pose_refine_batch",
     "sfd2_assemble_2d3d", "sfd2_verify_matches_batch", "sfd2_build_tracks", "sfd2_triangulate_tracks",
     "sfd2_pairs_retrieval", "sfd2_pairs_covisibility", "sfd2_pairs_poses", "sfd2_covis_clusters",
-    "sfd2_covis_frames",
+    "sfd2_covis_frames", "sfd2_vlad_assign", "sfd2_vlad_aggregate", "sfd2_vlad_kmeans",
 ]
 
 _lib = None
@@ -277,10 +279,13 @@ def load():
     lib.sfd2_pairs_poses.argtypes = [vp, vp, vp, ci, ci, cd, vp, vp, vp, ci]
     lib.sfd2_covis_clusters.argtypes = [vp, vp, vp, ci, vp, vp, ci, vp, vp, ci, vp, vp, ci]
     lib.sfd2_covis_frames.argtypes = [vp, ctypes.POINTER(FramesMap), ctypes.POINTER(FramesTask), ci, vp, vp, ci, vp, vp, vp, ci]
+    lib.sfd2_vlad_assign.argtypes = [vp, vp, i64, vp, ci, ci, vp, vp, ci]
+    lib.sfd2_vlad_aggregate.argtypes = [vp, vp, vp, ci, vp, ci, ci, ci, vp, vp, ci]
+    lib.sfd2_vlad_kmeans.argtypes = [vp, vp, i64, ci, ci, ci, vp, vp, vp, pi, ci]
     for name in EXPORTS:
         getattr(lib, name)  # raises AttributeError if the .so lacks a declared symbol
-    if lib.sfd2_version() < 115:
-        raise RuntimeError(f"{LIB_PATH} is version {lib.sfd2_version()}, this binding needs >= 115 (rebuild: __graft_entry__.build())")
+    if lib.sfd2_version() < 116:
+        raise RuntimeError(f"{LIB_PATH} is version {lib.sfd2_version()}, this binding needs >= 116 (rebuild: __graft_entry__.build())")
     _lib = lib
     return lib
 

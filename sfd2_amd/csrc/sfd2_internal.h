@@ -808,6 +808,20 @@ hipError_t launch_pairs_covis(hipStream_t st, const int64_t *obs_off, const int3
 hipError_t launch_pairs_poses(hipStream_t st, const double *qvec, const double *tvec, int n, int k, double thr_deg, int centres, double *rc,
                               int32_t *idx, double *dist, int32_t *n_found);
 
+// ------------------------------------------------------------------------------------------------ global descriptors (vlad_kernels.hip)
+// rows and centroids are [.][SFD2_VLAD_DIM] fp32 on the device; half = h_j of include/sfd2_hip.h; 1 <= k <= SFD2_VLAD_MAX_K
+hipError_t launch_vlad_half_norms(hipStream_t st, const float *centroids, int k, float *half);
+// assign[n] is read before it is written: moved (or NULL) receives the number of rows whose assignment changed; score may be NULL
+hipError_t launch_vlad_assign(hipStream_t st, const float *x, int64_t n, const float *centroids, const float *half, int k, int32_t *assign,
+                              float *score, unsigned long long *moved);
+// one workgroup per segment: offsets[n_seg + 1] (device), or NULL for chunks of SFD2_VLAD_CHUNK rows of the n.  norm >= 0: residual sums,
+// normalised, to out[n_seg][k][128]; norm < 0: plain sums to out and the rows per centroid to cnt[n_seg][k].  Assignments outside [0, k) are skipped.
+hipError_t launch_vlad_aggregate(hipStream_t st, const float *x, int64_t n, const int64_t *offsets, int64_t n_seg, const float *centroids, int k,
+                                 const int32_t *assign, int norm, float *out, int32_t *cnt);
+// centroid = (float)(fp64 sum of the chunks' partial sums, ascending / count) where count > 0; counts[k]
+hipError_t launch_vlad_update(hipStream_t st, const float *part_sum, const int32_t *part_cnt, int64_t n_chunks, int k, float *centroids,
+                              long long *counts);
+
 // ------------------------------------------------------------------------------------------------ covisibility clustering (cluster_kernels.hip)
 // the image -> list-position table (16 bits per image) stays in LDS up to SFD2_CLUSTER_LDS_IMAGES images (128 KB beside the 12 KB of
 // adjacency bits and per-frame words), else it is a row of global scratch per workgroup that arrives filled with 0xffff
