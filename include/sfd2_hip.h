@@ -85,7 +85,7 @@ typedef struct {
     int64_t n_candidates; /* N0 after NMS + threshold + border of the last extract          */
 } sfd2_timings;
 
-int sfd2_version(void);   /* 100 = rounds 1-4; 105 adds sfd2_extract_record_async, sfd2_desc_pack and host outputs with SFD2_FLAG_ASYNC; 106 adds sfd2_get_margin_status; 107 adds sfd2_get_relax_status (option "c3b_plain"); 108 adds sfd2_get_option, sfd2_device_pci_bus_id, SFD2_FLAG_DESC_STORE64; 109 adds the baseline JPEG decoder (sfd2_jpeg_*); 112 adds the SfM map (sfd2_verify_matches_batch, sfd2_build_tracks, sfd2_triangulate_tracks); 113 adds the pair selection (sfd2_pairs_retrieval, sfd2_pairs_covisibility, sfd2_pairs_poses); 114 adds sfd2_covis_clusters; 115 adds sfd2_covis_frames; 116 adds the VLAD global descriptors (sfd2_vlad_assign, sfd2_vlad_aggregate, sfd2_vlad_kmeans) */
+int sfd2_version(void);   /* 100 = rounds 1-4; 105 adds sfd2_extract_record_async, sfd2_desc_pack and host outputs with SFD2_FLAG_ASYNC; 106 adds sfd2_get_margin_status; 107 adds sfd2_get_relax_status (option "c3b_plain"); 108 adds sfd2_get_option, sfd2_device_pci_bus_id, SFD2_FLAG_DESC_STORE64; 109 adds the baseline JPEG decoder (sfd2_jpeg_*); 112 adds the SfM map (sfd2_verify_matches_batch, sfd2_build_tracks, sfd2_triangulate_tracks); 113 adds the pair selection (sfd2_pairs_retrieval, sfd2_pairs_covisibility, sfd2_pairs_poses); 114 adds sfd2_covis_clusters; 115 adds sfd2_covis_frames; 116 adds the VLAD global descriptors (sfd2_vlad_assign, sfd2_vlad_aggregate, sfd2_vlad_kmeans); 117 adds sfd2_relative_pose_batch */
 const char *sfd2_last_error(void);
 
 int sfd2_ctx_create(int device, sfd2_ctx **out);
@@ -573,6 +573,47 @@ int sfd2_absolute_pose_batch(sfd2_ctx *ctx, const sfd2_pose_problem *problems, i
  * inlier_mask, cfg), it_loc/localize_cv2.py:451. */
 int sfd2_pose_refine_batch(sfd2_ctx *ctx, const sfd2_pose_problem *problems, int k, const double *qvec_tvec_in,
                            const uint8_t *inlier_mask_u8, sfd2_pose_result *results, int flags);
+
+/* ------------------------------------------------------------------------------------------------ relative pose
+ * The calibrated two-view geometry of a matched pair, which COLMAP estimates inside matches_importer (hloc/triangulation.py:114,
+ * hloc/reconstruction.py:145), for many pairs of any sizes in one launch: LO-RANSAC over the five-point solver with fp64 scoring
+ * on the squared Sampson error, a refinement of the 5 pose parameters on the same error over the RANSAC inliers, and the choice
+ * among the four decompositions by the points in front of both cameras.  Essential matrix only: a rotation-only
+ * pair shows in the triangulation angles.  Results depend on the pair and the seed only and are bit-reproducible. */
+typedef struct {
+    int32_t n;                      /* correspondences                                                                     */
+    int32_t model0, model1;         /* SFD2_CAM_* of the two images; any other id is an error                              */
+    int32_t reserved;
+    double params0[8], params1[8];  /* the models' parameters in COLMAP order (unused tail ignored)                       */
+    const double *points2D_0;       /* host [n][2] pixels in image 0                                                       */
+    const double *points2D_1;       /* host [n][2] pixels in image 1                                                       */
+    double max_error_px;            /* inlier threshold in pixels: (max_error_px / mean of the two mean focal lengths)^2
+                                       bounds the squared Sampson error in normalised coordinates                         */
+} sfd2_two_view_problem;
+typedef struct {
+    double min_inlier_ratio;        /* limits max_num_trials as COLMAP's RANSAC does                                       */
+    int64_t min_num_trials, max_num_trials;
+    double confidence;
+    uint64_t seed;                  /* trial i of every pair draws its sample from (seed, i) only                         */
+    int32_t min_num_inliers;        /* success needs at least this many RANSAC inliers                                     */
+    int32_t reserved;
+} sfd2_two_view_conf;
+typedef struct {
+    int32_t success;                /* 1: num_inliers >= min_num_inliers and a decomposition has points in front of both
+                                       cameras; 0 otherwise, also with fewer than 5 correspondences (outputs finite)       */
+    int32_t num_inliers;            /* RANSAC inliers                                                                      */
+    int32_t num_trials;             /* RANSAC trials run                                                                   */
+    int32_t reserved;
+    double qvec[4];                 /* w, x, y, z: camera 0 to camera 1, x1 = R(qvec) x0 + tvec                            */
+    double tvec[3];                 /* unit length                                                                         */
+    double E[9];                    /* [tvec]x R(qvec), row-major: x1^T E x0 = 0 in normalised coordinates                 */
+} sfd2_two_view_result;
+
+/* k pairs; results[k]; inlier_mask_u8 and tri_angle_deg: host, sum(n) entries, the pairs concatenated in order: the RANSAC inlier
+ * mask, and the angle in degrees at the (midpoint-)triangulated point between the rays to the two centres, NaN for an outlier
+ * and for a point not in front of both cameras.  Non-finite input or a bad model / parameter is an error (-1).  flags: 0. */
+int sfd2_relative_pose_batch(sfd2_ctx *ctx, const sfd2_two_view_problem *problems, int k, const sfd2_two_view_conf *conf,
+                             sfd2_two_view_result *results, uint8_t *inlier_mask_u8, double *tri_angle_deg, int flags);
 
 /* ------------------------------------------------------------------------------------------------ 2D-3D assembly
  * Matches -> 2D-3D correspondences for a batch of jobs in one call: the per-key-point loops of it_loc/localize_cv2.py:571-632

@@ -102,6 +102,25 @@ class PoseResult(ctypes.Structure):
                 ("qvec", ctypes.c_double * 4), ("tvec", ctypes.c_double * 3)]
 
 
+class TwoViewProblem(ctypes.Structure):
+    """sfd2_two_view_problem (include/sfd2_hip.h)."""
+    _fields_ = [("n", ctypes.c_int32), ("model0", ctypes.c_int32), ("model1", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("params0", ctypes.c_double * 8), ("params1", ctypes.c_double * 8), ("points2D_0", ctypes.c_void_p),
+                ("points2D_1", ctypes.c_void_p), ("max_error_px", ctypes.c_double)]
+
+
+class TwoViewConf(ctypes.Structure):
+    """sfd2_two_view_conf (include/sfd2_hip.h)."""
+    _fields_ = [("min_inlier_ratio", ctypes.c_double), ("min_num_trials", ctypes.c_int64), ("max_num_trials", ctypes.c_int64),
+                ("confidence", ctypes.c_double), ("seed", ctypes.c_uint64), ("min_num_inliers", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class TwoViewResult(ctypes.Structure):
+    """sfd2_two_view_result (include/sfd2_hip.h)."""
+    _fields_ = [("success", ctypes.c_int32), ("num_inliers", ctypes.c_int32), ("num_trials", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("qvec", ctypes.c_double * 4), ("tvec", ctypes.c_double * 3), ("E", ctypes.c_double * 9)]
+
+
 class PointTable(ctypes.Structure):
     """sfd2_point_table (include/sfd2_hip.h)."""
     _fields_ = [("xyz", ctypes.c_void_p), ("track_len", ctypes.c_void_p), ("n_points", ctypes.c_int32), ("reserved", ctypes.c_int32)]
@@ -184,6 +203,7 @@ EXPORTS = [
     "sfd2_assemble_2d3d", "sfd2_verify_matches_batch", "sfd2_build_tracks", "sfd2_triangulate_tracks",
     "sfd2_pairs_retrieval", "sfd2_pairs_covisibility", "sfd2_pairs_poses", "sfd2_covis_clusters",
     "sfd2_covis_frames", "sfd2_vlad_assign", "sfd2_vlad_aggregate", "sfd2_vlad_kmeans",
+    "sfd2_relative_pose_batch",
 ]
 
 _lib = None
@@ -269,6 +289,7 @@ def load():
     lib.sfd2_jpeg_decode.argtypes = [vp, vp, i64, ctypes.POINTER(JpegInfo), ci, vp, i64, vp, ci]
     lib.sfd2_absolute_pose_batch.argtypes = [vp, ctypes.POINTER(PoseProblem), ci, ctypes.POINTER(PoseConf), ctypes.POINTER(PoseResult), vp, ci]
     lib.sfd2_pose_refine_batch.argtypes = [vp, ctypes.POINTER(PoseProblem), ci, vp, vp, ctypes.POINTER(PoseResult), ci]
+    lib.sfd2_relative_pose_batch.argtypes = [vp, ctypes.POINTER(TwoViewProblem), ci, ctypes.POINTER(TwoViewConf), ctypes.POINTER(TwoViewResult), vp, vp, ci]
     lib.sfd2_assemble_2d3d.argtypes = [vp, ctypes.POINTER(PointTable), ctypes.POINTER(AssembleJob), ci, ci, ci]
     cd = ctypes.c_double
     lib.sfd2_verify_matches_batch.argtypes = [vp, ctypes.POINTER(TriView), ci, vp, vp, vp, vp, ci, vp, cd, ci, vp, vp, ci]
@@ -284,8 +305,8 @@ def load():
     lib.sfd2_vlad_kmeans.argtypes = [vp, vp, i64, ci, ci, ci, vp, vp, vp, pi, ci]
     for name in EXPORTS:
         getattr(lib, name)  # raises AttributeError if the .so lacks a declared symbol
-    if lib.sfd2_version() < 116:
-        raise RuntimeError(f"{LIB_PATH} is version {lib.sfd2_version()}, this binding needs >= 116 (rebuild: __graft_entry__.build())")
+    if lib.sfd2_version() < 117:
+        raise RuntimeError(f"{LIB_PATH} is version {lib.sfd2_version()}, this binding needs >= 117 (rebuild: __graft_entry__.build())")
     _lib = lib
     return lib
 

@@ -1,5 +1,6 @@
-// libsfd2hip: the camera model shared by the pose kernels (pose_kernels.hip), the 2D-3D assembly's reprojection gate
-// (assemble_kernels.hip) and the SfM map kernels (tri_kernels.hip): COLMAP's cameras in OPENCV form (PoseCam, sfd2_internal.h), fp64, pure arithmetic.
+// libsfd2hip: the camera model shared by the pose kernels (pose_kernels.hip, two_view_kernels.hip), the 2D-3D assembly's reprojection gate
+// (assemble_kernels.hip) and the SfM map kernels (tri_kernels.hip): COLMAP's cameras in OPENCV form (PoseCam, sfd2_internal.h), and the
+// rotation <-> quaternion pair of the two pose kernels; fp64, pure arithmetic.
 #pragma once
 #include "sfd2_internal.h"
 
@@ -57,4 +58,27 @@ SFD2_PD void quat_to_rot(double w, double x, double y, double z, double R[9])
     R[0] = 1 - 2 * (y * y + z * z); R[1] = 2 * (x * y - w * z);     R[2] = 2 * (x * z + w * y);
     R[3] = 2 * (x * y + w * z);     R[4] = 1 - 2 * (x * x + z * z); R[5] = 2 * (y * z - w * x);
     R[6] = 2 * (x * z - w * y);     R[7] = 2 * (y * z + w * x);     R[8] = 1 - 2 * (x * x + y * y);
+}
+
+// unit quaternion (w >= 0) of a (nearly) orthonormal R
+SFD2_PD void rot_to_quat(const double R[9], double q[4])
+{
+    const double tr = R[0] + R[4] + R[8];
+    double w, x, y, z;
+    if (tr > 0) {
+        const double s = 0.5 / sqrt(tr + 1.0);
+        w = 0.25 / s; x = (R[7] - R[5]) * s; y = (R[2] - R[6]) * s; z = (R[3] - R[1]) * s;
+    } else if (R[0] > R[4] && R[0] > R[8]) {
+        const double s = 2.0 * sqrt(1.0 + R[0] - R[4] - R[8]);
+        w = (R[7] - R[5]) / s; x = 0.25 * s; y = (R[1] + R[3]) / s; z = (R[2] + R[6]) / s;
+    } else if (R[4] > R[8]) {
+        const double s = 2.0 * sqrt(1.0 + R[4] - R[0] - R[8]);
+        w = (R[2] - R[6]) / s; x = (R[1] + R[3]) / s; y = 0.25 * s; z = (R[5] + R[7]) / s;
+    } else {
+        const double s = 2.0 * sqrt(1.0 + R[8] - R[0] - R[4]);
+        w = (R[3] - R[1]) / s; x = (R[2] + R[6]) / s; y = (R[5] + R[7]) / s; z = 0.25 * s;
+    }
+    const double nq = sqrt(w * w + x * x + y * y + z * z);
+    const double sg = (w < 0 ? -1.0 : 1.0) / nq;
+    q[0] = w * sg; q[1] = x * sg; q[2] = y * sg; q[3] = z * sg;
 }

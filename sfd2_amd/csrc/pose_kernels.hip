@@ -52,29 +52,7 @@ SFD2_PD double det_cols(const double a[3], const double b[3], const double c[3])
     return dot3(a, x);
 }
 
-// (quat_to_rot: pose_camera.h)
-// unit quaternion (w >= 0) of a (nearly) orthonormal R
-SFD2_PD void rot_to_quat(const double R[9], double q[4])
-{
-    const double tr = R[0] + R[4] + R[8];
-    double w, x, y, z;
-    if (tr > 0) {
-        const double s = 0.5 / sqrt(tr + 1.0);
-        w = 0.25 / s; x = (R[7] - R[5]) * s; y = (R[2] - R[6]) * s; z = (R[3] - R[1]) * s;
-    } else if (R[0] > R[4] && R[0] > R[8]) {
-        const double s = 2.0 * sqrt(1.0 + R[0] - R[4] - R[8]);
-        w = (R[7] - R[5]) / s; x = 0.25 * s; y = (R[1] + R[3]) / s; z = (R[2] + R[6]) / s;
-    } else if (R[4] > R[8]) {
-        const double s = 2.0 * sqrt(1.0 + R[4] - R[0] - R[8]);
-        w = (R[2] - R[6]) / s; x = (R[1] + R[3]) / s; y = 0.25 * s; z = (R[5] + R[7]) / s;
-    } else {
-        const double s = 2.0 * sqrt(1.0 + R[8] - R[0] - R[4]);
-        w = (R[3] - R[1]) / s; x = (R[2] + R[6]) / s; y = (R[5] + R[7]) / s; z = 0.25 * s;
-    }
-    const double nq = sqrt(w * w + x * x + y * y + z * z);
-    const double sg = (w < 0 ? -1.0 : 1.0) / nq;
-    q[0] = w * sg; q[1] = x * sg; q[2] = y * sg; q[3] = z * sg;
-}
+// (quat_to_rot, rot_to_quat: pose_camera.h)
 SFD2_PD void orthonormalise(double R[9])
 {
     double q[4];

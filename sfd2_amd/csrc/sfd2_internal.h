@@ -730,6 +730,29 @@ struct PoseResDev {
 void launch_pose(hipStream_t st, const PoseProbDev *probs, int k, const PoseConfDev &conf, const double *p2, const double *p3, float4 *xf4,
                  float2 *xf2, double2 *xn, double *hyp, const unsigned char *mask_in, unsigned char *mask_out, PoseResDev *res);
 
+// ------------------------------------------------------------------------------------------------ relative pose (two_view_kernels.hip)
+#define SFD2_TV_WG 256                // threads of a pair's workgroup = RANSAC trials per round
+#define SFD2_TV_CAND 10               // essential matrices per trial at the most
+struct TvProbDev {
+    int64_t off;                      // first correspondence of the pair in the concatenated arrays
+    int32_t n, pad;
+    PoseCam cam0, cam1;
+    double thresh2;                   // (max_error_px / mean of the two mean focal lengths)^2, on the squared Sampson error
+};
+struct TvConfDev {
+    int64_t max_trials, min_trials;   // max_trials already limited by min_inlier_ratio
+    double confidence;
+    uint64_t seed;
+    int32_t min_num_inliers, pad;
+};
+struct TvResDev {
+    double q[4], t[3], E[9];
+    int32_t success, num_inliers, num_trials, pad;
+};
+// p0 / p1: pixels [N][2]; x0 / x1: work, normalised points [N]; hyp: work, k * SFD2_TV_WG * SFD2_TV_CAND * 9 doubles
+void launch_two_view(hipStream_t st, const TvProbDev *probs, int k, const TvConfDev &conf, const double *p0, const double *p1, double2 *x0,
+                     double2 *x1, double *hyp, unsigned char *mask_out, double *angle_out, TvResDev *res);
+
 // ------------------------------------------------------------------------------------------------ 2D-3D assembly (assemble_kernels.hip)
 #define SFD2_ASM_WG 256               // key points of one (job, image, chunk) block
 #define SFD2_ASM_ST_MATCH_RANGE 1     // status bits of AsmResDev: a match index >= the image's table length

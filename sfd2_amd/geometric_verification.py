@@ -1,0 +1,118 @@
+"""Geometric verification of a match store without poses: what `colmap matches_importer` does to the matches before COLMAP maps or
+triangulates them (hloc/triangulation.py:114, hloc/reconstruction.py:145), on the device through sfd2_amd.two_view.  For every pair of
+the pair list the relative pose is estimated from the pair's matches (five-point LO-RANSAC); the output store holds the
+input's groups and datasets with the rejected entries of matches0 set to -1, so that match_features' readers,
+`triangulation --skip_geometric_verification` and the localiser read it as they read any other match store.
+
+  python -m sfd2_amd.geometric_verification --pairs P --features F --matches M --output V
+         (--reference_sfm_model R | --intrinsics LIST...) [--max_error 4 --min_num_inliers 15 --relative_poses T]
+
+Intrinsics come from a COLMAP binary model (its poses go unused) or from lists `name model width height params...`
+(parsers.parse_image_lists_with_intrinsics).  A pair with an image without intrinsics is skipped, as triangulation.read_inputs skips
+it; a pair the match store lacks is an error.  --relative_poses writes one line per verified pair:
+name0 name1 success num_inliers qw qx qy qz tx ty tz tri_angle_deg."""
+import argparse
+import logging
+from pathlib import Path
+from types import SimpleNamespace
+
+import numpy as np
+
+from . import colmap_io, feature_io, parsers, two_view
+from .match_features import names_to_pair
+
+
+def read_cameras(reference_sfm_model=None, intrinsics=()):
+    """image name -> camera dict, from a COLMAP model and / or lists with intrinsics (a list entry wins)."""
+    out = {}
+    if reference_sfm_model is not None:
+        cameras = colmap_io.read_cameras_binary(Path(reference_sfm_model) / "cameras.bin")
+        for im in colmap_io.read_images_binary(Path(reference_sfm_model) / "images.bin").values():
+            out[im.name] = cameras[im.camera_id]
+    for lst in intrinsics or ():
+        out.update(dict(parsers.query_cameras(lst)))
+    if not out:
+        raise ValueError("no intrinsics: give --reference_sfm_model or --intrinsics")
+    return out
+
+
+def _write_group(store, name, arrays):
+    if hasattr(store, "write_group"):
+        store.write_group(name, arrays)
+        return
+    grp = store.create_group(name)
+    for k, v in arrays.items():
+        grp.create_dataset(k, data=v)
+
+
+def main(pairs, features, matches, output, reference_sfm_model=None, intrinsics=(), max_error=4.0,
+         min_num_inliers=two_view.DEFAULTS["min_num_inliers"], relative_poses=None, device=0, **ransac):
+    """Returns the per-pair result dicts of two_view.verify_pairs_two_view, keyed by (name0, name1)."""
+    name_cam = read_cameras(reference_sfm_model, intrinsics)
+    with open(str(pairs), "r") as f:
+        listed = [p.split() for p in f.readlines() if p.strip()]
+    ids = {}
+    todo, seen = [], set()
+    feats = feature_io.open_store(features, "r")
+    src = feature_io.open_store(matches, "r")
+    try:
+        for name0, name1 in listed:
+            if name0 not in name_cam or name1 not in name_cam or (name0, name1) in seen:
+                continue
+            pair = names_to_pair(name0, name1)
+            if pair not in src:
+                raise ValueError(f"Could not find pair {(name0, name1)} in {matches}")
+            seen |= {(name0, name1), (name1, name0)}
+            for n in (name0, name1):
+                ids.setdefault(n, len(ids))
+            todo.append((name0, name1, pair))
+        keypoints = {i: np.asarray(feats[n]["keypoints"].__array__(), dtype=np.float32).reshape(-1, 2)[:, :2] for n, i in ids.items()}
+        groups = {pair: {k: np.asarray(src[pair][k].__array__()) for k in src[pair].keys()} for _, _, pair in todo}
+    finally:
+        feats.close()
+        src.close()
+    images = {i: SimpleNamespace(camera_id=i, name=n) for n, i in ids.items()}
+    cameras = {i: name_cam[n] for n, i in ids.items()}
+    pair_matches = []
+    for name0, name1, pair in todo:
+        m0 = groups[pair]["matches0"].reshape(-1).astype(np.int64)
+        pair_matches.append((ids[name0], ids[name1], np.stack([np.arange(len(m0)), m0], 1)))
+    logging.info("Verifying %d pairs over %d images...", len(todo), len(ids))
+    m, off, _, results = two_view.verify_pairs_two_view(cameras, images, keypoints, pair_matches, max_error, min_num_inliers, device, **ransac)
+    dst = feature_io.open_store(output, "w")
+    try:
+        for p, (_, _, pair) in enumerate(todo):
+            g = dict(groups[pair])
+            kept = m[off[p]:off[p + 1], 1]
+            g["matches0"] = np.where(kept >= 0, g["matches0"].reshape(-1), -1).astype(g["matches0"].dtype).reshape(g["matches0"].shape)
+            _write_group(dst, pair, g)
+    finally:
+        dst.close()
+    if relative_poses is not None:
+        with open(str(relative_poses), "w") as f:
+            for (name0, name1, _), r in zip(todo, results):
+                vals = [*r["qvec"], *r["tvec"], r["tri_angle_deg"]]
+                f.write(f"{name0} {name1} {int(r['success'])} {r['num_inliers']} " + " ".join(f"{v:.17g}" for v in vals) + "\n")
+    return {(n0, n1): r for (n0, n1, _), r in zip(todo, results)}
+
+
+def parser():
+    p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    p.add_argument("--pairs", type=Path, required=True)
+    p.add_argument("--features", type=Path, required=True)
+    p.add_argument("--matches", type=Path, required=True)
+    p.add_argument("--output", type=Path, required=True)
+    p.add_argument("--reference_sfm_model", type=Path)
+    p.add_argument("--intrinsics", type=Path, nargs="+", default=[])
+    p.add_argument("--max_error", type=float, default=4.0)
+    p.add_argument("--min_num_inliers", type=int, default=two_view.DEFAULTS["min_num_inliers"])
+    p.add_argument("--relative_poses", type=Path)
+    return p
+
+
+if __name__ == "__main__":
+    args = parser().parse_args()
+    if args.reference_sfm_model is None and not args.intrinsics:
+        parser().error("one of --reference_sfm_model and --intrinsics is required")
+    logging.basicConfig(level=logging.INFO)
+    main(**args.__dict__)

@@ -1,0 +1,121 @@
+"""Relative pose on the device (include/sfd2_hip.h sfd2_relative_pose_batch): the calibrated two-view geometry COLMAP estimates inside
+`colmap matches_importer` (hloc/triangulation.py:114, hloc/reconstruction.py:145) -- five-point LO-RANSAC on the squared Sampson error,
+a refinement over the inliers and the cheirality choice.  Essential matrix only; a rotation-only pair is reported
+through the triangulation angle (`small_baseline`), not through a homography.
+
+Conventions: qvec = (w, x, y, z), camera 0 to camera 1, x1 = R(qvec) x0 + tvec with |tvec| = 1; E = [tvec]x R.  points2D are pixel
+coordinates taken as given; a camera is the dict of sfd2_amd.pose (model, params in COLMAP's order).  RANSAC defaults are COLMAP's
+two-view ones: max_error 4 px, confidence 0.999, max_num_trials 10000, min_num_trials 0, min_inlier_ratio 0.25, min_num_inliers 15.
+The result depends on the pair and the seed only.  Nothing here computes on the CPU: without a GPU the calls raise."""
+import ctypes
+
+import numpy as np
+
+try:        # torch's HIP runtime first (see sfd2_amd/jpeg.py)
+    import torch  # noqa: F401
+except Exception:  # pragma: no cover
+    pass
+
+from . import _lib
+from .pose import camera_model
+
+DEFAULTS = dict(min_inlier_ratio=0.25, min_num_trials=0, max_num_trials=10000, confidence=0.999, seed=0, min_num_inliers=15,
+                min_tri_angle=1.5)
+
+
+def _problem(points2D0, points2D1, camera0, camera1, max_error_px, keep):
+    p0 = np.ascontiguousarray(points2D0, dtype=np.float64).reshape(-1, 2)
+    p1 = np.ascontiguousarray(points2D1, dtype=np.float64).reshape(-1, 2)
+    if p0.shape[0] != p1.shape[0]:
+        raise ValueError(f"{p0.shape[0]} points in image 0 for {p1.shape[0]} in image 1")
+    if not (np.isfinite(p0).all() and np.isfinite(p1).all()):
+        raise ValueError("non-finite correspondences")
+    (m0, q0), (m1, q1) = camera_model(camera0), camera_model(camera1)
+    keep += [p0, p1]
+    pr = _lib.TwoViewProblem()
+    pr.n = p0.shape[0]
+    pr.model0, pr.model1 = m0, m1
+    for i in range(8):
+        pr.params0[i] = q0[i]
+        pr.params1[i] = q1[i]
+    pr.points2D_0 = p0.ctypes.data if p0.size else None
+    pr.points2D_1 = p1.ctypes.data if p1.size else None
+    pr.max_error_px = float(max_error_px)
+    return pr
+
+
+def relative_pose_batch(problems, max_error_px=4.0, min_inlier_ratio=DEFAULTS["min_inlier_ratio"], min_num_trials=DEFAULTS["min_num_trials"],
+                        max_num_trials=DEFAULTS["max_num_trials"], confidence=DEFAULTS["confidence"], seed=DEFAULTS["seed"],
+                        min_num_inliers=DEFAULTS["min_num_inliers"], min_tri_angle=DEFAULTS["min_tri_angle"], device=0):
+    """problems: a list of (points2D0 [n,2], points2D1 [n,2], camera0, camera1) or (..., max_error_px).  One device call; returns one
+    dict per pair, as relative_pose does."""
+    keep, probs = [], []
+    for p in problems:
+        probs.append(_problem(p[0], p[1], p[2], p[3], p[4] if len(p) > 4 else max_error_px, keep))
+    k = len(probs)
+    if k == 0:
+        return []
+    ctx = _lib.default_context(device)
+    arr = (_lib.TwoViewProblem * k)(*probs)
+    conf = _lib.TwoViewConf(float(min_inlier_ratio), int(min_num_trials), int(max_num_trials), float(confidence), int(seed) & (2 ** 64 - 1),
+                            int(min_num_inliers), 0)
+    res = (_lib.TwoViewResult * k)()
+    total = sum(pr.n for pr in probs)
+    mask = np.zeros(max(total, 1), dtype=np.uint8)
+    angle = np.full(max(total, 1), np.nan, dtype=np.float64)
+    _lib.check(ctx.lib.sfd2_relative_pose_batch(ctx.h, arr, k, ctypes.byref(conf), res, mask.ctypes.data, angle.ctypes.data, 0))
+    out, o = [], 0
+    for i, pr in enumerate(probs):
+        r, m, a = res[i], mask[o:o + pr.n].astype(bool), angle[o:o + pr.n].copy()
+        o += pr.n
+        fin = a[m & np.isfinite(a)]
+        med = float(np.median(fin)) if fin.size else float("nan")
+        out.append({"success": bool(r.success), "qvec": np.array(r.qvec[:], dtype=np.float64), "tvec": np.array(r.tvec[:], dtype=np.float64),
+                    "E": np.array(r.E[:], dtype=np.float64).reshape(3, 3), "num_inliers": int(r.num_inliers), "inliers": m,
+                    "num_trials": int(r.num_trials), "tri_angles_deg": a, "tri_angle_deg": med, "small_baseline": bool(med < min_tri_angle)})
+    return out
+
+
+def relative_pose(points2D0, points2D1, camera0, camera1, max_error_px=4.0, **ransac):
+    """The relative pose of one matched pair.  Returns {'success', 'qvec', 'tvec', 'E' [3,3], 'num_inliers', 'inliers' (bool [n]),
+    'num_trials', 'tri_angle_deg' (the median over the inliers with a finite angle, NaN when there are none), 'tri_angles_deg' [n],
+    'small_baseline' (tri_angle_deg < min_tri_angle, default 1.5)}; **ransac: relative_pose_batch's keywords.  Fewer than 5
+    correspondences: success False."""
+    return relative_pose_batch([(points2D0, points2D1, camera0, camera1)], max_error_px, **ransac)[0]
+
+
+def verify_pairs_two_view(cameras, images, keypoints, pair_matches, max_error=4.0, min_num_inliers=DEFAULTS["min_num_inliers"], device=0,
+                          **ransac):
+    """triangulation.verify_pairs without poses: every pair's relative pose is estimated from its matches (the poses in `images` are
+    ignored), the RANSAC inliers stay.  pair_matches: [(image id 0, image id 1, matches [m, 2])].  Returns (matches int32 [M, 2] of all
+    pairs concatenated with the rejected rows (-1, -1), offsets int64 [n_pairs + 1], counts int32 [n_pairs] = inliers of a pair before
+    the min_num_inliers rule, the pairs' relative_pose dicts).  Rows that come in negative stay rejected, a pair of an image with
+    itself and a pair below min_num_inliers (or without success) lose all; an index beyond an image's key points raises.  Key points
+    are taken as float32 plus COLMAP's +0.5, as verify_pairs takes them."""
+    kps = {}
+    problems, rows_of, ms = [], [], []
+    off = np.zeros(len(pair_matches) + 1, dtype=np.int64)
+    for p, (i0, i1, m) in enumerate(pair_matches):
+        m = np.asarray(m).reshape(-1, 2).astype(np.int32)
+        ms.append(m)
+        off[p + 1] = off[p] + len(m)
+        for i in (i0, i1):
+            if i not in kps:
+                kps[i] = np.asarray(keypoints[i], dtype=np.float32).reshape(-1, 2).astype(np.float64) + 0.5
+        live = np.flatnonzero((m[:, 0] >= 0) & (m[:, 1] >= 0))
+        for col, i in ((0, i0), (1, i1)):
+            if live.size and m[live, col].max() >= len(kps[i]):
+                raise ValueError(f"pair {p}: match index {int(m[live, col].max())} beyond the {len(kps[i])} key points of image {i}")
+        if i0 == i1:
+            live = live[:0]
+        rows_of.append(live)
+        problems.append((kps[i0][m[live, 0]], kps[i1][m[live, 1]], cameras[images[i0].camera_id], cameras[images[i1].camera_id]))
+    results = relative_pose_batch(problems, max_error, min_num_inliers=min_num_inliers, device=device, **ransac)
+    out = np.full((int(off[-1]), 2), -1, dtype=np.int32)
+    counts = np.zeros(len(pair_matches), dtype=np.int32)
+    for p, (live, r) in enumerate(zip(rows_of, results)):
+        counts[p] = r["num_inliers"]
+        if r["success"] and r["num_inliers"] >= min_num_inliers:
+            keep = live[r["inliers"]]
+            out[off[p] + keep] = ms[p][keep]
+    return out, off, counts, results

@@ -1,0 +1,106 @@
+"""The restatement of the relative pose solver (tests/two_view_ref.py) on its own, on the CPU: the sampling, the five-point solver
+against generating matrices, the closed-form trial counts, the derived band, the caps on banded and left-out cases, and that
+breaking a rule changes a compared quantity on the committed cases."""
+import numpy as np
+import pytest
+
+import pose_ref as pr
+import two_view_ref as tv
+
+
+def test_sampling_on_integers():
+    assert tv.mix64(0) == 0xE220A8397B1DCDAF and tv.mix64(1) == 0x910A2DEC89025CC1      # splitmix64's first outputs
+    for n in (5, 6, 7, 40, 300, 2 ** 31 - 1):
+        for trial in (0, 1, 255, 256, 10 ** 9):
+            s = tv.sample5(12345, trial, n)
+            assert len(set(s)) == 5 and all(0 <= i < n for i in s)
+            assert tuple(tv.sample5v(12345, [trial], n)[0]) == s
+    assert sorted(tv.sample5(0, 0, 5)) == [0, 1, 2, 3, 4]
+    assert tv.sample5(0, 0, 40) != tv.sample5(1, 0, 40) and tv.sample5(0, 0, 40) != tv.sample5(0, 1, 40)
+    # every index is drawn about equally often
+    hist = np.bincount(tv.sample5v(3, np.arange(20000), 10).ravel(), minlength=10)
+    assert hist.min() > 9500 and hist.max() < 10500
+
+
+def test_five_point_against_the_generating_matrix():
+    rs = np.random.RandomState(11)
+    cam = pr.camera("PINHOLE")
+    x0s, x1s, Es = [], [], []
+    for _ in range(2000):
+        R, t, p0, p1, _ = tv.two_view_scene(rs, cam, cam, 5)
+        x0s.append(pr.undistort(cam, p0))
+        x1s.append(pr.undistort(cam, p1))
+        E = tv.skew(t[None])[0] @ R
+        Es.append(E / np.linalg.norm(E))
+    sol, owner, near, _ = tv.five_point_ref(np.stack(x0s), np.stack(x1s))
+    sol = sol / np.linalg.norm(sol, axis=(1, 2))[:, None, None]
+    worst, counts = 0.0, np.bincount(owner, minlength=2000)
+    for h in range(2000):
+        c = sol[owner == h]
+        d = np.minimum(np.linalg.norm(c - Es[h], axis=(1, 2)), np.linalg.norm(c + Es[h], axis=(1, 2)))
+        worst = max(worst, float(d.min()))
+    print(f"worst distance to the generating matrix {worst:.3g}, {counts.mean():.2f} solutions per sample")
+    assert worst <= 1e-9 and counts.max() <= 10 and counts.min() >= 1
+    # every solution is an essential matrix through the five points
+    s = np.linalg.svd(sol, compute_uv=False)
+    assert np.max(np.abs(s[:, 0] - s[:, 1])) < 1e-9 and np.max(s[:, 2]) < 1e-9
+    assert np.max(np.sqrt(tv.sampson_f64(sol, np.stack(x0s)[owner], np.stack(x1s)[owner]))) < 1e-10
+
+
+def test_trial_counts_in_closed_form():
+    assert tv.num_trials_needed(0.5, 0.999) == np.ceil(np.log(0.001) / np.log(1 - 0.5 ** 5) * 3) == 653
+    assert tv.num_trials_needed(1.0, 0.999) == 1.0 and tv.num_trials_needed(0.0, 0.999) == np.inf and tv.num_trials_needed(0.5, 1.0) == np.inf
+    assert tv.num_trials_needed(0.5, 0.999, 2.0) == np.ceil(np.log(0.001) / np.log(1 - 0.5 ** 5) * 2)
+    assert tv.trial_limits(0.25, 0, 10000, 0.999) == (0, 10000)            # 21211 trials at a quarter of inliers: no limit below 10000
+    assert tv.trial_limits(0.6, 0, 10000, 0.999) == (0, 257)               # ceil(3 log(0.001) / log(1 - 0.6^5)) = 257
+    assert tv.trial_limits(0.25, 50000, 10000, 0.999) == (10000, 10000)
+    # the committed cases stop where the rule says
+    for ref in tv.ransac_refs():
+        t, need = ref["num_trials"], tv.num_trials_needed(ref["num_inliers"] / len(ref["inliers"]), 0.999)
+        assert t % tv.ROUND == 0 or t == 10000
+        assert t == 10000 or t >= need
+
+
+def test_band_is_derived_and_caps_hold():
+    measured = tv.measure_band()
+    print(f"largest relative disagreement in squared Sampson error over the probe families {measured:.3g}, band {tv.BAND:.3g}")
+    assert measured <= tv.MEASURED <= 4 * measured and tv.BAND == 100 * tv.MEASURED
+    for family in tv.PROBE_FAMILIES:
+        exp, _ = tv.probe_expect(family)
+        left = sum(e is None for e, _ in exp)
+        print(f"{family}: {left} of {len(exp)} left out, {sum(e is True for e, _ in exp)} true, {sum(e == 'either' for e, _ in exp)} either")
+        assert left <= len(exp) // 4
+        assert sum(e is True or e == "either" for e, _ in exp) >= len(exp) // 2
+    refs = tv.ransac_refs() + [tv.option_ref(**c) for c in tv.OPTION_RUNS]
+    banded = sum(r["banded"] for r in refs)
+    print(f"{banded} of {len(refs)} RANSAC and option cases banded")
+    assert banded <= len(refs) // 10
+    # the cases do what they are there for: several rounds, both trial limits, all inlier ratios
+    assert {r["num_trials"] for r in refs} >= {256, 257, 300, 512, 768, 1024, 8704}
+
+
+def _differs(a, b):
+    return (a["num_trials"], a["num_inliers"]) != (b["num_trials"], b["num_inliers"]) or not np.array_equal(a["inliers"], b["inliers"]) \
+        or max(tv.pose_error(a["R"], a["t"], b["R"], b["t"])) > 1e-6
+
+
+@pytest.mark.parametrize("rule", ["drop_root", "multiplier", "smaller_sum", "lo", "slots"])
+def test_breaking_a_rule_changes_a_compared_quantity(rule):
+    broken = {"drop_root": dict(drop_root=True), "multiplier": dict(multiplier=2.0), "smaller_sum": dict(smaller_sum=False),
+              "lo": dict(lo=False), "slots": dict(slots=tv.SLOTS[::-1])}[rule]
+    changed = 0
+    if rule == "slots":         # only a tie between decompositions shows the slot order
+        p0, p1, c0, c1, R, t = tv.tie_case()
+        good, bad = tv.relative_pose_ref(p0, p1, c0, c1, 4.0), tv.relative_pose_ref(p0, p1, c0, c1, 4.0, **broken)
+        assert good["success"] and max(tv.pose_error(good["R"], good["t"], R, t)) < 1e-6 and np.isfinite(good["angles"]).sum() == 12
+        assert _differs(good, bad)
+        return
+    if rule == "drop_root":     # one trial: the sample's last solution is the generating one in some probes, and nothing makes up for it
+        for (p0, p1, c0, c1, _, _), (e, _) in list(zip(tv.probes("generic"), tv.probe_expect("generic")[0]))[:24]:
+            conf = dict(max_error_px=tv.PROBE_ERROR_PX, min_num_inliers=5, max_num_trials=1)
+            changed += e is True and _differs(tv.relative_pose_ref(p0, p1, c0, c1, **conf), tv.relative_pose_ref(p0, p1, c0, c1, **conf, **broken))
+        assert changed >= 1
+        return
+    for (p0, p1, c0, c1, _, _, th), ref in [list(zip(tv.ransac_cases(), tv.ransac_refs()))[k] for k in (2, 4, 7, 9)]:
+        changed += _differs(tv.relative_pose_ref(p0, p1, c0, c1, th, **broken), ref)
+    assert changed >= 1
