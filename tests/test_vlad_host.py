@@ -1,5 +1,5 @@
 """The VLAD global descriptors, the parts that need no GPU: the caps on the banded share that tests/test_gpu_vlad.py relies on (with the
-restatement tests/vlad_ref.py alone), the retrieval scene's property, the command line, the vocabulary file, the header against the
+restatement tests/vlad_ref.py alone), what the generators of tests/test_gpu_vlad_edges.py claim, the retrieval scene's property, the command line, the vocabulary file, the header against the
 binding, and the compiled kernels' metadata."""
 import ctypes
 import functools
@@ -80,6 +80,147 @@ def test_duplicated_start_row_keeps_its_value():
     # (over further iterations the start row itself, which IS centroid 5, scores 0.5 against it and less against its cluster's mean: it returns)
     its = vr.kmeans_ref(x, start, 20)
     assert its[-1][2] == 0 and len(its) < 20 and its[-1][1][5] <= 1
+
+
+# ------------------------------------------------------------------------------------ the generators of tests/test_gpu_vlad_edges.py
+def _exact_bits(x, c):
+    """The fp64 scores of a case whose chains are exact: they ARE the fp32 scores."""
+    assert vr.chains_exact(x, c)
+    s = vr.scores64(x, c)
+    assert (s.astype(np.float32).astype(np.float64) == s).all()
+    return s
+
+
+@pytest.mark.parametrize("k", vr.EDGE_KS)
+def test_edge_k_cases_cover_every_centroid_and_stay_under_the_band_cap(k):
+    n = max(vr.EDGE_NS)
+    x, c = vr.covering_family("exact", 20 + k, n, k)
+    s = _exact_bits(x, c)
+    assert sorted(set(np.argmax(s, axis=1).tolist())) == list(range(k))            # every column of every accumulator tile wins a row
+    np.testing.assert_array_equal(np.argmax(s, axis=1)[:k], np.arange(k))
+    x, c = vr.exact_family(20 + k, n, k)
+    s = _exact_bits(x, c)
+    assert (np.argmax(s, axis=1)[::5] == 0).all() and (s[::5, 0] == s[::5, 1]).all()
+    x, c = vr.covering_family("float", 20 + k, n, k)
+    share_cover = float(vr.banded(x, c).mean())
+    assert sorted(set(np.argmax(vr.scores64(x, c), axis=1)[~vr.banded(x, c)].tolist())) == list(range(k))
+    x, c = vr.float_family(20 + k, 1000, k)
+    share = float(vr.banded(x, c).mean())
+    print(f"K = {k}: banded share of the covering float case {share_cover:.5f}, of the float case at n = 1000 {share:.5f}")
+    assert share_cover <= 0.01 and share <= 0.01
+
+
+@pytest.mark.parametrize("k", vr.LANE_TIE_KS)
+def test_lane_tie_family_ties_inside_a_lane(k):
+    n = 257
+    x, c, rows, want = vr.lane_tie_family(30 + k, n, k)
+    s = _exact_bits(x, c)
+    lanes = vr.lane_tie_lanes(k)
+    assert 15 in lanes and len(set(lanes)) == 2 and len(rows) >= 2 * (n // 8)
+    for lc in lanes:
+        group = list(range(lc, k, 16))
+        assert len(group) >= 2 and all((c[j] == c[lc]).all() for j in group)
+        r = rows[want == lc]
+        assert len(r) >= n // 8
+        assert (s[r][:, group] == s[r][:, [lc]]).all() and (s[r].max(1) == s[r, lc]).all()      # the whole lane ties at the row's best score
+    np.testing.assert_array_equal(np.argmax(s, axis=1)[rows], want)
+    print(f"lane ties K = {k}: lanes {lanes}, {len(rows)} designed rows of {n}")
+
+
+def test_all_equal_families_tie_as_many_ways_as_stated():
+    for k in (16, 17, 256):
+        x, c, want = vr.all_equal_family(257, k)
+        s = _exact_bits(x, c)
+        assert (s == s[:, :1]).all() and (want == 0).all() and (np.argmax(s, axis=1) == 0).all()
+    x, c, want = vr.all_equal_family(257, 96, group=16)
+    s = _exact_bits(x, c)
+    np.testing.assert_array_equal(np.argmax(s, axis=1), want)
+    assert sorted(set(want.tolist())) == [0, 16, 32, 48, 64, 80]
+    for i in range(len(x)):
+        assert (s[i, want[i]:want[i] + 16] == s[i].max()).all() and int((s[i] == s[i].max()).sum()) == 16
+
+
+def test_negative_family_scores_below_zero():
+    lo, hi = 0.0, -np.inf
+    for k in sorted(set(vr.NEGATIVE_KS) | {35, 48, 49, 65, 96, 97, 129, 192}):
+        x, c = vr.negative_family(40 + k, 257, k)
+        s = _exact_bits(x, c)
+        assert (s < 0).all()
+        lo, hi = min(lo, float(s.max(1).min())), max(hi, float(s.max(1).max()))
+    print(f"negative family: the largest score of a row lies in [{lo:.3f}, {hi:.3f}]")
+    assert hi < -3.5                                                  # far below the 0 a zero centroid row scores
+
+
+@functools.lru_cache(maxsize=None)
+def _large():
+    x, c = vr.exact_family(50, max(vr.LARGE_NS), 17)
+    return x, c
+
+
+def test_large_cases_have_exact_chains():
+    x, c = _large()
+    s = _exact_bits(x, c)
+    assert (np.argmax(s, axis=1)[::5] == 0).all() and (s[::5, 0] == s[::5, 1]).all()
+    for n in vr.LARGE_NS:
+        tiles = (n + 63) // 64
+        assert tiles > 1024 and n - 64 * (tiles - 1) == 1             # a block takes a further tile, and the last tile has one live row
+    x, c, rows, want = vr.lane_tie_family(51, vr.LARGE_NS[0], 35)
+    s = _exact_bits(x, c)
+    np.testing.assert_array_equal(np.argmax(s, axis=1)[rows], want)
+    assert len(rows) >= 2 * (len(x) // 8) and (rows >= 65536).any()
+
+
+def _check_kmeans_case(x, start, its):
+    assert its[-1][2] == 0 and 2 <= len(its) < 20 and its[0][2] == len(x)
+    c = start
+    for cen, counts, moved, a in its:
+        assert not vr.banded(x, c).any()
+        np.testing.assert_array_equal(a, np.argmax(vr.scores64(x, c), axis=1))
+        assert counts.sum() == len(x)
+        c = cen
+
+
+def test_large_kmeans_case_has_no_banded_row_and_converges():
+    seed, n, k = vr.KMEANS_LARGE
+    x, start = vr.separated(seed, n, k)
+    its = vr.kmeans_ref(x, start, 20)
+    _check_kmeans_case(x, start, its)
+    moved = [it[2] for it in its]
+    print(f"large k-means case: moved per iteration {moved}")
+    assert len(its) >= 3 and 0 < moved[1] < n                         # the second iteration's count is a partial one
+    assert (n + vr.CHUNK - 1) // vr.CHUNK == 17
+
+
+@pytest.mark.parametrize("i", range(len(vr.KMEANS_WIDE)))
+def test_wide_kmeans_cases_have_no_banded_row_and_converge(i):
+    seed, n, k, empty = vr.KMEANS_WIDE[i]
+    x, start, _ = vr.kmeans_wide_case(i)
+    its = vr.kmeans_ref(x, start, 20)
+    _check_kmeans_case(x, start, its)
+    print(f"wide k-means case K = {k}, n = {n}: moved per iteration {[it[2] for it in its]}")
+    assert n > vr.CHUNK
+    if k == 1:
+        assert [it[2] for it in its] == [n, 0]
+    if empty is None:
+        assert (its[0][1] > 0).all()                                  # every cluster has rows
+    else:
+        assert n > 2 * vr.CHUNK
+        for cen, counts, moved, a in its:
+            assert counts[empty] == 0 and cen[empty].tobytes() == start[empty].tobytes()
+        assert (np.delete(its[-1][1], empty) > 0).all()
+
+
+@pytest.mark.parametrize("k", vr.AGG_SEAM_KS)
+def test_aggregate_seam_cases_change_centroid_on_the_tile_seam(k):
+    for family in ("exact", "float"):
+        x, o, c, a, b = vr.aggregate_seam_case(60 + k, k, family)
+        if family == "exact":
+            _exact_bits(x, c)
+        share = float(vr.banded(x, c).mean()) if family == "float" else 0.0
+        assert share <= 0.01
+        want = np.argmax(vr.scores64(x, c), axis=1)
+        assert o.tolist() == [0, 31, 95, 128, 128, 193, 194] and a == k - 1 and (a & 1) != (b & 1)
+        assert (want[31:63] == a).all() and (want[63:95] == b).all()
 
 
 @functools.lru_cache(maxsize=None)

@@ -19,6 +19,9 @@ Families
   float   unit-norm rows around cluster centres, centroids = means of rows.  A row is banded when its two largest exact (fp64)
           scores lie within twice the rounding bound of an fp32 score, (128 + 2) 2^-24 (|x| |c_j| + h_j), the largest over j:
           gamma_n of a chain of 128 multiply-adds plus the subtraction, the argument of tests/pairs_ref.py's retrieval band.
+  edge    (tests/test_gpu_vlad_edges.py) covering: row i near centroid i, so every centroid wins; lane ties: all the centroids
+          16 nt + lc of a lane equal; all equal: k-way and 16-way ties; negative: centroids times 4, every score below 0.  The
+          exact-type ones keep exact chains (tests/test_vlad_host.py checks each at every K it is used with).
 """
 import numpy as np
 
@@ -34,6 +37,18 @@ AGG_KS = (1, 17, 64, 256)
 KMEANS_SEPARATED = ((2, 3000, 8), (2, 5000, 8))                # (seed, n, K): the second crosses a chunk seam
 KMEANS_OVERLAP = (5, 3000, 16)
 SCENE_SEED, SCENE_K, SCENE_ITERS, SCENE_TOP = 1, 16, 15, 5
+
+# tests/test_gpu_vlad_edges.py: the shapes the cases above do not reach
+EDGE_KS = (32, 33, 48, 49, 64, 65, 96, 97, 128, 129, 192, 193, 255)   # both sides of every seam between two accumulator counts, and 255
+EDGE_NS = (63, 65, 257)
+LANE_TIE_KS = (35, 48, 97, 193)
+NEGATIVE_KS = (1, 15, 17, 33, 100, 193, 255)
+LARGE_NS = (65665, 131073)             # 1 027 and 2 049 tiles on 1 024 blocks: a second and a third tile per block, the last with one live row
+KMEANS_LARGE = (7, 65665, 8)           # 17 chunks, two tiles in three of the assignment blocks (seed 2 has a banded row in iteration 1)
+# (seed, n, K, the centroid whose start row is tripled so that no row ever chooses it, or None)
+KMEANS_WIDE = ((2, 4097 + 33, 33, None), (2, 4097 + 255, 255, None), (2, 4098, 1, None), (29, 2 * 4096 + 10, 9, 4))
+AGG_SEAM_LENGTHS = (31, 64, 33, 0, 65, 1)                        # images start at the rows 0, 31, 95, 128, 128, 193
+AGG_SEAM_KS = (33, 34, 255)
 
 
 # ---------------------------------------------------------------------------------------------------------------- restatement
@@ -256,6 +271,104 @@ def aggregate_case(seed, k, family="float", lengths=AGG_LENGTHS):
         i = list(lengths).index(31)
         x[offsets[i]:offsets[i + 1]] = x[offsets[i]]
     return x, offsets, c
+
+
+# ---------------------------------------------------------------------------------------------------------------- edge families
+def covering_family(family, seed, n, k, noise=None):
+    """(x, centroids) in which row i < k sits near centroid i, so that with n >= k every centroid wins a row; the further rows go
+    to random centroids.  No centroid is duplicated.  exact: on the 2^-7 grid; float: unit rows, centroids = the means of their rows."""
+    rs = np.random.RandomState(seed)
+    centres = _unit(rs.standard_normal((k, DIM)))
+    which = np.concatenate([np.arange(k), rs.randint(0, k, max(n - k, 0))])[:n]
+    if family == "exact":
+        c = _grid(centres)
+        x = _grid(_unit(c[which] + (noise or 0.03) * rs.standard_normal((n, DIM))))
+        assert np.sqrt((x.astype(F64) ** 2).sum(1)).max() <= 1.1 and np.sqrt((c.astype(F64) ** 2).sum(1)).max() <= 1.1
+        return x, c
+    x = _unit(centres[which] + (noise or 0.05) * rs.standard_normal((n, DIM))).astype(F32)
+    c = centres.astype(F32)
+    for j in np.unique(which):
+        c[j] = x[which == j].astype(F64).mean(0).astype(F32)
+    return x, c
+
+
+def lane_tie_lanes(k):
+    """The two lanes (column index mod 16) whose columns lane_tie_family makes equal: 15, whose last column is padding when k is no
+    multiple of 16, and the lane of the last centroid -- or 2 where that is 15 again, or 0 or 1 (the exact family's centroid 1 is
+    centroid 0 with two elements swapped: a row near one of them may sit nearer the other)."""
+    return (15, (k - 1) % 16 if (k - 1) % 16 not in (15, 0, 1) else 2)
+
+
+def lane_tie_family(seed, n, k):
+    """(x, centroids, rows, want): the exact family with, for each lane lc of lane_tie_lanes(k), every centroid 16 nt + lc < k
+    (nt >= 1) a copy of centroid lc -- all the columns one lane of the assignment kernel holds are equal -- and the rows
+    1 + i, 9 + i, 17 + i, .. (i = 0, 1: the lane) near centroid lc.  `rows` are those rows, `want` the lc of each: the smallest
+    index of its group."""
+    x, c = exact_family(seed, n, k)
+    rs = np.random.RandomState(seed + 1000)
+    rows, want = [], []
+    for i, lc in enumerate(lane_tie_lanes(k)):
+        if lc >= k:
+            continue
+        for j in range(16 + lc, k, 16):
+            c[j] = c[lc]
+        r = np.arange(1 + i, n, 8)
+        x[r] = _grid(_unit(c[lc] + 0.03 * rs.standard_normal((len(r), DIM))))
+        rows.append(r)
+        want.append(np.full(len(r), lc))
+    assert np.sqrt((x.astype(F64) ** 2).sum(1)).max() <= 1.1
+    if not rows:
+        return x, c, np.zeros(0, np.int64), np.zeros(0, np.int64)
+    return x, c, np.concatenate(rows), np.concatenate(want)
+
+
+def all_equal_family(n, k, group=None):
+    """(x, centroids, want): every centroid is one grid vector, so every row ties k ways and goes to centroid 0.  With `group` the
+    centroids are equal in groups of that many consecutive indices and row i sits near the vector of group i mod (number of groups):
+    it ties `group` ways and goes to the group's first index."""
+    rs = np.random.RandomState(77)
+    g = group or k
+    n_groups = (k + g - 1) // g
+    vec = _grid(_unit(rs.standard_normal((n_groups, DIM))))
+    c = vec[np.arange(k) // g]
+    which = np.arange(n) % n_groups
+    x = _grid(_unit(vec[which] + 0.03 * rs.standard_normal((n, DIM))))
+    assert np.sqrt((x.astype(F64) ** 2).sum(1)).max() <= 1.1
+    return x, np.ascontiguousarray(c), (which * g).astype(np.int32)
+
+
+def negative_family(seed, n, k):
+    """(x, centroids): lane_tie_family with the centroids times 4 (a power of two: the chains stay exact).  Every score is
+    4 x . c - 8 |c|^2, about -4 for the nearest centroid and -8 for the others: the 0 of a padding column would beat them all."""
+    x, c, _, _ = lane_tie_family(seed, n, k)
+    return x, (F32(4) * c).astype(F32)
+
+
+def kmeans_wide_case(i):
+    """(x, start, empty) of KMEANS_WIDE[i]: a separated case; `empty` is the centroid whose start row is multiplied by 3 as in
+    aggregate_case (its score is negative even for its own cluster's rows, which the other centroids share out), or None."""
+    seed, n, k, empty = KMEANS_WIDE[i]
+    x, start = separated(seed, n, k)
+    if empty is not None:
+        start[empty] = F32(3) * start[empty]
+    return x, start, empty
+
+
+def aggregate_seam_case(seed, k, family):
+    """(x, offsets, centroids, a, b): images of AGG_SEAM_LENGTHS; the image of 64 rows starts at row 31 and its first 32 rows sit
+    near centroid a = k - 1, its last 32 near centroid b = 1 or 2, the one of the other parity (the other owner thread of the
+    aggregation kernel): the assignment changes on the seam between the image's two 32-row tiles."""
+    offsets = np.concatenate([[0], np.cumsum(AGG_SEAM_LENGTHS)]).astype(np.int64)
+    n = int(offsets[-1])
+    x, c = covering_family(family, seed, n, k)
+    rs = np.random.RandomState(seed + 1000)
+    a = k - 1
+    b = 2 if a & 1 else 1
+    r0 = int(offsets[1])
+    for j, lo in ((a, r0), (b, r0 + 32)):
+        v = _unit(c[j].astype(F64) / np.linalg.norm(c[j].astype(F64)) + (0.03 if family == "exact" else 0.05) * rs.standard_normal((32, DIM)))
+        x[lo:lo + 32] = _grid(v) if family == "exact" else v.astype(F32)
+    return x, offsets, c, a, b
 
 
 # ---------------------------------------------------------------------------------------------------------------- retrieval scene
