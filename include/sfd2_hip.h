@@ -85,7 +85,7 @@ typedef struct {
     int64_t n_candidates; /* N0 after NMS + threshold + border of the last extract          */
 } sfd2_timings;
 
-int sfd2_version(void);   /* 100 = rounds 1-4; 105 adds sfd2_extract_record_async, sfd2_desc_pack and host outputs with SFD2_FLAG_ASYNC; 106 adds sfd2_get_margin_status; 107 adds sfd2_get_relax_status (option "c3b_plain"); 108 adds sfd2_get_option, sfd2_device_pci_bus_id, SFD2_FLAG_DESC_STORE64; 109 adds the baseline JPEG decoder (sfd2_jpeg_*); 112 adds the SfM map (sfd2_verify_matches_batch, sfd2_build_tracks, sfd2_triangulate_tracks); 113 adds the pair selection (sfd2_pairs_retrieval, sfd2_pairs_covisibility, sfd2_pairs_poses); 114 adds sfd2_covis_clusters; 115 adds sfd2_covis_frames; 116 adds the VLAD global descriptors (sfd2_vlad_assign, sfd2_vlad_aggregate, sfd2_vlad_kmeans); 117 adds sfd2_relative_pose_batch */
+int sfd2_version(void);   /* 100 = rounds 1-4; 105 adds sfd2_extract_record_async, sfd2_desc_pack and host outputs with SFD2_FLAG_ASYNC; 106 adds sfd2_get_margin_status; 107 adds sfd2_get_relax_status (option "c3b_plain"); 108 adds sfd2_get_option, sfd2_device_pci_bus_id, SFD2_FLAG_DESC_STORE64; 109 adds the baseline JPEG decoder (sfd2_jpeg_*); 112 adds the SfM map (sfd2_verify_matches_batch, sfd2_build_tracks, sfd2_triangulate_tracks); 113 adds the pair selection (sfd2_pairs_retrieval, sfd2_pairs_covisibility, sfd2_pairs_poses); 114 adds sfd2_covis_clusters; 115 adds sfd2_covis_frames; 116 adds the VLAD global descriptors (sfd2_vlad_assign, sfd2_vlad_aggregate, sfd2_vlad_kmeans); 117 adds sfd2_relative_pose_batch; 118 adds sfd2_bundle_adjust */
 const char *sfd2_last_error(void);
 
 int sfd2_ctx_create(int device, sfd2_ctx **out);
@@ -716,6 +716,52 @@ typedef struct {
 int sfd2_triangulate_tracks(sfd2_ctx *ctx, const sfd2_tri_view *views, int n_views, const int64_t *track_offsets, const int64_t *track_labels,
                             int n_tracks, const int32_t *obs_view, const float *obs_xy, const sfd2_tri_conf *conf, double *xyz, double *error,
                             int32_t *n_obs, int8_t *obs_point, int32_t *track_status, int flags);
+
+/* ------------------------------------------------------------------------------------------------ bundle adjustment
+ * Levenberg-Marquardt over camera poses and 3D points with the points eliminated (Schur complement) and the reduced camera system
+ * solved by matrix-free preconditioned conjugate gradients, block-Jacobi preconditioned.  Conventions of the
+ * SfM-map section: host arrays, the call runs on sfd2_get_stream() and synchronises before it returns, returns -1 with
+ * sfd2_last_error() set on a bad argument, non-finite input or an index out of range (the message names the first offending index).
+ * fp64, fixed-order sums, no floating-point atomics: the result depends on the inputs (and the flags) only, two calls give the same
+ * bytes.  Intrinsics are constant. */
+#define SFD2_BA_LOSS_TRIVIAL 0
+#define SFD2_BA_LOSS_CAUCHY 1          /* rho(s) = c^2 log(1 + s / c^2), c = loss_scale, as an IRLS weight rho'(s)               */
+#define SFD2_BA_ST_GRADIENT 0          /* result status: max |g| <= gradient_tolerance                                          */
+#define SFD2_BA_ST_FUNCTION 1          /*   relative cost change of an accepted step <= function_tolerance                      */
+#define SFD2_BA_ST_MAX_ITERATIONS 2    /*   max_iterations steps were tried                                                      */
+#define SFD2_BA_ST_LAMBDA 3            /*   lambda grew past 1e12: no further progress (the best accepted state is returned)    */
+#define SFD2_BA_ST_NONFINITE 4         /*   the cost of the given state is not finite: nothing was written                      */
+#define SFD2_BA_FLAG_POINT_LANE 1      /* every point's sums by one lane, whatever its track length                             */
+#define SFD2_BA_FLAG_POINT_WAVE 2      /* every point's sums by one wave (default: a wave beyond 64 observations, else a lane)  */
+typedef struct {
+    int32_t max_iterations;         /* LM steps tried at the most (100)                                                    */
+    int32_t pcg_max_iterations;     /* conjugate-gradient iterations per step at the most (100)                            */
+    int32_t loss;                   /* SFD2_BA_LOSS_*                                                                      */
+    int32_t pcg_batch;              /* PCG iterations queued between two reads of the stopping word; 0: 16                 */
+    double gradient_tolerance;      /* 1e-10                                                                               */
+    double function_tolerance;      /* 0                                                                                   */
+    double pcg_tolerance;           /* PCG stops at |r_k| <= pcg_tolerance |r_0| (0.1)                                     */
+    double loss_scale;              /* c of the Cauchy loss, pixels                                                        */
+    double initial_lambda;          /* 1e-4                                                                                */
+    int32_t reserved[4];            /* zero                                                                                */
+} sfd2_ba_conf;
+typedef struct {
+    int32_t status;                 /* SFD2_BA_ST_*                                                                        */
+    int32_t iterations;             /* LM steps tried                                                                      */
+    int32_t accepted_steps;
+    int32_t pcg_iterations;         /* over all steps                                                                      */
+    double initial_cost, final_cost;   /* 1/2 sum rho(|r|^2), pixels^2                                                      */
+    double gradient_max;            /* max |g| at the returned state                                                       */
+    double lambda;                  /* the damping the next step would have used                                           */
+} sfd2_ba_result;
+/* views[n_views]: IN/OUT poses (a view that is constant or has no observation keeps its words bit for bit; the others come back
+ * with a unit qvec, w >= 0); view_constant[n_views] and point_constant[n_points]: non-zero = fixed; xyz[n_points][3]: IN/OUT;
+ * point p holds the observations point_offsets[p] .. point_offsets[p + 1]: obs_view (index into views) and obs_xy[.][2] (pixels as
+ * given: a model's xys already carry the +0.5).  The residual is the camera model's projection of R X + t minus obs_xy, without a
+ * depth test.  obs_error[n_obs]: the reprojection error of every observation at the returned state, pixels. */
+int sfd2_bundle_adjust(sfd2_ctx *ctx, sfd2_tri_view *views, int n_views, const uint8_t *view_constant, double *xyz, int n_points,
+                       const uint8_t *point_constant, const int64_t *point_offsets, const int32_t *obs_view, const double *obs_xy,
+                       const sfd2_ba_conf *conf, sfd2_ba_result *result, double *obs_error, int flags);
 
 /* ------------------------------------------------------------------------------------------------ pair selection
  * The image pairs the stages above are run on: hloc/pairs_from_retrieval.py (query-db pairs by global-descriptor similarity),

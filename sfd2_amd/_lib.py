@@ -158,6 +158,22 @@ class TriConf(ctypes.Structure):
                 ("reserved", ctypes.c_int32)]
 
 
+class BaConf(ctypes.Structure):
+    """sfd2_ba_conf (include/sfd2_hip.h)."""
+    _fields_ = [("max_iterations", ctypes.c_int32), ("pcg_max_iterations", ctypes.c_int32), ("loss", ctypes.c_int32), ("pcg_batch", ctypes.c_int32),
+                ("gradient_tolerance", ctypes.c_double), ("function_tolerance", ctypes.c_double), ("pcg_tolerance", ctypes.c_double),
+                ("loss_scale", ctypes.c_double), ("initial_lambda", ctypes.c_double), ("reserved", ctypes.c_int32 * 4)]
+
+
+class BaResult(ctypes.Structure):
+    """sfd2_ba_result (include/sfd2_hip.h)."""
+    _fields_ = [("status", ctypes.c_int32), ("iterations", ctypes.c_int32), ("accepted_steps", ctypes.c_int32), ("pcg_iterations", ctypes.c_int32),
+                ("initial_cost", ctypes.c_double), ("final_cost", ctypes.c_double), ("gradient_max", ctypes.c_double), ("lambda_", ctypes.c_double)]
+
+
+BA_LOSS_TRIVIAL, BA_LOSS_CAUCHY = 0, 1                                              # SFD2_BA_*
+BA_ST_GRADIENT, BA_ST_FUNCTION, BA_ST_MAX_ITERATIONS, BA_ST_LAMBDA, BA_ST_NONFINITE = 0, 1, 2, 3, 4
+BA_FLAG_POINT_LANE, BA_FLAG_POINT_WAVE = 1, 2
 TRI_MAX_POINTS = 4
 TRI_ST_RANGE, TRI_ST_NOT_CONVERGED = 1, 2
 PAIRS_MAX_K, PAIRS_POSES_MAX_K = 256, 1024
@@ -203,7 +219,7 @@ EXPORTS = [
     "sfd2_assemble_2d3d", "sfd2_verify_matches_batch", "sfd2_build_tracks", "sfd2_triangulate_tracks",
     "sfd2_pairs_retrieval", "sfd2_pairs_covisibility", "sfd2_pairs_poses", "sfd2_covis_clusters",
     "sfd2_covis_frames", "sfd2_vlad_assign", "sfd2_vlad_aggregate", "sfd2_vlad_kmeans",
-    "sfd2_relative_pose_batch",
+    "sfd2_relative_pose_batch", "sfd2_bundle_adjust",
 ]
 
 _lib = None
@@ -303,10 +319,11 @@ def load():
     lib.sfd2_vlad_assign.argtypes = [vp, vp, i64, vp, ci, ci, vp, vp, ci]
     lib.sfd2_vlad_aggregate.argtypes = [vp, vp, vp, ci, vp, ci, ci, ci, vp, vp, ci]
     lib.sfd2_vlad_kmeans.argtypes = [vp, vp, i64, ci, ci, ci, vp, vp, vp, pi, ci]
+    lib.sfd2_bundle_adjust.argtypes = [vp, ctypes.POINTER(TriView), ci, vp, vp, ci, vp, vp, vp, vp, ctypes.POINTER(BaConf), ctypes.POINTER(BaResult), vp, ci]
     for name in EXPORTS:
         getattr(lib, name)  # raises AttributeError if the .so lacks a declared symbol
-    if lib.sfd2_version() < 117:
-        raise RuntimeError(f"{LIB_PATH} is version {lib.sfd2_version()}, this binding needs >= 117 (rebuild: __graft_entry__.build())")
+    if lib.sfd2_version() < 118:
+        raise RuntimeError(f"{LIB_PATH} is version {lib.sfd2_version()}, this binding needs >= 118 (rebuild: __graft_entry__.build())")
     _lib = lib
     return lib
 

@@ -1,0 +1,56 @@
+// libsfd2hip: what bundle_kernels.hip and api_bundle.hip share -- the device-side state word block of the Levenberg-Marquardt loop and
+// the launchers of its passes.  fp64 throughout; every launcher queues on the given stream and returns.
+#pragma once
+#include "sfd2_internal.h"
+
+#define SFD2_BA_REC 20                // doubles per observation record: Jc[2][6], Jp[2][3], r[2], all weighted by sqrt(rho')
+#define SFD2_BA_LONG_TRACK 64         // a point with more observations than this gets a wave of its own, else one lane
+#define SFD2_BA_VIEW_WG 256           // threads of a view's workgroup
+#define SFD2_BA_VEC_WG 1024           // threads of the one workgroup that owns the 6 x n_views vectors
+#define SFD2_BA_RED_WG 256            // threads of a reduction block ...
+#define SFD2_BA_RED_CHUNK 2048        // ... and the elements it covers
+#define SFD2_BA_GATE_NONE 0           // a kernel runs always,
+#define SFD2_BA_GATE_ACCEPTED 1       //   only behind an accepted step,
+#define SFD2_BA_GATE_PCG 2            //   only while the conjugate gradients have not stopped
+#define SFD2_BA_OP_SUM 0
+#define SFD2_BA_OP_ABSMAX 1
+
+struct BaState {                      // one per call, in device memory; the host reads it once per LM iteration and once per PCG batch
+    double cost, prev_cost, trial_cost, lambda, gmax;
+    double rz, r0sq, rsq;             // PCG: r.z, |r_0|^2, |r_k|^2
+    int32_t accepted, n_accepted, pcg_done, pcg_iters;
+};
+
+struct BaPtrs {                       // the call's device arrays
+    BaState *st;
+    const PoseCam *cams;              // [nv]
+    const unsigned char *vconst, *pconst;
+    const int64_t *pt_off;            // [np + 1]
+    const int32_t *obs_view, *obs_pt; // [no]
+    const double2 *obs_xy;            // [no]
+    const int64_t *view_off;          // [nv + 1]: the by-view CSR,
+    const int32_t *view_obs;          //   observation indices ascending inside a view
+    const int32_t *short_ids, *long_ids;   // points by mapping
+    double *pose, *pose_trial;        // [nv][12]: R row-major, t
+    double *xyz, *xyz_trial;          // [np][3]
+    double *rec, *err, *obs_cost;     // [no][SFD2_BA_REC], [no], [no]
+    double *V, *gp, *Vinv, *zg, *z;   // per point: 6 (symmetric), 3, 6, 3, 3
+    double *B, *gc, *Minv, *Dd;       // per view: 36, 6, 36, 6
+    double *b, *x, *r, *zz, *p, *q;   // 6 x nv vectors of the reduced system
+    double *partial;                  // reduction partials
+    int nv, np, n_short, n_long;
+    int64_t no;
+};
+
+void launch_ba_linearise(hipStream_t st, const BaPtrs &P, int gate, bool full, bool trial, int loss, double c2);
+void launch_ba_reduce(hipStream_t st, const BaPtrs &P, int gate, const double *src, int64_t n, int op, double *dst, bool combine);
+void launch_ba_point_build(hipStream_t st, const BaPtrs &P, int gate);
+void launch_ba_point_invert(hipStream_t st, const BaPtrs &P);
+void launch_ba_point_apply(hipStream_t st, const BaPtrs &P, int gate, const double *x);
+void launch_ba_view_build(hipStream_t st, const BaPtrs &P, int gate);
+void launch_ba_view_precond(hipStream_t st, const BaPtrs &P);
+void launch_ba_view_apply(hipStream_t st, const BaPtrs &P, int gate, bool rhs);
+void launch_ba_pcg_init(hipStream_t st, const BaPtrs &P);
+void launch_ba_pcg_step(hipStream_t st, const BaPtrs &P, double tol2, int max_iters);
+void launch_ba_update(hipStream_t st, const BaPtrs &P);
+void launch_ba_decide_commit(hipStream_t st, const BaPtrs &P);
