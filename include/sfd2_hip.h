@@ -192,6 +192,12 @@ int sfd2_set_precision(sfd2_ctx *ctx, int mode);
  *   "sparse_da3" 1 (default) / 0: on the extract path (with "sparse_desc"), convDa.3 runs on the 4 x K bilinear corner pixels of the
  *               selected key points only instead of the whole 1/4-resolution map (-77 us per 1600x1200 / top-4096 extract;
  *               descriptors within 4e-5 of the dense path's: another fp32 summation order).  0 = dense.
+ *   "sparse_da0" 1 (default) / 0 / 2: with "sparse_da3" in effect (SFD2_PREC_F16 / F16C, plain descriptor branch), convDa.0 runs after the
+ *               selection on the 4 x 4 blocks of its map that convDa.3's sparse form reads -- 16 x K pixels -- instead of densely inside the
+ *               network pass; bit-identical outputs (the dense kernel's summation order at the same map size).  1 = where it pays:
+ *               16 x top_k <= 0.6 of the 1/4-resolution map (1600x1200 / top-4096: on, -45 us; 640x480 / top-4096: dense); 0 = always
+ *               dense; 2 = wherever the sparse head runs, whatever the size (tests, A/B runs).  After such an extract
+ *               sfd2_debug_activation("convDa.0") answers "not materialised": the map is written at the key points' blocks only.
  *   "fuse_rb23" 1 (default) / 0: with rb_inner = 2, ResBlock.conv2 + conv3 + residual in one kernel (the grouped conv's output tile
  *               stays in LDS); 0 = two launches.  Bit-identical.
  *   "comp_heads" 0 (default) / 1: SFD2_PREC_F16C compensates the four 3x3 layers of the two head branches as well

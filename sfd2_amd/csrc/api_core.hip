@@ -119,6 +119,7 @@ extern "C" int sfd2_set_option(sfd2_ctx *c, const char *key, int value)
     else if (k == "fuse_post") c->opt_fuse_post = value ? 1 : 0;
     else if (k == "sparse_desc") c->opt_sparse_desc = value ? 1 : 0;
     else if (k == "sparse_da3") c->opt_sparse_da3 = value ? 1 : 0;
+    else if (k == "sparse_da0") c->opt_sparse_da0 = value < 0 ? 0 : (value > 2 ? 2 : value);
     else if (k == "cu_limit") c->opt_cu_limit = value < 0 ? 0 : value;
     else if (k == "auto_range") c->opt_auto_range = value ? 1 : 0;
     else if (k == "range_fallback") c->opt_range_fallback = value ? 1 : 0;
@@ -151,7 +152,7 @@ extern "C" int sfd2_get_option(sfd2_ctx *c, const char *key, int *value)
     const std::string k(key);
     const struct { const char *name; int v; } tab[] = {
         {"fuse", c->fuse}, {"fuse_det", c->fuse_det}, {"alias", c->opt_alias}, {"graphs", c->use_graphs}, {"branches", c->opt_branches}, {"sta_side", c->opt_sta_side},
-        {"fuse_post", c->opt_fuse_post}, {"sparse_desc", c->opt_sparse_desc}, {"sparse_da3", c->opt_sparse_da3}, {"cu_limit", c->opt_cu_limit},
+        {"fuse_post", c->opt_fuse_post}, {"sparse_desc", c->opt_sparse_desc}, {"sparse_da3", c->opt_sparse_da3}, {"sparse_da0", c->opt_sparse_da0}, {"cu_limit", c->opt_cu_limit},
         {"auto_range", c->opt_auto_range}, {"range_fallback", c->opt_range_fallback}, {"x3_pp", c->opt_x3_pp}, {"x3_desc16", c->opt_x3_desc16},
         {"auto_margin", c->opt_auto_margin}, {"fp6_filters", c->opt_fp6_filters}, {"fp6_acts", c->opt_fp6_acts}, {"s2d", c->opt_s2d},
         {"trunk_r1", c->opt_trunk_r1}, {"fuse_pb", c->opt_fuse_pb}, {"generic_c", c->opt_generic_c}, {"comp_rb", c->opt_comp_rb},

@@ -224,6 +224,13 @@ extern "C" int sfd2_extract(sfd2_ctx *c, const void *img, int img_on_device, int
                                sel_cap, desc_dst, 1);
         } else if (plan.sparse_da3 || (plan.sparse_x3 && plan.desc16)) {      // (option "x3_desc16": f16x3's key points, the fp16 sparse head on convDa.0's fp16 output)
             HIPCHECK(c->da3_sparse.ensure((size_t)sel_cap * 4 * 256 * sizeof(half_t)));
+            if (plan.sparse_da0) {      // convDa.0 on the 4 x 4 blocks the next kernel reads, into the dense map at their true positions
+                const ConvW &L0 = c->da0;
+                ProfScope ps(c, "convDa.0", "sparse_da0_kernel", 2.0 * 16 * sel_cap * (double)L0.cout * L0.cin * 9,
+                             (double)sel_cap * (36 * 512 + 16 * 512) + 2.0 * L0.cout_pad * L0.cin * 9);
+                launch_sparse_da0(c->stream, c->da0_in.as<half_t>(), c->H4, c->W4, H, W, L0.w.as<half_t>(), L0.scale.as<float>(), L0.shift.as<float>(), 1,
+                                  c->kpts_cur, c->counters.as<unsigned int>() + 1, sel_cap, act_view(c, plan, T_DA0).as<half_t>());
+            }
             {
                 ProfScope ps(c, "convDa.3", "sparse_da3_kernel", 2.0 * 4 * sel_cap * 256.0 * 256.0 * 9, (double)sel_cap * (16 * 512 + 4 * 512) + 2.0 * 256 * 256 * 9);
                 launch_sparse_da3(c->stream, act_view(c, plan, T_DA0).as<half_t>(), c->H4, c->W4, H, W, c->da3.w.as<half_t>(), c->da3.wsl.as<half_t>(), c->da3.cout_pad, c->da3.scale.as<float>(),

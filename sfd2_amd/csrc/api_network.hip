@@ -17,6 +17,11 @@ static const int sl_level[] = {0 /* conv1b */, 1, 1 /* conv2a, conv2b */, 2, 2, 
 static_assert(sizeof(sl_level) == SL_COUNT * sizeof(int), "one level per StrictLayer");
 static bool on_planes(const StrictConv &s) { return s.kind == XK_PP || s.kind == XK_RF || s.kind == XK_S2D; }
 
+// Largest part of the 1/4-resolution map (16 pixels per key point of the capacity) at which convDa.0 runs on the key points' blocks instead of densely.
+// The sparse kernel's time goes by rounds of one 8-key-point tile per CU, the dense layer's by the map.  Measured at 1600x1200 / top-4096 (0.55 of
+// the map): 75.0 us against conv3x3_pp's 121.3 (profiles/sparse_da0_ab.txt), i.e. 37.5 us per round against ~1.0 ns per pixel -- the two meet at 0.88
+// of the map with two full rounds and at 0.44 with 1 024 key points (half a round's CUs idle).  0.6 sits between; DESIGN.md section 6.2.
+#define SFD2_DA0_FRAC 0.6
 // The one place that combines the options for a network pass (sfd2_ctx.h, PassPlan).  top_k and desc: sfd2_extract's arguments.
 PassPlan plan_pass(const sfd2_ctx *c, PassEntry entry, int H, int W, int top_k, bool desc)
 {
@@ -101,6 +106,12 @@ PassPlan plan_pass(const sfd2_ctx *c, PassEntry entry, int H, int W, int top_k, 
         p.sparse_da3 = p.sparse_desc && c->opt_sparse_da3 && !p.ch && !p.branches;
         // SFD2_PREC_F16X3: the same two steps in that mode's arithmetic (planes of convDa.0's output, three MFMA passes, fp32 results)
         p.sparse_x3 = x3 && c->opt_sparse_desc && c->opt_sparse_da3 && c->opt_x3_pp && few;
+        // ... and convDa.0 in front of it at the 4 x 4 blocks sparse_da3_kernel reads: 16 x K pixels (sparse_da0_kernel), bit-identical there.  Plain
+        // descriptor branch of the fp16 family only (sparse_da3 implies it).  Option "sparse_da0" = 1: when at most SFD2_DA0_FRAC of the map is
+        // computed; 2: at every size.  A 640x480 image with 4 096 key points stays dense.
+        p.sparse_da0 = p.sparse_da3 && c->opt_sparse_da0 && c->da0.w.p && c->da0.ks == 3 && c->da0.stride == 1 &&
+                       sparse_da0_serves(c->da0.cin, c->da0.cout_pad, H4, W4) &&
+                       (c->opt_sparse_da0 >= 2 || (double)16 * top_k <= SFD2_DA0_FRAC * (double)H4 * W4);
         p.skip_db = p.sparse_desc;
         p.skip_da3 = p.sparse_da3 || p.sparse_x3;
     }
@@ -245,14 +256,18 @@ int ensure_workspace(sfd2_ctx *c, const PassPlan &p, int H, int W)
         for (int k = 0; k < 3 && p.x3_rb; ++k) HIPCHECK(c->x3_rb_planes[k].ensure(P4 * 256 * pb));
         HIPCHECK(c->x3_da0_planes.ensure(da0 * pb));
         if (ensure_strict_filters(c, p)) return -1;
-    } else if (!layers) return 0;   // throughput path: intermediates live in aliased arena slots and are not readable
+    } else if (!layers) {           // throughput path: intermediates live in aliased arena slots and are not readable
+        // (convDa.0's map is a known tensor that the sparse form writes in part only: sfd2_debug_activation says "not materialised")
+        if (p.sparse_da0) reg(T_DA0, act_view(c, p, T_DA0).p, 0, 0, kTensor[T_DA0].ch).absent = true;
+        return 0;
+    }
     for (int id = 0; id < T_COUNT; ++id) {
         // throughput path of SFD2_PREC_F16X3: from the stem to convDa.0 the tensors exist as hi / lo' planes only; the fp32 buffers are
         // written for the last ResBlock's output and convPa.3's.  sfd2_debug_activation must say so instead of handing back what an
         // earlier sfd2_det left in them
         if (p.f32) reg(id, c->act32[id].p, 1, 0, kTensor[id].ch).absent = p.x3_fast && id != T_OUT_0 + 2 && id != T_PA;
         // (SFD2_PREC_F16C: each tensor with the corr records the plan has its producer write; the head branches' tensors as their hi planes)
-        else if (!on_chip(id)) reg(id, c->act16[id].p, 0, 0, kTensor[id].ch, id < T_PA0 ? p.rec[id] : Rec::None).absent = p.rb23 && id >= T_T2_0 && id < T_OUT_0;   // (t2 stays on chip in rb23_c_kernel)
+        else if (!on_chip(id)) reg(id, c->act16[id].p, 0, 0, kTensor[id].ch, id < T_PA0 ? p.rec[id] : Rec::None).absent = (p.rb23 && id >= T_T2_0 && id < T_OUT_0) || (p.sparse_da0 && id == T_DA0);   // (t2 stays on chip in rb23_c_kernel; convDa.0's map is written at the key points' blocks only)
     }
     return 0;
 }
@@ -721,7 +736,10 @@ int run_network(sfd2_ctx *c, const PassPlan &p, const float *img_dev, int normal
         convc(c, p, "convDa.0", c->da0, x, T_DA0, 1);
         convc(c, p, "convDa.3", c->da3, T_DA0, T_DA, 0);
     } else {
-        conv(c, p, "convDa.0", c->da0, x, T_DA0, 1);
+        // "sparse_da0": sfd2_extract runs the layer after the selection, on the key points' blocks; the backbone output must outlive this pass untouched
+        // (its arena slot is 0; convPa.0 / convPa.3 write slot 1, convDa.0's map is slot 2, and convDa.3 -- the one layer that would take slot 0 -- is skipped)
+        if (p.sparse_da0) c->da0_in = V(x);
+        else conv(c, p, "convDa.0", c->da0, x, T_DA0, 1);
         if (!p.skip_da3) conv(c, p, "convDa.3", c->da3, T_DA0, T_DA, 0);
     }
     if (!p.skip_db) conv(c, p, "convDb", c->db, T_DA, T_DB, 0, T_NONE, 1);

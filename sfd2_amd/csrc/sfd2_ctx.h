@@ -240,6 +240,9 @@ struct sfd2_ctx {
     DevBuf x3_da0_planes;              // X3_DA0: convDa.0's output as planes (sparse descriptor head of f16x3); with "x3_desc16" its fp16 output
     DevBuf db_sparse;                  // [sel_cap][4][128] fp32: convDb on the sampled corners (f16x3)
     int opt_sparse_da3 = 1;            // sfd2_set_option "sparse_da3": with the sparse descriptor head, convDa.3 on the sampled corners only
+    int opt_sparse_da0 = 1;            // sfd2_set_option "sparse_da0": with "sparse_da3", convDa.0 on the 4 x 4 blocks that kernel reads only (sparse_da0_kernel.hip):
+                                       // 1 = where the plan expects it to pay (plan_pass), 0 = always dense, 2 = wherever the arithmetic allows (tests, A/B runs at small sizes)
+    DevPtr da0_in;                     // ... the backbone output's fp16 plane as the last run_network left it: sfd2_extract's sparse convDa.0 reads it after the selection
     int opt_fuse_pb = 1;               // sfd2_set_option "fuse_pb": convPb inside the fused detector-head / heat-map kernel
     int opt_comp_rb = 1;               // sfd2_set_option "comp_rb": SFD2_PREC_F16C compensates the ResBlocks too (0: fused fp16 ResBlock kernel)
     int opt_rb_inner = 2;              // sfd2_set_option "rb_inner": SFD2_PREC_F16C ResBlocks, 1 = t2 (the grouped conv's output) stored as plain
@@ -411,6 +414,7 @@ struct PassPlan {
     bool branches = false, sta_early = false, sta_side = false;   // detector branch on the side stream; ConvSta before the heads / on the side stream
     bool skip_head = false, skip_pb = false, skip_db = false, skip_da3 = false;   // layers left to sfd2_extract's post-processing
     bool sparse_desc = false, sparse_da3 = false, sparse_x3 = false;           // its sparse descriptor head: fp16, fp16 with convDa.3, f16x3
+    bool sparse_da0 = false;                 // ... with sparse_da3: convDa.0 as well, on the 4 x 4 blocks around the key points' corners (run_network skips the layer)
     struct { int slot = -1; size_t off = 0; } at[T_COUNT];   // alias: each tensor's arena slot (-1: its own buffer) and its byte offset inside the slot
     int n_slots = 0;                         // ... slots in all, bytes per slot
     size_t slot_bytes = 0;

@@ -43,6 +43,18 @@ __device__ __forceinline__ float4 sfd2_lds_f4(const float *p)
     __builtin_memcpy(&r, &raw, 16);
     return r;
 }
+// nets/extractor.py:199-208 (F.grid_sample, bilinear, align_corners=False): the top-left corner of the key point's 2 x 2 block,
+// the arithmetic of post_kernels.hip's sample_geom.  One definition for the two kernels of the sparse descriptor head
+// (sparse_da0_kernel.hip, sparse_da3_kernel.hip): they must agree on every key point's block.
+__device__ __forceinline__ void sd_corner(float kx, float ky, float half_w, float half_h, int hc, int wc, int &x0, int &y0)
+{
+    const float gx = __fsub_rn(__fdiv_rn(kx, half_w), 1.0f);
+    const float gy = __fsub_rn(__fdiv_rn(ky, half_h), 1.0f);
+    const float ix = __fdiv_rn(__fsub_rn(__fmul_rn(__fadd_rn(gx, 1.0f), (float)wc), 1.0f), 2.0f);
+    const float iy = __fdiv_rn(__fsub_rn(__fmul_rn(__fadd_rn(gy, 1.0f), (float)hc), 1.0f), 2.0f);
+    x0 = (int)floorf(ix);
+    y0 = (int)floorf(iy);
+}
 #endif
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
@@ -411,6 +423,11 @@ void launch_conv1x1_c256_c(hipStream_t st, const half_t *in, const half_t *in_c,
                            const half_t *wc_frag, const float *scale, const float *shift, int relu, const half_t *res,
                            const half_t *res_c, half_t *out, half_t *out_c, const half_t *zero_page, int sbyte, unsigned int *range,
                            Rec rin /* None, Unit8 or Resid8 */, Rec rout /* None or Unit8 */);
+// sparse_da0_kernel.hip: convDa.0 on the 4 x 4 blocks sparse_da3_kernel reads only, stored into the dense map `out` [hc][wc][256] at the pixels'
+// true positions (in: the backbone output's fp16 plane; wpk: the layer's common packing; kpts / count / n_max / nh / nw as for launch_sparse_da3)
+bool sparse_da0_serves(int cin, int CoutP, int hc, int wc);
+void launch_sparse_da0(hipStream_t st, const half_t *in, int hc, int wc, int nh, int nw, const half_t *wpk, const float *scale, const float *shift,
+                       int relu, const float *kpts, const unsigned int *count, int n_max, half_t *out);
 // sparse_da3_kernel.hip: convDa.3 on the four bilinear corner pixels of every selected key point only -> out [n_max][4][256] fp16
 void launch_sparse_da3(hipStream_t st, const half_t *fmap, int hc, int wc, int nh, int nw, const half_t *wpk, const half_t *wsl, int CoutP,
                        const float *scale, const float *shift, int relu, const float *kpts, const unsigned int *count, int n_max,

@@ -38,17 +38,7 @@
 typedef __attribute__((address_space(3))) void sd_lds_t;
 typedef const __attribute__((address_space(1))) void sd_gbl_t;
 
-// nets/extractor.py:199-208 (F.grid_sample, bilinear, align_corners=False): the top-left corner of the key point's 2 x 2 block,
-// the arithmetic of post_kernels.hip's sample_geom
-__device__ __forceinline__ void sd_corner(float kx, float ky, float half_w, float half_h, int hc, int wc, int &x0, int &y0)
-{
-    const float gx = __fsub_rn(__fdiv_rn(kx, half_w), 1.0f);
-    const float gy = __fsub_rn(__fdiv_rn(ky, half_h), 1.0f);
-    const float ix = __fdiv_rn(__fsub_rn(__fmul_rn(__fadd_rn(gx, 1.0f), (float)wc), 1.0f), 2.0f);
-    const float iy = __fdiv_rn(__fsub_rn(__fmul_rn(__fadd_rn(gy, 1.0f), (float)hc), 1.0f), 2.0f);
-    x0 = (int)floorf(ix);
-    y0 = (int)floorf(iy);
-}
+// (sd_corner, the top-left corner of a key point's 2 x 2 block: sfd2_internal.h)
 
 // X3 (SFD2_PREC_F16X3): fmap / fmap_lo = convDa.0's output as hi / lo' planes, wpk = [hi chunks][lo' chunks], three MFMAs per K
 // slice into two accumulators (hi x hi; hi x lo' + lo' x hi, weighted 2^-11), fp32 output [n_max][4][256]
