@@ -85,7 +85,7 @@ typedef struct {
     int64_t n_candidates; /* N0 after NMS + threshold + border of the last extract          */
 } sfd2_timings;
 
-int sfd2_version(void);   /* 100 = rounds 1-4; 105 adds sfd2_extract_record_async, sfd2_desc_pack and host outputs with SFD2_FLAG_ASYNC; 106 adds sfd2_get_margin_status; 107 adds sfd2_get_relax_status (option "c3b_plain"); 108 adds sfd2_get_option, sfd2_device_pci_bus_id, SFD2_FLAG_DESC_STORE64; 109 adds the baseline JPEG decoder (sfd2_jpeg_*); 112 adds the SfM map (sfd2_verify_matches_batch, sfd2_build_tracks, sfd2_triangulate_tracks); 113 adds the pair selection (sfd2_pairs_retrieval, sfd2_pairs_covisibility, sfd2_pairs_poses); 114 adds sfd2_covis_clusters; 115 adds sfd2_covis_frames; 116 adds the VLAD global descriptors (sfd2_vlad_assign, sfd2_vlad_aggregate, sfd2_vlad_kmeans); 117 adds sfd2_relative_pose_batch; 118 adds sfd2_bundle_adjust */
+int sfd2_version(void);   /* 100 = rounds 1-4; 105 adds sfd2_extract_record_async, sfd2_desc_pack and host outputs with SFD2_FLAG_ASYNC; 106 adds sfd2_get_margin_status; 107 adds sfd2_get_relax_status (option "c3b_plain"); 108 adds sfd2_get_option, sfd2_device_pci_bus_id, SFD2_FLAG_DESC_STORE64; 109 adds the baseline JPEG decoder (sfd2_jpeg_*); 112 adds the SfM map (sfd2_verify_matches_batch, sfd2_build_tracks, sfd2_triangulate_tracks); 113 adds the pair selection (sfd2_pairs_retrieval, sfd2_pairs_covisibility, sfd2_pairs_poses); 114 adds sfd2_covis_clusters; 115 adds sfd2_covis_frames; 116 adds the VLAD global descriptors (sfd2_vlad_assign, sfd2_vlad_aggregate, sfd2_vlad_kmeans); 117 adds sfd2_relative_pose_batch; 118 adds sfd2_bundle_adjust; 119 adds the mapper's bookkeeping (sfd2_mapper_restrict, sfd2_mapper_filter, sfd2_mapper_visible, sfd2_mapper_assemble) */
 const char *sfd2_last_error(void);
 
 int sfd2_ctx_create(int device, sfd2_ctx **out);
@@ -768,6 +768,44 @@ typedef struct {
 int sfd2_bundle_adjust(sfd2_ctx *ctx, sfd2_tri_view *views, int n_views, const uint8_t *view_constant, double *xyz, int n_points,
                        const uint8_t *point_constant, const int64_t *point_offsets, const int32_t *obs_view, const double *obs_xy,
                        const sfd2_ba_conf *conf, sfd2_ba_result *result, double *obs_error, int flags);
+
+/* ------------------------------------------------------------------------------------------------ incremental mapper
+ * The bookkeeping between relative pose, absolute pose, triangulation and bundle adjustment in a round of sfd2_amd.reconstruction
+ * (DESIGN.md section 15).  Conventions of the SfM-map section: host arrays in and out, the calls run on sfd2_get_stream() and
+ * synchronise before they return, and return -1 with sfd2_last_error() set on a bad argument, non-finite input or an index out of
+ * range (the message names the first offending index).  The track table is sfd2_build_tracks': track t holds the observations
+ * track_offsets[t] .. track_offsets[t + 1] of obs_view (index into the n_views views) and obs_xy (key point as stored, float32).
+ * Integer work is exact; atomics are integer adds only, sums have a fixed order: results depend on the inputs (and the flags) only. */
+#define SFD2_MAPPER_FLAG_TRACK_LANE 1  /* every track's (point's) observations by one lane, whatever its length                */
+#define SFD2_MAPPER_FLAG_TRACK_WAVE 2  /* every track's (point's) by one wave (default: a wave beyond 64 observations, else a lane) */
+/* The tracks with observations in at least two distinct views that registered[n_views] marks (non-zero), in track order, each
+ * with its registered observations in observation order.  sub_track (capacity n_tracks): the source track; sub_offsets (capacity
+ * n_tracks + 1); sub_obs (the source observation index), sub_view and sub_xy[.][2] (capacity track_offsets[n_tracks]); the two lengths
+ * in *n_sub_tracks and *n_sub_obs.  flags: 0 or one SFD2_MAPPER_FLAG_*; both mappings give the same bytes. */
+int sfd2_mapper_restrict(sfd2_ctx *ctx, const int64_t *track_offsets, int n_tracks, const int32_t *obs_view, const float *obs_xy,
+                         const uint8_t *registered, int n_views, int32_t *sub_track, int64_t *sub_offsets, int32_t *sub_obs, int32_t *sub_view,
+                         float *sub_xy, int64_t *n_sub_tracks, int64_t *n_sub_obs, int flags);
+/* Point p holds the observations point_offsets[p] .. point_offsets[p + 1]: obs_view and obs_xy[.][2] (double pixels as
+ * sfd2_bundle_adjust takes them: the +0.5 applied).  e = |project(cam, R X + t) - xy|; obs_keep[o] = depth > 0 and e <=
+ * max_reproj_error (a NaN is not kept).  point_live[p] = kept observations in two distinct views and point_angle[p] >=
+ * min_tri_angle_deg; point_error[p]: the mean e of the kept (0 when none), summed in observation order (lane) or as 64 strided partial
+ * sums joined by a fixed tree (wave); point_angle[p]: the largest angle at X between the rays to the centres of two kept
+ * observations, degrees (NaN below two kept).  fp64.  flags: 0 or one SFD2_MAPPER_FLAG_*. */
+int sfd2_mapper_filter(sfd2_ctx *ctx, const sfd2_tri_view *views, int n_views, const double *xyz, int n_points, const int64_t *point_offsets,
+                       const int32_t *obs_view, const double *obs_xy, double max_reproj_error, double min_tri_angle_deg, uint8_t *obs_keep,
+                       uint8_t *point_live, double *point_error, double *point_angle, int flags);
+/* The points are point_track[n_points] (their track, ascending, at most SFD2_TRI_MAX_POINTS per track) with point_live[n_points].
+ * counts[n_views]: for an unregistered view the sum, over its observations, of the live points of the observation's track (the
+ * correspondences sfd2_mapper_assemble would write for it); 0 for a registered view.  flags: 0. */
+int sfd2_mapper_visible(sfd2_ctx *ctx, const int64_t *track_offsets, int n_tracks, const int32_t *obs_view, const uint8_t *registered, int n_views,
+                        const int32_t *point_track, const uint8_t *point_live, int n_points, int64_t *counts, int flags);
+/* The 2D-3D problems of the views cand[k]: per candidate every (observation of the view, live point of its track) pair, ordered by
+ * observation index and then by point index.  offsets[k + 1]; rows offsets[c] .. offsets[c + 1] of points2D[.][2] (stored xy + 0.5),
+ * points3D[.][3] (the point's xyz), src_obs and src_point.  capacity: rows the four arrays hold; when offsets[k] is larger the call
+ * returns -1 with only the offsets written (the sum of sfd2_mapper_visible's counts over the candidates is the size).  flags: 0. */
+int sfd2_mapper_assemble(sfd2_ctx *ctx, const int64_t *track_offsets, int n_tracks, const int32_t *obs_view, const float *obs_xy, int n_views,
+                         const int32_t *point_track, const uint8_t *point_live, const double *xyz, int n_points, const int32_t *cand, int k,
+                         int64_t capacity, int64_t *offsets, double *points2D, double *points3D, int32_t *src_obs, int32_t *src_point, int flags);
 
 /* ------------------------------------------------------------------------------------------------ pair selection
  * The image pairs the stages above are run on: hloc/pairs_from_retrieval.py (query-db pairs by global-descriptor similarity),

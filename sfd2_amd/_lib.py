@@ -174,6 +174,7 @@ class BaResult(ctypes.Structure):
 BA_LOSS_TRIVIAL, BA_LOSS_CAUCHY = 0, 1                                              # SFD2_BA_*
 BA_ST_GRADIENT, BA_ST_FUNCTION, BA_ST_MAX_ITERATIONS, BA_ST_LAMBDA, BA_ST_NONFINITE = 0, 1, 2, 3, 4
 BA_FLAG_POINT_LANE, BA_FLAG_POINT_WAVE = 1, 2
+MAPPER_FLAG_TRACK_LANE, MAPPER_FLAG_TRACK_WAVE = 1, 2                             # SFD2_MAPPER_*
 TRI_MAX_POINTS = 4
 TRI_ST_RANGE, TRI_ST_NOT_CONVERGED = 1, 2
 PAIRS_MAX_K, PAIRS_POSES_MAX_K = 256, 1024
@@ -220,6 +221,7 @@ EXPORTS = [
     "sfd2_pairs_retrieval", "sfd2_pairs_covisibility", "sfd2_pairs_poses", "sfd2_covis_clusters",
     "sfd2_covis_frames", "sfd2_vlad_assign", "sfd2_vlad_aggregate", "sfd2_vlad_kmeans",
     "sfd2_relative_pose_batch", "sfd2_bundle_adjust",
+    "sfd2_mapper_restrict", "sfd2_mapper_filter", "sfd2_mapper_visible", "sfd2_mapper_assemble",
 ]
 
 _lib = None
@@ -320,10 +322,14 @@ def load():
     lib.sfd2_vlad_aggregate.argtypes = [vp, vp, vp, ci, vp, ci, ci, ci, vp, vp, ci]
     lib.sfd2_vlad_kmeans.argtypes = [vp, vp, i64, ci, ci, ci, vp, vp, vp, pi, ci]
     lib.sfd2_bundle_adjust.argtypes = [vp, ctypes.POINTER(TriView), ci, vp, vp, ci, vp, vp, vp, vp, ctypes.POINTER(BaConf), ctypes.POINTER(BaResult), vp, ci]
+    lib.sfd2_mapper_restrict.argtypes = [vp, vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, ctypes.POINTER(i64), ctypes.POINTER(i64), ci]
+    lib.sfd2_mapper_filter.argtypes = [vp, ctypes.POINTER(TriView), ci, vp, ci, vp, vp, vp, cd, cd, vp, vp, vp, vp, ci]
+    lib.sfd2_mapper_visible.argtypes = [vp, vp, ci, vp, vp, ci, vp, vp, ci, vp, ci]
+    lib.sfd2_mapper_assemble.argtypes = [vp, vp, ci, vp, vp, ci, vp, vp, vp, ci, vp, ci, i64, vp, vp, vp, vp, vp, ci]
     for name in EXPORTS:
         getattr(lib, name)  # raises AttributeError if the .so lacks a declared symbol
-    if lib.sfd2_version() < 118:
-        raise RuntimeError(f"{LIB_PATH} is version {lib.sfd2_version()}, this binding needs >= 118 (rebuild: __graft_entry__.build())")
+    if lib.sfd2_version() < 119:
+        raise RuntimeError(f"{LIB_PATH} is version {lib.sfd2_version()}, this binding needs >= 119 (rebuild: __graft_entry__.build())")
     _lib = lib
     return lib
 

@@ -303,6 +303,7 @@ struct sfd2_ctx {
     ScratchBuf pairs_in, pairs_ws;          // sfd2_pairs_retrieval / _covisibility / _poses (api_pairs.hip), sfd2_covis_clusters (api_cluster.hip) and sfd2_covis_frames (api_frames.hip): uploaded inputs, partial lists / counters / slot rows and results
     ScratchBuf vlad_in, vlad_ws;            // sfd2_vlad_assign / _aggregate / _kmeans (api_vlad.hip): uploaded rows, centroids and offsets; assignments, sums, partials and results
     ScratchBuf ba_in, ba_ws;                // sfd2_bundle_adjust (api_bundle.hip): uploaded inputs and the two CSRs; state, Jacobian records, blocks, PCG vectors and results
+    ScratchBuf map_in, map_ws;              // sfd2_mapper_restrict / _filter / _visible / _assemble (api_mapper.hip): uploaded tables and lists; flags, scans, per-observation work and results
     DevBuf img_scaled, ms_kp, ms_sc, ms_de, ms_keys, ms_sorted, ms_cnt;
     unsigned int ms_cand_seen[8] = {};
     int ms_cand_cap[8] = {};
