@@ -7,7 +7,12 @@ FLOORS holds the two routes' disagreements and RADII the near-tie radii (bundle_
 measured here on the CPU; the GPU tolerances are 10 x the floor that bundle_ref computes on the machine the test runs on, ceiling
 1e-6.  The disagreements are differences of rounding noise, so another numpy may move them: the check below allows a factor of 100.
 The largest disagreement over all scenes is 2.1e-10 of the scene's size ('trajectory'), 2.3e-12 of the step's norm on the one-step
-test; the largest near-tie radius 3.2e-7 ('trajectory')."""
+test; the largest near-tie radius 3.2e-7 ('trajectory').
+
+The scenes of tests/test_gpu_bundle_edges.py are too large for a dense H: their references are bundle_ref.lm_blocks (independent clusters)
+and bundle_ref.arrow_step (few views, very many points), checked here against the dense routes on small scenes.  Their floors are recorded
+the same way; PCG holds what a conjugate-gradient residual of 1e-14 may do to a step of the cluster scenes, SUMS how far the fp64 sums of the
+'wide' scenes are from numpy.longdouble and math.fsum.  The new scenes' references take about 20 s here, computed once (bundle_ref.cached)."""
 import ctypes
 import os
 import re
@@ -30,6 +35,16 @@ FLOORS = {"arc_step": 2.3e-12, "arc": 1.1e-11, "arc_cauchy": 2.7e-14, "long_trac
 # scene -> near-tie radius at the restatement's minimum (bundle_ref.near_tie_radius), same measure
 RADII = {"arc": 1.2e-8, "arc_cauchy": 1.3e-8, "trajectory": 3.2e-7, "views_constant": 6.6e-9, "points_constant": 5.4e-9, "one_point_constant": 1.2e-8,
          "mix": 7.1e-9}
+# the scenes of tests/test_gpu_bundle_edges.py.  "*_step": the two routes' disagreement on the first step, relative to its norm; the others
+# state_diff's measure after the steps NEW_RUNS names
+FLOORS.update({"clusters_step": 3.1e-12, "clusters": 2.3e-14, "clusters_point_max_step": 1.9e-12, "clusters_point_max": 3.5e-14, "wide_step": 2.2e-12,
+               "short_tracks": 2.4e-14, "reject_first": 1.0e-11, "arc_function_tolerance": 1.2e-14})
+NEW_RUNS = {**br.CLUSTER_RUNS, "short_tracks": dict(max_iterations=2),
+            "reject_first": br.REJECT_FIRST, "arc_function_tolerance": dict(function_tolerance=1e-6, max_iterations=100)}
+# scene of clusters -> what a PCG residual of 1e-14 may do to the first step (bundle_ref.pcg_allowance: of the step's norm, state_diff's measure)
+PCG = {"clusters": (3.8e-12, 4.3e-13), "clusters_point_max": (5.8e-13, 2.1e-14)}
+# scene -> the fp64 restatement's cost and max |g| against numpy.longdouble and math.fsum, relative (bundle_ref.sum_floors)
+SUMS = {"wide": (1.5e-16, 2.1e-16), "wide_first": (1.5e-16, 4.1e-16)}
 CONVERGED = ("arc", "arc_cauchy", "trajectory", "views_constant", "points_constant", "one_point_constant", "mix")
 TWO_STEPS = ("long_tracks", "busy_views")
 
@@ -238,3 +253,120 @@ def test_scenes_stay_inside_their_conditions():
     r, _ = br.residuals(P, (P.truth[0], P.truth[1], P.truth[2]))
     assert abs((np.linalg.norm(r, axis=1) > 20).mean() - 0.1) < 0.005              # 10 % gross outliers
     assert br.solution("arc", gradient_tolerance=0.0)["status"] == "lambda_overflow"
+
+
+# ---------------------------------------------------------------------------------------------------------------- the large scenes
+def test_structured_solvers_match_the_dense_routes():
+    for name, bound in (("arc", 100 * FLOORS["arc_step"]), ("mix", 100 * FLOORS["mix"])):
+        P = br.scene(name)
+        for route in (br.ROUTE_A, br.ROUTE_B):
+            H, g, _ = br.normal_equations(P, P.state(), route[0])
+            dense = br.split_step(P, br.solve_step(P, H, g, 1e-4, route[1]))
+            d = br.step_diff(br.arrow_step(P, P.state(), 1e-4, route), dense)
+            print("arrow_step", name, route, d)
+            assert d <= bound, (name, route, d)
+        gc, gp, c = br.gradients(P, P.state())
+        assert max(np.abs(gc).max(), np.abs(gp).max()) == np.abs(g).max() and c == br.cost(P, P.state())
+        assert (gc[P.vconst] == 0).all() and (gp[P.pconst] == 0).all()
+    three = br.clusters("clusters")[:3]
+    M = br.merge(three)
+    assert (M.nv, M.np_, len(M.obs_view)) == (15, 36, 180) and M.obs_view[60:120].min() == 5 and M.off[12:25].tolist() == list(range(60, 125, 5))
+    for route in (br.ROUTE_A, br.ROUTE_B):
+        a, b = br.lm_blocks(three, route, max_iterations=2), br.lm(M, route, max_iterations=2)
+        d = br.state_diff(a["state"], b["state"])
+        print("lm_blocks", route, d)
+        assert d <= 100 * FLOORS["clusters"] and a["accepted"] == b["accepted"] == 2 and abs(a["cost"] - b["cost"]) <= 1e-12 * b["cost"]
+        assert br.step_diff(a["first_step"], b["first_step"]) <= 100 * FLOORS["clusters_step"]
+    # one cluster: the same arithmetic as lm(), rejections and the function tolerance included
+    for name, kw in (("reject_first", br.REJECT_FIRST), ("arc", dict(function_tolerance=1e-6))):
+        a, b = br.lm_blocks([br.scene(name)], br.ROUTE_B, **kw), br.solution(name, br.ROUTE_B, **kw)
+        assert all(np.array_equal(x, y) for x, y in zip(a["state"], b["state"]))
+        assert [a[k] for k in ("cost", "lambda", "iterations", "accepted", "status")] == [b[k] for k in ("cost", "lambda", "iterations", "accepted", "status")]
+
+
+def test_the_new_scenes_floors_are_as_recorded():
+    measured = {n: br.disagreement(n.replace("arc_function_tolerance", "arc"), **kw) for n, kw in NEW_RUNS.items()}
+    measured.update({n + "_step": br.step_diff(*br.first_steps(n)) for n in ("clusters", "clusters_point_max", "wide")})
+    print({k: float("%.2g" % v) for k, v in measured.items()})
+    for k, v in measured.items():
+        assert v <= 100 * FLOORS[k] and 10 * v < 1e-6, (k, v)
+    for n in br.CLUSTER_SCENES:
+        rel, ab = br.pcg_allowance(n)
+        print("pcg allowance", n, float("%.2g" % rel), float("%.2g" % ab))
+        assert PCG[n][0] / 100 <= rel <= 100 * PCG[n][0] and PCG[n][1] / 100 <= ab <= 100 * PCG[n][1]
+        assert br.step_floor(n) == max(measured[n + "_step"], rel) and br.floor(n, **NEW_RUNS[n]) == max(measured[n], ab)
+        assert br.step_tolerance(n) < 1e-9 and br.tolerance(n, **NEW_RUNS[n]) < 1e-10
+    assert np.finfo(np.longdouble).eps < 1e-18                  # the extended figures are worth their name
+    for n in ("wide", "wide_first"):
+        fc, fg, mc, mg = br.sum_floors(n)
+        print("sums", n, float("%.2g" % mc), float("%.2g" % mg))
+        assert mc <= 100 * SUMS[n][0] and mg <= 100 * SUMS[n][1]
+        assert fc == max(mc, br.SUM_DEPTH * 2.0 ** -53) and fg == max(mg, br.SUM_DEPTH * 2.0 ** -53) and max(fc, fg) < 1e-13
+    # the depth of the device's largest reduction (256 strided sums per 2048-element chunk, a tree over them; 256 strided
+    # sums over the partials, a tree over them) stays inside SUM_DEPTH
+    no = len(br.scene("wide").obs_view)
+    partials = -(-no // 2048)
+    assert 2048 // 256 + 8 + -(-partials // 256) + 8 <= br.SUM_DEPTH
+
+
+def test_the_new_scenes_stay_inside_their_conditions():
+    for name in br.CLUSTER_SCENES:
+        P, steps = br.scene(name), NEW_RUNS[name]["max_iterations"]
+        assert (P.nv, P.np_, len(P.obs_view)) == (1030, 2472, 12360) and P.nv > 1024 + 5
+        groups = P.vconst.reshape(-1, 5).tolist()
+        assert all(g == [True, False, False, False, True] for c, g in enumerate(groups) if (name, c) != ("clusters_point_max", br.POINT_MAX_CLUSTER))
+        assert not P.vconst[1026:1029].any()                                                 # variable views beyond the first 1024
+        for route in (br.ROUTE_A, br.ROUTE_B):
+            s = br.solution(name, route, **NEW_RUNS[name])
+            assert s["accepted"] == s["iterations"] == steps and all(abs(t - c) > 1e-6 * c for c, t, _, _ in s["history"]), (name, route)
+            for st in (P.state(), s["state"]):
+                assert br.residuals(P, st)[1].min() > 1.0, name
+        gc, gp, _ = br.gradients(P, P.state())
+        gc, gp = np.abs(gc).ravel(), np.abs(gp).ravel()
+        if name == "clusters":       # the largest entry: a view's, behind the first reduction chunk, in the cluster beyond view 1024
+            assert gc.argmax() >= 2048 and gc.argmax() // 6 >= 1025 and gc.max() > 1.05 * np.sort(gc)[-2] and gc.max() > 10 * gp.max()
+            assert 6 * P.nv > 2 * 2048 + 1 and np.sort(gc[:2048])[-1] < gc.max()
+        else:                        # a point's, behind the points' first chunk; every view entry smaller
+            assert gp.argmax() >= 2048 and gp.max() > 1.2 * gc.max() and gp.max() > 2 * np.sort(gp)[-2] and groups[br.POINT_MAX_CLUSTER] == [True] * 5
+            assert gp.argmax() // 3 == 12 * br.POINT_MAX_CLUSTER + 11
+    for name in ("wide", "wide_first"):
+        P = br.scene(name)
+        assert (P.nv, P.np_, len(P.obs_view)) == (3, 262145, 525290) and P.vconst.tolist() == [True, False, True]
+        assert -(-len(P.obs_view) // 2048) == 257 and -(-3 * P.np_ // 2048) == 385          # one more than the final pass's 256 lanes
+        lens = np.diff(P.off)
+        assert (lens == 3).sum() == 1000 and (lens == 2).sum() == P.np_ - 1000 and lens[0] == lens[-1] == 2
+        assert (P.obs_view[P.off[:-1]] == 0).all() and (P.obs_view[P.off[1:] - 1] == 2).all() and (P.obs_view[P.off[:-1][lens == 3] + 1] == 1).all()
+        gc, gp, c = br.gradients(P, P.state())
+        gp = np.abs(gp).ravel()
+        want = 0 if name == "wide_first" else P.np_ - 1
+        assert gp.argmax() // 3 == want and gp.max() > 2 * np.sort(gp)[-2] and gp.max() > 2 * np.abs(gc).max()
+        assert (gp.argmax() // 2048 >= 256) == (name == "wide")                              # the partial that holds it: second pass or first
+        assert br.residuals(P, P.state())[1].min() > 1.0
+    P = br.scene("wide")
+    for step in br.first_steps("wide"):
+        trial = br.apply_split(P.state(), step)
+        assert br.cost(P, trial) < 0.5 * br.cost(P, P.state()) and br.residuals(P, trial)[1].min() > 1.0
+        assert np.abs(step[0][1]).min() > 1e-5 and (step[0][[0, 2]] == 0).all()               # the middle view moves, the outer two do not
+    P, s = br.scene("short_tracks"), br.solution("short_tracks", max_iterations=2)
+    assert np.diff(P.off)[list(br.SHORT_AT)].tolist() == [1, 0] * 4 and P.obs_view[P.off[:-1][list(br.SHORT_AT[::2])]].tolist() == [2, 3, 4, 5]
+    assert P.np_ == 68 and (np.delete(np.diff(P.off), br.SHORT_AT) == 6).all() and s["accepted"] == 2
+    assert all(np.array_equal(s["state"][2][j], P.X[j]) for j in br.SHORT_AT[1::2])          # never seen: never moved
+    assert all(np.abs(s["state"][2][j] - P.X[j]).max() > 1e-3 for j in br.SHORT_AT[::2])     # seen once: moved, held by the damping
+    for st in (P.state(), s["state"]):
+        assert br.residuals(P, st)[1].min() > 1.0
+    P = br.scene("reject_first")
+    for route in (br.ROUTE_A, br.ROUTE_B):
+        s = br.lm_blocks([P], route, **br.REJECT_FIRST)
+        pattern = [ok for _, _, ok, _ in s["history"]]
+        assert pattern == [True, False, False, False, True] and s["iterations"] == 5 and s["accepted"] == 2 and s["lambda"] == br.solution("reject_first", **br.REJECT_FIRST)["lambda"]
+        assert all(abs(t - c) > 1e-6 * c for c, t, _, _ in s["history"]), [abs(t - c) / c for c, t, _, _ in s["history"]]
+        assert br.residuals(P, s["state"])[1].min() > 1.0 and br.residuals(P, P.state())[1].min() > 1.0
+
+
+def test_function_tolerance_decides_far_from_a_tie():
+    for route in (br.ROUTE_A, br.ROUTE_B):
+        s = br.lm_blocks([br.scene("arc")], route, function_tolerance=1e-6)
+        assert s["status"] == "function_tolerance" and s["iterations"] == s["accepted"] == 3
+        ratios = [abs(c - t) / c for c, t, ok, _ in s["history"] if ok]
+        print("function tolerance", route, ratios)
+        assert ratios[-1] < 1e-6 / 10 and ratios[-2] > 1e-6 * 10
