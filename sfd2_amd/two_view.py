@@ -1,7 +1,9 @@
 """Relative pose on the device (include/sfd2_hip.h sfd2_relative_pose_batch): the calibrated two-view geometry COLMAP estimates inside
 `colmap matches_importer` (hloc/triangulation.py:114, hloc/reconstruction.py:145) -- five-point LO-RANSAC on the squared Sampson error,
 a refinement over the inliers and the cheirality choice.  Essential matrix only; a rotation-only pair is reported
-through the triangulation angle (`small_baseline`), not through a homography.
+through the triangulation angle (`small_baseline`), not through a homography.  That holds for a rotation with noise on the points;
+correspondences that are a rotation exactly have no isolated solution and give no result (no inliers, success False,
+`small_baseline` False): a caller takes `success`, not `small_baseline` alone, for "this pair has a pose".
 
 Conventions: qvec = (w, x, y, z), camera 0 to camera 1, x1 = R(qvec) x0 + tvec with |tvec| = 1; E = [tvec]x R.  points2D are pixel
 coordinates taken as given; a camera is the dict of sfd2_amd.pose (model, params in COLMAP's order).  RANSAC defaults are COLMAP's

@@ -8,7 +8,7 @@ import two_view_ref as tv
 
 pytestmark = pytest.mark.gpu
 
-POSE_TOL = 1e-6        # radians: DESIGN.md 9's pose tolerance
+POSE_TOL = tv.POSE_TOL
 
 
 def _tv():
@@ -67,16 +67,7 @@ def test_solver_probes(family):
     assert not missed, missed
 
 
-def _compare(r, ref, worst):
-    assert r["num_trials"] == ref["num_trials"] and r["num_inliers"] == ref["num_inliers"]
-    assert (r["inliers"] == ref["inliers"]).all() and r["success"] == ref["success"]
-    if ref["num_inliers"] >= 5:
-        dr, dt = tv.pose_error(_R(r), r["tvec"], ref["R"], ref["t"])
-        worst[0], worst[1] = max(worst[0], dr), max(worst[1], dt)
-        assert dr <= POSE_TOL and dt <= POSE_TOL, (dr, dt)
-        both = np.isfinite(ref["angles"])
-        assert (np.isfinite(r["tri_angles_deg"]) == both).all()
-        assert np.allclose(r["tri_angles_deg"][both], ref["angles"][both], rtol=0, atol=1e-4)
+_compare = tv.compare       # shared with tests/test_gpu_two_view_edges.py
 
 
 def test_ransac_cases_against_the_restatement():

@@ -104,3 +104,77 @@ def test_breaking_a_rule_changes_a_compared_quantity(rule):
     for (p0, p1, c0, c1, _, _, th), ref in [list(zip(tv.ransac_cases(), tv.ransac_refs()))[k] for k in (2, 4, 7, 9)]:
         changed += _differs(tv.relative_pose_ref(p0, p1, c0, c1, th, **broken), ref)
     assert changed >= 1
+
+
+def test_seeds_are_64_bits_without_a_sign():
+    for n in (5, 60, 4096):
+        for trial in (0, 255, 256, 10 ** 9):
+            for seed in tv.SEED_RUNS:
+                assert tuple(tv.sample5v(seed, [trial], n)[0]) == tv.sample5(seed, trial, n)
+            assert tv.sample5(-1, trial, n) == tv.sample5(2 ** 64 - 1, trial, n) == tuple(tv.sample5v(-1, [trial], n)[0])
+    # the top bit reaches the draw
+    assert tv.sample5(2 ** 63, 0, 60) != tv.sample5(0, 0, 60) and tv.sample5(2 ** 64 - 1, 0, 60) != tv.sample5(2 ** 63 - 1, 0, 60)
+
+
+def test_edge_tables_stay_within_their_caps():
+    """The tables of tests/test_gpu_two_view_edges.py, on the CPU: they build, the restatement bands no more of them than the GPU
+    tests allow, and they still are what they are there for (the trial counts, every repeated point an inlier, nothing found on the
+    degenerate pairs).  Measured: 0 banded of the size, limit and repeat cases, 5 of the 258 small pairs (the final refinement
+    of each had not converged); about 20 s."""
+    refs = [tv.size_ref(k) for k in range(len(tv.SIZE_CASES))]
+    assert len(refs) == 15 and sum(r["banded"] for r in refs) <= 1
+    for (_, n, o), (p0, *_), r in zip(tv.SIZE_CASES, tv.size_cases(), refs):
+        assert len(p0) == n and r["success"] and r["num_inliers"] >= 0.9 * (1 - o) * n
+        assert r["num_trials"] == 256 if o <= 0.3 else 1536 <= r["num_trials"] <= 2048
+    assert {len(c[0]) for c in tv.size_cases()} == {255, 256, 257, 511, 512, 513, 1025}
+    # a stride that is skipped, or an element that is dropped at a seam, shows in the compared mask: the element at every seam is an
+    # inlier of some case, and where a pair ends in a partial stride that stride holds inliers in some case of that size
+    masks = [r["inliers"] for r in refs if not r["banded"]]
+    for seam in (256, 512, 768, 1024):
+        assert any(len(m) > seam and m[seam] for m in masks), seam
+    for n in (255, 257, 511, 513, 1025):
+        assert any(m[(n - 1) // 256 * 256:].any() for m in masks if len(m) == n), n
+
+    assert len(tv.LIMIT_RUNS) == 11
+    for conf, trials in tv.LIMIT_RUNS:
+        r = tv.limit_ref(**conf)
+        assert r["num_trials"] == trials and not r["banded"], conf
+    for seed in tv.SEED_RUNS:
+        assert not tv.limit_ref(seed=seed)["banded"]
+    assert tv.limit_ref(seed=-1)["inliers"].tolist() == tv.limit_ref(seed=2 ** 64 - 1)["inliers"].tolist()
+    # a partial round that ran its idle trials as well shows in the runs of one trial (the other runs' local optimisation leads
+    # every good hypothesis to the same 32 inliers)
+    p0, p1, c0, c1, _, _, th = tv.limit_case()
+    for conf in (dict(max_num_trials=1), dict(confidence=0.0), dict(min_inlier_ratio=1.0)):
+        assert _differs(tv.limit_ref(**conf), tv.relative_pose_ref(p0, p1, c0, c1, th, dead_lanes=True, **conf))
+
+    refs = [tv.repeat_ref(k) for k in range(len(tv.REPEAT_CASES))]
+    assert len(refs) == 12 and sum(r["banded"] for r in refs) <= 1
+    for (_, classes, copies, noise), (p0, p1, _, _, R, t, _), r in zip(tv.REPEAT_CASES, tv.repeat_cases(), refs):
+        assert len(p0) == classes * copies and r["num_inliers"] == classes * copies in (128, 120) and r["success"] and r["num_trials"] == 256
+        assert noise > 0 or max(tv.pose_error(r["R"], r["t"], R, t)) <= 1e-6
+        # most samples of such a list hold a correspondence twice, and those give no hypothesis
+        idx = tv.sample5v(0, np.arange(256), len(p0)) % classes
+        twice = np.array([len(set(row)) < 5 for row in idx.tolist()])
+        assert 0.45 <= twice.mean() <= 0.8
+        x0, x1 = pr.undistort(pr.camera("OPENCV"), p0), pr.undistort(pr.camera("OPENCV"), p1)
+        smp = tv.sample5v(0, np.arange(256), len(p0))
+        _, owner, _, _ = tv.five_point_ref(x0[smp], x1[smp])
+        assert not twice[owner].any() and len(np.unique(owner)) >= 0.8 * (~twice).sum()
+
+    cases = tv.many_cases()
+    assert len(cases) == 300 and [len(c[0]) for c in cases[:7]] == list(tv.MANY_NS)
+    small = [i for i, c in enumerate(cases) if len(c[0]) <= 12]
+    banded = sum(tv.many_ref(i)["banded"] for i in small)
+    assert len(small) == 258 and banded <= len(small) // 10
+    assert sum(tv.many_ref(i)["success"] for i in small) >= 150
+
+    for name in ("identical", "four_classes", "rotation_exact", "identity"):
+        r = tv.degenerate_ref(name)
+        assert r["num_inliers"] == 0 and not r["success"] and r["num_trials"] == 512 and not np.isfinite(r["angles"]).any(), name
+    r = tv.degenerate_ref("all_outliers")
+    assert not r["banded"] and not r["success"] and r["num_trials"] == 1024 and 5 <= r["num_inliers"] < 15
+    p0, p1, *_ = tv.degenerate("collinear")
+    for p in (p0, p1):                                     # on a line in both images
+        assert np.linalg.svd(p - p.mean(0), compute_uv=False)[1] <= 1e-9 * np.linalg.norm(p - p.mean(0))
+    assert len(p0) == 40 and tv.degenerate_ref("collinear")["num_trials"] == 512

@@ -3,8 +3,8 @@ from the text and not from the kernel: the sampling on integers, a five-point so
 space in its own chart, LU, the action matrix of multiplication by y and LAPACK's eigenvectors, where the kernel reduces by Gauss-Jordan, picks
 its chart, and runs its own QR iteration and inverse iteration on the action matrix of x), the fp64 Sampson error,
 the LO-RANSAC rounds with their support order and stopping rule, the final refinement, the cheirality choice and the triangulation
-angles; and the committed cases the GPU tests (tests/test_gpu_two_view.py) and the CPU checks (tests/test_two_view_ref_host.py)
-share.  Everything is batched over hypotheses so that a round of 256 trials is a handful of numpy calls."""
+angles; and the committed cases the GPU tests (tests/test_gpu_two_view.py, tests/test_gpu_two_view_edges.py) and the CPU checks
+(tests/test_two_view_ref_host.py) share.  Everything is batched over hypotheses so that a round of 256 trials is a handful of numpy calls."""
 import numpy as np
 
 import pose_ref as pr
@@ -19,6 +19,11 @@ ROOT_SEP = pr.ROOT_SEP       # two solutions of one sample closer than this (uni
 # generating matrix is MEASURED; the band is 100 x that.  It is used, relative, around the inlier threshold and for "equal" sums.
 MEASURED = 1.1e-7
 BAND = 100 * MEASURED
+EXACT_SUM = 1e-24            # a sum of squared Sampson errors below this is that of an exact solution (rounding only)
+# The final refinement ends after REF_ITERS steps or when lambda runs away, converged or not.  Where it has not, its end point
+# depends on which steps rounding let pass (`cost <= cost before` in a flat valley), and two implementations end apart by about the
+# step that remains: a case whose remaining Gauss-Newton step is longer than a hundredth of the pose tolerance is too close to call.
+REFINE_LEFT = 1e-8
 _M64 = (1 << 64) - 1
 mix64 = pr.mix64
 
@@ -293,7 +298,8 @@ def _in_band(e, th2):
 
 
 def _close(a, b):
-    return abs(a - b) <= BAND * max(abs(a), abs(b))
+    """Two sums of squared errors are too close to order: within the band of each other, or both an exact fit's (rounding only)."""
+    return abs(a - b) <= BAND * max(abs(a), abs(b)) or max(abs(a), abs(b)) < EXACT_SUM
 
 
 def _distinct(Ea, Eb):
@@ -310,15 +316,17 @@ def _lo_tie_matters(e, th2):
 
 
 def lo_ransac_ref(x0, x1, th2, min_inlier_ratio=0.25, min_num_trials=0, max_num_trials=10000, confidence=0.999, seed=0, multiplier=3.0,
-                  lo=True, smaller_sum=True, drop_root=False):
-    """The rounds on normalised points.  Returns {'E' (None without a hypothesis), 'cnt', 'sum', 'trials', 'banded', 'why' (the reasons)}.  multiplier,
-    lo, smaller_sum, drop_root: the rule breaks of the host test."""
+                  lo=True, smaller_sum=True, drop_root=False, dead_lanes=False):
+    """The rounds on normalised points.  Returns {'E' (None without a hypothesis), 'cnt', 'sum', 'trials', 'banded', 'why' (the reasons),
+    'either' (the other matrices that fit every point to rounding as the best one does)}.  multiplier, lo, smaller_sum, drop_root,
+    dead_lanes (a partial round runs all its 256 trials): the rule breaks of the host test."""
     n = len(x0)
     mn, mx = trial_limits(min_inlier_ratio, min_num_trials, max_num_trials, confidence, multiplier)
     best, bE, why, trials, rnd = (-1, 0.0, np.inf), None, [], 0, 0
+    either = []
     sg = 1.0 if smaller_sum else -1.0
     while True:
-        tr = np.arange(rnd * ROUND, min((rnd + 1) * ROUND, mx))
+        tr = np.arange(rnd * ROUND, (rnd + 1) * ROUND if dead_lanes else min((rnd + 1) * ROUND, mx))
         idx = sample5v(seed, tr, n)
         Es, owner, near, _ = five_point_ref(x0[idx], x1[idx], drop_root)
         if len(Es):
@@ -328,7 +336,15 @@ def lo_ransac_ref(x0, x1, th2, min_inlier_ratio=0.25, min_num_trials=0, max_num_
             win = (int(cnt[w]), float(sm[w]), int(tr[owner[w]]))
             if (win[0], -sg * win[1], -win[2]) > (best[0], -sg * best[1], -best[2]):
                 rivals = [k for k in order[1:] if cnt[k] == cnt[w] and _close(sm[k], sm[w]) and _distinct(Es[k], Es[w])]
-                why += ["rival"] * int(bool(rivals)) + ["threshold"] * int(_in_band(err[w], th2)) + ["near"] * int(near[owner[w]])
+                # A winner that fits every point to rounding (n = 5: each of the sample's solutions does; a planar scene: both
+                # plane-consistent ones do) is ordered among its like by rounding alone.  Those rivals are not a reason to leave
+                # the case out: they are reported, and any one of them is a right answer.
+                exact = win[0] == n and win[1] < EXACT_SUM
+                either = []
+                for k in rivals if exact else []:
+                    if all(_distinct(Es[k], Eo) for Eo in either):
+                        either.append(Es[k])
+                why += ["rival"] * int(bool(rivals) and not exact) + ["threshold"] * int(_in_band(err[w], th2)) + ["near"] * int(near[owner[w]])
                 why += ["tie"] * int(best[0] == win[0] and _close(best[1], win[1]))
                 best, bE = win, Es[w]
                 if lo:
@@ -353,7 +369,7 @@ def lo_ransac_ref(x0, x1, th2, min_inlier_ratio=0.25, min_num_trials=0, max_num_
         if trials >= mn and best[0] > 0 and trials >= num_trials_needed(best[0] / n, confidence, multiplier):
             break
         rnd += 1
-    return {"E": bE, "cnt": best[0], "sum": best[1], "trials": trials, "banded": bool(why), "why": why}
+    return {"E": bE, "cnt": best[0], "sum": best[1], "trials": trials, "banded": bool(why), "why": why, "either": either}
 
 
 # ------------------------------------------------------------------------------------------------------------ final stage
@@ -376,7 +392,8 @@ SLOTS = ((0, 1.0), (0, -1.0), (1, 1.0), (1, -1.0))       # (R or R' = (2 t t^T -
 
 def final_stage(E, mask, x0, x1, slots=SLOTS):
     """Levenberg-Marquardt over the masked correspondences from decompose(E), then the first slot with the most masked points in
-    front of both cameras.  Returns (R, t, angles [n] with NaN outside, chosen)."""
+    front of both cameras.  Returns (R, t, angles [n] with NaN outside, chosen, other = the same four of the slot -E would have
+    led to, None when that is the same slot; left = the length of the Gauss-Newton step that remains at the returned pose)."""
     R, t = decompose(E[None])
     w = mask.astype(np.float64)[None]
     H, g, c = normal_equations(R, t, x0[None], x1[None], w)
@@ -397,6 +414,8 @@ def final_stage(E, mask, x0, x1, slots=SLOTS):
             lam *= 10.0
             if lam > 1e12 or step < 1e-26:
                 break
+    d, ok = solve5(H, g)
+    left = float(np.linalg.norm(d[0])) if ok[0] else np.inf
     R, t = R[0], t[0]
     Rs = (R, (2.0 * np.outer(t, t) - np.eye(3)) @ R)
     counts, cand = [], []
@@ -406,7 +425,13 @@ def final_stage(E, mask, x0, x1, slots=SLOTS):
         counts.append(int(front.sum()))
         cand.append((Rs[r], s * t, np.where(front, deg, np.nan)))
     k = int(np.argmax(counts))                             # the first of the largest
-    return cand[k][0], cand[k][1], cand[k][2], counts[k] > 0
+    # E and -E are one hypothesis, and which of the two a solver returns is its own affair; decompose(-E) gives R' where
+    # decompose(E) gives R, so under -E the slots come in the order 2, 3, 0, 1.  When a slot of R and one of R' tie for the most
+    # points in front (a handful of points, a wrong hypothesis) the text does not say which wins: the other one is returned too.
+    flipped = sorted(range(len(slots)), key=lambda j: (slots[j][0] == slots[0][0], j))
+    o = max(flipped, key=lambda j: (counts[j], -flipped.index(j)))
+    other = None if o == k else (cand[o][0], cand[o][1], cand[o][2], counts[o] > 0)
+    return cand[k][0], cand[k][1], cand[k][2], counts[k] > 0, other, left
 
 
 def threshold2(cam0, cam1, max_error_px):
@@ -414,12 +439,14 @@ def threshold2(cam0, cam1, max_error_px):
 
 
 def relative_pose_ref(p0, p1, cam0, cam1, max_error_px=4.0, min_num_inliers=15, slots=SLOTS, **conf):
-    """The whole estimator on pixels.  Returns {'success', 'R', 't', 'num_inliers', 'inliers', 'num_trials', 'angles', 'banded'}."""
+    """The whole estimator on pixels.  Returns {'success', 'R', 't', 'num_inliers', 'inliers', 'num_trials', 'angles', 'banded', 'either':
+    [{'R', 't', 'angles', 'success'}] of the other exact fits of every point and of a cheirality tie that the sign of E decides
+    (final_stage), each as right an answer as the first}."""
     x0, x1 = pr.undistort(cam0, p0), pr.undistort(cam1, p1)
     th2 = threshold2(cam0, cam1, max_error_px)
     n = len(x0)
     out = {"success": False, "R": np.eye(3), "t": np.zeros(3), "num_inliers": 0, "inliers": np.zeros(n, bool), "num_trials": 0,
-           "angles": np.full(n, np.nan), "banded": False}
+           "angles": np.full(n, np.nan), "banded": False, "either": []}
     if n < 5:
         return out
     r = lo_ransac_ref(x0, x1, th2, **conf)
@@ -427,8 +454,18 @@ def relative_pose_ref(p0, p1, cam0, cam1, max_error_px=4.0, min_num_inliers=15, 
     if r["cnt"] < 5:
         return out
     mask = sampson_f64(r["E"], x0, x1) <= th2
-    R, t, ang, chosen = final_stage(r["E"], mask, x0, x1, slots)
+    R, t, ang, chosen, other, left = final_stage(r["E"], mask, x0, x1, slots)
     out.update(R=R, t=t, num_inliers=r["cnt"], inliers=mask, angles=ang, success=bool(chosen and r["cnt"] >= min_num_inliers))
+    others = [other]
+    for Ek in r["either"]:                                 # exact fits of every point, as E is: the same mask
+        fs = final_stage(Ek, mask, x0, x1, slots)
+        others += [fs[:4], fs[4]]
+        left = max(left, fs[5])
+    if not left <= REFINE_LEFT:
+        out["banded"] = True
+        out["why"] = out["why"] + ["refinement"]
+    for Rk, tk, angk, chk in [o for o in others if o is not None]:
+        out["either"].append({"R": Rk, "t": tk, "angles": angk, "success": bool(chk and r["cnt"] >= min_num_inliers)})
     return out
 
 
@@ -574,9 +611,6 @@ def probes(family):
     return _cached(("probes", family), make)
 
 
-EXACT_SUM = 1e-24            # a sum of squared Sampson errors below this is that of an exact solution (rounding only)
-
-
 def probe_expect(family):
     """Per probe (expectation, poses): True -- the sample yields the generating matrix, which holds every point and wins, poses =
     [the generating pose]; 'either' -- a second exact solution holds every point as well (all points on one plane: the two-fold
@@ -624,3 +658,169 @@ def probe_expect(family):
 def measure_band():
     """The largest disagreement of probe_expect over the families whose samples are well conditioned."""
     return max(max(probe_expect(f)[1]) for f in PROBE_FAMILIES)
+
+
+# ------------------------------------------------------------------------------------------------------------ comparison
+POSE_TOL = 1e-6        # radians: DESIGN.md 9's pose tolerance
+
+
+def compare(r, ref, worst):
+    """A device result (two_view.relative_pose's dict) against relative_pose_ref's: trials, count and mask equal; then success, the
+    pose within POSE_TOL, the same angles finite and within 1e-4 degrees, against the restatement's answer or one of its 'either'.
+    worst [rotation, translation] keeps the largest differences."""
+    assert r["num_trials"] == ref["num_trials"] and r["num_inliers"] == ref["num_inliers"], \
+        (r["num_trials"], ref["num_trials"], r["num_inliers"], ref["num_inliers"])
+    assert (r["inliers"] == ref["inliers"]).all()
+    if ref["num_inliers"] < 5:
+        assert r["success"] == ref["success"]
+        return
+    cands = [ref] + ref.get("either", [])
+    errs = [pose_error(pr.qvec2rotmat(r["qvec"]), r["tvec"], c["R"], c["t"]) for c in cands]
+    k = int(np.argmin([max(e) for e in errs]))
+    c, (dr, dt) = cands[k], errs[k]
+    assert dr <= POSE_TOL and dt <= POSE_TOL, errs
+    worst[0], worst[1] = max(worst[0], dr), max(worst[1], dt)
+    assert r["success"] == c["success"], (r["success"], c["success"])
+    both = np.isfinite(c["angles"])
+    assert (np.isfinite(r["tri_angles_deg"]) == both).all()
+    assert np.allclose(r["tri_angles_deg"][both], c["angles"][both], rtol=0, atol=1e-4)
+
+
+# ------------------------------------------------------------------------------------------------------------ edge cases
+# (tests/test_gpu_two_view_edges.py; tests/test_two_view_ref_host.py keeps them honest on the CPU)
+_MODELS = ("SIMPLE_PINHOLE", "PINHOLE", "SIMPLE_RADIAL", "OPENCV")
+# the correspondences are walked in strides of 256: one under, at and over one, two and four strides; (index i, n, outlier ratio)
+SIZE_CASES = [(i, n, o) for i, n in enumerate((255, 256, 257, 511, 512, 513, 1025)) for o in (0.3, 0.6)]
+SIZE_CASES.append((7, 1025, 0.0))       # index 1024 is an outlier in both cases above: here the fifth stride's one element is an inlier
+
+
+def size_cases():
+    """[(p0, p1, cam0, cam1, R, t, max_error_px)] of SIZE_CASES: scene seed 100 + i, camera models i and i + 1 of the four, 0.5 px noise."""
+    def make():
+        out = []
+        for i, n, o in SIZE_CASES:
+            cam0, cam1 = pr.camera(_MODELS[i % 4]), pr.camera(_MODELS[(i + 1) % 4])
+            R, t, p0, p1, _ = two_view_scene(np.random.RandomState(100 + i), cam0, cam1, n, o, noise_px=0.5)
+            out.append((p0, p1, cam0, cam1, R, t, 4.0))
+        return out
+    return _cached("size_cases", make)
+
+
+def size_ref(k):
+    p0, p1, c0, c1, _, _, th = size_cases()[k]
+    return _cached(("size_ref", k), lambda: relative_pose_ref(p0, p1, c0, c1, th))
+
+
+# (options, the num_trials they must give) on LIMIT_SCENE: the trial limit one under, at and over a round and at two rounds, a single
+# trial, the closed ends of confidence and min_inlier_ratio, min_num_trials between and beyond the limits
+LIMIT_SCENE = (60, 0.5, "OPENCV", "OPENCV", 21, 4.0)
+LIMIT_RUNS = [(dict(max_num_trials=255), 255), (dict(max_num_trials=256), 256), (dict(max_num_trials=257), 257),
+              (dict(max_num_trials=512), 512), (dict(max_num_trials=1), 1), (dict(confidence=0.0), 1),
+              (dict(confidence=1.0, max_num_trials=600), 600), (dict(min_inlier_ratio=0.0, max_num_trials=600), 512),
+              (dict(min_inlier_ratio=1.0), 1), (dict(min_num_trials=513, max_num_trials=5000), 768),
+              (dict(min_num_trials=5000, max_num_trials=600), 600)]
+SEED_RUNS = [2 ** 64 - 1, 2 ** 63]      # a seed is 64 bits without a sign: -1 through the Python wrapper is the first of these
+
+
+def limit_case():
+    return _cached("limit", lambda: _case(*LIMIT_SCENE))
+
+
+def limit_ref(**conf):
+    p0, p1, c0, c1, _, _, th = limit_case()
+    return _cached(("limit_ref", tuple(sorted(conf.items()))), lambda: relative_pose_ref(p0, p1, c0, c1, th, **conf))
+
+
+# (scene seed, classes, copies, noise px): `classes` distinct correspondences without outliers, the whole list `copies` times over, as
+# a match list with repeated key points.  A sample with a repeated correspondence is rank-deficient and yields nothing: 1 -
+# prod_k (1 - k (copies - 1) / (n - k)) of all samples, 0.71 (8 x 16) and 0.56 (12 x 10).
+REPEAT_CASES = [(s, c, k, nz) for s in range(4) for c, k, nz in ((8, 16, 0.0), (8, 16, 0.5), (12, 10, 0.5))]
+
+
+def repeat_cases():
+    """[(p0, p1, cam, cam, R, t, max_error_px)] of REPEAT_CASES (OPENCV)."""
+    def make():
+        out, cam = [], pr.camera("OPENCV")
+        for s, c, k, nz in REPEAT_CASES:
+            R, t, p0, p1, _ = two_view_scene(np.random.RandomState(200 + s), cam, cam, c, 0.0, noise_px=nz)
+            out.append((np.tile(p0, (k, 1)), np.tile(p1, (k, 1)), cam, cam, R, t, 4.0))
+        return out
+    return _cached("repeat_cases", make)
+
+
+def repeat_ref(k):
+    p0, p1, c0, c1, _, _, th = repeat_cases()[k]
+    return _cached(("repeat_ref", k), lambda: relative_pose_ref(p0, p1, c0, c1, th))
+
+
+# 300 small pairs for one call: (n, scene seed) of pair i
+MANY = 300
+MANY_NS = (0, 3, 5, 6, 9, 12, 40)
+MANY_CONF = dict(max_num_trials=64, min_num_inliers=5)
+MANY_SEED = 3000
+
+
+def many_cases():
+    """[(p0, p1, cam0, cam1, max_error_px)]: pair i has MANY_NS[i % 7] correspondences (a quarter outliers from n = 9 on, 0.5 px
+    noise), camera models i and i + 1 of the four."""
+    def make():
+        out = []
+        for i in range(MANY):
+            n = MANY_NS[i % len(MANY_NS)]
+            cam0, cam1 = pr.camera(_MODELS[i % 4]), pr.camera(_MODELS[(i + 1) % 4])
+            p0 = p1 = np.zeros((0, 2))
+            if n:
+                _, _, p0, p1, _ = two_view_scene(np.random.RandomState(MANY_SEED + i), cam0, cam1, n, 0.25 if n >= 9 else 0.0, noise_px=0.5)
+            out.append((p0, p1, cam0, cam1, 4.0))
+        return out
+    return _cached("many_cases", make)
+
+
+def many_ref(i):
+    p0, p1, c0, c1, th = many_cases()[i]
+    return _cached(("many_ref", i), lambda: relative_pose_ref(p0, p1, c0, c1, th, **MANY_CONF))
+
+
+# name -> options; degenerate() gives the pair
+DEGENERATE = {"identical": dict(max_num_trials=512), "four_classes": dict(max_num_trials=512), "all_outliers": dict(max_num_trials=1024),
+              "rotation_exact": dict(max_num_trials=512), "identity": dict(max_num_trials=512), "collinear": dict(max_num_trials=512)}
+
+
+def degenerate(name):
+    """(p0, p1, cam, cam, R, t) of a DEGENERATE case (R, t the generating pose, None where there is none).  identical: one
+    correspondence 20 times (every sample is rank-deficient).  four_classes: four correspondences 16 times each (every sample holds one
+    twice, and a matrix through its four others would hold all 64).  all_outliers: 60 pixels of image 0 against uniformly random pixels of
+    image 1.  rotation_exact: 60 exact correspondences under a rotation alone (every [t]x R fits: no isolated solution).  identity:
+    the same 60 pixels in both images.  collinear: 40 exact correspondences of points on one line in space (a line in both images;
+    their essential matrix is not unique)."""
+    def make():
+        cam = pr.camera("OPENCV")
+        if name == "identical":
+            _, _, p0, p1, _ = two_view_scene(np.random.RandomState(6), cam, cam, 1)
+            return np.tile(p0, (20, 1)), np.tile(p1, (20, 1)), cam, cam, None, None
+        if name == "four_classes":
+            _, _, p0, p1, _ = two_view_scene(np.random.RandomState(9), cam, cam, 4, noise_px=0.5)
+            return np.tile(p0, (16, 1)), np.tile(p1, (16, 1)), cam, cam, None, None
+        if name == "all_outliers":
+            _, _, p0, p1, _ = two_view_scene(np.random.RandomState(7), cam, cam, 60, 1.0, noise_px=0.5)
+            return p0, p1, cam, cam, None, None
+        if name in ("rotation_exact", "identity"):
+            R, _, p0, p1, _ = two_view_scene(np.random.RandomState(5), cam, cam, 60, 0.0, noise_px=0.0, baseline=0.0)
+            return (p0, p1, cam, cam, R, None) if name == "rotation_exact" else (p0, p0.copy(), cam, cam, np.eye(3), None)
+        if name == "collinear":
+            cam = pr.camera("PINHOLE")
+            rs = np.random.RandomState(8)
+            X = np.array([-1.0, 0.4, 6.0]) + np.sort(rs.uniform(-1, 1, 40))[:, None] * np.array([1.5, 0.5, 2.0])
+            R = _exp_so3(np.array([[0.03, -0.1, 0.02]]))[0]
+            t = np.array([0.9, -0.1, 0.1])
+            p0, _ = pr.project(cam, [1.0, 0, 0, 0], np.zeros(3), X)
+            p1, z1 = pr.project(cam, pr.rotmat2qvec(R), t, X)
+            assert (z1 > 0).all()
+            return p0, p1, cam, cam, R, t / np.linalg.norm(t)
+        raise KeyError(name)
+    return _cached(("degenerate", name), make)
+
+
+def degenerate_ref(name):
+    p0, p1, c0, c1, _, _ = degenerate(name)
+    return _cached(("degenerate_ref", name), lambda: relative_pose_ref(p0, p1, c0, c1, 4.0, **DEGENERATE[name]))
