@@ -1,0 +1,98 @@
+// libsfd2hip: sfd2_fundamental_batch -- checks and packs the pairs, one launch of fundamental_kernels.hip.
+#include "sfd2_ctx.h"
+#include "api_scratch.h"
+
+namespace {
+
+// COLMAP ComputeNumTrials (sample size 7, dyn_num_trials_multiplier 3)
+double num_trials(double inlier_ratio, double confidence)
+{
+    const double nom = 1.0 - confidence;
+    if (nom <= 0) return 1e300;
+    const double den = 1.0 - std::pow(inlier_ratio, 7);
+    if (den <= 0) return 1.0;
+    if (den == 1.0 || std::fabs(std::log(den)) < 1e-16) return 1e300;
+    return std::ceil(std::log(nom) / std::log(den) * 3.0);
+}
+
+}  // namespace
+
+extern "C" int sfd2_fundamental_batch(sfd2_ctx *c, const sfd2_fundamental_problem *problems, int k, const sfd2_two_view_conf *conf,
+                                      sfd2_fundamental_result *results, uint8_t *inlier_mask_u8, int flags)
+{
+    const std::string F("sfd2_fundamental_batch");
+    if (!c || !conf || (k > 0 && (!problems || !results))) return fail(F + ": null argument");
+    if (k < 0) return fail(F + ": negative k");
+    if (flags != 0) return fail(F + ": unknown flags");
+    if (!(conf->confidence >= 0 && conf->confidence <= 1) || !(conf->min_inlier_ratio >= 0 && conf->min_inlier_ratio <= 1))
+        return fail(F + ": confidence and min_inlier_ratio must lie in [0, 1]");
+    if (conf->max_num_trials < 1 || conf->max_num_trials > 1000000000 || conf->min_num_trials < 0)
+        return fail(F + ": trial limits out of range (1 <= max_num_trials <= 1e9, min_num_trials >= 0)");
+    if (conf->min_num_inliers < 0) return fail(F + ": negative min_num_inliers");
+    TvConfDev d;
+    memset(&d, 0, sizeof(d));
+    // COLMAP's RANSAC: max_num_trials limited by the trial count of an assumed min_inlier_ratio (kNumSamples = 100000)
+    const double dyn = num_trials(std::floor(conf->min_inlier_ratio * 100000) / 100000.0, conf->confidence);
+    d.max_trials = std::max<int64_t>(1, std::min<double>((double)conf->max_num_trials, dyn));
+    d.min_trials = std::min(conf->min_num_trials, d.max_trials);
+    d.confidence = conf->confidence;
+    d.seed = conf->seed;
+    d.min_num_inliers = conf->min_num_inliers;
+    std::vector<FmProbDev> pd(k);
+    int64_t total = 0;
+    for (int i = 0; i < k; ++i) {
+        const sfd2_fundamental_problem &p = problems[i];
+        const std::string at = F + ": problem " + std::to_string(i) + ": ";
+        if (p.n < 0) return fail(at + "negative n");
+        if (p.n > 0 && (!p.points2D_0 || !p.points2D_1)) return fail(at + "null points");
+        if (!all_finite(p.points2D_0, 2 * (int64_t)p.n) || !all_finite(p.points2D_1, 2 * (int64_t)p.n)) return fail(at + "non-finite points");
+        if (!(std::isfinite(p.max_error_px) && p.max_error_px > 0)) return fail(at + "max_error_px must be positive and finite");
+        FmProbDev &o = pd[i];
+        memset(&o, 0, sizeof(o));
+        o.off = total;
+        o.n = p.n;
+        o.max_error_px = p.max_error_px;
+        total += p.n;
+    }
+    if (total > 0 && !inlier_mask_u8) return fail(F + ": null inlier mask");
+    if (k == 0) return 0;
+    HIPCHECK(hipSetDevice(c->device));
+    const int64_t N = std::max<int64_t>(total, 1);
+    Carve ci, cw, co;
+    // inputs: problems | points of image 0 | of image 1;  work: normalised points 0 | 1;  out: results | mask
+    const size_t o_pd = ci.take(sizeof(FmProbDev) * k), o_p0 = ci.take(16 * N), o_p1 = ci.take(16 * N);
+    const size_t o_x0 = cw.take(16 * N), o_x1 = cw.take(16 * N);
+    const size_t o_res = co.take(sizeof(FmResDev) * k), o_m = co.take(N);
+    HIPCHECK(hipStreamSynchronize(c->stream));              // earlier calls on this stream may still read the buffers
+    HIPCHECK(grow(c->fm_in, ci.off));
+    HIPCHECK(grow(c->fm_ws, cw.off));
+    HIPCHECK(grow(c->fm_out, co.off));
+    std::vector<double> p0(2 * (size_t)N), p1(2 * (size_t)N);
+    for (int i = 0; i < k; ++i) {
+        const int64_t o = pd[i].off, n = pd[i].n;
+        if (n) {
+            memcpy(p0.data() + 2 * o, problems[i].points2D_0, 16 * n);
+            memcpy(p1.data() + 2 * o, problems[i].points2D_1, 16 * n);
+        }
+    }
+    char *in = c->fm_in.as<char>(), *ws = c->fm_ws.as<char>(), *out = c->fm_out.as<char>();
+    HIPCHECK(hipMemcpyAsync(in + o_pd, pd.data(), sizeof(FmProbDev) * k, hipMemcpyHostToDevice, c->stream));
+    HIPCHECK(hipMemcpyAsync(in + o_p0, p0.data(), 16 * total, hipMemcpyHostToDevice, c->stream));
+    HIPCHECK(hipMemcpyAsync(in + o_p1, p1.data(), 16 * total, hipMemcpyHostToDevice, c->stream));
+    launch_fundamental(c->stream, at<const FmProbDev>(in, o_pd), k, d, at<const double>(in, o_p0), at<const double>(in, o_p1), at<double2>(ws, o_x0),
+                       at<double2>(ws, o_x1), at<unsigned char>(out, o_m), at<FmResDev>(out, o_res));
+    HIPCHECK(hipGetLastError());
+    std::vector<FmResDev> r(k);
+    HIPCHECK(hipMemcpyAsync(r.data(), out + o_res, sizeof(FmResDev) * k, hipMemcpyDeviceToHost, c->stream));
+    if (total) HIPCHECK(hipMemcpyAsync(inlier_mask_u8, out + o_m, total, hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(hipStreamSynchronize(c->stream));
+    for (int i = 0; i < k; ++i) {
+        sfd2_fundamental_result &o = results[i];
+        o.success = r[i].success;
+        o.num_inliers = r[i].num_inliers;
+        o.num_trials = r[i].num_trials;
+        o.reserved = 0;
+        for (int j = 0; j < 9; ++j) o.F[j] = r[i].F[j];
+    }
+    return 0;
+}

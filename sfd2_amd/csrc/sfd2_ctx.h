@@ -299,7 +299,8 @@ struct sfd2_ctx {
     ScratchBuf asm_in, asm_ws, asm_out;     // sfd2_assemble_2d3d (api_assemble.hip): descriptors and host inputs, per-(image, key point) work, host-bound outputs
     ScratchBuf pose_in, pose_ws, pose_out;  // sfd2_absolute_pose_batch / sfd2_pose_refine_batch (api_pose.hip): inputs, per-point work, results
     ScratchBuf tv_in, tv_ws, tv_out;        // sfd2_relative_pose_batch (api_two_view.hip): inputs, normalised points and the trials' matrices, results
-    ScratchBuf tri_in, tri_ws;              // sfd2_verify_matches_batch / sfd2_build_tracks / sfd2_triangulate_tracks (api_triangulate.hip): inputs, work and results
+    ScratchBuf fm_in, fm_ws, fm_out;        // sfd2_fundamental_batch (api_fundamental.hip): inputs, normalised points, results
+    ScratchBuf tri_in, tri_ws;             // sfd2_verify_matches_batch / sfd2_build_tracks / sfd2_triangulate_tracks (api_triangulate.hip): inputs, work and results
     ScratchBuf pairs_in, pairs_ws;          // sfd2_pairs_retrieval / _covisibility / _poses (api_pairs.hip), sfd2_covis_clusters (api_cluster.hip) and sfd2_covis_frames (api_frames.hip): uploaded inputs, partial lists / counters / slot rows and results
     ScratchBuf vlad_in, vlad_ws;            // sfd2_vlad_assign / _aggregate / _kmeans (api_vlad.hip): uploaded rows, centroids and offsets; assignments, sums, partials and results
     ScratchBuf ba_in, ba_ws;                // sfd2_bundle_adjust (api_bundle.hip): uploaded inputs and the two CSRs; state, Jacobian records, blocks, PCG vectors and results

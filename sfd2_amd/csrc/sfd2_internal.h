@@ -770,6 +770,20 @@ struct TvResDev {
 void launch_two_view(hipStream_t st, const TvProbDev *probs, int k, const TvConfDev &conf, const double *p0, const double *p1, double2 *x0,
                      double2 *x1, double *hyp, unsigned char *mask_out, double *angle_out, TvResDev *res);
 
+// ------------------------------------------------------------------------------------------------ fundamental matrix (fundamental_kernels.hip)
+struct FmProbDev {
+    int64_t off;                      // first correspondence of the pair in the concatenated arrays
+    int32_t n, pad;
+    double max_error_px;              // the kernel scales it by the pair's normalisation
+};
+struct FmResDev {
+    double F[9];
+    int32_t success, num_inliers, num_trials, pad;
+};
+// p0 / p1: pixels [N][2]; x0 / x1: work, normalised points [N]; conf: TvConfDev as for launch_two_view (sample size 7 in the kernel)
+void launch_fundamental(hipStream_t st, const FmProbDev *probs, int k, const TvConfDev &conf, const double *p0, const double *p1, double2 *x0,
+                        double2 *x1, unsigned char *mask_out, FmResDev *res);
+
 // ------------------------------------------------------------------------------------------------ 2D-3D assembly (assemble_kernels.hip)
 #define SFD2_ASM_WG 256               // key points of one (job, image, chunk) block
 #define SFD2_ASM_ST_MATCH_RANGE 1     // status bits of AsmResDev: a match index >= the image's table length

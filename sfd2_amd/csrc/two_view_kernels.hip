@@ -21,6 +21,7 @@
 #include "sfd2_internal.h"
 #include "pose_camera.h"
 #include "five_point.h"
+#include "ransac_common.h"
 
 namespace {
 
@@ -42,94 +43,6 @@ SFD2_PD void cross3(const double a[3], const double b[3], double o[3])
     o[2] = a[0] * b[1] - a[1] * b[0];
 }
 SFD2_PD double dot3(const double a[3], const double b[3]) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
-
-// ---------------------------------------------------------------------------------------------------------------- reductions
-template <int N>
-__device__ __forceinline__ void wg_sum(double (&v)[N], double *red)
-{
-#pragma unroll
-    for (int i = 0; i < N; ++i)
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) v[i] += __shfl_xor(v[i], m, 64);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0)
-#pragma unroll
-        for (int i = 0; i < N; ++i) red[w * N + i] = v[i];
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        double s = red[i];
-#pragma unroll
-        for (int q = 1; q < kWaves; ++q) s += red[q * N + i];
-        v[i] = s;
-    }
-}
-
-struct Support {
-    int cnt;          // -1: no hypothesis
-    double sum;
-    long long trial;
-};
-__device__ __forceinline__ bool better(const Support &a, const Support &b)
-{
-    if (a.cnt != b.cnt) return a.cnt > b.cnt;
-    if (a.sum != b.sum) return a.sum < b.sum;
-    return a.trial < b.trial;
-}
-__device__ __forceinline__ Support wg_best(Support s, Support *red)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        Support o;
-        o.cnt = __shfl_xor(s.cnt, m, 64);
-        o.sum = __shfl_xor(s.sum, m, 64);
-        o.trial = __shfl_xor(s.trial, m, 64);
-        if (better(o, s)) s = o;
-    }
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) red[w] = s;
-    __syncthreads();
-    Support b = red[0];
-#pragma unroll
-    for (int q = 1; q < kWaves; ++q)
-        if (better(red[q], b)) b = red[q];
-    return b;
-}
-
-// ---------------------------------------------------------------------------------------------------------------- sampling
-SFD2_PD uint64_t mix64(uint64_t z)
-{
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-// five distinct indices in [0, n), n >= 5, from (seed, trial) only: draw k is h_k mod (n - k) from the chain h_0 = mix64(seed ^
-// mix64(trial)), h_k = mix64(h_k-1), then stepped over the earlier indices in ascending order (sample3's scheme, pose_kernels.hip)
-SFD2_PD void sample5(uint64_t seed, int64_t trial, int n, int (&id)[5])
-{
-    uint64_t h = mix64(seed ^ mix64((uint64_t)trial));
-    int srt[5];                                         // the earlier indices, ascending
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-        if (k) h = mix64(h);
-        int v = (int)(h % (uint64_t)(n - k));
-#pragma unroll
-        for (int p = 0; p < k; ++p)
-            if (v >= srt[p]) ++v;
-        id[k] = v;
-        int ins = v;                                    // insert v into srt[0 .. k]
-#pragma unroll
-        for (int p = 0; p < k; ++p) {
-            const int lo = min(srt[p], ins), hi = max(srt[p], ins);
-            srt[p] = lo;
-            ins = hi;
-        }
-        srt[k] = ins;
-    }
-}
 
 // ---------------------------------------------------------------------------------------------------------------- geometry
 // squared Sampson error of x1^T E x0 (COLMAP's ComputeSquaredSampsonError)

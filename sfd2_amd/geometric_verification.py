@@ -6,11 +6,17 @@ input's groups and datasets with the rejected entries of matches0 set to -1, so 
 
   python -m sfd2_amd.geometric_verification --pairs P --features F --matches M --output V
          (--reference_sfm_model R | --intrinsics LIST...) [--max_error 4 --min_num_inliers 15 --relative_poses T]
+  python -m sfd2_amd.geometric_verification --model fundamental --pairs P --features F --matches M --output V
+         [--max_error 4 --min_num_inliers 15 --fundamental_matrices T]
 
 Intrinsics come from a COLMAP binary model (its poses go unused) or from lists `name model width height params...`
 (parsers.parse_image_lists_with_intrinsics).  A pair with an image without intrinsics is skipped, as triangulation.read_inputs skips
 it; a pair the match store lacks is an error.  --relative_poses writes one line per verified pair:
-name0 name1 success num_inliers qw qx qy qz tx ty tz tri_angle_deg."""
+name0 name1 success num_inliers qw qx qy qz tx ty tz tri_angle_deg.
+
+--model fundamental needs no intrinsics: every listed pair is verified by its fundamental matrix (seven-point LO-RANSAC),
+as COLMAP verifies a pair without a trusted focal length.  --fundamental_matrices writes one line per verified pair:
+name0 name1 success num_inliers and the nine entries of F (row-major, x1^T F x0 = 0 in pixels)."""
 import argparse
 import logging
 from pathlib import Path
@@ -46,9 +52,17 @@ def _write_group(store, name, arrays):
 
 
 def main(pairs, features, matches, output, reference_sfm_model=None, intrinsics=(), max_error=4.0,
-         min_num_inliers=two_view.DEFAULTS["min_num_inliers"], relative_poses=None, device=0, **ransac):
-    """Returns the per-pair result dicts of two_view.verify_pairs_two_view, keyed by (name0, name1)."""
-    name_cam = read_cameras(reference_sfm_model, intrinsics)
+         min_num_inliers=two_view.DEFAULTS["min_num_inliers"], relative_poses=None, device=0, model="essential", fundamental_matrices=None,
+         **ransac):
+    """Returns the per-pair result dicts of two_view.verify_pairs_two_view (model "essential") or two_view.verify_pairs_fundamental
+    (model "fundamental", no intrinsics), keyed by (name0, name1)."""
+    if model not in ("essential", "fundamental"):
+        raise ValueError(f"unknown model {model!r}")
+    if model == "fundamental" and relative_poses is not None:
+        raise ValueError("--relative_poses needs --model essential: a fundamental matrix has no pose")
+    if model == "essential" and fundamental_matrices is not None:
+        raise ValueError("--fundamental_matrices needs --model fundamental")
+    name_cam = read_cameras(reference_sfm_model, intrinsics) if model == "essential" else None
     with open(str(pairs), "r") as f:
         listed = [p.split() for p in f.readlines() if p.strip()]
     ids = {}
@@ -57,7 +71,7 @@ def main(pairs, features, matches, output, reference_sfm_model=None, intrinsics=
     src = feature_io.open_store(matches, "r")
     try:
         for name0, name1 in listed:
-            if name0 not in name_cam or name1 not in name_cam or (name0, name1) in seen:
+            if (name_cam is not None and (name0 not in name_cam or name1 not in name_cam)) or (name0, name1) in seen:
                 continue
             pair = names_to_pair(name0, name1)
             if pair not in src:
@@ -71,14 +85,17 @@ def main(pairs, features, matches, output, reference_sfm_model=None, intrinsics=
     finally:
         feats.close()
         src.close()
-    images = {i: SimpleNamespace(camera_id=i, name=n) for n, i in ids.items()}
-    cameras = {i: name_cam[n] for n, i in ids.items()}
     pair_matches = []
     for name0, name1, pair in todo:
         m0 = groups[pair]["matches0"].reshape(-1).astype(np.int64)
         pair_matches.append((ids[name0], ids[name1], np.stack([np.arange(len(m0)), m0], 1)))
     logging.info("Verifying %d pairs over %d images...", len(todo), len(ids))
-    m, off, _, results = two_view.verify_pairs_two_view(cameras, images, keypoints, pair_matches, max_error, min_num_inliers, device, **ransac)
+    if model == "fundamental":
+        m, off, _, results = two_view.verify_pairs_fundamental(keypoints, pair_matches, max_error, min_num_inliers, device, **ransac)
+    else:
+        images = {i: SimpleNamespace(camera_id=i, name=n) for n, i in ids.items()}
+        cameras = {i: name_cam[n] for n, i in ids.items()}
+        m, off, _, results = two_view.verify_pairs_two_view(cameras, images, keypoints, pair_matches, max_error, min_num_inliers, device, **ransac)
     dst = feature_io.open_store(output, "w")
     try:
         for p, (_, _, pair) in enumerate(todo):
@@ -93,6 +110,10 @@ def main(pairs, features, matches, output, reference_sfm_model=None, intrinsics=
             for (name0, name1, _), r in zip(todo, results):
                 vals = [*r["qvec"], *r["tvec"], r["tri_angle_deg"]]
                 f.write(f"{name0} {name1} {int(r['success'])} {r['num_inliers']} " + " ".join(f"{v:.17g}" for v in vals) + "\n")
+    if fundamental_matrices is not None:
+        with open(str(fundamental_matrices), "w") as f:
+            for (name0, name1, _), r in zip(todo, results):
+                f.write(f"{name0} {name1} {int(r['success'])} {r['num_inliers']} " + " ".join(f"{v:.17g}" for v in r["F"].reshape(-1)) + "\n")
     return {(n0, n1): r for (n0, n1, _), r in zip(todo, results)}
 
 
@@ -107,12 +128,18 @@ def parser():
     p.add_argument("--max_error", type=float, default=4.0)
     p.add_argument("--min_num_inliers", type=int, default=two_view.DEFAULTS["min_num_inliers"])
     p.add_argument("--relative_poses", type=Path)
+    p.add_argument("--model", choices=("essential", "fundamental"), default="essential")
+    p.add_argument("--fundamental_matrices", type=Path)
     return p
 
 
 if __name__ == "__main__":
     args = parser().parse_args()
-    if args.reference_sfm_model is None and not args.intrinsics:
+    if args.model == "essential" and args.reference_sfm_model is None and not args.intrinsics:
         parser().error("one of --reference_sfm_model and --intrinsics is required")
+    if args.model == "fundamental" and args.relative_poses is not None:
+        parser().error("--relative_poses needs --model essential")
+    if args.model == "essential" and args.fundamental_matrices is not None:
+        parser().error("--fundamental_matrices needs --model fundamental")
     logging.basicConfig(level=logging.INFO)
     main(**args.__dict__)

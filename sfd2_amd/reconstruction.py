@@ -15,7 +15,11 @@ verified matches; the points are a function of the registered views and their po
 
   python -m sfd2_amd.reconstruction --sfm_dir S --image_dir D --pairs P --features F --matches M
          [--reference_sfm_model R | --intrinsics LIST...] [--single_camera] [--skip_geometric_verification]
-         [--min_match_score X] [--min_num_matches N]
+         [--min_match_score X] [--min_num_matches N] [--verification essential|fundamental]
+
+--verification fundamental (reconstruct(..., verification="fundamental")): for cameras nobody trusts, i.e. the focal-length prior.  Step 1
+verifies every pair by its fundamental matrix (two_view.verify_pairs_fundamental) and continues as
+--skip_geometric_verification does on the verified matches; the init_max_pairs pairs with the most survivors get a relative pose.
 
 Deviations from COLMAP: one model; intrinsics are not refined (a map built from the focal-length prior is only as good as that
 prior); the gauge is held by whole views: the first image of the initial pair is constant in every
@@ -143,6 +147,9 @@ class DeviceStages:
     def two_view(self, cameras, images, keypoints, pair_matches, max_error, min_num_inliers, seed):
         return two_view.verify_pairs_two_view(cameras, images, keypoints, pair_matches, max_error, min_num_inliers, self.device, seed=seed)
 
+    def fundamental(self, keypoints, pair_matches, max_error, min_num_inliers, seed):
+        return two_view.verify_pairs_fundamental(keypoints, pair_matches, max_error, min_num_inliers, self.device, seed=seed)
+
     def build_tracks(self, n_nodes, edges, max_rounds):
         return triangulation.build_tracks(n_nodes, edges, max_rounds, self.device)
 
@@ -213,12 +220,17 @@ def select_candidates(counts, registered, tries, max_reg_trials, min_count, roun
     return [v for v in idx if counts[v] >= round_ratio * best][:max_images]
 
 
-def reconstruct(cameras, images, keypoints, pair_matches, skip_geometric_verification=False, device=0, stages=None, report=None, **options):
+def reconstruct(cameras, images, keypoints, pair_matches, skip_geometric_verification=False, device=0, stages=None, report=None,
+                verification="essential", **options):
     """cameras: id -> camera dict; images: id -> record with .name and .camera_id; keypoints: image id -> [n, 2] as the feature store holds
     them; pair_matches: [(image id 0, image id 1, matches [m, 2])].  options: DEFAULTS.  stages: the stage calls (DeviceStages).  report:
     a dict that receives 'initial_pair', 'rounds' (per round: candidates, registered, points, observations, the adjustment's report, seconds
     per stage) and 'final'.  Returns (images, points3D) as colmap_io writes them: image ids 1..n in sorted-name order, registered images
-    only; point ids 1-based in (track, slot) order."""
+    only; point ids 1-based in (track, slot) order.  verification "fundamental": for cameras nobody trusts (the prior focal length), the
+    matches are verified by every pair's fundamental matrix instead of an essential matrix at those cameras; the map then
+    starts as with skip_geometric_verification on the verified matches."""
+    if verification not in ("essential", "fundamental"):
+        raise ValueError(f"unknown verification {verification!r}")
     unknown = set(options) - set(DEFAULTS)
     if unknown:
         raise TypeError(f"unknown options {sorted(unknown)}")
@@ -237,7 +249,10 @@ def reconstruct(cameras, images, keypoints, pair_matches, skip_geometric_verific
     # 1. verification and the pairs' relative poses
     t0 = clock()
     n_pairs = len(pair_matches)
-    if skip_geometric_verification:
+    if verification == "fundamental" and not skip_geometric_verification:
+        m_all, off, _, _ = S.fundamental(keypoints, pair_matches, o["max_error"], o["min_num_matches"], o["seed"])
+        pair_matches = [(a, b, m_all[off[p]:off[p + 1]]) for p, (a, b, _) in enumerate(pair_matches)]
+    if skip_geometric_verification or verification == "fundamental":
         sizes = [int(((m[:, 0] >= 0) & (m[:, 1] >= 0)).sum()) for _, _, m in pair_matches]
         for p, (a, b, m) in enumerate(pair_matches):
             if len(m) and (m[:, 0].max() >= kp_off[index[a] + 1] - kp_off[index[a]] or m[:, 1].max() >= kp_off[index[b] + 1] - kp_off[index[b]]):
@@ -428,7 +443,7 @@ def read_images(pairs_path, features_path, single_camera=False, reference_sfm_mo
 
 
 def main(sfm_dir, image_dir, pairs, features, matches, colmap_path=None, single_camera=False, skip_geometric_verification=False,
-         min_match_score=None, min_num_matches=None, reference_sfm_model=None, intrinsics=(), device=0, **options):
+         min_match_score=None, min_num_matches=None, reference_sfm_model=None, intrinsics=(), device=0, verification="essential", **options):
     """hloc/reconstruction.py main(): image_dir and colmap_path are accepted and unused.  Writes sfm_dir/models/0/{cameras,images,
     points3D}.bin and sfm_dir/stats.txt (one `key: value` per line; the reference writes the same keys without the newline); returns
     the statistics."""
@@ -442,7 +457,8 @@ def main(sfm_dir, image_dir, pairs, features, matches, colmap_path=None, single_
     keypoints, pair_matches = triangulation.read_inputs(images, pairs, features, matches, min_match_score)
     logging.info("Reconstructing from %d pairs over %d images...", len(pair_matches), len(images))
     report = {}
-    out_images, points3D = reconstruct(cameras, images, keypoints, pair_matches, skip_geometric_verification, device=device, report=report, **options)
+    out_images, points3D = reconstruct(cameras, images, keypoints, pair_matches, skip_geometric_verification, device=device, report=report,
+                                       verification=verification, **options)
     model = sfm_dir / "models" / "0"
     model.mkdir(parents=True, exist_ok=True)
     used = {im.camera_id for im in out_images.values()}
@@ -471,6 +487,7 @@ def parser():
     ap.add_argument("--reference_sfm_model", type=Path)
     ap.add_argument("--intrinsics", type=Path, nargs="+", default=[])
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--verification", choices=("essential", "fundamental"), default="essential")
     return ap
 
 

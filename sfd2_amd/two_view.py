@@ -8,7 +8,11 @@ correspondences that are a rotation exactly have no isolated solution and give n
 Conventions: qvec = (w, x, y, z), camera 0 to camera 1, x1 = R(qvec) x0 + tvec with |tvec| = 1; E = [tvec]x R.  points2D are pixel
 coordinates taken as given; a camera is the dict of sfd2_amd.pose (model, params in COLMAP's order).  RANSAC defaults are COLMAP's
 two-view ones: max_error 4 px, confidence 0.999, max_num_trials 10000, min_num_trials 0, min_inlier_ratio 0.25, min_num_inliers 15.
-The result depends on the pair and the seed only.  Nothing here computes on the CPU: without a GPU the calls raise."""
+The result depends on the pair and the seed only.  Nothing here computes on the CPU: without a GPU the calls raise.
+
+Without cameras: fundamental_matrix(_batch) and verify_pairs_fundamental at the end of this file
+estimate the fundamental matrix instead -- seven-point LO-RANSAC on the squared Sampson error in pixels, x1^T F x0 = 0, what COLMAP
+runs for a pair without a trusted focal length.  Same RANSAC keywords and defaults; no pose, no angles."""
 import ctypes
 
 import numpy as np
@@ -113,6 +117,92 @@ def verify_pairs_two_view(cameras, images, keypoints, pair_matches, max_error=4.
         rows_of.append(live)
         problems.append((kps[i0][m[live, 0]], kps[i1][m[live, 1]], cameras[images[i0].camera_id], cameras[images[i1].camera_id]))
     results = relative_pose_batch(problems, max_error, min_num_inliers=min_num_inliers, device=device, **ransac)
+    out = np.full((int(off[-1]), 2), -1, dtype=np.int32)
+    counts = np.zeros(len(pair_matches), dtype=np.int32)
+    for p, (live, r) in enumerate(zip(rows_of, results)):
+        counts[p] = r["num_inliers"]
+        if r["success"] and r["num_inliers"] >= min_num_inliers:
+            keep = live[r["inliers"]]
+            out[off[p] + keep] = ms[p][keep]
+    return out, off, counts, results
+
+
+# ------------------------------------------------------------------------------------------------ without cameras
+def _fundamental_problem(points2D0, points2D1, max_error_px, keep):
+    p0 = np.ascontiguousarray(points2D0, dtype=np.float64).reshape(-1, 2)
+    p1 = np.ascontiguousarray(points2D1, dtype=np.float64).reshape(-1, 2)
+    if p0.shape[0] != p1.shape[0]:
+        raise ValueError(f"{p0.shape[0]} points in image 0 for {p1.shape[0]} in image 1")
+    if not (np.isfinite(p0).all() and np.isfinite(p1).all()):
+        raise ValueError("non-finite correspondences")
+    keep += [p0, p1]
+    pr = _lib.FundamentalProblem()
+    pr.n = p0.shape[0]
+    pr.points2D_0 = p0.ctypes.data if p0.size else None
+    pr.points2D_1 = p1.ctypes.data if p1.size else None
+    pr.max_error_px = float(max_error_px)
+    return pr
+
+
+def fundamental_matrix_batch(problems, max_error_px=4.0, min_inlier_ratio=DEFAULTS["min_inlier_ratio"], min_num_trials=DEFAULTS["min_num_trials"],
+                             max_num_trials=DEFAULTS["max_num_trials"], confidence=DEFAULTS["confidence"], seed=DEFAULTS["seed"],
+                             min_num_inliers=DEFAULTS["min_num_inliers"], device=0):
+    """problems: a list of (points2D0 [n,2], points2D1 [n,2]) or (..., max_error_px).  One device call (sfd2_fundamental_batch: seven-point
+    LO-RANSAC, no camera); returns one dict per pair, as fundamental_matrix does."""
+    keep, probs = [], []
+    for p in problems:
+        probs.append(_fundamental_problem(p[0], p[1], p[2] if len(p) > 2 else max_error_px, keep))
+    k = len(probs)
+    if k == 0:
+        return []
+    ctx = _lib.default_context(device)
+    arr = (_lib.FundamentalProblem * k)(*probs)
+    conf = _lib.TwoViewConf(float(min_inlier_ratio), int(min_num_trials), int(max_num_trials), float(confidence), int(seed) & (2 ** 64 - 1),
+                            int(min_num_inliers), 0)
+    res = (_lib.FundamentalResult * k)()
+    total = sum(pr.n for pr in probs)
+    mask = np.zeros(max(total, 1), dtype=np.uint8)
+    _lib.check(ctx.lib.sfd2_fundamental_batch(ctx.h, arr, k, ctypes.byref(conf), res, mask.ctypes.data, 0))
+    out, o = [], 0
+    for i, pr in enumerate(probs):
+        r, m = res[i], mask[o:o + pr.n].astype(bool)
+        o += pr.n
+        out.append({"success": bool(r.success), "F": np.array(r.F[:], dtype=np.float64).reshape(3, 3), "num_inliers": int(r.num_inliers),
+                    "inliers": m, "num_trials": int(r.num_trials)})
+    return out
+
+
+def fundamental_matrix(points2D0, points2D1, max_error_px=4.0, **ransac):
+    """The fundamental matrix of one matched pair, no camera needed.  Returns {'success', 'F' [3,3] (x1^T F x0 = 0 in pixels, rank 2,
+    unit Frobenius norm), 'num_inliers', 'inliers' (bool [n]), 'num_trials'}; **ransac: fundamental_matrix_batch's keywords.  Fewer
+    than 7 correspondences: success False, F = 0."""
+    return fundamental_matrix_batch([(points2D0, points2D1)], max_error_px, **ransac)[0]
+
+
+def verify_pairs_fundamental(keypoints, pair_matches, max_error=4.0, min_num_inliers=DEFAULTS["min_num_inliers"], device=0, **ransac):
+    """verify_pairs_two_view without cameras: every pair's fundamental matrix is estimated from its matches, the RANSAC inliers stay.
+    The return shape and the rules are verify_pairs_two_view's (the results are fundamental_matrix dicts): rows that come in negative
+    stay rejected, a pair of an image with itself and a pair below min_num_inliers lose all; an index beyond an image's key points
+    raises.  Key points are taken as float32 plus COLMAP's +0.5."""
+    kps = {}
+    problems, rows_of, ms = [], [], []
+    off = np.zeros(len(pair_matches) + 1, dtype=np.int64)
+    for p, (i0, i1, m) in enumerate(pair_matches):
+        m = np.asarray(m).reshape(-1, 2).astype(np.int32)
+        ms.append(m)
+        off[p + 1] = off[p] + len(m)
+        for i in (i0, i1):
+            if i not in kps:
+                kps[i] = np.asarray(keypoints[i], dtype=np.float32).reshape(-1, 2).astype(np.float64) + 0.5
+        live = np.flatnonzero((m[:, 0] >= 0) & (m[:, 1] >= 0))
+        for col, i in ((0, i0), (1, i1)):
+            if live.size and m[live, col].max() >= len(kps[i]):
+                raise ValueError(f"pair {p}: match index {int(m[live, col].max())} beyond the {len(kps[i])} key points of image {i}")
+        if i0 == i1:
+            live = live[:0]
+        rows_of.append(live)
+        problems.append((kps[i0][m[live, 0]], kps[i1][m[live, 1]]))
+    results = fundamental_matrix_batch(problems, max_error, min_num_inliers=min_num_inliers, device=device, **ransac)
     out = np.full((int(off[-1]), 2), -1, dtype=np.int32)
     counts = np.zeros(len(pair_matches), dtype=np.int32)
     for p, (live, r) in enumerate(zip(rows_of, results)):
