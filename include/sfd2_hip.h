@@ -85,7 +85,7 @@ typedef struct {
     int64_t n_candidates; /* N0 after NMS + threshold + border of the last extract          */
 } sfd2_timings;
 
-int sfd2_version(void);   /* 100 = rounds 1-4; 105 adds sfd2_extract_record_async, sfd2_desc_pack and host outputs with SFD2_FLAG_ASYNC; 106 adds sfd2_get_margin_status; 107 adds sfd2_get_relax_status (option "c3b_plain"); 108 adds sfd2_get_option, sfd2_device_pci_bus_id, SFD2_FLAG_DESC_STORE64; 109 adds the baseline JPEG decoder (sfd2_jpeg_*); 112 adds the SfM map (sfd2_verify_matches_batch, sfd2_build_tracks, sfd2_triangulate_tracks); 113 adds the pair selection (sfd2_pairs_retrieval, sfd2_pairs_covisibility, sfd2_pairs_poses); 114 adds sfd2_covis_clusters; 115 adds sfd2_covis_frames; 116 adds the VLAD global descriptors (sfd2_vlad_assign, sfd2_vlad_aggregate, sfd2_vlad_kmeans); 117 adds sfd2_relative_pose_batch; 118 adds sfd2_bundle_adjust; 119 adds the mapper's bookkeeping (sfd2_mapper_restrict, sfd2_mapper_filter, sfd2_mapper_visible, sfd2_mapper_assemble); 120 adds sfd2_fundamental_batch */
+int sfd2_version(void);   /* 100 = rounds 1-4; 105 adds sfd2_extract_record_async, sfd2_desc_pack and host outputs with SFD2_FLAG_ASYNC; 106 adds sfd2_get_margin_status; 107 adds sfd2_get_relax_status (option "c3b_plain"); 108 adds sfd2_get_option, sfd2_device_pci_bus_id, SFD2_FLAG_DESC_STORE64; 109 adds the baseline JPEG decoder (sfd2_jpeg_*); 112 adds the SfM map (sfd2_verify_matches_batch, sfd2_build_tracks, sfd2_triangulate_tracks); 113 adds the pair selection (sfd2_pairs_retrieval, sfd2_pairs_covisibility, sfd2_pairs_poses); 114 adds sfd2_covis_clusters; 115 adds sfd2_covis_frames; 116 adds the VLAD global descriptors (sfd2_vlad_assign, sfd2_vlad_aggregate, sfd2_vlad_kmeans); 117 adds sfd2_relative_pose_batch; 118 adds sfd2_bundle_adjust; 119 adds the mapper's bookkeeping (sfd2_mapper_restrict, sfd2_mapper_filter, sfd2_mapper_visible, sfd2_mapper_assemble); 120 adds sfd2_fundamental_batch; 121 adds sfd2_homography_batch */
 const char *sfd2_last_error(void);
 
 int sfd2_ctx_create(int device, sfd2_ctx **out);
@@ -625,7 +625,8 @@ int sfd2_relative_pose_batch(sfd2_ctx *ctx, const sfd2_two_view_problem *problem
  * The uncalibrated two-view geometry of a matched pair, which COLMAP estimates for a pair without a trusted focal length
  * (EstimateUncalibrated), for many pairs of any sizes in one launch: LO-RANSAC over the seven-point solver with fp64 scoring on the
  * squared Sampson error in pixels, then a refinement of 7 parameters of a rank-2 chart on the same error over the RANSAC inliers
- * (DESIGN.md 16).  No camera, no pose, no cheirality test, no decision between F and H.  Results depend on the pair and the seed
+ * (DESIGN.md 16).  No camera, no pose, no cheirality test; H is sfd2_homography_batch below, and the decision between E, F and H
+ * is the caller's (sfd2_amd.two_view.decide_two_view_geometry).  Results depend on the pair and the seed
  * only and are bit-reproducible.  sfd2_two_view_conf is taken as sfd2_relative_pose_batch takes it (sample size 7). */
 typedef struct {
     int32_t n;                      /* correspondences                                                                     */
@@ -648,6 +649,35 @@ typedef struct {
  * is an error (-1).  flags: 0. */
 int sfd2_fundamental_batch(sfd2_ctx *ctx, const sfd2_fundamental_problem *problems, int k, const sfd2_two_view_conf *conf,
                            sfd2_fundamental_result *results, uint8_t *inlier_mask_u8, int flags);
+
+/* ------------------------------------------------------------------------------------------------ homography (version 121)
+ * The homography of a matched pair, which COLMAP estimates next to E and F for every pair to tell a plane or a panorama from a
+ * general scene, for many pairs of any sizes in one launch: LO-RANSAC over the closed-form four-point solver with fp64 scoring on the
+ * squared one-sided transfer error |x1 - pi(H x0)|^2 in image 1, then a refinement of 8 parameters (the entry of largest magnitude
+ * held constant) on the same error over the RANSAC inliers.  No camera, no decomposition, no pose.  Results depend
+ * on the pair and the seed only and are bit-reproducible.  sfd2_two_view_conf is taken as sfd2_relative_pose_batch takes it
+ * (sample size 4). */
+typedef struct {
+    int32_t n;                      /* correspondences                                                                     */
+    int32_t reserved;
+    const double *points2D_0;       /* host [n][2] pixels in image 0                                                       */
+    const double *points2D_1;       /* host [n][2] pixels in image 1                                                       */
+    double max_error_px;            /* inlier threshold in pixels: max_error_px^2 bounds the squared transfer error        */
+} sfd2_homography_problem;
+typedef struct {
+    int32_t success;                /* 1: num_inliers >= min_num_inliers; 0 otherwise, also with fewer than 4 correspondences
+                                       or point sets without extent (H = 0, mask 0, num_trials 0)                          */
+    int32_t num_inliers;            /* RANSAC inliers                                                                      */
+    int32_t num_trials;             /* RANSAC trials run                                                                   */
+    int32_t reserved;
+    double H[9];                    /* row-major, x1 ~ H x0 in pixels; unit Frobenius norm, the first entry of largest
+                                       magnitude positive; all 0 without a result                                          */
+} sfd2_homography_result;
+
+/* k pairs; results[k]; inlier_mask_u8: host, sum(n) bytes, the pairs' RANSAC inlier masks concatenated in order.  Non-finite input
+ * is an error (-1).  flags: 0. */
+int sfd2_homography_batch(sfd2_ctx *ctx, const sfd2_homography_problem *problems, int k, const sfd2_two_view_conf *conf,
+                          sfd2_homography_result *results, uint8_t *inlier_mask_u8, int flags);
 
 /* ------------------------------------------------------------------------------------------------ 2D-3D assembly
  * Matches -> 2D-3D correspondences for a batch of jobs in one call: the per-key-point loops of it_loc/localize_cv2.py:571-632

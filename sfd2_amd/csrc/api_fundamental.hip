@@ -1,15 +1,16 @@
-// libsfd2hip: sfd2_fundamental_batch -- checks and packs the pairs, one launch of fundamental_kernels.hip.
+// libsfd2hip: sfd2_fundamental_batch -- checks and packs the pairs, one launch of fundamental_kernels.hip.  The checking, packing and
+// scratch layer is pairs_batch below; sfd2_homography_batch (api_homography.hip) goes through it too with its own kernel and sample size.
 #include "sfd2_ctx.h"
 #include "api_scratch.h"
 
 namespace {
 
-// COLMAP ComputeNumTrials (sample size 7, dyn_num_trials_multiplier 3)
-double num_trials(double inlier_ratio, double confidence)
+// COLMAP ComputeNumTrials (dyn_num_trials_multiplier 3)
+double num_trials(double inlier_ratio, double confidence, int sample_size)
 {
     const double nom = 1.0 - confidence;
     if (nom <= 0) return 1e300;
-    const double den = 1.0 - std::pow(inlier_ratio, 7);
+    const double den = 1.0 - std::pow(inlier_ratio, sample_size);
     if (den <= 0) return 1.0;
     if (den == 1.0 || std::fabs(std::log(den)) < 1e-16) return 1e300;
     return std::ceil(std::log(nom) / std::log(den) * 3.0);
@@ -17,10 +18,12 @@ double num_trials(double inlier_ratio, double confidence)
 
 }  // namespace
 
-extern "C" int sfd2_fundamental_batch(sfd2_ctx *c, const sfd2_fundamental_problem *problems, int k, const sfd2_two_view_conf *conf,
-                                      sfd2_fundamental_result *results, uint8_t *inlier_mask_u8, int flags)
+// k pairs of pixel correspondences without cameras through one launch of `launch`: the checks, the concatenation with one offset per
+// pair, the context's fm_* scratch blocks, the copies.  name: the entry point in the error texts; sample_size: of the trial count.
+int pairs_batch(const char *name, int sample_size, PairsLaunch launch, sfd2_ctx *c, const sfd2_fundamental_problem *problems, int k,
+                const sfd2_two_view_conf *conf, sfd2_fundamental_result *results, uint8_t *inlier_mask_u8, int flags)
 {
-    const std::string F("sfd2_fundamental_batch");
+    const std::string F(name);
     if (!c || !conf || (k > 0 && (!problems || !results))) return fail(F + ": null argument");
     if (k < 0) return fail(F + ": negative k");
     if (flags != 0) return fail(F + ": unknown flags");
@@ -32,7 +35,7 @@ extern "C" int sfd2_fundamental_batch(sfd2_ctx *c, const sfd2_fundamental_proble
     TvConfDev d;
     memset(&d, 0, sizeof(d));
     // COLMAP's RANSAC: max_num_trials limited by the trial count of an assumed min_inlier_ratio (kNumSamples = 100000)
-    const double dyn = num_trials(std::floor(conf->min_inlier_ratio * 100000) / 100000.0, conf->confidence);
+    const double dyn = num_trials(std::floor(conf->min_inlier_ratio * 100000) / 100000.0, conf->confidence, sample_size);
     d.max_trials = std::max<int64_t>(1, std::min<double>((double)conf->max_num_trials, dyn));
     d.min_trials = std::min(conf->min_num_trials, d.max_trials);
     d.confidence = conf->confidence;
@@ -79,8 +82,8 @@ extern "C" int sfd2_fundamental_batch(sfd2_ctx *c, const sfd2_fundamental_proble
     HIPCHECK(hipMemcpyAsync(in + o_pd, pd.data(), sizeof(FmProbDev) * k, hipMemcpyHostToDevice, c->stream));
     HIPCHECK(hipMemcpyAsync(in + o_p0, p0.data(), 16 * total, hipMemcpyHostToDevice, c->stream));
     HIPCHECK(hipMemcpyAsync(in + o_p1, p1.data(), 16 * total, hipMemcpyHostToDevice, c->stream));
-    launch_fundamental(c->stream, at<const FmProbDev>(in, o_pd), k, d, at<const double>(in, o_p0), at<const double>(in, o_p1), at<double2>(ws, o_x0),
-                       at<double2>(ws, o_x1), at<unsigned char>(out, o_m), at<FmResDev>(out, o_res));
+    launch(c->stream, at<const FmProbDev>(in, o_pd), k, d, at<const double>(in, o_p0), at<const double>(in, o_p1), at<double2>(ws, o_x0),
+           at<double2>(ws, o_x1), at<unsigned char>(out, o_m), at<FmResDev>(out, o_res));
     HIPCHECK(hipGetLastError());
     std::vector<FmResDev> r(k);
     HIPCHECK(hipMemcpyAsync(r.data(), out + o_res, sizeof(FmResDev) * k, hipMemcpyDeviceToHost, c->stream));
@@ -95,4 +98,10 @@ extern "C" int sfd2_fundamental_batch(sfd2_ctx *c, const sfd2_fundamental_proble
         for (int j = 0; j < 9; ++j) o.F[j] = r[i].F[j];
     }
     return 0;
+}
+
+extern "C" int sfd2_fundamental_batch(sfd2_ctx *c, const sfd2_fundamental_problem *problems, int k, const sfd2_two_view_conf *conf,
+                                      sfd2_fundamental_result *results, uint8_t *inlier_mask_u8, int flags)
+{
+    return pairs_batch("sfd2_fundamental_batch", 7, launch_fundamental, c, problems, k, conf, results, inlier_mask_u8, flags);
 }

@@ -1,4 +1,4 @@
-// libsfd2hip: what the two-view RANSAC kernels (two_view_kernels.hip, fundamental_kernels.hip) share -- the workgroup reductions in a
+// libsfd2hip: what the two-view RANSAC kernels (two_view_kernels.hip, fundamental_kernels.hip, homography_kernels.hip) share -- the workgroup reductions in a
 // fixed order (wave butterflies, then the waves in index order), the support order and the sampler.  A workgroup is SFD2_TV_WG threads.
 #pragma once
 #include "sfd2_internal.h"

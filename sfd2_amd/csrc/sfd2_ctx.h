@@ -299,7 +299,7 @@ struct sfd2_ctx {
     ScratchBuf asm_in, asm_ws, asm_out;     // sfd2_assemble_2d3d (api_assemble.hip): descriptors and host inputs, per-(image, key point) work, host-bound outputs
     ScratchBuf pose_in, pose_ws, pose_out;  // sfd2_absolute_pose_batch / sfd2_pose_refine_batch (api_pose.hip): inputs, per-point work, results
     ScratchBuf tv_in, tv_ws, tv_out;        // sfd2_relative_pose_batch (api_two_view.hip): inputs, normalised points and the trials' matrices, results
-    ScratchBuf fm_in, fm_ws, fm_out;        // sfd2_fundamental_batch (api_fundamental.hip): inputs, normalised points, results
+    ScratchBuf fm_in, fm_ws, fm_out;        // sfd2_fundamental_batch / sfd2_homography_batch (api_fundamental.hip pairs_batch): inputs, normalised points, results
     ScratchBuf tri_in, tri_ws;             // sfd2_verify_matches_batch / sfd2_build_tracks / sfd2_triangulate_tracks (api_triangulate.hip): inputs, work and results
     ScratchBuf pairs_in, pairs_ws;          // sfd2_pairs_retrieval / _covisibility / _poses (api_pairs.hip), sfd2_covis_clusters (api_cluster.hip) and sfd2_covis_frames (api_frames.hip): uploaded inputs, partial lists / counters / slot rows and results
     ScratchBuf vlad_in, vlad_ws;            // sfd2_vlad_assign / _aggregate / _kmeans (api_vlad.hip): uploaded rows, centroids and offsets; assignments, sums, partials and results
@@ -322,6 +322,11 @@ struct sfd2_ctx {
 };
 
 void graphs_release(sfd2_ctx *c);
+// api_fundamental.hip: the checking, packing and scratch layer of the camera-less pair estimators, one launch of `launch`
+typedef void (*PairsLaunch)(hipStream_t, const FmProbDev *, int, const TvConfDev &, const double *, const double *, double2 *, double2 *,
+                            unsigned char *, FmResDev *);
+int pairs_batch(const char *name, int sample_size, PairsLaunch launch, sfd2_ctx *c, const sfd2_fundamental_problem *problems, int k,
+                const sfd2_two_view_conf *conf, sfd2_fundamental_result *results, uint8_t *inlier_mask_u8, int flags);
 #define PROF_SLOTS 48
 struct ProfScope {   // records an event pair around one launch when profiling is on
     sfd2_ctx *c; int slot;

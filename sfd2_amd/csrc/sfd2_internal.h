@@ -783,6 +783,9 @@ struct FmResDev {
 // p0 / p1: pixels [N][2]; x0 / x1: work, normalised points [N]; conf: TvConfDev as for launch_two_view (sample size 7 in the kernel)
 void launch_fundamental(hipStream_t st, const FmProbDev *probs, int k, const TvConfDev &conf, const double *p0, const double *p1, double2 *x0,
                         double2 *x1, unsigned char *mask_out, FmResDev *res);
+// homography_kernels.hip: the same arguments (sample size 4 in the kernel); FmResDev::F holds H
+void launch_homography(hipStream_t st, const FmProbDev *probs, int k, const TvConfDev &conf, const double *p0, const double *p1, double2 *x0,
+                       double2 *x1, unsigned char *mask_out, FmResDev *res);
 
 // ------------------------------------------------------------------------------------------------ 2D-3D assembly (assemble_kernels.hip)
 #define SFD2_ASM_WG 256               // key points of one (job, image, chunk) block

@@ -8,6 +8,8 @@ input's groups and datasets with the rejected entries of matches0 set to -1, so 
          (--reference_sfm_model R | --intrinsics LIST...) [--max_error 4 --min_num_inliers 15 --relative_poses T]
   python -m sfd2_amd.geometric_verification --model fundamental --pairs P --features F --matches M --output V
          [--max_error 4 --min_num_inliers 15 --fundamental_matrices T]
+  python -m sfd2_amd.geometric_verification --model geometry --pairs P --features F --matches M --output V
+         [--reference_sfm_model R | --intrinsics LIST...] [--max_error 4 --min_num_inliers 15 --two_view_geometries T]
 
 Intrinsics come from a COLMAP binary model (its poses go unused) or from lists `name model width height params...`
 (parsers.parse_image_lists_with_intrinsics).  A pair with an image without intrinsics is skipped, as triangulation.read_inputs skips
@@ -16,7 +18,12 @@ name0 name1 success num_inliers qw qx qy qz tx ty tz tri_angle_deg.
 
 --model fundamental needs no intrinsics: every listed pair is verified by its fundamental matrix (seven-point LO-RANSAC),
 as COLMAP verifies a pair without a trusted focal length.  --fundamental_matrices writes one line per verified pair:
-name0 name1 success num_inliers and the nine entries of F (row-major, x1^T F x0 = 0 in pixels)."""
+name0 name1 success num_inliers and the nine entries of F (row-major, x1^T F x0 = 0 in pixels).
+
+--model geometry estimates F and H for every pair, and E too where intrinsics are given, and keeps the matches of
+two_view.decide_two_view_geometry's choice, as COLMAP labels a pair calibrated, uncalibrated, planar, panoramic or degenerate: a planar or
+rotation-only pair keeps its matches through H where a fundamental matrix alone loses or pollutes them.  --two_view_geometries writes one
+line per verified pair: name0 name1 config num_inliers_E num_inliers_F num_inliers_H num_kept (num_inliers_E is -1 without intrinsics)."""
 import argparse
 import logging
 from pathlib import Path
@@ -53,16 +60,21 @@ def _write_group(store, name, arrays):
 
 def main(pairs, features, matches, output, reference_sfm_model=None, intrinsics=(), max_error=4.0,
          min_num_inliers=two_view.DEFAULTS["min_num_inliers"], relative_poses=None, device=0, model="essential", fundamental_matrices=None,
-         **ransac):
-    """Returns the per-pair result dicts of two_view.verify_pairs_two_view (model "essential") or two_view.verify_pairs_fundamental
-    (model "fundamental", no intrinsics), keyed by (name0, name1)."""
-    if model not in ("essential", "fundamental"):
+         two_view_geometries=None, **ransac):
+    """Returns the per-pair result dicts of two_view.verify_pairs_two_view (model "essential"), two_view.verify_pairs_fundamental
+    (model "fundamental", no intrinsics) or two_view.verify_pairs_geometry (model "geometry", with or without intrinsics), keyed by
+    (name0, name1)."""
+    if model not in ("essential", "fundamental", "geometry"):
         raise ValueError(f"unknown model {model!r}")
-    if model == "fundamental" and relative_poses is not None:
+    if model != "essential" and relative_poses is not None:
         raise ValueError("--relative_poses needs --model essential: a fundamental matrix has no pose")
-    if model == "essential" and fundamental_matrices is not None:
+    if model != "fundamental" and fundamental_matrices is not None:
         raise ValueError("--fundamental_matrices needs --model fundamental")
-    name_cam = read_cameras(reference_sfm_model, intrinsics) if model == "essential" else None
+    if model != "geometry" and two_view_geometries is not None:
+        raise ValueError("--two_view_geometries needs --model geometry")
+    name_cam = None
+    if model == "essential" or (model == "geometry" and (reference_sfm_model is not None or intrinsics)):
+        name_cam = read_cameras(reference_sfm_model, intrinsics)
     with open(str(pairs), "r") as f:
         listed = [p.split() for p in f.readlines() if p.strip()]
     ids = {}
@@ -90,11 +102,16 @@ def main(pairs, features, matches, output, reference_sfm_model=None, intrinsics=
         m0 = groups[pair]["matches0"].reshape(-1).astype(np.int64)
         pair_matches.append((ids[name0], ids[name1], np.stack([np.arange(len(m0)), m0], 1)))
     logging.info("Verifying %d pairs over %d images...", len(todo), len(ids))
-    if model == "fundamental":
-        m, off, _, results = two_view.verify_pairs_fundamental(keypoints, pair_matches, max_error, min_num_inliers, device, **ransac)
-    else:
+    images = cameras = None
+    if name_cam is not None:
         images = {i: SimpleNamespace(camera_id=i, name=n) for n, i in ids.items()}
         cameras = {i: name_cam[n] for n, i in ids.items()}
+    if model == "fundamental":
+        m, off, _, results = two_view.verify_pairs_fundamental(keypoints, pair_matches, max_error, min_num_inliers, device, **ransac)
+    elif model == "geometry":
+        m, off, _, results = two_view.verify_pairs_geometry(keypoints, pair_matches, cameras, images, max_error, min_num_inliers, device=device,
+                                                            **ransac)
+    else:
         m, off, _, results = two_view.verify_pairs_two_view(cameras, images, keypoints, pair_matches, max_error, min_num_inliers, device, **ransac)
     dst = feature_io.open_store(output, "w")
     try:
@@ -114,6 +131,11 @@ def main(pairs, features, matches, output, reference_sfm_model=None, intrinsics=
         with open(str(fundamental_matrices), "w") as f:
             for (name0, name1, _), r in zip(todo, results):
                 f.write(f"{name0} {name1} {int(r['success'])} {r['num_inliers']} " + " ".join(f"{v:.17g}" for v in r["F"].reshape(-1)) + "\n")
+    if two_view_geometries is not None:
+        with open(str(two_view_geometries), "w") as f:
+            for (name0, name1, _), r in zip(todo, results):
+                nE = r["E"]["num_inliers"] if r["E"] is not None else -1
+                f.write(f"{name0} {name1} {r['config']} {nE} {r['F']['num_inliers']} {r['H']['num_inliers']} {r['num_inliers']}\n")
     return {(n0, n1): r for (n0, n1, _), r in zip(todo, results)}
 
 
@@ -128,8 +150,9 @@ def parser():
     p.add_argument("--max_error", type=float, default=4.0)
     p.add_argument("--min_num_inliers", type=int, default=two_view.DEFAULTS["min_num_inliers"])
     p.add_argument("--relative_poses", type=Path)
-    p.add_argument("--model", choices=("essential", "fundamental"), default="essential")
+    p.add_argument("--model", choices=("essential", "fundamental", "geometry"), default="essential")
     p.add_argument("--fundamental_matrices", type=Path)
+    p.add_argument("--two_view_geometries", type=Path)
     return p
 
 
@@ -137,9 +160,11 @@ if __name__ == "__main__":
     args = parser().parse_args()
     if args.model == "essential" and args.reference_sfm_model is None and not args.intrinsics:
         parser().error("one of --reference_sfm_model and --intrinsics is required")
-    if args.model == "fundamental" and args.relative_poses is not None:
+    if args.model != "essential" and args.relative_poses is not None:
         parser().error("--relative_poses needs --model essential")
-    if args.model == "essential" and args.fundamental_matrices is not None:
+    if args.model != "fundamental" and args.fundamental_matrices is not None:
         parser().error("--fundamental_matrices needs --model fundamental")
+    if args.model != "geometry" and args.two_view_geometries is not None:
+        parser().error("--two_view_geometries needs --model geometry")
     logging.basicConfig(level=logging.INFO)
     main(**args.__dict__)

@@ -15,11 +15,14 @@ verified matches; the points are a function of the registered views and their po
 
   python -m sfd2_amd.reconstruction --sfm_dir S --image_dir D --pairs P --features F --matches M
          [--reference_sfm_model R | --intrinsics LIST...] [--single_camera] [--skip_geometric_verification]
-         [--min_match_score X] [--min_num_matches N] [--verification essential|fundamental]
+         [--min_match_score X] [--min_num_matches N] [--verification essential|fundamental|geometry]
 
 --verification fundamental (reconstruct(..., verification="fundamental")): for cameras nobody trusts, i.e. the focal-length prior.  Step 1
 verifies every pair by its fundamental matrix (two_view.verify_pairs_fundamental) and continues as
 --skip_geometric_verification does on the verified matches; the init_max_pairs pairs with the most survivors get a relative pose.
+--verification geometry verifies every pair by E, F and H and keeps the matches of the decision between them (two_view.verify_pairs_geometry,
+DESIGN.md section 17): a planar or rotation-only pair keeps its matches, and a pair labelled panoramic, planar_or_panoramic or
+degenerate is not taken as the initial pair.
 
 Deviations from COLMAP: one model; intrinsics are not refined (a map built from the focal-length prior is only as good as that
 prior); the gauge is held by whole views: the first image of the initial pair is constant in every
@@ -150,6 +153,9 @@ class DeviceStages:
     def fundamental(self, keypoints, pair_matches, max_error, min_num_inliers, seed):
         return two_view.verify_pairs_fundamental(keypoints, pair_matches, max_error, min_num_inliers, self.device, seed=seed)
 
+    def geometry(self, cameras, images, keypoints, pair_matches, max_error, min_num_inliers, seed):
+        return two_view.verify_pairs_geometry(keypoints, pair_matches, cameras, images, max_error, min_num_inliers, device=self.device, seed=seed)
+
     def build_tracks(self, n_nodes, edges, max_rounds):
         return triangulation.build_tracks(n_nodes, edges, max_rounds, self.device)
 
@@ -228,8 +234,11 @@ def reconstruct(cameras, images, keypoints, pair_matches, skip_geometric_verific
     per stage) and 'final'.  Returns (images, points3D) as colmap_io writes them: image ids 1..n in sorted-name order, registered images
     only; point ids 1-based in (track, slot) order.  verification "fundamental": for cameras nobody trusts (the prior focal length), the
     matches are verified by every pair's fundamental matrix instead of an essential matrix at those cameras; the map then
-    starts as with skip_geometric_verification on the verified matches."""
-    if verification not in ("essential", "fundamental"):
+    starts as with skip_geometric_verification on the verified matches.  verification "geometry": E, F and H are estimated for every pair and
+    the matches of two_view.decide_two_view_geometry's choice stay, so a planar or rotation-only pair keeps its matches
+    through H; a pair labelled panoramic, planar_or_panoramic or degenerate is no initial pair (planar is: the five-point pose holds on a
+    plane).  The map then starts as with "fundamental"."""
+    if verification not in ("essential", "fundamental", "geometry"):
         raise ValueError(f"unknown verification {verification!r}")
     unknown = set(options) - set(DEFAULTS)
     if unknown:
@@ -252,12 +261,18 @@ def reconstruct(cameras, images, keypoints, pair_matches, skip_geometric_verific
     if verification == "fundamental" and not skip_geometric_verification:
         m_all, off, _, _ = S.fundamental(keypoints, pair_matches, o["max_error"], o["min_num_matches"], o["seed"])
         pair_matches = [(a, b, m_all[off[p]:off[p + 1]]) for p, (a, b, _) in enumerate(pair_matches)]
-    if skip_geometric_verification or verification == "fundamental":
+    barred = set()                                                               # pairs without a baseline to start from
+    if verification == "geometry" and not skip_geometric_verification:
+        m_all, off, _, decisions = S.geometry(cameras, images, keypoints, pair_matches, o["max_error"], o["min_num_matches"], o["seed"])
+        pair_matches = [(a, b, m_all[off[p]:off[p + 1]]) for p, (a, b, _) in enumerate(pair_matches)]
+        barred = {p for p, d in enumerate(decisions) if d["config"] in two_view.NO_INITIAL_PAIR}
+        rep["two_view_configs"] = [d["config"] for d in decisions]
+    if skip_geometric_verification or verification in ("fundamental", "geometry"):
         sizes = [int(((m[:, 0] >= 0) & (m[:, 1] >= 0)).sum()) for _, _, m in pair_matches]
         for p, (a, b, m) in enumerate(pair_matches):
             if len(m) and (m[:, 0].max() >= kp_off[index[a] + 1] - kp_off[index[a]] or m[:, 1].max() >= kp_off[index[b] + 1] - kp_off[index[b]]):
                 raise ValueError(f"pair {p}: a match index beyond its image's key points")
-        top = sorted((p for p in range(n_pairs) if sizes[p] >= o["min_num_matches"]), key=lambda p: (-sizes[p], p))[:o["init_max_pairs"]]
+        top = sorted((p for p in range(n_pairs) if sizes[p] >= o["min_num_matches"] and p not in barred), key=lambda p: (-sizes[p], p))[:o["init_max_pairs"]]
         _, _, _, res = S.two_view(cameras, images, keypoints, [pair_matches[p] for p in top], o["max_error"], o["min_num_matches"], o["seed"])
         results = {p: r for p, r in zip(top, res)}
         eligible = list(top)
@@ -487,7 +502,7 @@ def parser():
     ap.add_argument("--reference_sfm_model", type=Path)
     ap.add_argument("--intrinsics", type=Path, nargs="+", default=[])
     ap.add_argument("--device", type=int, default=0)
-    ap.add_argument("--verification", choices=("essential", "fundamental"), default="essential")
+    ap.add_argument("--verification", choices=("essential", "fundamental", "geometry"), default="essential")
     return ap
 
 
