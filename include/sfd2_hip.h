@@ -85,7 +85,7 @@ typedef struct {
     int64_t n_candidates; /* N0 after NMS + threshold + border of the last extract          */
 } sfd2_timings;
 
-int sfd2_version(void);   /* 100 = rounds 1-4; 105 adds sfd2_extract_record_async, sfd2_desc_pack and host outputs with SFD2_FLAG_ASYNC; 106 adds sfd2_get_margin_status; 107 adds sfd2_get_relax_status (option "c3b_plain"); 108 adds sfd2_get_option, sfd2_device_pci_bus_id, SFD2_FLAG_DESC_STORE64; 109 adds the baseline JPEG decoder (sfd2_jpeg_*); 112 adds the SfM map (sfd2_verify_matches_batch, sfd2_build_tracks, sfd2_triangulate_tracks); 113 adds the pair selection (sfd2_pairs_retrieval, sfd2_pairs_covisibility, sfd2_pairs_poses); 114 adds sfd2_covis_clusters; 115 adds sfd2_covis_frames; 116 adds the VLAD global descriptors (sfd2_vlad_assign, sfd2_vlad_aggregate, sfd2_vlad_kmeans); 117 adds sfd2_relative_pose_batch; 118 adds sfd2_bundle_adjust; 119 adds the mapper's bookkeeping (sfd2_mapper_restrict, sfd2_mapper_filter, sfd2_mapper_visible, sfd2_mapper_assemble); 120 adds sfd2_fundamental_batch; 121 adds sfd2_homography_batch */
+int sfd2_version(void);   /* 100 = rounds 1-4; 105 adds sfd2_extract_record_async, sfd2_desc_pack and host outputs with SFD2_FLAG_ASYNC; 106 adds sfd2_get_margin_status; 107 adds sfd2_get_relax_status (option "c3b_plain"); 108 adds sfd2_get_option, sfd2_device_pci_bus_id, SFD2_FLAG_DESC_STORE64; 109 adds the baseline JPEG decoder (sfd2_jpeg_*); 112 adds the SfM map (sfd2_verify_matches_batch, sfd2_build_tracks, sfd2_triangulate_tracks); 113 adds the pair selection (sfd2_pairs_retrieval, sfd2_pairs_covisibility, sfd2_pairs_poses); 114 adds sfd2_covis_clusters; 115 adds sfd2_covis_frames; 116 adds the VLAD global descriptors (sfd2_vlad_assign, sfd2_vlad_aggregate, sfd2_vlad_kmeans); 117 adds sfd2_relative_pose_batch; 118 adds sfd2_bundle_adjust; 119 adds the mapper's bookkeeping (sfd2_mapper_restrict, sfd2_mapper_filter, sfd2_mapper_visible, sfd2_mapper_assemble); 120 adds sfd2_fundamental_batch; 121 adds sfd2_homography_batch; 122 adds sfd2_match_guided_batch */
 const char *sfd2_last_error(void);
 
 int sfd2_ctx_create(int device, sfd2_ctx **out);
@@ -678,6 +678,37 @@ typedef struct {
  * is an error (-1).  flags: 0. */
 int sfd2_homography_batch(sfd2_ctx *ctx, const sfd2_homography_problem *problems, int k, const sfd2_two_view_conf *conf,
                           sfd2_homography_result *results, uint8_t *inlier_mask_u8, int flags);
+
+/* ------------------------------------------------------------------------------------------------ guided matching (version 122)
+ * A pair matched AGAIN under its two-view model, what COLMAP has next to its two-view estimation as guided_matching:
+ * sim[i][j] = d0_i . d1_j where the key points i and j agree with the model within max_error_px, -inf elsewhere, and on that masked
+ * matrix the rule of SFD2_MATCH_HLOC -- per row the best value at the first index on a tie, the second best counted with multiplicity
+ * among the gated candidates only, ratio / distance / mutual tests as sfd2_match applies them.  A row without a gated candidate gives
+ * -1 and score 0; a row (column) with one gated candidate passes the ratio test.  The gate, on per-point records computed once per key
+ * point in fp64 from M and rounded to fp32, the test itself in fp32:
+ *   F: l = F (x0, y0, 1), m = F^T (x1, y1, 1), r = x1 l0 + y1 l1 + l2; the pair passes iff r^2 <= max_error_px^2 (l0^2 + l1^2 + m0^2 + m1^2)
+ *      (the four-term Sampson error of sfd2_fundamental_batch without the division)
+ *   H: p = pi(H (x0, y0, 1)); iff p is finite and |x1 - p|^2 <= max_error_px^2 (the one-sided transfer error of sfd2_homography_batch)
+ * Both directions of the mutual check evaluate ONE function on the same records, so they see the same mask bit for bit.  An essential
+ * matrix is served through F = K1^-T E K0^-1.  Only SFD2_MATCH_HLOC with SFD2_SIM_F16; key points as stored (no +0.5: M must be in the
+ * same pixel frame as xy0 / xy1). */
+#define SFD2_GUIDE_F 0
+#define SFD2_GUIDE_H 1
+typedef struct {
+    sfd2_desc_set d0, d1;        /* as sfd2_match_batch takes them (host or device-resident packed fp16); rows must be NULL */
+    const float *xy0, *xy1;      /* host [n][2] pixels */
+    int32_t model, reserved;     /* SFD2_GUIDE_* */
+    double M[9];                 /* row-major; F: x1^T F x0 = 0, H: x1 ~ H x0, pixels */
+    double max_error_px;
+} sfd2_guided_problem;
+
+/* k pairs in one launch sequence; matches0 / scores0: host, sum(d0.n) entries, the pairs concatenated in order.  Non-finite key points
+ * or matrix, max_error_px <= 0, an unknown model, a flavour other than SFD2_MATCH_HLOC, a sim_mode other than SFD2_SIM_F16 or a
+ * non-NULL rows give -1 with sfd2_last_error() naming the pair and the field.  d0.n == 0 or d1.n == 0 is no error (rows -1, score 0).
+ * The candidates of a direction are swept in `splits` chunks of ceil(n / splits) rounded up to 32; the result does not depend on
+ * splits.  flags: 0. */
+int sfd2_match_guided_batch(sfd2_ctx *ctx, const sfd2_guided_problem *problems, int k, int dim, const sfd2_match_conf *conf,
+                            int64_t *matches0, float *scores0, int flags);
 
 /* ------------------------------------------------------------------------------------------------ 2D-3D assembly
  * Matches -> 2D-3D correspondences for a batch of jobs in one call: the per-key-point loops of it_loc/localize_cv2.py:571-632

@@ -133,6 +133,15 @@ class HomographyResult(ctypes.Structure):
                 ("H", ctypes.c_double * 9)]
 
 
+GUIDE_F, GUIDE_H = 0, 1                                                             # SFD2_GUIDE_*
+
+
+class GuidedProblem(ctypes.Structure):
+    """sfd2_guided_problem (include/sfd2_hip.h)."""
+    _fields_ = [("d0", DescSet), ("d1", DescSet), ("xy0", ctypes.c_void_p), ("xy1", ctypes.c_void_p), ("model", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("M", ctypes.c_double * 9), ("max_error_px", ctypes.c_double)]
+
+
 class TwoViewConf(ctypes.Structure):
     """sfd2_two_view_conf (include/sfd2_hip.h)."""
     _fields_ = [("min_inlier_ratio", ctypes.c_double), ("min_num_trials", ctypes.c_int64), ("max_num_trials", ctypes.c_int64),
@@ -244,7 +253,7 @@ EXPORTS = [
     "sfd2_assemble_2d3d", "sfd2_verify_matches_batch", "sfd2_build_tracks", "sfd2_triangulate_tracks",
     "sfd2_pairs_retrieval", "sfd2_pairs_covisibility", "sfd2_pairs_poses", "sfd2_covis_clusters",
     "sfd2_covis_frames", "sfd2_vlad_assign", "sfd2_vlad_aggregate", "sfd2_vlad_kmeans",
-    "sfd2_relative_pose_batch", "sfd2_fundamental_batch", "sfd2_homography_batch", "sfd2_bundle_adjust",
+    "sfd2_relative_pose_batch", "sfd2_fundamental_batch", "sfd2_homography_batch", "sfd2_match_guided_batch", "sfd2_bundle_adjust",
     "sfd2_mapper_restrict", "sfd2_mapper_filter", "sfd2_mapper_visible", "sfd2_mapper_assemble",
 ]
 
@@ -334,6 +343,7 @@ def load():
     lib.sfd2_relative_pose_batch.argtypes = [vp, ctypes.POINTER(TwoViewProblem), ci, ctypes.POINTER(TwoViewConf), ctypes.POINTER(TwoViewResult), vp, vp, ci]
     lib.sfd2_fundamental_batch.argtypes = [vp, ctypes.POINTER(FundamentalProblem), ci, ctypes.POINTER(TwoViewConf), ctypes.POINTER(FundamentalResult), vp, ci]
     lib.sfd2_homography_batch.argtypes = [vp, ctypes.POINTER(HomographyProblem), ci, ctypes.POINTER(TwoViewConf), ctypes.POINTER(HomographyResult), vp, ci]
+    lib.sfd2_match_guided_batch.argtypes = [vp, ctypes.POINTER(GuidedProblem), ci, ci, ctypes.POINTER(MatchConf), vp, vp, ci]
     lib.sfd2_assemble_2d3d.argtypes = [vp, ctypes.POINTER(PointTable), ctypes.POINTER(AssembleJob), ci, ci, ci]
     cd = ctypes.c_double
     lib.sfd2_verify_matches_batch.argtypes = [vp, ctypes.POINTER(TriView), ci, vp, vp, vp, vp, ci, vp, cd, ci, vp, vp, ci]
@@ -354,8 +364,8 @@ def load():
     lib.sfd2_mapper_assemble.argtypes = [vp, vp, ci, vp, vp, ci, vp, vp, vp, ci, vp, ci, i64, vp, vp, vp, vp, vp, ci]
     for name in EXPORTS:
         getattr(lib, name)  # raises AttributeError if the .so lacks a declared symbol
-    if lib.sfd2_version() < 121:
-        raise RuntimeError(f"{LIB_PATH} is version {lib.sfd2_version()}, this binding needs >= 121 (rebuild: __graft_entry__.build())")
+    if lib.sfd2_version() < 122:
+        raise RuntimeError(f"{LIB_PATH} is version {lib.sfd2_version()}, this binding needs >= 122 (rebuild: __graft_entry__.build())")
     _lib = lib
     return lib
 

@@ -552,3 +552,42 @@ void launch_match_finalize(hipStream_t st, const MatchFinal *fin_dev, int npairs
     hipLaunchKernelGGL(match_decide_kernel, dim3((max_n + NT - 1) / NT, npairs), dim3(NT), 0, st, fin_dev, flavour,
                        mutual, ratio, dist);
 }
+
+// ---------------------------------------------------------------- guided matching (guided_match_kernels.hip)
+// match_decide_kernel's hloc branch for a MASKED similarity matrix, a kernel of its own so that the paths above keep their code:
+// s1 == -inf says "no gated candidate" -> no match, score 0.  (hloc_pass(-inf, -inf) is true without a distance threshold --
+// inf <= r^2 inf -- so the unguarded rule would match an empty row to column 0.)  A row with ONE gated candidate has s2 = -inf and
+// passes the ratio test: the existing one-candidate rule.  The back direction needs no guard of its own: sim[i][j] > -inf puts
+// a gated candidate into column j.
+__global__ __launch_bounds__(NT)
+void guided_decide_kernel(const MatchFinal *__restrict__ fins, int mutual, float ratio, float dist)
+{
+    const MatchFinal f = fins[blockIdx.y];
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= f.n0) return;
+    long long m = -1;
+    float score = 0.0f;
+    if (f.n1 > 0) {
+        const float s1 = f.red_f[i], s2 = f.red_f[(size_t)f.n0 + i];
+        const int j = reinterpret_cast<const int *>(f.red_f)[2 * (size_t)f.n0 + i];
+        if (s1 > -INFINITY && hloc_pass(s1, s2, ratio, dist)) {
+            score = (s1 + 1.0f) / 2.0f;   // scores0 come from the forward direction only
+            m = j;
+            if (mutual) {
+                const float t1 = f.red_r[j], t2 = f.red_r[(size_t)f.n1 + j];
+                const int back = reinterpret_cast<const int *>(f.red_r)[2 * (size_t)f.n1 + j];
+                if (!(t1 > -INFINITY && hloc_pass(t1, t2, ratio, dist) && back == i)) m = -1;
+            }
+        }
+    }
+    f.matches0[i] = m;
+    f.scores0[i] = score;
+}
+
+void launch_guided_finalize(hipStream_t st, const MatchFinal *fin_dev, int npairs, int max_n, int splits, int mutual, float ratio,
+                            float dist)
+{
+    if (npairs <= 0 || max_n <= 0) return;
+    hipLaunchKernelGGL(match_reduce_kernel, dim3((max_n + NT - 1) / NT, npairs, 2), dim3(NT), 0, st, fin_dev, splits);
+    hipLaunchKernelGGL(guided_decide_kernel, dim3((max_n + NT - 1) / NT, npairs), dim3(NT), 0, st, fin_dev, mutual, ratio, dist);
+}

@@ -300,6 +300,7 @@ struct sfd2_ctx {
     ScratchBuf pose_in, pose_ws, pose_out;  // sfd2_absolute_pose_batch / sfd2_pose_refine_batch (api_pose.hip): inputs, per-point work, results
     ScratchBuf tv_in, tv_ws, tv_out;        // sfd2_relative_pose_batch (api_two_view.hip): inputs, normalised points and the trials' matrices, results
     ScratchBuf fm_in, fm_ws, fm_out;        // sfd2_fundamental_batch / sfd2_homography_batch (api_fundamental.hip pairs_batch): inputs, normalised points, results
+    ScratchBuf gm_in, gm_ws;                // sfd2_match_guided_batch (api_guided.hip): uploaded key points, descriptors and job descriptors; fp16 sets, gate records, partials and results
     ScratchBuf tri_in, tri_ws;             // sfd2_verify_matches_batch / sfd2_build_tracks / sfd2_triangulate_tracks (api_triangulate.hip): inputs, work and results
     ScratchBuf pairs_in, pairs_ws;          // sfd2_pairs_retrieval / _covisibility / _poses (api_pairs.hip), sfd2_covis_clusters (api_cluster.hip) and sfd2_covis_frames (api_frames.hip): uploaded inputs, partial lists / counters / slot rows and results
     ScratchBuf vlad_in, vlad_ws;            // sfd2_vlad_assign / _aggregate / _kmeans (api_vlad.hip): uploaded rows, centroids and offsets; assignments, sums, partials and results

@@ -653,6 +653,35 @@ struct MatchFinal {
 void launch_match_finalize(hipStream_t st, const MatchFinal *fin_dev, int npairs, int max_n, int splits,
                            int flavour, int mutual, float ratio, float dist);
 
+// ---- guided matching (guided_match_kernels.hip): the two-GEMM matcher with a geometric gate in the epilogue
+struct GuidedProbDev {     // one pair for guided_prep_kernel
+    double M[9];           // row-major F (x1^T F x0 = 0) or H (x1 ~ H x0), pixels
+    int model;             // SFD2_GUIDE_*
+    int n0, n1;
+    int pad_;
+    long long off0, off1;  // the pair's first key point in the concatenated xy0 / rec0 and xy1 / rec1
+};
+struct GuidedJob {         // one direction of one pair
+    const half_t *a_hi;    // reduced side (candidates j), [na][128]
+    const half_t *b_hi;    // kept side (queries i), [nb][128]
+    const float4 *a_rec;   // the candidates' gate records [na]
+    const float4 *b_rec;   // the queries' [nb]
+    int na, nb;
+    int model;             // SFD2_GUIDE_*
+    int dir;               // 0: the queries are image-0 points (forward), 1: image-1 points (reverse)
+    float t2;              // max_error_px^2
+    int pad_;
+    float *part_v1;        // [splits][nb], as MatchJob's
+    float *part_v2;
+    int *part_i1;
+};
+void launch_guided_prep(hipStream_t st, const GuidedProbDev *probs_dev, int k, int max_n, const float *xy0, const float *xy1,
+                        float4 *rec0, float4 *rec1);
+void launch_guided_top2(hipStream_t st, const GuidedJob *jobs_dev, int njobs, int max_nb, int splits);
+// match_reduce_kernel as it is, then the hloc decisions on a MASKED matrix: a row (column) whose best value is -inf has no candidate
+void launch_guided_finalize(hipStream_t st, const MatchFinal *fin_dev, int npairs, int max_n, int splits, int mutual, float ratio,
+                            float dist);
+
 // persistent streaming 1x1 conv, 256 -> 256 (ResBlock conv1 / conv3); w_rowmajor = [256 out][256 in] fp16; zero page >= 512 B
 void launch_conv1x1_c256(hipStream_t st, const half_t *in, int npix, const half_t *w_rowmajor, const float *scale,
                          const float *shift, int relu, const half_t *res, half_t *out, const half_t *zero_page);

@@ -23,7 +23,14 @@ name0 name1 success num_inliers and the nine entries of F (row-major, x1^T F x0 
 --model geometry estimates F and H for every pair, and E too where intrinsics are given, and keeps the matches of
 two_view.decide_two_view_geometry's choice, as COLMAP labels a pair calibrated, uncalibrated, planar, panoramic or degenerate: a planar or
 rotation-only pair keeps its matches through H where a fundamental matrix alone loses or pollutes them.  --two_view_geometries writes one
-line per verified pair: name0 name1 config num_inliers_E num_inliers_F num_inliers_H num_kept (num_inliers_E is -1 without intrinsics)."""
+line per verified pair: name0 name1 config num_inliers_E num_inliers_F num_inliers_H num_kept (num_inliers_E is -1 without intrinsics).
+
+--guided_matching (with any --model) takes the opposite step after the estimation: every verified pair's descriptors, read
+from the feature store, are matched again with only those candidates allowed that agree with the pair's model within --max_error
+(two_view.guided_match_pairs: E through F from focal lengths and principal points, F, or H, whichever mask the pair kept), under the
+rule --guided_conf names (a key of match_features.confs, default NNM).  matches0 and matching_scores0 of the output then hold the
+guided result, in the input datasets' types and shapes; a pair without a model keeps all -1.  `reconstruction
+--skip_geometric_verification` reads that store as it is."""
 import argparse
 import logging
 from pathlib import Path
@@ -32,7 +39,7 @@ from types import SimpleNamespace
 import numpy as np
 
 from . import colmap_io, feature_io, parsers, two_view
-from .match_features import names_to_pair
+from .match_features import confs as match_confs, names_to_pair
 
 
 def read_cameras(reference_sfm_model=None, intrinsics=()):
@@ -60,7 +67,7 @@ def _write_group(store, name, arrays):
 
 def main(pairs, features, matches, output, reference_sfm_model=None, intrinsics=(), max_error=4.0,
          min_num_inliers=two_view.DEFAULTS["min_num_inliers"], relative_poses=None, device=0, model="essential", fundamental_matrices=None,
-         two_view_geometries=None, **ransac):
+         two_view_geometries=None, guided_matching=False, guided_conf="NNM", **ransac):
     """Returns the per-pair result dicts of two_view.verify_pairs_two_view (model "essential"), two_view.verify_pairs_fundamental
     (model "fundamental", no intrinsics) or two_view.verify_pairs_geometry (model "geometry", with or without intrinsics), keyed by
     (name0, name1)."""
@@ -72,6 +79,8 @@ def main(pairs, features, matches, output, reference_sfm_model=None, intrinsics=
         raise ValueError("--fundamental_matrices needs --model fundamental")
     if model != "geometry" and two_view_geometries is not None:
         raise ValueError("--two_view_geometries needs --model geometry")
+    if guided_conf not in match_confs:
+        raise ValueError(f"unknown --guided_conf {guided_conf!r} (one of {', '.join(match_confs)})")
     name_cam = None
     if model == "essential" or (model == "geometry" and (reference_sfm_model is not None or intrinsics)):
         name_cam = read_cameras(reference_sfm_model, intrinsics)
@@ -94,6 +103,9 @@ def main(pairs, features, matches, output, reference_sfm_model=None, intrinsics=
             todo.append((name0, name1, pair))
         keypoints = {i: np.asarray(feats[n]["keypoints"].__array__(), dtype=np.float32).reshape(-1, 2)[:, :2] for n, i in ids.items()}
         groups = {pair: {k: np.asarray(src[pair][k].__array__()) for k in src[pair].keys()} for _, _, pair in todo}
+        descriptors = None
+        if guided_matching:     # stored [128, n] (match_features reads them so)
+            descriptors = {i: np.ascontiguousarray(np.asarray(feats[n]["descriptors"].__array__(), dtype=np.float32).T) for n, i in ids.items()}
     finally:
         feats.close()
         src.close()
@@ -113,12 +125,21 @@ def main(pairs, features, matches, output, reference_sfm_model=None, intrinsics=
                                                             **ransac)
     else:
         m, off, _, results = two_view.verify_pairs_two_view(cameras, images, keypoints, pair_matches, max_error, min_num_inliers, device, **ransac)
+    if guided_matching:
+        logging.info("Matching %d pairs again under their models (%s)...", len(todo), guided_conf)
+        gm, goff, _, gs = two_view.guided_match_pairs(keypoints, descriptors, pair_matches, results, max_error, match_confs[guided_conf], cameras,
+                                                      images, device)
     dst = feature_io.open_store(output, "w")
     try:
         for p, (_, _, pair) in enumerate(todo):
             g = dict(groups[pair])
-            kept = m[off[p]:off[p + 1], 1]
-            g["matches0"] = np.where(kept >= 0, g["matches0"].reshape(-1), -1).astype(g["matches0"].dtype).reshape(g["matches0"].shape)
+            if guided_matching:
+                g["matches0"] = gm[goff[p]:goff[p + 1], 1].astype(g["matches0"].dtype).reshape(g["matches0"].shape)
+                if "matching_scores0" in g:
+                    g["matching_scores0"] = gs[goff[p]:goff[p + 1]].astype(g["matching_scores0"].dtype).reshape(g["matching_scores0"].shape)
+            else:
+                kept = m[off[p]:off[p + 1], 1]
+                g["matches0"] = np.where(kept >= 0, g["matches0"].reshape(-1), -1).astype(g["matches0"].dtype).reshape(g["matches0"].shape)
             _write_group(dst, pair, g)
     finally:
         dst.close()
@@ -153,6 +174,8 @@ def parser():
     p.add_argument("--model", choices=("essential", "fundamental", "geometry"), default="essential")
     p.add_argument("--fundamental_matrices", type=Path)
     p.add_argument("--two_view_geometries", type=Path)
+    p.add_argument("--guided_matching", action="store_true")
+    p.add_argument("--guided_conf", type=str, default="NNM", choices=list(match_confs))
     return p
 
 

@@ -19,7 +19,11 @@ x1 ~ H x0 in pixels -- closed-form four-point LO-RANSAC on the one-sided squared
 decide_two_view_geometry(E, F, H) is a pure host function on three result dicts that labels the pair calibrated, uncalibrated, planar,
 panoramic, planar_or_panoramic or degenerate and names the mask to keep, modelled on COLMAP's EstimateCalibrated / EstimateUncalibrated;
 two_view_geometry_batch and verify_pairs_geometry make the two (F, H) or three (E too, with cameras) device calls with one threshold
-and seed and decide per pair."""
+and seed and decide per pair.
+
+Guided matching: guided_matches(_batch) match a pair's descriptors again with only those
+candidates allowed whose key points agree with the pair's F or H; guide_of takes (kind, matrix) from any result above (E through
+fundamental_from_essential), guided_match_pairs does it for all pairs of a verify_pairs_* call."""
 import ctypes
 
 import numpy as np
@@ -352,3 +356,150 @@ def verify_pairs_geometry(keypoints, pair_matches, cameras=None, images=None, ma
     results = two_view_geometry_batch(problems, cams, max_error, min_num_inliers, min_E_F_inlier_ratio, max_H_inlier_ratio, device, **ransac)
     out, counts = _keep_rows(rows_of, ms, off, results, lambda r: r["inliers"] if r["config"] != "degenerate" else None)
     return out, off, counts, results
+
+
+# ------------------------------------------------------------------------------------------------ guided matching
+GUIDED_CONF = {"ratio_threshold": None, "distance_threshold": None, "do_mutual_check": True}      # match_features.confs["NNM"]'s rule
+
+
+def fundamental_from_essential(E, camera0, camera1):
+    """F = K1^-T E K0^-1 in pixels (x1^T F x0 = 0), unit Frobenius norm, from the cameras' focal lengths and principal points ONLY:
+    distortion is ignored, so for a SIMPLE_RADIAL or OPENCV camera the epipolar lines are those of the undistorted image and a guide
+    made from F is off by the distortion at the key point."""
+    def K_inv(camera):
+        model, q = camera_model(camera)
+        fx, fy, cx, cy = (q[0], q[0], q[1], q[2]) if model in (0, 2) else (q[0], q[1], q[2], q[3])
+        return np.array([[1.0 / fx, 0.0, -cx / fx], [0.0, 1.0 / fy, -cy / fy], [0.0, 0.0, 1.0]])
+    F = K_inv(camera1).T @ np.asarray(E, dtype=np.float64).reshape(3, 3) @ K_inv(camera0)
+    n = np.linalg.norm(F)
+    return F / n if n > 0 else F
+
+
+def guide_of(result, camera0=None, camera1=None):
+    """(kind, matrix) of the model whose mask a result kept, kind 'F' or 'H', or None where there is nothing to guide by (no success,
+    a 'degenerate' decision).  result: a relative_pose dict (E -> F through fundamental_from_essential, which needs the two cameras), a
+    fundamental_matrix dict, a homography dict, or a decision dict of two_view_geometry_batch (the model its 'model' key names)."""
+    if "config" in result:
+        if result["config"] == "degenerate" or result["model"] is None:
+            return None
+        return guide_of(result[result["model"]], camera0, camera1)
+    if not result["success"]:
+        return None
+    if "E" in result:
+        if camera0 is None or camera1 is None:
+            raise ValueError("an essential matrix guides through F: the two cameras are needed")
+        return "F", fundamental_from_essential(result["E"], camera0, camera1)
+    if "F" in result:
+        return "F", np.asarray(result["F"], dtype=np.float64).reshape(3, 3)
+    if "H" in result:
+        return "H", np.asarray(result["H"], dtype=np.float64).reshape(3, 3)
+    raise ValueError("not a two-view result: none of the keys 'E', 'F', 'H', 'config'")
+
+
+def _match_conf(conf):
+    conf = dict(GUIDED_CONF, **(conf.get("model", conf) if conf else {}))
+    unknown = set(conf) - set(GUIDED_CONF) - {"name", "sim_mode"}
+    if unknown:
+        raise ValueError(f"unknown matcher options {sorted(unknown)}")
+    if conf.get("sim_mode", "f16") != "f16":
+        raise ValueError("guided matching supports sim_mode 'f16' only")
+    return _lib.MatchConf(_lib.MATCH_HLOC, int(bool(conf["do_mutual_check"])), float(conf["ratio_threshold"] or 0.0),
+                          float(conf["distance_threshold"] or 0.0), _lib.SIM_F16)
+
+
+def guided_matches_batch(problems, max_error_px=4.0, conf=None, device=0):
+    """problems: a list of (desc0 [n0,128], desc1 [n1,128], kp0 [n0,2], kp1 [n1,2], kind 'F' | 'H', matrix [3,3]) or (..., max_error_px).
+    One device call (sfd2_match_guided_batch): every pair's descriptors are matched again with only those candidates allowed whose key
+    points agree with the model within max_error_px -- F: the Sampson error, x1^T F x0 = 0; H: the transfer error in image 1, x1 ~ H x0
+    -- under the NearestNeighbor rule of `conf` (a match_features.confs entry, its 'model' dict, or None = mutual nearest neighbours:
+    ratio_threshold, distance_threshold, do_mutual_check).  Key points and matrix must share one pixel frame.  Returns one
+    (matches0 int64 [n0], scores0 float32 [n0]) per pair; a row without an allowed candidate gets -1 and score 0."""
+    mc = _match_conf(conf)
+    keep, probs = [], []
+    for i, p in enumerate(problems):
+        d0 = np.ascontiguousarray(p[0], dtype=np.float32)
+        d1 = np.ascontiguousarray(p[1], dtype=np.float32)
+        k0 = np.ascontiguousarray(p[2], dtype=np.float32).reshape(-1, 2)
+        k1 = np.ascontiguousarray(p[3], dtype=np.float32).reshape(-1, 2)
+        if d0.ndim != 2 or d1.ndim != 2 or d0.shape[1] != 128 or d1.shape[1] != 128:
+            raise ValueError(f"pair {i}: descriptors must be [n, 128], got {d0.shape} and {d1.shape}")
+        if len(k0) != len(d0) or len(k1) != len(d1):
+            raise ValueError(f"pair {i}: {len(k0)} and {len(k1)} key points for {len(d0)} and {len(d1)} descriptors")
+        if p[4] not in ("F", "H"):
+            raise ValueError(f"pair {i}: unknown guide kind {p[4]!r} (one of 'F', 'H')")
+        M = np.ascontiguousarray(p[5], dtype=np.float64).reshape(-1)
+        if M.size != 9:
+            raise ValueError(f"pair {i}: the guide matrix must be 3 x 3")
+        if not (np.isfinite(k0).all() and np.isfinite(k1).all() and np.isfinite(M).all()):
+            raise ValueError(f"pair {i}: non-finite key points or matrix")
+        err = float(p[6] if len(p) > 6 else max_error_px)
+        if not (np.isfinite(err) and err > 0):
+            raise ValueError(f"pair {i}: max_error_px must be positive")
+        keep += [d0, d1, k0, k1]
+        pr = _lib.GuidedProblem()
+        for s, d in ((pr.d0, d0), (pr.d1, d1)):
+            s.data, s.n, s.dtype, s.layout, s.on_device, s.rows, s.n_rows = (d.ctypes.data if d.size else None), len(d), _lib.DT_F32, _lib.LAYOUT_ND, 0, None, 0
+        pr.xy0, pr.xy1 = (k0.ctypes.data if k0.size else None), (k1.ctypes.data if k1.size else None)
+        pr.model = _lib.GUIDE_F if p[4] == "F" else _lib.GUIDE_H
+        for j in range(9):
+            pr.M[j] = M[j]
+        pr.max_error_px = err
+        probs.append(pr)
+    k = len(probs)
+    if k == 0:
+        return []
+    ctx = _lib.default_context(device)
+    total = sum(pr.d0.n for pr in probs)
+    m = np.full(max(total, 1), -1, dtype=np.int64)
+    s = np.zeros(max(total, 1), dtype=np.float32)
+    _lib.check(ctx.lib.sfd2_match_guided_batch(ctx.h, (_lib.GuidedProblem * k)(*probs), k, 128, ctypes.byref(mc), m.ctypes.data, s.ctypes.data, 0))
+    out, o = [], 0
+    for pr in probs:
+        out.append((m[o:o + pr.d0.n].copy(), s[o:o + pr.d0.n].copy()))
+        o += pr.d0.n
+    return out
+
+
+def guided_matches(desc0, desc1, kp0, kp1, kind, matrix, max_error_px=4.0, conf=None, device=0):
+    """One pair of guided_matches_batch: (matches0 int64 [n0], scores0 float32 [n0])."""
+    return guided_matches_batch([(desc0, desc1, kp0, kp1, kind, matrix)], max_error_px, conf, device)[0]
+
+
+def _guide_for_stored(kind, M):
+    """The guide of a model estimated on key points + 0.5 (verify_pairs_*), for the key points as stored: with T the shift by +0.5,
+    F' = T^T F T and H' = T^-1 H T, exact in fp64 up to rounding -- the stored float32 coordinates stay as they are."""
+    T = np.array([[1.0, 0.0, 0.5], [0.0, 1.0, 0.5], [0.0, 0.0, 1.0]])
+    return T.T @ M @ T if kind == "F" else np.linalg.inv(T) @ M @ T
+
+
+def guided_match_pairs(keypoints, descriptors, pair_matches, results, max_error=4.0, conf=None, cameras=None, images=None, device=0):
+    """The step after verify_pairs_*: every pair is matched again under the model its verification kept.  keypoints / descriptors: image
+    id -> [n,2] as stored / [n,128]; pair_matches: [(image id 0, image id 1, matches [m,2])] as verify_pairs_* took them (only the
+    image ids and, for the shape of the output, m are used); results: the dicts verify_pairs_* returned; cameras and images: as
+    verify_pairs_two_view takes them, needed where a result's guide is an essential matrix.  Returns (matches int32 [M,2], offsets int64
+    [n_pairs + 1], counts int32 [n_pairs], scores float32 [M]) in verify_pairs_*'s shape with m = the key points of image 0: row r of a
+    pair is (r, its guided match) or (-1, -1), counts the matched rows.  A pair whose result failed or is 'degenerate', and a pair of an
+    image with itself, keeps all -1."""
+    if len(results) != len(pair_matches):
+        raise ValueError(f"{len(results)} results for {len(pair_matches)} pairs")
+    off = np.zeros(len(pair_matches) + 1, dtype=np.int64)
+    problems, where = [], []
+    for p, ((i0, i1, _), r) in enumerate(zip(pair_matches, results)):
+        n0 = len(np.asarray(keypoints[i0]).reshape(-1, 2))
+        off[p + 1] = off[p] + n0
+        cams = (cameras[images[i0].camera_id], cameras[images[i1].camera_id]) if cameras is not None else (None, None)
+        g = None if i0 == i1 else guide_of(r, *cams)
+        if g is None:
+            continue
+        where.append(p)
+        problems.append((descriptors[i0], descriptors[i1], keypoints[i0], keypoints[i1], g[0], _guide_for_stored(*g)))
+    out = np.full((int(off[-1]), 2), -1, dtype=np.int32)
+    scores = np.zeros(int(off[-1]), dtype=np.float32)
+    counts = np.zeros(len(pair_matches), dtype=np.int32)
+    for p, (m, s) in zip(where, guided_matches_batch(problems, max_error, conf, device)):
+        rows = np.flatnonzero(m >= 0)
+        out[off[p] + rows, 0] = rows
+        out[off[p] + rows, 1] = m[rows]
+        scores[off[p]:off[p + 1]] = s
+        counts[p] = len(rows)
+    return out, off, counts, scores
