@@ -32,7 +32,7 @@ def needs_build():
     """True when libsfd2hip.so is missing or older than any of its sources."""
     if not os.path.exists(LIB):
         return True
-    srcs = [os.path.join(CSRC, s) for s in SOURCES] + [os.path.join(CSRC, "sfd2_internal.h"), os.path.join(CSRC, "sfd2_ctx.h"), os.path.join(CSRC, "api_scratch.h"), os.path.join(CSRC, "pose_camera.h"), os.path.join(CSRC, "five_point.h"), os.path.join(CSRC, "ransac_common.h"), os.path.join(CSRC, "seven_point.h"), os.path.join(CSRC, "four_point.h"), os.path.join(CSRC, "bundle.h"), os.path.join(CSRC, "mapper.h"),
+    srcs = [os.path.join(CSRC, s) for s in SOURCES] + [os.path.join(CSRC, "sfd2_internal.h"), os.path.join(CSRC, "sfd2_ctx.h"), os.path.join(CSRC, "api_scratch.h"), os.path.join(CSRC, "pose_camera.h"), os.path.join(CSRC, "five_point.h"), os.path.join(CSRC, "ransac_common.h"), os.path.join(CSRC, "ransac_math.h"), os.path.join(CSRC, "seven_point.h"), os.path.join(CSRC, "four_point.h"), os.path.join(CSRC, "bundle.h"), os.path.join(CSRC, "mapper.h"),
                                                       os.path.join(HERE, "..", "include", "sfd2_hip.h")]
     return any(os.path.exists(s) and os.path.getmtime(s) > os.path.getmtime(LIB) for s in srcs)
 
@@ -42,7 +42,7 @@ def build_lib(force=False, verbose=False, out=None, extra_flags=()):
     side directory so the product objects are not disturbed."""
     hipcc = _hipcc()
     objs = []
-    deps = [os.path.join(CSRC, "sfd2_internal.h"), os.path.join(CSRC, "sfd2_ctx.h"), os.path.join(CSRC, "api_scratch.h"), os.path.join(CSRC, "pose_camera.h"), os.path.join(CSRC, "five_point.h"), os.path.join(CSRC, "ransac_common.h"), os.path.join(CSRC, "seven_point.h"), os.path.join(CSRC, "four_point.h"), os.path.join(CSRC, "bundle.h"), os.path.join(CSRC, "mapper.h"), os.path.join(HERE, "..", "include", "sfd2_hip.h")]
+    deps = [os.path.join(CSRC, "sfd2_internal.h"), os.path.join(CSRC, "sfd2_ctx.h"), os.path.join(CSRC, "api_scratch.h"), os.path.join(CSRC, "pose_camera.h"), os.path.join(CSRC, "five_point.h"), os.path.join(CSRC, "ransac_common.h"), os.path.join(CSRC, "ransac_math.h"), os.path.join(CSRC, "seven_point.h"), os.path.join(CSRC, "four_point.h"), os.path.join(CSRC, "bundle.h"), os.path.join(CSRC, "mapper.h"), os.path.join(HERE, "..", "include", "sfd2_hip.h")]
     procs = []
     lib = out or LIB
     odir = CSRC

@@ -16,6 +16,9 @@
 //   4. stopping: COLMAP's trial count (sample size 7, multiplier 3) after every round, clamped to [min_trials, max_trials].
 //   5. final: Levenberg-Marquardt on the same chart and cost over the RANSAC inliers; F_px = T1^T F T0 at unit Frobenius norm, the first
 //      entry of largest magnitude positive.  No cheirality test, no pose.
+// Shared with the other RANSAC kernels (ransac_common.h, ransac_math.h): the sampler, reductions, winner broadcast,
+// Cholesky solve, stopping rule and output convention (finish_matrix).  Here: the solver call, the Sampson error and the scoring loops,
+// the preparation, the chart with its residual and update, the LO loop and the Levenberg-Marquardt loop.
 // Every reduction runs in a fixed order (wave butterflies, then the waves in index order) and nothing depends on another workgroup,
 // so a pair's result depends on the pair and the seed only.  All loops are bounded.  No private segment, no spills.
 #include "sfd2_internal.h"
@@ -31,8 +34,6 @@ constexpr int kLoGN = 3;
 constexpr int kRefIters = 50;
 constexpr int kNP = 7;               // parameters of the chart
 constexpr int kNS = 36;              // normal equations: 28 (upper triangle) + 7 (gradient) + 1 (cost)
-
-SFD2_PD bool finite_d(double v) { return __builtin_isfinite(v); }
 
 // squared Sampson error of x1^T F x0 (COLMAP's ComputeSquaredSampsonError)
 SFD2_PD double sampson(const double F[9], double2 a, double2 b)
@@ -132,69 +133,6 @@ SFD2_PD void residual(const double F[9], const Chart &c, double2 a, double2 b, d
     J[5] = gk[0] * c.f[0] + gk[1] * c.f[1] + gk[2] * c.f[2];
     J[6] = gk[0] * c.f[3] + gk[1] * c.f[4] + gk[2] * c.f[5];
 }
-SFD2_PD void acc_normal(double (&s)[kNS], const double (&J)[kNP], double r)
-{
-    int k = 0;
-#pragma unroll
-    for (int a = 0; a < kNP; ++a)
-#pragma unroll
-        for (int b = a; b < kNP; ++b, ++k) s[k] += J[a] * J[b];
-#pragma unroll
-    for (int a = 0; a < kNP; ++a) s[28 + a] += J[a] * r;
-    s[35] += r * r;
-}
-// Solves (H + lambda diag(H) + 1e-15 max diag(H) I) d = -g by Cholesky; false when not positive definite or not finite.
-SFD2_PD bool solve7(const double (&s)[kNS], double lambda, double (&d)[kNP])
-{
-    constexpr int N = kNP;
-    double A[N * N];
-    int k = 0;
-#pragma unroll
-    for (int a = 0; a < N; ++a)
-#pragma unroll
-        for (int b = a; b < N; ++b, ++k) { A[a * N + b] = s[k]; A[b * N + a] = s[k]; }
-    double mx = 0;
-#pragma unroll
-    for (int a = 0; a < N; ++a) mx = fmax(mx, A[a * (N + 1)]);
-    if (!(mx > 0) || !finite_d(mx)) return false;
-#pragma unroll
-    for (int a = 0; a < N; ++a) A[a * (N + 1)] += lambda * A[a * (N + 1)] + 1e-15 * mx;
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-        double dj = A[j * (N + 1)];
-#pragma unroll
-        for (int p = 0; p < j; ++p) dj -= A[j * N + p] * A[j * N + p];
-        if (!(dj > 0)) return false;
-        const double l = sqrt(dj);
-        A[j * (N + 1)] = l;
-#pragma unroll
-        for (int i = j + 1; i < N; ++i) {
-            double v = A[i * N + j];
-#pragma unroll
-            for (int p = 0; p < j; ++p) v -= A[i * N + p] * A[j * N + p];
-            A[i * N + j] = v / l;
-        }
-    }
-    double y[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        double v = -s[28 + i];
-#pragma unroll
-        for (int p = 0; p < i; ++p) v -= A[i * N + p] * y[p];
-        y[i] = v / A[i * (N + 1)];
-    }
-#pragma unroll
-    for (int i = N - 1; i >= 0; --i) {
-        double v = y[i];
-#pragma unroll
-        for (int p = i + 1; p < N; ++p) v -= A[p * N + i] * d[p];
-        d[i] = v / A[i * (N + 1)];
-    }
-    bool ok = true;
-#pragma unroll
-    for (int i = 0; i < N; ++i) ok = ok && finite_d(d[i]);
-    return ok;
-}
 SFD2_PD void apply_update(Chart &c, const double (&d)[kNP])
 {
 #pragma unroll
@@ -287,7 +225,7 @@ __global__ __launch_bounds__(kWG) void fundamental_kernel(const FmProbDev *__res
             if (!use(j, a, b)) continue;
             double r, J[kNP];
             residual(F, c, a, b, r, J);
-            acc_normal(s, J, r);
+            normal_acc(s, J, r);
         }
         wg_sum(s, red);
     };
@@ -343,12 +281,7 @@ __global__ __launch_bounds__(kWG) void fundamental_kernel(const FmProbDev *__res
         }
         const Support win = wg_best(mine, sred);
         if (win.cnt >= 0 && better(win, best)) {
-            if (win.trial == trial)
-#pragma unroll
-                for (int i = 0; i < 9; ++i) shF[i] = mF[i];
-            __syncthreads();
-#pragma unroll
-            for (int i = 0; i < 9; ++i) bF[i] = shF[i];
+            publish_winner(win.trial == trial, mF, shF, bF);
             best = win;
             // ---- 3. local optimisation over the best matrix's inliers
             for (int lo = 0; lo < kLoSteps; ++lo) {
@@ -358,7 +291,7 @@ __global__ __launch_bounds__(kWG) void fundamental_kernel(const FmProbDev *__res
                     double s[kNS];
                     accumulate(ch, s, [&](int, double2 a, double2 b) { return sampson(bF, a, b) <= th2; });
                     double d[kNP];
-                    good = solve7(s, 0.0, d);
+                    good = chol_solve<kNP>(s, 0.0, d);
                     if (good) apply_update(ch, d);
                 }
                 if (!good) break;
@@ -376,19 +309,8 @@ __global__ __launch_bounds__(kWG) void fundamental_kernel(const FmProbDev *__res
         }
         // ---- 4. stopping (COLMAP ComputeNumTrials on the best inlier ratio, sample size 7, multiplier 3)
         trials = min((round + 1) * kWG, conf.max_trials);
-        if (trials >= conf.max_trials) break;
-        if (trials >= conf.min_trials && best.cnt > 0) {
-            const double ratio = (double)best.cnt / n;
-            const double r2 = ratio * ratio, r4 = r2 * r2;
-            const double nom = 1.0 - conf.confidence;
-            const double den = 1.0 - r4 * r2 * ratio;
-            double need;
-            if (nom <= 0) need = 1e300;
-            else if (den <= 0) need = 1.0;
-            else if (den == 1.0 || fabs(log(den)) < 1e-16) need = 1e300;
-            else need = ceil(log(nom) / log(den) * 3.0);
-            if ((double)trials >= need) break;
-        }
+        // (the power is spelt out, not pow(): its last bit reaches num_trials)
+        if (ransac_enough(trials, conf, n, best.cnt, [](double r) { const double r2 = r * r, r4 = r2 * r2; return r4 * r2 * r; })) break;
         __syncthreads();                                      // shF and the reductions' LDS are reused by the next round
     }
     out.num_trials = (int)trials;
@@ -408,7 +330,7 @@ __global__ __launch_bounds__(kWG) void fundamental_kernel(const FmProbDev *__res
         double lambda = 1e-4;
         for (int it = 0; it < kRefIters; ++it) {
             double d[kNP];
-            if (!solve7(s, lambda, d)) break;
+            if (!chol_solve<kNP>(s, lambda, d)) break;
             Chart cn = ch;
             apply_update(cn, d);
             double sn[kNS];
@@ -444,22 +366,7 @@ __global__ __launch_bounds__(kWG) void fundamental_kernel(const FmProbDev *__res
             P[3 + q] = sc * G[3 + q];
             P[6 + q] = G[6 + q] - sc * (cen[2] * G[q] + cen[3] * G[3 + q]);
         }
-        double nn = 0;
-#pragma unroll
-        for (int i = 0; i < 9; ++i) nn += P[i] * P[i];
-        double inv = 1.0 / sqrt(nn);
-        double lead = P[0];                                  // the first entry of largest magnitude
-#pragma unroll
-        for (int i = 1; i < 9; ++i)
-            if (fabs(P[i]) > fabs(lead)) lead = P[i];
-        if (lead < 0) inv = -inv;
-        bool fin = finite_d(inv);
-#pragma unroll
-        for (int i = 0; i < 9; ++i) { out.F[i] = P[i] * inv; fin = fin && finite_d(out.F[i]); }
-        out.success = (fin && best.cnt >= conf.min_num_inliers) ? 1 : 0;
-        if (!fin)
-#pragma unroll
-            for (int i = 0; i < 9; ++i) out.F[i] = 0.0;
+        finish_matrix(P, best.cnt, conf, out);
         res[pi] = out;
     }
 }

@@ -14,6 +14,9 @@
 //   4. stopping: COLMAP's trial count (sample size 4, multiplier 3) after every round, clamped to [min_trials, max_trials].
 //   5. final: Levenberg-Marquardt on the same chart and cost over the RANSAC inliers; H_px = T1^-1 H T0 at unit Frobenius norm, the
 //      first entry of largest magnitude positive.  No decomposition, no pose.
+// Shared with the other RANSAC kernels (ransac_common.h, ransac_math.h): the sampler, reductions, scoring loops, winner
+// broadcast, Cholesky solve, stopping rule and output convention (finish_matrix).  Here: the solver call, the transfer error, the
+// preparation, the chart with its residual and update, the LO loop and the Levenberg-Marquardt loop.
 // Every reduction runs in a fixed order (wave butterflies, then the waves in index order) and nothing depends on another workgroup,
 // so a pair's result depends on the pair and the seed only.  All loops are bounded.  No private segment, no spills.
 #include "sfd2_internal.h"
@@ -28,10 +31,7 @@ constexpr int kLoSteps = 8;
 constexpr int kLoGN = 3;
 constexpr int kRefIters = 50;
 constexpr int kNP = 8;               // parameters of the chart
-constexpr int kNT = 36;              // upper triangle of the normal equations
 constexpr int kNS = 45;              // 36 (upper triangle) + 8 (gradient) + 1 (cost)
-
-SFD2_PD bool finite_d(double v) { return __builtin_isfinite(v); }
 
 // squared one-sided transfer error in image 1 (COLMAP's HomographyMatrixEstimator::Residuals); NaN or inf when the denominator is 0
 SFD2_PD double transfer(const double H[9], double2 a, double2 b)
@@ -67,69 +67,6 @@ SFD2_PD void residual(const double H[9], int fix, double2 a, double2 b, double (
         Jx[m] = m < fix ? gx[m] : gx[m + 1];
         Jy[m] = m < fix ? gy[m] : gy[m + 1];
     }
-}
-SFD2_PD void acc_normal(double (&s)[kNS], const double (&J)[kNP], double r)
-{
-    int k = 0;
-#pragma unroll
-    for (int a = 0; a < kNP; ++a)
-#pragma unroll
-        for (int b = a; b < kNP; ++b, ++k) s[k] += J[a] * J[b];
-#pragma unroll
-    for (int a = 0; a < kNP; ++a) s[kNT + a] += J[a] * r;
-    s[kNS - 1] += r * r;
-}
-// Solves (H + lambda diag(H) + 1e-15 max diag(H) I) d = -g by Cholesky; false when not positive definite or not finite.
-SFD2_PD bool solve8(const double (&s)[kNS], double lambda, double (&d)[kNP])
-{
-    constexpr int N = kNP;
-    double A[N * N];
-    int k = 0;
-#pragma unroll
-    for (int a = 0; a < N; ++a)
-#pragma unroll
-        for (int b = a; b < N; ++b, ++k) { A[a * N + b] = s[k]; A[b * N + a] = s[k]; }
-    double mx = 0;
-#pragma unroll
-    for (int a = 0; a < N; ++a) mx = fmax(mx, A[a * (N + 1)]);
-    if (!(mx > 0) || !finite_d(mx)) return false;
-#pragma unroll
-    for (int a = 0; a < N; ++a) A[a * (N + 1)] += lambda * A[a * (N + 1)] + 1e-15 * mx;
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-        double dj = A[j * (N + 1)];
-#pragma unroll
-        for (int p = 0; p < j; ++p) dj -= A[j * N + p] * A[j * N + p];
-        if (!(dj > 0)) return false;
-        const double l = sqrt(dj);
-        A[j * (N + 1)] = l;
-#pragma unroll
-        for (int i = j + 1; i < N; ++i) {
-            double v = A[i * N + j];
-#pragma unroll
-            for (int p = 0; p < j; ++p) v -= A[i * N + p] * A[j * N + p];
-            A[i * N + j] = v / l;
-        }
-    }
-    double y[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        double v = -s[kNT + i];
-#pragma unroll
-        for (int p = 0; p < i; ++p) v -= A[i * N + p] * y[p];
-        y[i] = v / A[i * (N + 1)];
-    }
-#pragma unroll
-    for (int i = N - 1; i >= 0; --i) {
-        double v = y[i];
-#pragma unroll
-        for (int p = i + 1; p < N; ++p) v -= A[p * N + i] * d[p];
-        d[i] = v / A[i * (N + 1)];
-    }
-    bool ok = true;
-#pragma unroll
-    for (int i = 0; i < N; ++i) ok = ok && finite_d(d[i]);
-    return ok;
 }
 SFD2_PD void apply_update(double (&H)[9], int fix, const double (&d)[kNP])
 {
@@ -197,17 +134,6 @@ __global__ __launch_bounds__(kWG) void homography_kernel(const FmProbDev *__rest
     best.cnt = -1; best.sum = 0.0; best.trial = 0x7fffffffffffffffll;
     int64_t trials = 0;
 
-    // one matrix scored by the whole workgroup (strided), totals in a fixed order
-    auto score_wg = [&](const double (&H)[9], int &cnt, double &sum) {
-        double v[2] = {0.0, 0.0};
-        for (int j = tid; j < n; j += kWG) {
-            const double e = transfer(H, x0[j], x1[j]);
-            if (e <= th2) { v[0] += 1.0; v[1] += e; }
-        }
-        wg_sum(v, red);
-        cnt = (int)v[0];
-        sum = v[1];
-    };
     // the normal equations of the chart over the correspondences `use` selects
     auto accumulate = [&](const double (&H)[9], int fix, double (&s)[kNS], auto use) {
 #pragma unroll
@@ -217,8 +143,8 @@ __global__ __launch_bounds__(kWG) void homography_kernel(const FmProbDev *__rest
             if (!use(j, a, b)) continue;
             double r[2], Jx[kNP], Jy[kNP];
             residual(H, fix, a, b, r, Jx, Jy);
-            acc_normal(s, Jx, r[0]);
-            acc_normal(s, Jy, r[1]);
+            normal_acc(s, Jx, r[0]);
+            normal_acc(s, Jy, r[1]);
         }
         wg_sum(s, red);
     };
@@ -242,25 +168,11 @@ __global__ __launch_bounds__(kWG) void homography_kernel(const FmProbDev *__rest
             have = four_point(a, b, mH);
         }
         if (have) {
-            int cnt = 0;
-            double sum = 0.0;
-            for (int j = 0; j < n; ++j) {                   // j is wave-uniform: one load per wave and point
-                const double e = transfer(mH, x0[j], x1[j]);
-                const bool in = e <= th2;
-                cnt += in ? 1 : 0;
-                sum += in ? e : 0.0;
-            }
-            mine.cnt = cnt;
-            mine.sum = sum;
+            score_lane(transfer, mH, x0, x1, n, th2, mine.cnt, mine.sum);
         }
         const Support win = wg_best(mine, sred);
         if (win.cnt >= 0 && better(win, best)) {
-            if (win.trial == trial)
-#pragma unroll
-                for (int i = 0; i < 9; ++i) shH[i] = mH[i];
-            __syncthreads();
-#pragma unroll
-            for (int i = 0; i < 9; ++i) bH[i] = shH[i];
+            publish_winner(win.trial == trial, mH, shH, bH);
             best = win;
             // ---- 3. local optimisation over the best matrix's inliers
             for (int lo = 0; lo < kLoSteps; ++lo) {
@@ -273,13 +185,13 @@ __global__ __launch_bounds__(kWG) void homography_kernel(const FmProbDev *__rest
                     double s[kNS];
                     accumulate(Hn, fix, s, [&](int, double2 a, double2 b) { return transfer(bH, a, b) <= th2; });
                     double d[kNP];
-                    good = solve8(s, 0.0, d);
+                    good = chol_solve<kNP>(s, 0.0, d);
                     if (good) apply_update(Hn, fix, d);
                 }
                 if (!good) break;
                 int cnt;
                 double sum;
-                score_wg(Hn, cnt, sum);
+                score_wg(transfer, Hn, x0, x1, n, th2, red, cnt, sum);
                 if (!(cnt > best.cnt || (cnt == best.cnt && sum < best.sum))) break;
                 best.cnt = cnt;
                 best.sum = sum;
@@ -289,19 +201,8 @@ __global__ __launch_bounds__(kWG) void homography_kernel(const FmProbDev *__rest
         }
         // ---- 4. stopping (COLMAP ComputeNumTrials on the best inlier ratio, sample size 4, multiplier 3)
         trials = min((round + 1) * kWG, conf.max_trials);
-        if (trials >= conf.max_trials) break;
-        if (trials >= conf.min_trials && best.cnt > 0) {
-            const double ratio = (double)best.cnt / n;
-            const double r2 = ratio * ratio;
-            const double nom = 1.0 - conf.confidence;
-            const double den = 1.0 - r2 * r2;
-            double need;
-            if (nom <= 0) need = 1e300;
-            else if (den <= 0) need = 1.0;
-            else if (den == 1.0 || fabs(log(den)) < 1e-16) need = 1e300;
-            else need = ceil(log(nom) / log(den) * 3.0);
-            if ((double)trials >= need) break;
-        }
+        // (the power is spelt out, not pow(): its last bit reaches num_trials)
+        if (ransac_enough(trials, conf, n, best.cnt, [](double r) { const double r2 = r * r; return r2 * r2; })) break;
         __syncthreads();                                      // shH and the reductions' LDS are reused by the next round
     }
     out.num_trials = (int)trials;
@@ -324,7 +225,7 @@ __global__ __launch_bounds__(kWG) void homography_kernel(const FmProbDev *__rest
         double lambda = 1e-4;
         for (int it = 0; it < kRefIters; ++it) {
             double d[kNP];
-            if (!solve8(s, lambda, d)) break;
+            if (!chol_solve<kNP>(s, lambda, d)) break;
             double Hc[9];
 #pragma unroll
             for (int i = 0; i < 9; ++i) Hc[i] = H[i];
@@ -362,22 +263,7 @@ __global__ __launch_bounds__(kWG) void homography_kernel(const FmProbDev *__rest
             P[3 + q] = G[3 + q] / s1 + cen[3] * G[6 + q];
             P[6 + q] = G[6 + q];
         }
-        double nn = 0;
-#pragma unroll
-        for (int i = 0; i < 9; ++i) nn += P[i] * P[i];
-        double inv = 1.0 / sqrt(nn);
-        double lead = P[0];                                  // the first entry of largest magnitude
-#pragma unroll
-        for (int i = 1; i < 9; ++i)
-            if (fabs(P[i]) > fabs(lead)) lead = P[i];
-        if (lead < 0) inv = -inv;
-        bool fin = finite_d(inv);
-#pragma unroll
-        for (int i = 0; i < 9; ++i) { out.F[i] = P[i] * inv; fin = fin && finite_d(out.F[i]); }
-        out.success = (fin && best.cnt >= conf.min_num_inliers) ? 1 : 0;
-        if (!fin)
-#pragma unroll
-            for (int i = 0; i < 9; ++i) out.F[i] = 0.0;
+        finish_matrix(P, best.cnt, conf, out);
         res[pi] = out;
     }
 }

@@ -16,10 +16,14 @@
 //      every round, clamped to [min_num_trials, max_num_trials]; the round structure makes the stopping point deterministic.
 //   5. refinement (pycolmap's RefineAbsolutePose with the intrinsics fixed): Levenberg-Marquardt on sum rho(|pi(R X + t) - x|^2)
 //      in pixels through the camera model over the RANSAC inliers, rho = Cauchy with a 1 px scale, fp64.
+// Shared with the two-view RANSAC kernels (ransac_common.h, ransac_math.h): the sampler (sample_k<3>), reductions,
+// Cholesky solve and stopping rule.  Here: P3P, the fp32 support and scoring, the weighted two-row normal equations, the LO loop and
+// the Levenberg-Marquardt loop on the robust cost.
 // Every reduction runs in a fixed order (wave butterflies, then the waves in index order) and nothing depends on another
 // workgroup, so results are bit-identical whatever the batch, its order and the scheduling.  All loops are bounded.
 #include "sfd2_internal.h"
 #include "pose_camera.h"              // SFD2_PD, distort, img_to_norm: the camera model, shared with assemble_kernels.hip and tri_kernels.hip
+#include "ransac_common.h"            // wg_sum, wg_best, sample_k, chol_solve, ransac_enough: shared with the two-view kernels
 
 namespace {
 
@@ -29,8 +33,8 @@ constexpr int kLoSteps = 8;          // local optimisation: re-estimations per i
 constexpr int kLoGN = 3;             // Gauss-Newton iterations per re-estimation
 constexpr int kRefIters = 100;       // refinement iterations (pycolmap's max_num_iterations)
 constexpr int kHypD = 12;            // doubles per stored hypothesis (R row-major, t)
-
-SFD2_PD bool finite_d(double v) { return __builtin_isfinite(v); }
+constexpr int kNP = 6;               // so(3), translation
+constexpr int kNS = 28;              // normal equations: 21 (upper triangle) + 6 (gradient) + 1 (robust cost, the refinement's only)
 
 // ---------------------------------------------------------------------------------------------------------------- camera model
 // (distort: pose_camera.h)
@@ -61,7 +65,7 @@ SFD2_PD void orthonormalise(double R[9])
 }
 
 // R <- Exp(w) R, t <- Exp(w) t + d  (left perturbation: x_cam' = Exp(w) x_cam + d)
-SFD2_PD void apply_update(double R[9], double t[3], const double d[6])
+SFD2_PD void apply_update(double R[9], double t[3], const double (&d)[kNP])
 {
     const double th2 = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
     const double th = sqrt(th2);
@@ -86,7 +90,8 @@ SFD2_PD void apply_update(double R[9], double t[3], const double d[6])
     for (int i = 0; i < 3; ++i) t[i] = tn[i];
 }
 
-// Normal equations of 6 unknowns: H packed upper triangle (21), g (6), plus extra values.  Accumulation helper.
+// One point's two residual rows under the weight w into the normal equations (ransac_math.h's layout).  Not normal_acc twice:
+// w (j0a j0b + j1a j1b) rounds differently from two separate accumulations, and the results are pinned.
 template <int N>
 SFD2_PD void acc_normal(double (&s)[N], const double j0[6], const double j1[6], double r0, double r1, double w)
 {
@@ -99,143 +104,26 @@ SFD2_PD void acc_normal(double (&s)[N], const double j0[6], const double j1[6], 
     for (int a = 0; a < 6; ++a) s[21 + a] += w * (j0[a] * r0 + j1[a] * r1);
 }
 
-// Solves (H + lambda diag(H)) d = -g by Cholesky; false when not positive definite or not finite.
-template <int N>
-SFD2_PD bool solve6(const double (&s)[N], double lambda, double d[6])
-{
-    double A[36];
-    int k = 0;
-#pragma unroll
-    for (int a = 0; a < 6; ++a)
-#pragma unroll
-        for (int b = a; b < 6; ++b, ++k) { A[a * 6 + b] = s[k]; A[b * 6 + a] = s[k]; }
-    double mx = 0;
-#pragma unroll
-    for (int a = 0; a < 6; ++a) mx = fmax(mx, A[a * 7]);
-    if (!(mx > 0) || !finite_d(mx)) return false;
-#pragma unroll
-    for (int a = 0; a < 6; ++a) A[a * 7] += lambda * A[a * 7] + 1e-15 * mx;
-    // Cholesky A = L L^T in place (lower)
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        double dj = A[j * 7];
-#pragma unroll
-        for (int p = 0; p < j; ++p) dj -= A[j * 6 + p] * A[j * 6 + p];
-        if (!(dj > 0)) return false;
-        const double l = sqrt(dj);
-        A[j * 7] = l;
-#pragma unroll
-        for (int i = j + 1; i < 6; ++i) {
-            double v = A[i * 6 + j];
-#pragma unroll
-            for (int p = 0; p < j; ++p) v -= A[i * 6 + p] * A[j * 6 + p];
-            A[i * 6 + j] = v / l;
-        }
-    }
-    double y[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        double v = -s[21 + i];
-#pragma unroll
-        for (int p = 0; p < i; ++p) v -= A[i * 6 + p] * y[p];
-        y[i] = v / A[i * 7];
-    }
-#pragma unroll
-    for (int i = 5; i >= 0; --i) {
-        double v = y[i];
-#pragma unroll
-        for (int p = i + 1; p < 6; ++p) v -= A[p * 6 + i] * d[p];
-        d[i] = v / A[i * 7];
-    }
-    bool ok = true;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) ok = ok && finite_d(d[i]);
-    return ok;
-}
-
-// ---------------------------------------------------------------------------------------------------------------- reductions
-// Sum over the workgroup in a fixed order: xor butterflies inside each wave, then the wave totals in wave order.  Every thread
-// receives the same totals.  red: kWaves * N doubles of LDS.
-template <int N>
-__device__ __forceinline__ void wg_sum(double (&v)[N], double *red)
-{
-#pragma unroll
-    for (int i = 0; i < N; ++i)
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) v[i] += __shfl_xor(v[i], m, 64);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0)
-#pragma unroll
-        for (int i = 0; i < N; ++i) red[w * N + i] = v[i];
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        double s = red[i];
-#pragma unroll
-        for (int q = 1; q < kWaves; ++q) s += red[q * N + i];
-        v[i] = s;
-    }
-}
-
-struct Support {
+// ---------------------------------------------------------------------------------------------------------------- support
+// fp32 by design: the sum is the scoring loop's own fp32 accumulator
+struct PoseSupport {
     int cnt;        // -1: no hypothesis
     float sum;
     long long key;  // 4 * trial + slot
 };
-__device__ __forceinline__ bool better(const Support &a, const Support &b)
+__device__ __forceinline__ bool better(const PoseSupport &a, const PoseSupport &b)
 {
     if (a.cnt != b.cnt) return a.cnt > b.cnt;
     if (a.sum != b.sum) return a.sum < b.sum;
     return a.key < b.key;
 }
-__device__ __forceinline__ Support shfl_support(const Support &s, int m)
+__device__ __forceinline__ PoseSupport shfl_support(const PoseSupport &s, int m)
 {
-    Support o;
+    PoseSupport o;
     o.cnt = __shfl_xor(s.cnt, m, 64);
     o.sum = __shfl_xor(s.sum, m, 64);
     o.key = __shfl_xor(s.key, m, 64);
     return o;
-}
-// the best support of the workgroup (a total order, so the result does not depend on the reduction's shape)
-__device__ __forceinline__ Support wg_best(Support s, Support *red)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const Support o = shfl_support(s, m);
-        if (better(o, s)) s = o;
-    }
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) red[w] = s;
-    __syncthreads();
-    Support b = red[0];
-#pragma unroll
-    for (int q = 1; q < kWaves; ++q)
-        if (better(red[q], b)) b = red[q];
-    return b;
-}
-
-// ---------------------------------------------------------------------------------------------------------------- sampling
-SFD2_PD uint64_t mix64(uint64_t z)
-{
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-// three distinct indices in [0, n), n >= 3, from (seed, trial) only
-SFD2_PD void sample3(uint64_t seed, int64_t trial, int n, int &i0, int &i1, int &i2)
-{
-    const uint64_t h0 = mix64(seed ^ mix64((uint64_t)trial));
-    const uint64_t h1 = mix64(h0), h2 = mix64(h1);
-    i0 = (int)(h0 % (uint64_t)n);
-    i1 = (int)(h1 % (uint64_t)(n - 1));
-    if (i1 >= i0) ++i1;
-    i2 = (int)(h2 % (uint64_t)(n - 2));
-    const int lo = min(i0, i1), hi = max(i0, i1);
-    if (i2 >= lo) ++i2;
-    if (i2 >= hi) ++i2;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- P3P
@@ -449,7 +337,7 @@ __device__ __forceinline__ bool eval_f32(const PoseF &p, float4 X, float2 x, flo
 }
 
 // one pose scored over every point by the whole workgroup (strided), totals in a fixed order
-__device__ __forceinline__ Support score_wg(const PoseF &p, const float4 *Xf, const float2 *xf, int n, float th2, double *red, long long key)
+__device__ __forceinline__ PoseSupport score_wg(const PoseF &p, const float4 *Xf, const float2 *xf, int n, float th2, double *red, long long key)
 {
     int cnt = 0;
     float sum = 0.f;
@@ -459,7 +347,7 @@ __device__ __forceinline__ Support score_wg(const PoseF &p, const float4 *Xf, co
     }
     double v[2] = {(double)cnt, (double)sum};
     wg_sum(v, red);
-    Support s;
+    PoseSupport s;
     s.cnt = (int)v[0];
     s.sum = (float)v[1];
     s.key = key;
@@ -472,8 +360,8 @@ __global__ __launch_bounds__(kWG) void pose_kernel(const PoseProbDev *__restrict
                                                    double2 *__restrict__ xng, double *__restrict__ hypg, const unsigned char *__restrict__ mask_in,
                                                    unsigned char *__restrict__ mask_out, PoseResDev *__restrict__ res)
 {
-    __shared__ double red[kWaves * 28];
-    __shared__ Support sred[kWaves];
+    __shared__ double red[kWaves * kNS];
+    __shared__ PoseSupport sred[kWaves];
     const int pi = blockIdx.x, tid = threadIdx.x;
     const PoseProbDev &pb = probs[pi];
     const int64_t off = pb.off;
@@ -513,7 +401,7 @@ __global__ __launch_bounds__(kWG) void pose_kernel(const PoseProbDev *__restrict
     __syncthreads();
     const float th2 = (float)pb.thresh2;
     double bR[9], bt[3];
-    Support best;
+    PoseSupport best;
     best.cnt = -1; best.sum = 0.f; best.key = 0x7fffffffffffffffll;
     int64_t trials = 0;
     if (conf.refine_only) {
@@ -530,11 +418,11 @@ __global__ __launch_bounds__(kWG) void pose_kernel(const PoseProbDev *__restrict
         double *hyp = hypg + (size_t)pi * kWG * 4 * kHypD;
         for (int64_t round = 0;; ++round) {
             const int64_t trial = round * kWG + tid;
-            Support mine;
+            PoseSupport mine;
             mine.cnt = -1; mine.sum = 0.f; mine.key = 0x7fffffffffffffffll;
             if (trial < conf.max_trials) {
                 int id[3];
-                sample3(conf.seed, trial, n, id[0], id[1], id[2]);
+                sample_k<3>(conf.seed, trial, n, id);
                 double y[3][3], X[3][3];
 #pragma unroll
                 for (int s = 0; s < 3; ++s) {
@@ -576,14 +464,14 @@ __global__ __launch_bounds__(kWG) void pose_kernel(const PoseProbDev *__restrict
                 }
 #pragma unroll
                 for (int s = 0; s < 4; ++s) {
-                    Support h;
+                    PoseSupport h;
                     h.cnt = ok[s] ? cnt[s] : -1;
                     h.sum = sum[s];
                     h.key = trial * 4 + s;
                     if (ok[s] && better(h, mine)) mine = h;
                 }
             }
-            const Support win = wg_best(mine, sred);       // (its barriers also publish the stored hypotheses)
+            const PoseSupport win = wg_best(mine, sred);       // (its barriers also publish the stored hypotheses)
             if (win.cnt >= 0 && better(win, best)) {
                 const int wt = (int)((win.key >> 2) - round * kWG), ws = (int)(win.key & 3);
                 const double *h = hyp + ((size_t)wt * 4 + ws) * kHypD;
@@ -628,11 +516,11 @@ __global__ __launch_bounds__(kWG) void pose_kernel(const PoseProbDev *__restrict
                         }
                         wg_sum(s, red);
                         double d[6];
-                        good = solve6(s, 0.0, d);
+                        good = chol_solve<kNP>(s, 0.0, d);
                         if (good) apply_update(R, t, d);
                     }
                     if (!good) break;
-                    const Support ls = score_wg(to_f32(R, t), Xf, xf, n, th2, red, best.key);
+                    const PoseSupport ls = score_wg(to_f32(R, t), Xf, xf, n, th2, red, best.key);
                     if (!(ls.cnt > best.cnt || (ls.cnt == best.cnt && ls.sum < best.sum))) break;
                     best.cnt = ls.cnt;
                     best.sum = ls.sum;
@@ -644,18 +532,8 @@ __global__ __launch_bounds__(kWG) void pose_kernel(const PoseProbDev *__restrict
             }
             // ---- stopping (COLMAP ComputeNumTrials on the best inlier ratio, multiplier 3)
             trials = min((round + 1) * kWG, conf.max_trials);
-            if (trials >= conf.max_trials) break;
-            if (trials >= conf.min_trials && best.cnt > 0) {
-                const double ratio = (double)best.cnt / n;
-                const double nom = 1.0 - conf.confidence;
-                const double den = 1.0 - ratio * ratio * ratio;
-                double need;
-                if (nom <= 0) need = 1e300;
-                else if (den <= 0) need = 1.0;
-                else if (den == 1.0 || fabs(log(den)) < 1e-16) need = 1e300;
-                else need = ceil(log(nom) / log(den) * 3.0);
-                if ((double)trials >= need) break;
-            }
+            // (the power is spelt out, not pow(): its last bit reaches num_trials)
+            if (ransac_enough(trials, conf, n, best.cnt, [](double r) { return r * r * r; })) break;
             __syncthreads();                                  // the next round overwrites the stored hypotheses
         }
         out.num_trials = (int)trials;
@@ -716,7 +594,7 @@ __global__ __launch_bounds__(kWG) void pose_kernel(const PoseProbDev *__restrict
     double lambda = 1e-4;
     for (int it = 0; it < kRefIters; ++it) {
         double d[6];
-        if (!solve6(s, lambda, d)) break;
+        if (!chol_solve<kNP>(s, lambda, d)) break;
         double Rn[9], tn[3];
 #pragma unroll
         for (int i = 0; i < 9; ++i) Rn[i] = R[i];

@@ -4,7 +4,7 @@
 //
 // One workgroup of SFD2_TV_WG threads owns one pair from start to end; a batch of pairs of any sizes is one launch.
 //   1. preparation: both point sets go to normalised coordinates through their own camera model (img_to_norm, pose_camera.h).
-//   2. RANSAC rounds of SFD2_TV_WG trials, one per lane: the sample of trial i is drawn by sample5 from (seed, i) only.  The
+//   2. RANSAC rounds of SFD2_TV_WG trials, one per lane: the sample of trial i is drawn by sample_k<5> from (seed, i) only.  The
 //      five-point solver (five_point.h: action matrix, QR iteration) keeps its matrices in LDS: kSlots workspaces, four lanes of each wave solve at a time.  Its
 //      <= 10 matrices go to a per-pair scratch; then every lane takes its trial's matrices one at a time, polishes each by kPolish
 //      Gauss-Newton steps on the sample's five Sampson residuals (so that the matrix no longer depends on the solver's route) and
@@ -16,6 +16,9 @@
 //   5. final: Levenberg-Marquardt on the same 5 parameters and cost over the RANSAC inliers, then among (R, t), (R, -t), (R', t),
 //      (R', -t), R' = (2 t t^T - I) R, the first with the most inliers in front of both cameras (midpoint triangulation); the
 //      triangulation angle of every such inlier.
+// Shared with the other RANSAC kernels (ransac_common.h, ransac_math.h): the sampler, reductions, scoring loops, winner
+// broadcast, Cholesky solve and stopping rule.  Here: the solver call and polish, the Sampson error, E <-> (R, t), the frame with its
+// residual and update, the LO loop, the Levenberg-Marquardt loop and the cheirality choice.
 // Every reduction runs in a fixed order (wave butterflies, then the waves in index order) and nothing depends on another workgroup,
 // so a pair's result depends on the pair and the seed only.  All loops are bounded.  No private segment, no spills.
 #include "sfd2_internal.h"
@@ -33,9 +36,9 @@ constexpr int kPolish = 3;
 constexpr int kLoSteps = 8;
 constexpr int kLoGN = 3;
 constexpr int kRefIters = 50;
+constexpr int kNP = 5;               // so(3) and the tangent plane of the unit t
 constexpr int kNS = 21;              // normal equations: 15 (upper triangle) + 5 (gradient) + 1 (cost)
 
-SFD2_PD bool finite_d(double v) { return __builtin_isfinite(v); }
 SFD2_PD void cross3(const double a[3], const double b[3], double o[3])
 {
     o[0] = a[1] * b[2] - a[2] * b[1];
@@ -157,68 +160,6 @@ SFD2_PD void residual(const double E[9], const Frame &f, double2 a, double2 b, d
         J[k] = s;
     }
 }
-SFD2_PD void acc_normal(double (&s)[kNS], const double (&J)[5], double r)
-{
-    int k = 0;
-#pragma unroll
-    for (int a = 0; a < 5; ++a)
-#pragma unroll
-        for (int b = a; b < 5; ++b, ++k) s[k] += J[a] * J[b];
-#pragma unroll
-    for (int a = 0; a < 5; ++a) s[15 + a] += J[a] * r;
-    s[20] += r * r;
-}
-// Solves (H + lambda diag(H) + 1e-15 max diag(H) I) d = -g by Cholesky; false when not positive definite or not finite.
-SFD2_PD bool solve5(const double (&s)[kNS], double lambda, double (&d)[5])
-{
-    double A[25];
-    int k = 0;
-#pragma unroll
-    for (int a = 0; a < 5; ++a)
-#pragma unroll
-        for (int b = a; b < 5; ++b, ++k) { A[a * 5 + b] = s[k]; A[b * 5 + a] = s[k]; }
-    double mx = 0;
-#pragma unroll
-    for (int a = 0; a < 5; ++a) mx = fmax(mx, A[a * 6]);
-    if (!(mx > 0) || !finite_d(mx)) return false;
-#pragma unroll
-    for (int a = 0; a < 5; ++a) A[a * 6] += lambda * A[a * 6] + 1e-15 * mx;
-#pragma unroll
-    for (int j = 0; j < 5; ++j) {
-        double dj = A[j * 6];
-#pragma unroll
-        for (int p = 0; p < j; ++p) dj -= A[j * 5 + p] * A[j * 5 + p];
-        if (!(dj > 0)) return false;
-        const double l = sqrt(dj);
-        A[j * 6] = l;
-#pragma unroll
-        for (int i = j + 1; i < 5; ++i) {
-            double v = A[i * 5 + j];
-#pragma unroll
-            for (int p = 0; p < j; ++p) v -= A[i * 5 + p] * A[j * 5 + p];
-            A[i * 5 + j] = v / l;
-        }
-    }
-    double y[5];
-#pragma unroll
-    for (int i = 0; i < 5; ++i) {
-        double v = -s[15 + i];
-#pragma unroll
-        for (int p = 0; p < i; ++p) v -= A[i * 5 + p] * y[p];
-        y[i] = v / A[i * 6];
-    }
-#pragma unroll
-    for (int i = 4; i >= 0; --i) {
-        double v = y[i];
-#pragma unroll
-        for (int p = i + 1; p < 5; ++p) v -= A[p * 5 + i] * d[p];
-        d[i] = v / A[i * 6];
-    }
-    bool ok = true;
-#pragma unroll
-    for (int i = 0; i < 5; ++i) ok = ok && finite_d(d[i]);
-    return ok;
-}
 // R <- Exp(d[0..2]) R, t <- normalise(t + d[3] b1 + d[4] b2)
 SFD2_PD void apply_update(double R[9], double t[3], const double (&d)[5])
 {
@@ -327,17 +268,6 @@ __global__ __launch_bounds__(kWG) void two_view_kernel(const TvProbDev *__restri
     const int lane = tid & 63;
     double *wsl = ws + (tid >> 6) * kSlotsPerWave + (lane & (kSlotsPerWave - 1));
 
-    // one matrix scored by the whole workgroup (strided), totals in a fixed order
-    auto score_wg = [&](const double (&E)[9], int &cnt, double &sum) {
-        double v[2] = {0.0, 0.0};
-        for (int j = tid; j < n; j += kWG) {
-            const double e = sampson(E, x0[j], x1[j]);
-            if (e <= th2) { v[0] += 1.0; v[1] += e; }
-        }
-        wg_sum(v, red);
-        cnt = (int)v[0];
-        sum = v[1];
-    };
     // the normal equations of (R, t) over the correspondences `use` selects
     auto accumulate = [&](const double (&R)[9], const double (&t)[3], double (&s)[kNS], auto use) {
         Frame f;
@@ -351,7 +281,7 @@ __global__ __launch_bounds__(kWG) void two_view_kernel(const TvProbDev *__restri
             if (!use(j, a, b)) continue;
             double r, J[5];
             residual(E, f, a, b, r, J);
-            acc_normal(s, J, r);
+            normal_acc(s, J, r);
         }
         wg_sum(s, red);
     };
@@ -360,7 +290,7 @@ __global__ __launch_bounds__(kWG) void two_view_kernel(const TvProbDev *__restri
         const int64_t trial = round * kWG + tid;
         const bool live = trial < conf.max_trials;
         int id[5] = {0, 1, 2, 3, 4};
-        if (live) sample5(conf.seed, trial, n, id);
+        if (live) sample_k<5>(conf.seed, trial, n, id);
         // ---- 2a. the five-point solver, kSlotsPerWave lanes of every wave at a time (their workspaces are the wave's own)
         int ncand = 0;
         for (int sub = 0; sub < 64 / kSlotsPerWave; ++sub) {
@@ -410,10 +340,10 @@ __global__ __launch_bounds__(kWG) void two_view_kernel(const TvProbDev *__restri
                     for (int k = 0; k < 5; ++k) {
                         double r, J[5];
                         residual(Ec, f, sa[k], sb[k], r, J);
-                        acc_normal(s, J, r);
+                        normal_acc(s, J, r);
                     }
                     double d[5];
-                    good = solve5(s, 0.0, d);
+                    good = chol_solve<kNP>(s, 0.0, d);
                     if (good) apply_update(R, t, d);
                 }
                 if (good) {
@@ -428,14 +358,9 @@ __global__ __launch_bounds__(kWG) void two_view_kernel(const TvProbDev *__restri
                     }
                 }
             }
-            int cnt = 0;
-            double sum = 0.0;
-            for (int j = 0; j < n; ++j) {                   // j is wave-uniform: one load per wave and point
-                const double e = sampson(E, x0[j], x1[j]);
-                const bool in = e <= th2;
-                cnt += in ? 1 : 0;
-                sum += in ? e : 0.0;
-            }
+            int cnt;
+            double sum;
+            score_lane(sampson, E, x0, x1, n, th2, cnt, sum);
             if (cnt > mine.cnt || (cnt == mine.cnt && sum < mine.sum)) {
                 mine.cnt = cnt;
                 mine.sum = sum;
@@ -445,12 +370,7 @@ __global__ __launch_bounds__(kWG) void two_view_kernel(const TvProbDev *__restri
         }
         const Support win = wg_best(mine, sred);
         if (win.cnt >= 0 && better(win, best)) {
-            if (win.trial == trial)
-#pragma unroll
-                for (int i = 0; i < 9; ++i) shE[i] = mE[i];
-            __syncthreads();
-#pragma unroll
-            for (int i = 0; i < 9; ++i) bE[i] = shE[i];
+            publish_winner(win.trial == trial, mE, shE, bE);
             best = win;
             // ---- 3. local optimisation over the best matrix's inliers
             double R[9], t[3];
@@ -460,7 +380,7 @@ __global__ __launch_bounds__(kWG) void two_view_kernel(const TvProbDev *__restri
                     double s[kNS];
                     accumulate(R, t, s, [&](int, double2 a, double2 b) { return sampson(bE, a, b) <= th2; });
                     double d[5];
-                    good = solve5(s, 0.0, d);
+                    good = chol_solve<kNP>(s, 0.0, d);
                     if (good) apply_update(R, t, d);
                 }
                 if (!good) break;
@@ -468,7 +388,7 @@ __global__ __launch_bounds__(kWG) void two_view_kernel(const TvProbDev *__restri
                 essential(R, t, En);
                 int cnt;
                 double sum;
-                score_wg(En, cnt, sum);
+                score_wg(sampson, En, x0, x1, n, th2, red, cnt, sum);
                 if (!(cnt > best.cnt || (cnt == best.cnt && sum < best.sum))) break;
                 best.cnt = cnt;
                 best.sum = sum;
@@ -478,18 +398,8 @@ __global__ __launch_bounds__(kWG) void two_view_kernel(const TvProbDev *__restri
         }
         // ---- 4. stopping (COLMAP ComputeNumTrials on the best inlier ratio, sample size 5, multiplier 3)
         trials = min((round + 1) * kWG, conf.max_trials);
-        if (trials >= conf.max_trials) break;
-        if (trials >= conf.min_trials && best.cnt > 0) {
-            const double ratio = (double)best.cnt / n;
-            const double nom = 1.0 - conf.confidence;
-            const double den = 1.0 - ratio * ratio * ratio * ratio * ratio;
-            double need;
-            if (nom <= 0) need = 1e300;
-            else if (den <= 0) need = 1.0;
-            else if (den == 1.0 || fabs(log(den)) < 1e-16) need = 1e300;
-            else need = ceil(log(nom) / log(den) * 3.0);
-            if ((double)trials >= need) break;
-        }
+        // (the power is spelt out, not pow(): its last bit reaches num_trials)
+        if (ransac_enough(trials, conf, n, best.cnt, [](double r) { return r * r * r * r * r; })) break;
         __syncthreads();                                      // shE and the reductions' LDS are reused by the next round
     }
     out.num_trials = (int)trials;
@@ -512,7 +422,7 @@ __global__ __launch_bounds__(kWG) void two_view_kernel(const TvProbDev *__restri
         double lambda = 1e-4;
         for (int it = 0; it < kRefIters; ++it) {
             double d[5];
-            if (!solve5(s, lambda, d)) break;
+            if (!chol_solve<kNP>(s, lambda, d)) break;
             double Rn[9], tn[3];
 #pragma unroll
             for (int i = 0; i < 9; ++i) Rn[i] = R[i];

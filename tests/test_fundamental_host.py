@@ -71,10 +71,15 @@ def test_sources_are_in_the_build_list():
     assert "fundamental_kernels.hip" in build.SOURCES and "api_fundamental.hip" in build.SOURCES
     for f in ("fundamental_kernels.hip", "api_fundamental.hip", "seven_point.h", "ransac_common.h"):
         assert os.path.exists(os.path.join(build.CSRC, f))
-    # both RANSAC kernels take the shared helpers from the one header
-    for f in ("fundamental_kernels.hip", "two_view_kernels.hip"):
-        text = open(os.path.join(build.CSRC, f)).read()
-        assert '#include "ransac_common.h"' in text and "uint64_t mix64" not in text
+    assert os.path.exists(os.path.join(build.CSRC, "ransac_math.h"))
+    text = open(os.path.join(build.CSRC, "fundamental_kernels.hip")).read()
+    assert "uint64_t mix64" not in text
+    # the shared layer (ransac_common.h, ransac_math.h) is the one definition of what the four RANSAC kernels share
+    assert '#include "ransac_common.h"' in text
+    for pat in (r"\bmix64\s*\(\s*uint64_t", r"\bvoid\s+wg_sum\s*\(", r"\bwg_best\s*\([^)]*\*", r"\bbool\s+finite_d\s*\(", r"\bsolve\d\b", r"\bsample[35]\b"):
+        assert not re.search(pat, text), pat
+    for helper in ("chol_solve<kNP>(", "normal_acc(", "publish_winner(", "ransac_enough(", "finish_matrix(", "sample_k<7>("):
+        assert helper in text, helper
 
 
 def test_fundamental_kernels_compile_without_private_segment_or_spills(tmp_path):

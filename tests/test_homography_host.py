@@ -89,6 +89,12 @@ def test_sources_are_in_the_build_list():
     for helper in ("wg_sum(", "wg_best(", "better(", "sample_k<4>("):
         assert helper in text, helper
     assert "atomic" not in text
+    # the shared layer (ransac_common.h, ransac_math.h) is the one definition of what the four RANSAC kernels share
+    assert '#include "ransac_common.h"' in text
+    for pat in (r"\bmix64\s*\(\s*uint64_t", r"\bvoid\s+wg_sum\s*\(", r"\bwg_best\s*\([^)]*\*", r"\bbool\s+finite_d\s*\(", r"\bsolve\d\b", r"\bsample[35]\b"):
+        assert not re.search(pat, text), pat
+    for helper in ("chol_solve<kNP>(", "normal_acc(", "score_lane(", "score_wg(", "publish_winner(", "ransac_enough(", "finish_matrix("):
+        assert helper in text, helper
     # one packing and scratch layer for the camera-less estimators: the new entry point calls api_fundamental.hip's
     api = open(os.path.join(build.CSRC, "api_homography.hip")).read()
     assert "pairs_batch(" in api and "hipMemcpy" not in api and "Carve" not in api

@@ -195,6 +195,19 @@ def test_pose_from_clusters_outcomes(case):
     assert {"first": 60, "later": 70, "fallback": 0, "failure": -1}[case] == n
 
 
+def test_pose_kernel_takes_the_shared_ransac_layer():
+    text = open(os.path.join(build.CSRC, "pose_kernels.hip")).read()
+    # the shared layer (ransac_common.h, ransac_math.h) is the one definition of what the four RANSAC kernels share
+    assert '#include "ransac_common.h"' in text
+    for pat in (r"\bmix64\s*\(\s*uint64_t", r"\bvoid\s+wg_sum\s*\(", r"\bwg_best\s*\([^)]*\*", r"\bbool\s+finite_d\s*\(", r"\bsolve\d\b", r"\bsample[35]\b"):
+        assert not re.search(pat, text), pat
+    for helper in ("chol_solve<kNP>(", "ransac_enough(", "sample_k<3>(", "wg_best(", "wg_sum("):
+        assert helper in text, helper
+    for f in os.listdir(build.CSRC):        # the sampler has one name everywhere
+        if f.endswith((".hip", ".h")):
+            assert "sample3" not in open(os.path.join(build.CSRC, f)).read(), f
+
+
 def test_pose_kernels_compile_without_private_segment_or_spills(tmp_path):
     if not build.have_hipcc():
         pytest.skip("no hipcc")

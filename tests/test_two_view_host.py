@@ -58,8 +58,15 @@ def test_raises_without_gpu():
 
 def test_sources_are_in_the_build_list():
     assert "two_view_kernels.hip" in build.SOURCES and "api_two_view.hip" in build.SOURCES
-    for f in ("two_view_kernels.hip", "api_two_view.hip", "five_point.h"):
+    for f in ("two_view_kernels.hip", "api_two_view.hip", "five_point.h", "ransac_common.h", "ransac_math.h"):
         assert os.path.exists(os.path.join(build.CSRC, f))
+    text = open(os.path.join(build.CSRC, "two_view_kernels.hip")).read()
+    # the shared layer (ransac_common.h, ransac_math.h) is the one definition of what the four RANSAC kernels share
+    assert '#include "ransac_common.h"' in text
+    for pat in (r"\bmix64\s*\(\s*uint64_t", r"\bvoid\s+wg_sum\s*\(", r"\bwg_best\s*\([^)]*\*", r"\bbool\s+finite_d\s*\(", r"\bsolve\d\b", r"\bsample[35]\b"):
+        assert not re.search(pat, text), pat
+    for helper in ("chol_solve<kNP>(", "normal_acc(", "score_lane(", "score_wg(", "publish_winner(", "ransac_enough(", "sample_k<5>("):
+        assert helper in text, helper
 
 
 def test_two_view_kernels_compile_without_private_segment_or_spills(tmp_path):
