@@ -85,7 +85,7 @@ typedef struct {
     int64_t n_candidates; /* N0 after NMS + threshold + border of the last extract          */
 } sfd2_timings;
 
-int sfd2_version(void);   /* 100 = rounds 1-4; 105 adds sfd2_extract_record_async, sfd2_desc_pack and host outputs with SFD2_FLAG_ASYNC; 106 adds sfd2_get_margin_status; 107 adds sfd2_get_relax_status (option "c3b_plain"); 108 adds sfd2_get_option, sfd2_device_pci_bus_id, SFD2_FLAG_DESC_STORE64; 109 adds the baseline JPEG decoder (sfd2_jpeg_*); 112 adds the SfM map (sfd2_verify_matches_batch, sfd2_build_tracks, sfd2_triangulate_tracks); 113 adds the pair selection (sfd2_pairs_retrieval, sfd2_pairs_covisibility, sfd2_pairs_poses); 114 adds sfd2_covis_clusters; 115 adds sfd2_covis_frames; 116 adds the VLAD global descriptors (sfd2_vlad_assign, sfd2_vlad_aggregate, sfd2_vlad_kmeans); 117 adds sfd2_relative_pose_batch; 118 adds sfd2_bundle_adjust; 119 adds the mapper's bookkeeping (sfd2_mapper_restrict, sfd2_mapper_filter, sfd2_mapper_visible, sfd2_mapper_assemble); 120 adds sfd2_fundamental_batch; 121 adds sfd2_homography_batch; 122 adds sfd2_match_guided_batch */
+int sfd2_version(void);   /* 100 = rounds 1-4; 105 adds sfd2_extract_record_async, sfd2_desc_pack and host outputs with SFD2_FLAG_ASYNC; 106 adds sfd2_get_margin_status; 107 adds sfd2_get_relax_status (option "c3b_plain"); 108 adds sfd2_get_option, sfd2_device_pci_bus_id, SFD2_FLAG_DESC_STORE64; 109 adds the baseline JPEG decoder (sfd2_jpeg_*); 112 adds the SfM map (sfd2_verify_matches_batch, sfd2_build_tracks, sfd2_triangulate_tracks); 113 adds the pair selection (sfd2_pairs_retrieval, sfd2_pairs_covisibility, sfd2_pairs_poses); 114 adds sfd2_covis_clusters; 115 adds sfd2_covis_frames; 116 adds the VLAD global descriptors (sfd2_vlad_assign, sfd2_vlad_aggregate, sfd2_vlad_kmeans); 117 adds sfd2_relative_pose_batch; 118 adds sfd2_bundle_adjust; 119 adds the mapper's bookkeeping (sfd2_mapper_restrict, sfd2_mapper_filter, sfd2_mapper_visible, sfd2_mapper_assemble); 120 adds sfd2_fundamental_batch; 121 adds sfd2_homography_batch; 122 adds sfd2_match_guided_batch; 123 adds sfd2_bundle_adjust_cameras */
 const char *sfd2_last_error(void);
 
 int sfd2_ctx_create(int device, sfd2_ctx **out);
@@ -818,7 +818,7 @@ int sfd2_triangulate_tracks(sfd2_ctx *ctx, const sfd2_tri_view *views, int n_vie
  * SfM-map section: host arrays, the call runs on sfd2_get_stream() and synchronises before it returns, returns -1 with
  * sfd2_last_error() set on a bad argument, non-finite input or an index out of range (the message names the first offending index).
  * fp64, fixed-order sums, no floating-point atomics: the result depends on the inputs (and the flags) only, two calls give the same
- * bytes.  Intrinsics are constant. */
+ * bytes.  Intrinsics are constant in sfd2_bundle_adjust; sfd2_bundle_adjust_cameras refines them. */
 #define SFD2_BA_LOSS_TRIVIAL 0
 #define SFD2_BA_LOSS_CAUCHY 1          /* rho(s) = c^2 log(1 + s / c^2), c = loss_scale, as an IRLS weight rho'(s)               */
 #define SFD2_BA_ST_GRADIENT 0          /* result status: max |g| <= gradient_tolerance                                          */
@@ -857,6 +857,24 @@ typedef struct {
 int sfd2_bundle_adjust(sfd2_ctx *ctx, sfd2_tri_view *views, int n_views, const uint8_t *view_constant, double *xyz, int n_points,
                        const uint8_t *point_constant, const int64_t *point_offsets, const int32_t *obs_view, const double *obs_xy,
                        const sfd2_ba_conf *conf, sfd2_ba_result *result, double *obs_error, int flags);
+/* The same adjustment with camera intrinsics among the unknowns.  cameras[n_cameras]: IN/OUT; view_camera[n_views]
+ * maps every view to one (one shared camera, one per view, or anything between).  refine selects COLMAP's three parameter groups; a
+ * group the model does not have contributes nothing, refine == 0 is a constant camera.  The views' own model / params words are not
+ * read; on return they hold their camera's final values.  A camera that is constant, or whose views have no observation, comes back
+ * bit for bit, as does every camera when no step was accepted.  A trial state with a non-finite camera parameter or a focal length
+ * <= 0 is rejected as a non-finite cost is.  Every other argument, the result and the flags: as sfd2_bundle_adjust.  -1 also on a
+ * camera index out of range, unknown refine bits, a bad model or non-finite parameters (the message names the first offending index). */
+#define SFD2_BA_REFINE_FOCAL 1         /* f, or fx and fy (SIMPLE_* models: the one f)                                          */
+#define SFD2_BA_REFINE_PRINCIPAL 2     /* cx, cy                                                                                */
+#define SFD2_BA_REFINE_EXTRA 4         /* k; k1, k2, p1, p2                                                                     */
+typedef struct {
+    int32_t model, refine;          /* SFD2_CAM_*, SFD2_BA_REFINE_* bits                                                   */
+    double params[8];               /* the model's parameters in COLMAP order, IN/OUT                                      */
+} sfd2_ba_camera;
+int sfd2_bundle_adjust_cameras(sfd2_ctx *ctx, sfd2_ba_camera *cameras, int n_cameras, const int32_t *view_camera, sfd2_tri_view *views,
+                               int n_views, const uint8_t *view_constant, double *xyz, int n_points, const uint8_t *point_constant,
+                               const int64_t *point_offsets, const int32_t *obs_view, const double *obs_xy, const sfd2_ba_conf *conf,
+                               sfd2_ba_result *result, double *obs_error, int flags);
 
 /* ------------------------------------------------------------------------------------------------ incremental mapper
  * The bookkeeping between relative pose, absolute pose, triangulation and bundle adjustment in a round of sfd2_amd.reconstruction

@@ -204,6 +204,12 @@ class BaResult(ctypes.Structure):
                 ("initial_cost", ctypes.c_double), ("final_cost", ctypes.c_double), ("gradient_max", ctypes.c_double), ("lambda_", ctypes.c_double)]
 
 
+class BaCamera(ctypes.Structure):
+    """sfd2_ba_camera (include/sfd2_hip.h)."""
+    _fields_ = [("model", ctypes.c_int32), ("refine", ctypes.c_int32), ("params", ctypes.c_double * 8)]
+
+
+BA_REFINE_FOCAL, BA_REFINE_PRINCIPAL, BA_REFINE_EXTRA = 1, 2, 4
 BA_LOSS_TRIVIAL, BA_LOSS_CAUCHY = 0, 1                                              # SFD2_BA_*
 BA_ST_GRADIENT, BA_ST_FUNCTION, BA_ST_MAX_ITERATIONS, BA_ST_LAMBDA, BA_ST_NONFINITE = 0, 1, 2, 3, 4
 BA_FLAG_POINT_LANE, BA_FLAG_POINT_WAVE = 1, 2
@@ -253,7 +259,7 @@ EXPORTS = [
     "sfd2_assemble_2d3d", "sfd2_verify_matches_batch", "sfd2_build_tracks", "sfd2_triangulate_tracks",
     "sfd2_pairs_retrieval", "sfd2_pairs_covisibility", "sfd2_pairs_poses", "sfd2_covis_clusters",
     "sfd2_covis_frames", "sfd2_vlad_assign", "sfd2_vlad_aggregate", "sfd2_vlad_kmeans",
-    "sfd2_relative_pose_batch", "sfd2_fundamental_batch", "sfd2_homography_batch", "sfd2_match_guided_batch", "sfd2_bundle_adjust",
+    "sfd2_relative_pose_batch", "sfd2_fundamental_batch", "sfd2_homography_batch", "sfd2_match_guided_batch", "sfd2_bundle_adjust", "sfd2_bundle_adjust_cameras",
     "sfd2_mapper_restrict", "sfd2_mapper_filter", "sfd2_mapper_visible", "sfd2_mapper_assemble",
 ]
 
@@ -358,6 +364,7 @@ def load():
     lib.sfd2_vlad_aggregate.argtypes = [vp, vp, vp, ci, vp, ci, ci, ci, vp, vp, ci]
     lib.sfd2_vlad_kmeans.argtypes = [vp, vp, i64, ci, ci, ci, vp, vp, vp, pi, ci]
     lib.sfd2_bundle_adjust.argtypes = [vp, ctypes.POINTER(TriView), ci, vp, vp, ci, vp, vp, vp, vp, ctypes.POINTER(BaConf), ctypes.POINTER(BaResult), vp, ci]
+    lib.sfd2_bundle_adjust_cameras.argtypes = [vp, ctypes.POINTER(BaCamera), ci, vp] + lib.sfd2_bundle_adjust.argtypes[1:]
     lib.sfd2_mapper_restrict.argtypes = [vp, vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, ctypes.POINTER(i64), ctypes.POINTER(i64), ci]
     lib.sfd2_mapper_filter.argtypes = [vp, ctypes.POINTER(TriView), ci, vp, ci, vp, vp, vp, cd, cd, vp, vp, vp, vp, ci]
     lib.sfd2_mapper_visible.argtypes = [vp, vp, ci, vp, vp, ci, vp, vp, ci, vp, ci]

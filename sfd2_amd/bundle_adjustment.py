@@ -1,12 +1,15 @@
 """Bundle adjustment on the device (include/sfd2_hip.h sfd2_bundle_adjust): Levenberg-Marquardt over camera
 poses and 3D points, the points eliminated, the reduced camera system solved by matrix-free preconditioned conjugate gradients.
-The joint refinement `colmap bundle_adjuster` does for a model, reduced to what is built: intrinsics stay fixed, the loss is trivial
-or Cauchy.
+The joint refinement `colmap bundle_adjuster` does for a model, reduced to what is built: the loss is trivial or Cauchy; intrinsics
+stay fixed unless one of the refine options is set (sfd2_bundle_adjust_cameras).
 
   adjust          the C call on numpy arrays.
-  bundle_adjust   on colmap_io records: returns new images, new points3D (error = mean reprojection error of the point) and the report.
+  adjust_cameras  the C call with camera intrinsics among the unknowns, on numpy arrays.
+  bundle_adjust   on colmap_io records: returns new images, new points3D (error = mean reprojection error of the point) and the report;
+                  with a refine option also the new cameras, first.
   main / command  python -m sfd2_amd.bundle_adjustment --input_path M --output_path O [--max_num_iterations N]
                   [--loss trivial|cauchy] [--loss_scale S] [--constant_images FILE]
+                  [--refine_focal_length 0|1] [--refine_principal_point 0|1] [--refine_extra_params 0|1]
 
 Without --constant_images the two registered images with the smallest ids keep their poses.  COLMAP fixes the first image's pose and
 one coordinate of the second's translation; fixing both poses completely is this project's deviation (it removes the same seven
@@ -49,10 +52,50 @@ def _conf(options):
     return conf
 
 
+def refine_mask(refine_focal_length=False, refine_principal_point=False, refine_extra_params=False):
+    """The SFD2_BA_REFINE_* bits of the three options."""
+    return ((_lib.BA_REFINE_FOCAL if refine_focal_length else 0) | (_lib.BA_REFINE_PRINCIPAL if refine_principal_point else 0) |
+            (_lib.BA_REFINE_EXTRA if refine_extra_params else 0))
+
+
 def adjust(views, n_views, view_constant, xyz, point_constant, point_offsets, obs_view, obs_xy, flags=0, device=0, **options):
     """views: triangulation.make_views()'s array (poses IN/OUT); view_constant [n_views], point_constant [n_points]: non-zero = fixed;
     xyz [n_points, 3]; point p holds the observations point_offsets[p] .. point_offsets[p + 1] of (obs_view, obs_xy in pixels as
     given).  options: DEFAULTS.  Returns (xyz [n_points, 3], obs_error [n_obs], report dict); the views array holds the new poses."""
+    return _adjust(None, views, n_views, view_constant, xyz, point_constant, point_offsets, obs_view, obs_xy, flags, device, options)
+
+
+def adjust_cameras(cam_models, cam_params, cam_refine, view_camera, views, n_views, view_constant, xyz, point_constant, point_offsets, obs_view, obs_xy,
+                   flags=0, device=0, **options):
+    """adjust() with camera intrinsics among the unknowns.  cam_models [n_cameras] (model ids), cam_params [n_cameras, 8] (COLMAP order,
+    zero padded), cam_refine [n_cameras] (SFD2_BA_REFINE_* bits, 0 = constant), view_camera [n_views] (index into the cameras).  The
+    views' own model / params words are not read; they leave with their camera's new values.  Returns (cam_params [n_cameras, 8], xyz,
+    obs_error, report)."""
+    models = np.ascontiguousarray(cam_models, dtype=np.int32).reshape(-1)
+    params = np.array(cam_params, dtype=np.float64).reshape(-1, 8)
+    refine = np.ascontiguousarray(cam_refine, dtype=np.int32).reshape(-1)
+    vcam = np.ascontiguousarray(view_camera, dtype=np.int32).reshape(-1)
+    n = len(models)
+    if n < 1 or len(params) != n or len(refine) != n or len(vcam) != int(n_views):
+        raise ValueError("the camera arrays and view_camera do not fit together")
+    bad = np.nonzero((vcam < 0) | (vcam >= n))[0]
+    if len(bad):
+        raise ValueError(f"view {int(bad[0])}: camera index out of range")
+    bad = np.nonzero(refine & ~(_lib.BA_REFINE_FOCAL | _lib.BA_REFINE_PRINCIPAL | _lib.BA_REFINE_EXTRA))[0]
+    if len(bad):
+        raise ValueError(f"camera {int(bad[0])}: unknown refine bits")
+    bad = np.nonzero(~np.isfinite(params).all(1))[0]
+    if len(bad):
+        raise ValueError(f"camera {int(bad[0])}: non-finite parameters")
+    cams = (_lib.BaCamera * n)()
+    for i in range(n):
+        cams[i].model, cams[i].refine = int(models[i]), int(refine[i])
+        cams[i].params[:] = params[i].tolist()
+    pts, err, report = _adjust((cams, n, vcam), views, n_views, view_constant, xyz, point_constant, point_offsets, obs_view, obs_xy, flags, device, options)
+    return np.array([list(c.params) for c in cams], dtype=np.float64), pts, err, report
+
+
+def _adjust(cameras, views, n_views, view_constant, xyz, point_constant, point_offsets, obs_view, obs_xy, flags, device, options):
     conf = _conf(options)
     n_views = int(n_views)
     vc = np.ascontiguousarray(np.asarray(view_constant).reshape(-1) != 0, dtype=np.uint8)
@@ -78,8 +121,12 @@ def adjust(views, n_views, view_constant, xyz, point_constant, point_offsets, ob
     err = np.zeros(len(ov), dtype=np.float64)
     res = _lib.BaResult()
     ctx = _lib.default_context(device)
-    _lib.check(ctx.lib.sfd2_bundle_adjust(ctx.h, views, n_views, vc.ctypes.data, pts.ctypes.data, P, pc.ctypes.data, off.ctypes.data, ov.ctypes.data,
-                                          xy.ctypes.data, ctypes.byref(conf), ctypes.byref(res), err.ctypes.data, int(flags)))
+    rest = (views, n_views, vc.ctypes.data, pts.ctypes.data, P, pc.ctypes.data, off.ctypes.data, ov.ctypes.data, xy.ctypes.data, ctypes.byref(conf),
+            ctypes.byref(res), err.ctypes.data, int(flags))
+    if cameras is None:
+        _lib.check(ctx.lib.sfd2_bundle_adjust(ctx.h, *rest))
+    else:
+        _lib.check(ctx.lib.sfd2_bundle_adjust_cameras(ctx.h, cameras[0], cameras[1], cameras[2].ctypes.data, *rest))
     report = {"status": STATUS[res.status], "iterations": int(res.iterations), "accepted_steps": int(res.accepted_steps),
               "pcg_iterations": int(res.pcg_iterations), "initial_cost": float(res.initial_cost), "final_cost": float(res.final_cost),
               "gradient_max": float(res.gradient_max), "lambda": float(res.lambda_)}
@@ -113,18 +160,34 @@ def pack_model(cameras, images, points3D):
             np.array(xy, dtype=np.float64).reshape(-1, 2))
 
 
-def bundle_adjust(cameras, images, points3D, constant_images=(), constant_points=(), flags=0, device=0, **options):
+def bundle_adjust(cameras, images, points3D, constant_images=(), constant_points=(), flags=0, device=0, refine_focal_length=False,
+                  refine_principal_point=False, refine_extra_params=False, constant_cameras=(), **options):
     """cameras, images, points3D: colmap_io records.  constant_images / constant_points: ids whose pose / position stays.  Returns (new
     images, new points3D with error = the point's mean reprojection error, report).  An image without observations is returned
-    unchanged."""
+    unchanged.  With a refine option set the intrinsics of every camera id not in constant_cameras are refined too (one camera id is
+    one camera: images that share it share its parameters), and the return is (new cameras, new images, new points3D, report)."""
     _conf(options)
+    mask = refine_mask(refine_focal_length, refine_principal_point, refine_extra_params)
     ids, views, pids, xyz, off, ov, xy = pack_model(cameras, images, points3D)
     if not ids:
         raise ValueError("the model has no observations")
     cset, pset = set(int(i) for i in constant_images), set(int(p) for p in constant_points)
     vc = np.array([iid in cset for iid in ids], dtype=np.uint8)
     pc = np.array([pid in pset for pid in pids], dtype=np.uint8)
-    new_xyz, err, report = adjust(views, len(ids), vc, xyz, pc, off, ov, xy, flags=flags, device=device, **options)
+    if mask:
+        held = set(int(c) for c in constant_cameras)
+        cam_ids = sorted(set(images[iid].camera_id for iid in ids))
+        cam_index = {cid: k for k, cid in enumerate(cam_ids)}
+        packed = [camera_model(cameras[cid]) for cid in cam_ids]
+        cam_params, new_xyz, err, report = adjust_cameras([m for m, _ in packed], [p for _, p in packed], [0 if cid in held else mask for cid in cam_ids],
+                                                          [cam_index[images[iid].camera_id] for iid in ids], views, len(ids), vc, xyz, pc, off, ov, xy,
+                                                          flags=flags, device=device, **options)
+        out_cameras = dict(cameras)
+        for k, cid in enumerate(cam_ids):
+            cam = cameras[cid]
+            out_cameras[cid] = colmap_io.Camera(cam["id"], cam["model"], cam["width"], cam["height"], cam_params[k][:len(cam["params"])])
+    else:
+        new_xyz, err, report = adjust(views, len(ids), vc, xyz, pc, off, ov, xy, flags=flags, device=device, **options)
     out_images = dict(images)
     for k, iid in enumerate(ids):
         im = images[iid]
@@ -138,6 +201,8 @@ def bundle_adjust(cameras, images, points3D, constant_images=(), constant_points
     report["obs_error"] = err
     report["point_offsets"] = off
     report["point_ids"] = pids
+    if mask:
+        return out_cameras, out_images, out_points, report
     return out_images, out_points, report
 
 
@@ -161,13 +226,19 @@ def read_constant_images(path, images):
     return out
 
 
-def main(input_path, output_path, max_num_iterations=DEFAULTS["max_iterations"], loss="trivial", loss_scale=1.0, constant_images=None, **options):
-    """Reads the model at input_path, adjusts it, writes it to output_path; returns the report."""
+def main(input_path, output_path, max_num_iterations=DEFAULTS["max_iterations"], loss="trivial", loss_scale=1.0, constant_images=None,
+         refine_focal_length=0, refine_principal_point=0, refine_extra_params=0, **options):
+    """Reads the model at input_path, adjusts it, writes it to output_path (with a refine option: the refined cameras too); returns the
+    report."""
     input_path, output_path = Path(input_path), Path(output_path)
     cameras, images, points3D = colmap_io.read_model(input_path)
     const = default_constant_images(images) if constant_images is None else read_constant_images(constant_images, images)
-    out_images, out_points, report = bundle_adjust(cameras, images, points3D, constant_images=const, max_iterations=max_num_iterations, loss=loss,
-                                                   loss_scale=loss_scale, **options)
+    out = bundle_adjust(cameras, images, points3D, constant_images=const, max_iterations=max_num_iterations, loss=loss, loss_scale=loss_scale,
+                        refine_focal_length=bool(refine_focal_length), refine_principal_point=bool(refine_principal_point),
+                        refine_extra_params=bool(refine_extra_params), **options)
+    if len(out) == 4:
+        cameras = out[0]
+    out_images, out_points, report = out[-3:]
     output_path.mkdir(parents=True, exist_ok=True)
     colmap_io.write_model(cameras, out_images, out_points, output_path)
     logging.info("Bundle adjustment: %s", {k: v for k, v in report.items() if not isinstance(v, (np.ndarray, list))})
@@ -182,6 +253,9 @@ def parser():
     ap.add_argument("--loss", choices=sorted(LOSSES), default="trivial")
     ap.add_argument("--loss_scale", type=float, default=1.0)
     ap.add_argument("--constant_images", type=Path, default=None)
+    ap.add_argument("--refine_focal_length", type=int, choices=(0, 1), default=0)
+    ap.add_argument("--refine_principal_point", type=int, choices=(0, 1), default=0)
+    ap.add_argument("--refine_extra_params", type=int, choices=(0, 1), default=0)
     return ap
 
 

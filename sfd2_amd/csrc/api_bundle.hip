@@ -1,10 +1,11 @@
-// libsfd2hip: sfd2_bundle_adjust -- checks and packs the inputs, builds the by-view CSR, and drives the Levenberg-Marquardt loop of
-// bundle_kernels.hip on the context's stream.  The accept / reject decision is taken on the device, so the host
-// reads the state block once per LM iteration and once per batch of PCG iterations.
+// libsfd2hip: sfd2_bundle_adjust and sfd2_bundle_adjust_cameras -- check and pack the inputs, build the by-view CSR, and drive the
+// Levenberg-Marquardt loop of bundle_kernels.hip on the context's stream.  The accept / reject decision is taken on
+// the device, so the host reads the state block once per LM iteration and once per batch of PCG iterations.  With cameras among the
+// unknowns (section 20) the same loop queues the passes of bundle_cam_kernels.hip where a pass has to know about them.
 #include "sfd2_ctx.h"
 #include "api_scratch.h"
 #include "pose_camera.h"
-#include "bundle.h"
+#include "bundle_cam.h"
 
 namespace {
 
@@ -15,13 +16,47 @@ template <typename T> int64_t first_nonfinite(const T *p, int64_t n)
     return n;
 }
 
-}  // namespace
-
-extern "C" int sfd2_bundle_adjust(sfd2_ctx *c, sfd2_tri_view *views, int n_views, const uint8_t *view_constant, double *xyz, int n_points,
-                                  const uint8_t *point_constant, const int64_t *point_offsets, const int32_t *obs_view, const double *obs_xy,
-                                  const sfd2_ba_conf *conf, sfd2_ba_result *result, double *obs_error, int flags)
+// the active parameters of a camera: (SFD2_BA_SLOT_*, index into the model's COLMAP parameters) each, in COLMAP order
+int cam_slots(int model, int refine, int32_t slot[SFD2_BA_CAM_K], int param[SFD2_BA_CAM_K])
 {
-    const std::string F("sfd2_bundle_adjust: ");
+    int k = 0;
+    auto add = [&](int s, int p) { slot[k] = s; param[k] = p; ++k; };
+    const bool simple = model == SFD2_CAM_SIMPLE_PINHOLE || model == SFD2_CAM_SIMPLE_RADIAL;
+    const int pp = simple ? 1 : 2;                           // where cx stands
+    if (refine & SFD2_BA_REFINE_FOCAL) {
+        if (simple) add(SFD2_BA_SLOT_F, 0);
+        else { add(SFD2_BA_SLOT_FX, 0); add(SFD2_BA_SLOT_FY, 1); }
+    }
+    if (refine & SFD2_BA_REFINE_PRINCIPAL) { add(SFD2_BA_SLOT_CX, pp); add(SFD2_BA_SLOT_CY, pp + 1); }
+    if (refine & SFD2_BA_REFINE_EXTRA) {
+        if (model == SFD2_CAM_SIMPLE_RADIAL) add(SFD2_BA_SLOT_K1, 3);
+        if (model == SFD2_CAM_OPENCV) { add(SFD2_BA_SLOT_K1, 4); add(SFD2_BA_SLOT_K2, 5); add(SFD2_BA_SLOT_P1, 6); add(SFD2_BA_SLOT_P2, 7); }
+    }
+    const int n = k;
+    for (; k < SFD2_BA_CAM_K; ++k) { slot[k] = SFD2_BA_SLOT_NONE; param[k] = -1; }
+    return n;
+}
+
+double cam_word(const PoseCam &c, int slot)
+{
+    switch (slot) {
+    case SFD2_BA_SLOT_F: case SFD2_BA_SLOT_FX: return c.f[0];
+    case SFD2_BA_SLOT_FY: return c.f[1];
+    case SFD2_BA_SLOT_CX: return c.c[0];
+    case SFD2_BA_SLOT_CY: return c.c[1];
+    case SFD2_BA_SLOT_K1: return c.k1;
+    case SFD2_BA_SLOT_K2: return c.k2;
+    case SFD2_BA_SLOT_P1: return c.p1;
+    default: return c.p2;
+    }
+}
+
+// cameras == nullptr: sfd2_bundle_adjust, every view with the constant camera of its own words
+int ba_run(sfd2_ctx *c, const std::string &F, sfd2_ba_camera *cameras, int n_cameras, const int32_t *view_camera, sfd2_tri_view *views, int n_views,
+           const uint8_t *view_constant, double *xyz, int n_points, const uint8_t *point_constant, const int64_t *point_offsets, const int32_t *obs_view,
+           const double *obs_xy, const sfd2_ba_conf *conf, sfd2_ba_result *result, double *obs_error, int flags)
+{
+    const bool CAM = cameras != nullptr;
     if (!c || !views || !view_constant || !point_offsets || !conf || !result || (n_points > 0 && (!xyz || !point_constant))) return fail(F + "null argument");
     if (n_views < 1 || n_points < 0) return fail(F + "n_views must be positive and n_points non-negative");
     if (flags & ~(SFD2_BA_FLAG_POINT_LANE | SFD2_BA_FLAG_POINT_WAVE) || flags == (SFD2_BA_FLAG_POINT_LANE | SFD2_BA_FLAG_POINT_WAVE))
@@ -44,13 +79,27 @@ extern "C" int sfd2_bundle_adjust(sfd2_ctx *c, sfd2_tri_view *views, int n_views
     if (!all_finite(obs_xy, 2 * O)) return fail(F + "observation " + std::to_string(first_nonfinite(obs_xy, 2 * O) / 2) + ": non-finite coordinates");
     if (!all_finite(xyz, 3 * (int64_t)n_points)) return fail(F + "point " + std::to_string(first_nonfinite(xyz, 3 * (int64_t)n_points) / 3) + ": non-finite coordinates");
 
-    const size_t nv = (size_t)n_views, np = (size_t)n_points, no = (size_t)O;
-    std::vector<PoseCam> cams(nv);
+    const size_t nv = (size_t)n_views, np = (size_t)n_points, no = (size_t)O, nc = CAM ? (size_t)n_cameras : 0;
+    std::vector<PoseCam> cams(CAM ? nc : nv);
+    std::vector<int32_t> slots(SFD2_BA_CAM_K * nc), slot_param(SFD2_BA_CAM_K * nc);
+    int kmax = 0;
+    for (size_t i = 0; i < nc; ++i) {
+        std::string w;
+        if (cameras[i].refine & ~(SFD2_BA_REFINE_FOCAL | SFD2_BA_REFINE_PRINCIPAL | SFD2_BA_REFINE_EXTRA))
+            return fail(F + "camera " + std::to_string(i) + ": unknown refine bits");
+        if (!sfd2_pose_cam(cameras[i].model, cameras[i].params, cams[i], w)) return fail(F + "camera " + std::to_string(i) + ": " + w);
+        kmax = std::max(kmax, cam_slots(cameras[i].model, cameras[i].refine, &slots[SFD2_BA_CAM_K * i], &slot_param[SFD2_BA_CAM_K * i]));
+    }
+    if (CAM)
+        if (const int64_t v = first_outside(view_camera, n_views, n_cameras); v < n_views)
+            return fail(F + "view " + std::to_string(v) + ": camera index out of range");
     std::vector<double> pose(12 * nv);
     for (int i = 0; i < n_views; ++i) {
         std::string w;
-        memset(&cams[i], 0, sizeof(PoseCam));
-        if (!sfd2_pose_cam(views[i].model, views[i].params, cams[i], w)) return fail(F + "view " + std::to_string(i) + ": " + w);
+        if (!CAM) {
+            memset(&cams[i], 0, sizeof(PoseCam));
+            if (!sfd2_pose_cam(views[i].model, views[i].params, cams[i], w)) return fail(F + "view " + std::to_string(i) + ": " + w);
+        }
         const double *q = views[i].qvec;
         const double nq = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
         if (!all_finite(q, 4) || !all_finite(views[i].tvec, 3) || !(nq > 0))
@@ -67,6 +116,15 @@ extern "C" int sfd2_bundle_adjust(sfd2_ctx *c, sfd2_tri_view *views, int n_views
         std::vector<int64_t> fill(view_off.begin(), view_off.end() - 1);
         for (size_t o = 0; o < no; ++o) view_obs[(size_t)fill[(size_t)obs_view[o]]++] = (int32_t)o;
     }
+    // the by-camera list the same way: a camera's views in ascending index
+    std::vector<int64_t> cam_off(nc + 1, 0);
+    std::vector<int32_t> cam_views(nv);
+    if (CAM) {
+        for (size_t v = 0; v < nv; ++v) ++cam_off[(size_t)view_camera[v] + 1];
+        for (size_t i = 0; i < nc; ++i) cam_off[i + 1] += cam_off[i];
+        std::vector<int64_t> fill(cam_off.begin(), cam_off.end() - 1);
+        for (size_t v = 0; v < nv; ++v) cam_views[(size_t)fill[(size_t)view_camera[v]]++] = (int32_t)v;
+    }
     // points by mapping: a lane each up to SFD2_BA_LONG_TRACK observations, beyond that a wave each (the flags force either side)
     std::vector<int32_t> short_ids, long_ids;
     for (int j = 0; j < n_points; ++j) {
@@ -78,21 +136,37 @@ extern "C" int sfd2_bundle_adjust(sfd2_ctx *c, sfd2_tri_view *views, int n_views
 
     HIPCHECK(hipSetDevice(c->device));
     Carve in, ws;
-    const size_t o_cam = in.take(sizeof(PoseCam) * nv), o_vc = in.take(nv), o_pc = in.take(np), o_po = in.take(8 * (np + 1)), o_ov = in.take(4 * no),
+    const size_t o_cam = in.take(sizeof(PoseCam) * cams.size()), o_vc = in.take(nv), o_pc = in.take(np), o_po = in.take(8 * (np + 1)), o_ov = in.take(4 * no),
                  o_op = in.take(4 * no), o_xy = in.take(16 * no), o_vo = in.take(8 * (nv + 1)), o_vb = in.take(4 * no), o_sh = in.take(4 * short_ids.size()),
                  o_lg = in.take(4 * long_ids.size());
-    const size_t nred = (std::max(std::max(no, 3 * np), 6 * nv) + SFD2_BA_RED_CHUNK - 1) / SFD2_BA_RED_CHUNK + 1;
+    const size_t nx = 48 * nv + 8 * SFD2_BA_CAM_K * nc;      // bytes of a vector of the reduced system
+    const size_t nred = (std::max(std::max(std::max(no, 3 * np), 6 * nv), SFD2_BA_CAM_K * nc) + SFD2_BA_RED_CHUNK - 1) / SFD2_BA_RED_CHUNK + 1;
     const size_t o_st = ws.take(sizeof(BaState)), o_pose = ws.take(96 * nv), o_poset = ws.take(96 * nv), o_xyz = ws.take(24 * np), o_xyzt = ws.take(24 * np),
                  o_rec = ws.take(8 * SFD2_BA_REC * no), o_err = ws.take(8 * no), o_oc = ws.take(8 * no), o_V = ws.take(48 * np), o_gp = ws.take(24 * np),
                  o_Vi = ws.take(48 * np), o_zg = ws.take(24 * np), o_z = ws.take(24 * np), o_B = ws.take(288 * nv), o_gc = ws.take(48 * nv),
-                 o_Mi = ws.take(288 * nv), o_Dd = ws.take(48 * nv), o_b = ws.take(48 * nv), o_x = ws.take(48 * nv), o_r = ws.take(48 * nv),
-                 o_zz = ws.take(48 * nv), o_p = ws.take(48 * nv), o_q = ws.take(48 * nv), o_part = ws.take(8 * nred);
+                 o_Mi = ws.take(288 * nv), o_Dd = ws.take(48 * nv), o_b = ws.take(nx), o_x = ws.take(nx), o_r = ws.take(nx), o_zz = ws.take(nx),
+                 o_p = ws.take(nx), o_q = ws.take(nx), o_part = ws.take(8 * nred);
+    size_t o_vcam = 0, o_slot = 0, o_co = 0, o_cv = 0, o_camc = 0, o_camt = 0, o_bad = 0, o_reck = 0, o_W = 0, o_Cp = 0, o_gkp = 0, o_qkp = 0, o_C = 0, o_gk = 0,
+           o_Ci = 0, o_Dk = 0;
+    if (CAM) {
+        o_vcam = in.take(4 * nv); o_slot = in.take(4 * SFD2_BA_CAM_K * nc); o_co = in.take(8 * (nc + 1)); o_cv = in.take(4 * nv);
+        o_camc = ws.take(sizeof(PoseCam) * nc); o_camt = ws.take(sizeof(PoseCam) * nc); o_bad = ws.take(4); o_reck = ws.take(16 * (size_t)kmax * no);
+        o_W = ws.take(8 * 48 * nv); o_Cp = ws.take(8 * 36 * nv); o_gkp = ws.take(8 * SFD2_BA_CAM_K * nv); o_qkp = ws.take(8 * SFD2_BA_CAM_K * nv);
+        o_C = ws.take(8 * 64 * nc); o_gk = ws.take(8 * SFD2_BA_CAM_K * nc); o_Ci = ws.take(8 * 64 * nc); o_Dk = ws.take(8 * SFD2_BA_CAM_K * nc);
+    }
     HIPCHECK(hipStreamSynchronize(c->stream));
     HIPCHECK(grow(c->ba_in, in.off));
     HIPCHECK(grow(c->ba_ws, ws.off));
     char *di = c->ba_in.as<char>(), *dw = c->ba_ws.as<char>();
     hipStream_t s = c->stream;
-    HIPCHECK(hipMemcpyAsync(di + o_cam, cams.data(), sizeof(PoseCam) * nv, hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemcpyAsync(di + o_cam, cams.data(), sizeof(PoseCam) * cams.size(), hipMemcpyHostToDevice, s));
+    if (CAM) {
+        HIPCHECK(hipMemcpyAsync(dw + o_camc, cams.data(), sizeof(PoseCam) * nc, hipMemcpyHostToDevice, s));
+        HIPCHECK(hipMemcpyAsync(di + o_vcam, view_camera, 4 * nv, hipMemcpyHostToDevice, s));
+        HIPCHECK(hipMemcpyAsync(di + o_slot, slots.data(), 4 * SFD2_BA_CAM_K * nc, hipMemcpyHostToDevice, s));
+        HIPCHECK(hipMemcpyAsync(di + o_co, cam_off.data(), 8 * (nc + 1), hipMemcpyHostToDevice, s));
+        HIPCHECK(hipMemcpyAsync(di + o_cv, cam_views.data(), 4 * nv, hipMemcpyHostToDevice, s));
+    }
     HIPCHECK(hipMemcpyAsync(di + o_vc, view_constant, nv, hipMemcpyHostToDevice, s));
     HIPCHECK(hipMemcpyAsync(di + o_po, point_offsets, 8 * (np + 1), hipMemcpyHostToDevice, s));
     HIPCHECK(hipMemcpyAsync(di + o_vo, view_off.data(), 8 * (nv + 1), hipMemcpyHostToDevice, s));
@@ -116,8 +190,9 @@ extern "C" int sfd2_bundle_adjust(sfd2_ctx *c, sfd2_tri_view *views, int n_views
     HIPCHECK(hipMemcpyAsync(dw + o_st, &hs, sizeof(hs), hipMemcpyHostToDevice, s));
     HIPCHECK(hipMemsetAsync(dw + o_oc, 0, std::max<size_t>(8 * no, 1), s));
 
-    BaPtrs P;
-    memset(&P, 0, sizeof(P));
+    BaCamPtrs Q;
+    memset(&Q, 0, sizeof(Q));
+    BaPtrs &P = Q.P;
     P.st = at<BaState>(dw, o_st);
     P.cams = at<const PoseCam>(di, o_cam);
     P.vconst = at<const unsigned char>(di, o_vc);
@@ -140,15 +215,30 @@ extern "C" int sfd2_bundle_adjust(sfd2_ctx *c, sfd2_tri_view *views, int n_views
     P.partial = at<double>(dw, o_part);
     P.nv = n_views; P.np = n_points; P.n_short = (int)short_ids.size(); P.n_long = (int)long_ids.size();
     P.no = O;
+    if (CAM) {
+        Q.view_cam = at<const int32_t>(di, o_vcam); Q.slots = at<const int32_t>(di, o_slot);
+        Q.cam_off = at<const int64_t>(di, o_co); Q.cam_views = at<const int32_t>(di, o_cv);
+        Q.cams = at<PoseCam>(dw, o_camc); Q.cams_trial = at<PoseCam>(dw, o_camt); Q.bad = at<int32_t>(dw, o_bad);
+        Q.reck = at<double>(dw, o_reck);
+        Q.W = at<double>(dw, o_W); Q.Cp = at<double>(dw, o_Cp); Q.gkp = at<double>(dw, o_gkp); Q.qkp = at<double>(dw, o_qkp);
+        Q.C = at<double>(dw, o_C); Q.gk = at<double>(dw, o_gk); Q.Cinv = at<double>(dw, o_Ci); Q.Dk = at<double>(dw, o_Dk);
+        Q.nc = n_cameras; Q.kmax = kmax;
+    }
 
     const double c2 = conf->loss == SFD2_BA_LOSS_CAUCHY ? conf->loss_scale * conf->loss_scale : 1.0;
     // the state's Jacobians, blocks, gradients and max |g|: behind the start (gate none) or behind an accepted step
+    auto linearise = [&](int gate, bool full, bool trial) {
+        if (CAM) launch_bac_linearise(s, Q, gate, full, trial, conf->loss, c2);
+        else launch_ba_linearise(s, P, gate, full, trial, conf->loss, c2);
+    };
     auto relinearise = [&](int gate) {
-        launch_ba_linearise(s, P, gate, true, false, conf->loss, c2);
+        linearise(gate, true, false);
         launch_ba_point_build(s, P, gate);
         launch_ba_view_build(s, P, gate);
+        if (CAM) launch_bac_cam_build(s, Q, gate);
         launch_ba_reduce(s, P, gate, P.gc, 6 * (int64_t)nv, SFD2_BA_OP_ABSMAX, &P.st->gmax, false);
         if (np) launch_ba_reduce(s, P, gate, P.gp, 3 * (int64_t)np, SFD2_BA_OP_ABSMAX, &P.st->gmax, true);
+        if (CAM) launch_ba_reduce(s, P, gate, Q.gk, SFD2_BA_CAM_K * (int64_t)nc, SFD2_BA_OP_ABSMAX, &P.st->gmax, true);
     };
     auto read_state = [&]() -> hipError_t {
         hipError_t e = hipMemcpyAsync(&hs, P.st, sizeof(hs), hipMemcpyDeviceToHost, s);
@@ -158,7 +248,7 @@ extern "C" int sfd2_bundle_adjust(sfd2_ctx *c, sfd2_tri_view *views, int n_views
     memset(result, 0, sizeof(*result));
     {
         ProfScope ps(c, "bundle_adjust", "ba_linearise+build", 0.0, 8.0 * SFD2_BA_REC * (double)no);
-        launch_ba_linearise(s, P, SFD2_BA_GATE_NONE, false, false, conf->loss, c2);
+        linearise(SFD2_BA_GATE_NONE, false, false);
         launch_ba_reduce(s, P, SFD2_BA_GATE_NONE, P.obs_cost, O, SFD2_BA_OP_SUM, &P.st->cost, false);
         relinearise(SFD2_BA_GATE_NONE);
     }
@@ -181,23 +271,42 @@ extern "C" int sfd2_bundle_adjust(sfd2_ctx *c, sfd2_tri_view *views, int n_views
         if (iters >= conf->max_iterations) break;
         launch_ba_point_invert(s, P);
         launch_ba_view_precond(s, P);
-        launch_ba_view_apply(s, P, SFD2_BA_GATE_NONE, true);
-        launch_ba_pcg_init(s, P);
+        if (CAM) {
+            launch_bac_cam_precond(s, Q);
+            launch_bac_apply(s, Q, SFD2_BA_GATE_NONE, true);
+            launch_bac_pcg_init(s, Q);
+        } else {
+            launch_ba_view_apply(s, P, SFD2_BA_GATE_NONE, true);
+            launch_ba_pcg_init(s, P);
+        }
         for (int k = 0; k < conf->pcg_max_iterations;) {
             for (int e = std::min(conf->pcg_max_iterations, k + batch); k < e; ++k) {
-                launch_ba_point_apply(s, P, SFD2_BA_GATE_PCG, P.p);
-                launch_ba_view_apply(s, P, SFD2_BA_GATE_PCG, false);
-                launch_ba_pcg_step(s, P, tol2, conf->pcg_max_iterations);
+                if (CAM) {
+                    launch_bac_point_apply(s, Q, SFD2_BA_GATE_PCG, P.p);
+                    launch_bac_apply(s, Q, SFD2_BA_GATE_PCG, false);
+                    launch_bac_pcg_step(s, Q, tol2, conf->pcg_max_iterations);
+                } else {
+                    launch_ba_point_apply(s, P, SFD2_BA_GATE_PCG, P.p);
+                    launch_ba_view_apply(s, P, SFD2_BA_GATE_PCG, false);
+                    launch_ba_pcg_step(s, P, tol2, conf->pcg_max_iterations);
+                }
             }
             HIPCHECK(read_state());
             if (hs.pcg_done) break;
         }
         pcg_total += hs.pcg_iters;
-        launch_ba_point_apply(s, P, SFD2_BA_GATE_NONE, P.x);
+        if (CAM) {
+            launch_bac_point_apply(s, Q, SFD2_BA_GATE_NONE, P.x);
+            launch_bac_update_cams(s, Q);
+        } else {
+            launch_ba_point_apply(s, P, SFD2_BA_GATE_NONE, P.x);
+        }
         launch_ba_update(s, P);
-        launch_ba_linearise(s, P, SFD2_BA_GATE_NONE, false, true, conf->loss, c2);
+        linearise(SFD2_BA_GATE_NONE, false, true);
         launch_ba_reduce(s, P, SFD2_BA_GATE_NONE, P.obs_cost, O, SFD2_BA_OP_SUM, &P.st->trial_cost, false);
+        if (CAM) launch_bac_veto(s, Q);
         launch_ba_decide_commit(s, P);
+        if (CAM) launch_bac_commit_cams(s, Q);
         relinearise(SFD2_BA_GATE_ACCEPTED);
         HIPCHECK(hipGetLastError());
         HIPCHECK(read_state());
@@ -214,11 +323,46 @@ extern "C" int sfd2_bundle_adjust(sfd2_ctx *c, sfd2_tri_view *views, int n_views
     HIPCHECK(hipMemcpyAsync(pose.data(), P.pose, 96 * nv, hipMemcpyDeviceToHost, s));
     if (np) HIPCHECK(hipMemcpyAsync(xyz, P.xyz, 24 * np, hipMemcpyDeviceToHost, s));
     if (no) HIPCHECK(hipMemcpyAsync(obs_error, P.err, 8 * no, hipMemcpyDeviceToHost, s));
+    if (CAM) HIPCHECK(hipMemcpyAsync(cams.data(), Q.cams, sizeof(PoseCam) * nc, hipMemcpyDeviceToHost, s));
     HIPCHECK(hipStreamSynchronize(s));
     for (int i = 0; i < n_views; ++i) {                      // a constant or unobserved view keeps its words as they came
         if (view_constant[i] || view_off[(size_t)i + 1] == view_off[(size_t)i] || hs.n_accepted == 0) continue;
         rot_to_quat(&pose[12 * (size_t)i], views[i].qvec);
         for (int a = 0; a < 3; ++a) views[i].tvec[a] = pose[12 * (size_t)i + 9 + a];
     }
+    for (size_t i = 0; i < nc; ++i) {                        // a constant or unobserved camera keeps its words as they came
+        bool observed = false;
+        for (int64_t k = cam_off[i]; k < cam_off[i + 1] && !observed; ++k)
+            observed = view_off[(size_t)cam_views[(size_t)k] + 1] > view_off[(size_t)cam_views[(size_t)k]];
+        if (!observed || hs.n_accepted == 0) continue;
+        for (int k = 0; k < SFD2_BA_CAM_K && slots[SFD2_BA_CAM_K * i + k] != SFD2_BA_SLOT_NONE; ++k)
+            cameras[i].params[slot_param[SFD2_BA_CAM_K * i + k]] = cam_word(cams[i], slots[SFD2_BA_CAM_K * i + k]);
+    }
+    for (size_t v = 0; v < nv && CAM; ++v) {                 // every view leaves with its camera's words
+        views[v].model = cameras[view_camera[v]].model;
+        memcpy(views[v].params, cameras[view_camera[v]].params, sizeof(views[v].params));
+    }
     return 0;
+}
+
+}  // namespace
+
+extern "C" int sfd2_bundle_adjust(sfd2_ctx *c, sfd2_tri_view *views, int n_views, const uint8_t *view_constant, double *xyz, int n_points,
+                                  const uint8_t *point_constant, const int64_t *point_offsets, const int32_t *obs_view, const double *obs_xy,
+                                  const sfd2_ba_conf *conf, sfd2_ba_result *result, double *obs_error, int flags)
+{
+    return ba_run(c, "sfd2_bundle_adjust: ", nullptr, 0, nullptr, views, n_views, view_constant, xyz, n_points, point_constant, point_offsets, obs_view, obs_xy,
+                  conf, result, obs_error, flags);
+}
+
+extern "C" int sfd2_bundle_adjust_cameras(sfd2_ctx *c, sfd2_ba_camera *cameras, int n_cameras, const int32_t *view_camera, sfd2_tri_view *views, int n_views,
+                                          const uint8_t *view_constant, double *xyz, int n_points, const uint8_t *point_constant,
+                                          const int64_t *point_offsets, const int32_t *obs_view, const double *obs_xy, const sfd2_ba_conf *conf,
+                                          sfd2_ba_result *result, double *obs_error, int flags)
+{
+    const std::string F("sfd2_bundle_adjust_cameras: ");
+    if (!cameras || !view_camera) return fail(F + "null argument");
+    if (n_cameras < 1) return fail(F + "n_cameras must be positive");
+    return ba_run(c, F, cameras, n_cameras, view_camera, views, n_views, view_constant, xyz, n_points, point_constant, point_offsets, obs_view, obs_xy, conf,
+                  result, obs_error, flags);
 }

@@ -42,6 +42,31 @@ struct BaPtrs {                       // the call's device arrays
     int64_t no;
 };
 
+// device helpers of bundle_kernels.hip and bundle_cam_kernels.hip
+static __device__ __forceinline__ bool ba_gated(const BaState *st, int gate)
+{
+    return (gate == SFD2_BA_GATE_ACCEPTED && !st->accepted) || (gate == SFD2_BA_GATE_PCG && st->pcg_done);
+}
+
+// a[0..K) summed over the NT threads of the block by a fixed tree; sh holds K * NT doubles; every thread gets the sums
+template <int K, int NT> static __device__ __forceinline__ void ba_tree_sum(double *a, double *sh)
+{
+    const int t = threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < K; ++k) sh[k * NT + t] = a[k];
+    __syncthreads();
+    for (int s = NT / 2; s > 0; s >>= 1) {
+        if (t < s) {
+#pragma unroll
+            for (int k = 0; k < K; ++k) sh[k * NT + t] += sh[k * NT + t + s];
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) a[k] = sh[k * NT];
+    __syncthreads();
+}
+
 void launch_ba_linearise(hipStream_t st, const BaPtrs &P, int gate, bool full, bool trial, int loss, double c2);
 void launch_ba_reduce(hipStream_t st, const BaPtrs &P, int gate, const double *src, int64_t n, int op, double *dst, bool combine);
 void launch_ba_point_build(hipStream_t st, const BaPtrs &P, int gate);

@@ -13,30 +13,6 @@
 
 namespace {
 
-__device__ __forceinline__ bool ba_gated(const BaState *st, int gate)
-{
-    return (gate == SFD2_BA_GATE_ACCEPTED && !st->accepted) || (gate == SFD2_BA_GATE_PCG && st->pcg_done);
-}
-
-// a[0..K) summed over the NT threads of the block by a fixed tree; sh holds K * NT doubles; every thread gets the sums
-template <int K, int NT> __device__ __forceinline__ void ba_tree_sum(double *a, double *sh)
-{
-    const int t = threadIdx.x;
-#pragma unroll
-    for (int k = 0; k < K; ++k) sh[k * NT + t] = a[k];
-    __syncthreads();
-    for (int s = NT / 2; s > 0; s >>= 1) {
-        if (t < s) {
-#pragma unroll
-            for (int k = 0; k < K; ++k) sh[k * NT + t] += sh[k * NT + t + s];
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int k = 0; k < K; ++k) a[k] = sh[k * NT];
-    __syncthreads();
-}
-
 // ---------------------------------------------------------------------------------------------------------------- linearise
 // residual, IRLS weight, the 2x6 and 2x3 Jacobians and the cost term of one observation per lane; FULL = false: the cost term only
 template <bool FULL>

@@ -16,6 +16,11 @@ verified matches; the points are a function of the registered views and their po
   python -m sfd2_amd.reconstruction --sfm_dir S --image_dir D --pairs P --features F --matches M
          [--reference_sfm_model R | --intrinsics LIST...] [--single_camera] [--skip_geometric_verification]
          [--min_match_score X] [--min_num_matches N] [--verification essential|fundamental|geometry]
+         [--refine_focal_length 0|1] [--refine_principal_point 0|1] [--refine_extra_params 0|1] [--intrinsics_min_views N]
+
+The refine options (default off) let every round's adjustment, from intrinsics_min_views registered views on, refine the cameras'
+intrinsics with the poses and points (bundle_adjustment.adjust_cameras): the next round triangulates, filters and
+registers with the refined cameras, and the written model carries them.
 
 --verification fundamental (reconstruct(..., verification="fundamental")): for cameras nobody trusts, i.e. the focal-length prior.  Step 1
 verifies every pair by its fundamental matrix (two_view.verify_pairs_fundamental) and continues as
@@ -24,8 +29,8 @@ verifies every pair by its fundamental matrix (two_view.verify_pairs_fundamental
 DESIGN.md section 17): a planar or rotation-only pair keeps its matches, and a pair labelled panoramic, planar_or_panoramic or
 degenerate is not taken as the initial pair.
 
-Deviations from COLMAP: one model; intrinsics are not refined (a map built from the focal-length prior is only as good as that
-prior); the gauge is held by whole views: the first image of the initial pair is constant in every
+Deviations from COLMAP: one model; intrinsics are refined only on request (without the refine options a map built from the focal-length
+prior is only as good as that prior); the gauge is held by whole views: the first image of the initial pair is constant in every
 adjustment, the second only until a third image is registered (option fix_initial_pair keeps it constant throughout), after which the
 scale is left to the damping; no local bundle adjustment, no track merging or re-triangulation beyond the per-round triangulation; no
 database.db, no EXIF.  The host takes the decisions on arrays of
@@ -47,10 +52,12 @@ except Exception:  # pragma: no cover
 from . import _lib, bundle_adjustment, colmap_io, feature_io, geometric_verification, pose, triangulation, two_view
 from .pose import camera_model
 
+INTRINSICS_MIN_VIEWS = 4              # registered views from which a round's adjustment refines the intrinsics
 DEFAULTS = dict(max_error=4.0, min_num_matches=15, init_max_pairs=50, init_min_tri_angle=16.0, min_tri_angle=1.5, create_max_angle_error=2.0,
                 max_reproj_error=4.0, ba_round_iterations=25, ba_final_iterations=100, ba_loss_scale=1.0, max_reg_trials=3,
                 abs_pose_min_num_inliers=30, abs_pose_min_inlier_ratio=0.25, abs_pose_max_error=12.0, round_ratio=0.5, max_images_per_round=16,
-                seed=0, max_refine_iterations=50, max_rounds=64, fix_initial_pair=False)
+                seed=0, max_refine_iterations=50, max_rounds=64, fix_initial_pair=False, refine_focal_length=False, refine_principal_point=False,
+                refine_extra_params=False, intrinsics_min_views=INTRINSICS_MIN_VIEWS)
 STAT_KEYS = triangulation.STAT_KEYS + ("num_input_images",)
 
 
@@ -168,6 +175,11 @@ class DeviceStages:
     def adjust(self, views, n_views, view_constant, xyz, point_constant, point_offsets, obs_view, obs_xy, **kw):
         return bundle_adjustment.adjust(views, n_views, view_constant, xyz, point_constant, point_offsets, obs_view, obs_xy, device=self.device, **kw)
 
+    def adjust_cameras(self, cam_models, cam_params, cam_refine, view_camera, views, n_views, view_constant, xyz, point_constant, point_offsets, obs_view,
+                       obs_xy, **kw):
+        return bundle_adjustment.adjust_cameras(cam_models, cam_params, cam_refine, view_camera, views, n_views, view_constant, xyz, point_constant,
+                                                point_offsets, obs_view, obs_xy, device=self.device, **kw)
+
     def filter(self, views, n_views, xyz, point_offsets, obs_view, obs_xy, max_reproj_error, min_tri_angle):
         return filter_points(views, n_views, xyz, point_offsets, obs_view, obs_xy, max_reproj_error, min_tri_angle, device=self.device)
 
@@ -237,7 +249,8 @@ def reconstruct(cameras, images, keypoints, pair_matches, skip_geometric_verific
     starts as with skip_geometric_verification on the verified matches.  verification "geometry": E, F and H are estimated for every pair and
     the matches of two_view.decide_two_view_geometry's choice stay, so a planar or rotation-only pair keeps its matches
     through H; a pair labelled panoramic, planar_or_panoramic or degenerate is no initial pair (planar is: the five-point pose holds on a
-    plane).  The map then starts as with "fundamental"."""
+    plane).  The map then starts as with "fundamental".  With one of the options refine_focal_length, refine_principal_point,
+    refine_extra_params set the return is (cameras, images, points3D): the camera records with the refined intrinsics first."""
     if verification not in ("essential", "fundamental", "geometry"):
         raise ValueError(f"unknown verification {verification!r}")
     unknown = set(options) - set(DEFAULTS)
@@ -245,6 +258,9 @@ def reconstruct(cameras, images, keypoints, pair_matches, skip_geometric_verific
         raise TypeError(f"unknown options {sorted(unknown)}")
     o = dict(DEFAULTS, **options)
     S = DeviceStages(device) if stages is None else stages
+    mask = bundle_adjustment.refine_mask(o["refine_focal_length"], o["refine_principal_point"], o["refine_extra_params"])
+    if mask:
+        cameras = dict(cameras)                                                   # the refined records replace the given ones, round by round
     rep = {} if report is None else report
     order = sorted(images, key=lambda i: (images[i].name, i))                    # view k <-> input id order[k] <-> output id k + 1
     index = {iid: k for k, iid in enumerate(order)}
@@ -308,6 +324,9 @@ def reconstruct(cameras, images, keypoints, pair_matches, skip_geometric_verific
     _set_pose(views[v1], results[p0]["qvec"], results[p0]["tvec"])
     registered = np.zeros(nv, dtype=bool)
     registered[[v0, v1]] = True
+    cam_ids = sorted({images[i].camera_id for i in order})
+    cam_index = {cid: k for k, cid in enumerate(cam_ids)}
+    view_camera = np.array([cam_index[images[i].camera_id] for i in order], dtype=np.int32)
     constant = np.ones(nv, dtype=np.uint8)                                        # an unregistered view has no observation; it stays as it is
     tries = np.zeros(nv, dtype=np.int64)
     rep.update(initial_pair=(order[v0], order[v1]), initial_pair_index=int(p0), initial_tri_angle_bound=angle, n_pairs=n_pairs,
@@ -347,8 +366,21 @@ def reconstruct(cameras, images, keypoints, pair_matches, skip_geometric_verific
         vc[v0] = 1
         if o["fix_initial_pair"] or registered.sum() == 2:    # the pair's relative pose is held only while nothing else can correct it
             vc[v1] = 1
-        xyz, _, ba = S.adjust(views, nv, vc, xyz, np.zeros(len(xyz), np.uint8), p_off, p_view, p_xy, max_iterations=int(iterations), loss="cauchy",
-                              loss_scale=o["ba_loss_scale"])
+        if mask and registered.sum() >= o["intrinsics_min_views"]:
+            packed = [camera_model(cameras[cid]) for cid in cam_ids]
+            cam_params, xyz, _, ba = S.adjust_cameras([m for m, _ in packed], [p for _, p in packed], [mask] * len(cam_ids), view_camera, views, nv, vc, xyz,
+                                                      np.zeros(len(xyz), np.uint8), p_off, p_view, p_xy, max_iterations=int(iterations), loss="cauchy",
+                                                      loss_scale=o["ba_loss_scale"])
+            for c, cid in enumerate(cam_ids):                 # the records and the views: what the next stage calls read
+                cam = cameras[cid]
+                cameras[cid] = colmap_io.Camera(cam["id"], cam["model"], cam["width"], cam["height"], cam_params[c][:len(cam["params"])])
+            for k in range(nv):
+                for i in range(8):
+                    views[k].params[i] = float(cam_params[view_camera[k]][i])
+            ba = dict(ba, refined_intrinsics=True)
+        else:
+            xyz, _, ba = S.adjust(views, nv, vc, xyz, np.zeros(len(xyz), np.uint8), p_off, p_view, p_xy, max_iterations=int(iterations), loss="cauchy",
+                                  loss_scale=o["ba_loss_scale"])
         tm["adjust_s"] = clock() - t
         t = clock()
         flt = S.filter(views, nv, xyz, p_off, p_view, p_xy, o["max_reproj_error"], o["min_tri_angle"])
@@ -415,6 +447,8 @@ def reconstruct(cameras, images, keypoints, pair_matches, skip_geometric_verific
         pid = int(pid_of_row[r])
         points3D[pid] = colmap_io.Point3D(pid, M["xyz"][r].copy(), np.zeros(3, np.uint8), float(flt["point_error"][r]), (node_view[a:b] + 1).astype(np.int32),
                                           node_idx[a:b].astype(np.int32))
+    if mask:
+        return cameras, out_images, points3D
     return out_images, points3D
 
 
@@ -458,22 +492,32 @@ def read_images(pairs_path, features_path, single_camera=False, reference_sfm_mo
 
 
 def main(sfm_dir, image_dir, pairs, features, matches, colmap_path=None, single_camera=False, skip_geometric_verification=False,
-         min_match_score=None, min_num_matches=None, reference_sfm_model=None, intrinsics=(), device=0, verification="essential", **options):
+         min_match_score=None, min_num_matches=None, reference_sfm_model=None, intrinsics=(), device=0, verification="essential",
+         refine_focal_length=0, refine_principal_point=0, refine_extra_params=0, intrinsics_min_views=None, **options):
     """hloc/reconstruction.py main(): image_dir and colmap_path are accepted and unused.  Writes sfm_dir/models/0/{cameras,images,
     points3D}.bin and sfm_dir/stats.txt (one `key: value` per line; the reference writes the same keys without the newline); returns
-    the statistics."""
+    the statistics.  With a refine option set cameras.bin holds the refined intrinsics."""
     sfm_dir = Path(sfm_dir)
     assert Path(pairs).exists(), pairs
     assert Path(features).exists(), features
     assert Path(matches).exists(), matches
     if min_num_matches is not None:
         options["min_num_matches"] = int(min_num_matches)
+    for key, value in (("refine_focal_length", refine_focal_length), ("refine_principal_point", refine_principal_point),
+                       ("refine_extra_params", refine_extra_params)):
+        if value:
+            options[key] = True
+    if intrinsics_min_views is not None:
+        options["intrinsics_min_views"] = int(intrinsics_min_views)
     cameras, images = read_images(pairs, features, single_camera, reference_sfm_model, intrinsics)
     keypoints, pair_matches = triangulation.read_inputs(images, pairs, features, matches, min_match_score)
     logging.info("Reconstructing from %d pairs over %d images...", len(pair_matches), len(images))
     report = {}
-    out_images, points3D = reconstruct(cameras, images, keypoints, pair_matches, skip_geometric_verification, device=device, report=report,
-                                       verification=verification, **options)
+    out = reconstruct(cameras, images, keypoints, pair_matches, skip_geometric_verification, device=device, report=report, verification=verification,
+                      **options)
+    if len(out) == 3:
+        cameras = out[0]
+    out_images, points3D = out[-2:]
     model = sfm_dir / "models" / "0"
     model.mkdir(parents=True, exist_ok=True)
     used = {im.camera_id for im in out_images.values()}
@@ -503,6 +547,10 @@ def parser():
     ap.add_argument("--intrinsics", type=Path, nargs="+", default=[])
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--verification", choices=("essential", "fundamental", "geometry"), default="essential")
+    ap.add_argument("--refine_focal_length", type=int, choices=(0, 1), default=0)
+    ap.add_argument("--refine_principal_point", type=int, choices=(0, 1), default=0)
+    ap.add_argument("--refine_extra_params", type=int, choices=(0, 1), default=0)
+    ap.add_argument("--intrinsics_min_views", type=int, default=None)
     return ap
 
 

@@ -7,6 +7,12 @@ and no earlier path to compare with.
 
     python tools/bundle_bench.py [--images 200] [--points 60000] [--window 10] [--reps 3] [--out profiles/bundle_bench.json]
 
+With one of --refine_focal_length / --refine_principal_point / --refine_extra_params 1 every camera's focal
+lengths start --focal_off (0.1) too long, the map is triangulated with those cameras, and the same figures are taken three times in
+the same run: intrinsics fixed (adjust, today's call), the scene's four cameras each shared by its images, and a camera per image
+(adjust_cameras); with the mean relative focal-length error before and after.
+    python tools/bundle_bench.py --refine_focal_length 1 --refine_extra_params 1 --out profiles/bundle_cam_bench.json
+
 Kernel times come from a kernel trace of the same tool (no counters in that run):
     rocprofv3 --kernel-trace --stats -d DIR -o ba -- python tools/bundle_bench.py --reps 1"""
 import argparse
@@ -40,6 +46,10 @@ def main():
     ap.add_argument("--shift", type=float, default=0.03)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--refine_focal_length", type=int, choices=(0, 1), default=0)
+    ap.add_argument("--refine_principal_point", type=int, choices=(0, 1), default=0)
+    ap.add_argument("--refine_extra_params", type=int, choices=(0, 1), default=0)
+    ap.add_argument("--focal_off", type=float, default=0.1)
     a = ap.parse_args()
     import torch
     import pose_ref as pr
@@ -47,6 +57,11 @@ def main():
     from triangulate_bench import make_scene
     from sfd2_amd import bundle_adjustment as B, triangulation as T
     cameras, truth, keypoints, pair_m0 = make_scene(a.images, a.points, a.window, 0.0, 0.3, 0)
+    mask = B.refine_mask(a.refine_focal_length, a.refine_principal_point, a.refine_extra_params)
+    true_cameras = cameras
+    if mask:
+        focal = lambda c: [0] if c["model"].startswith("SIMPLE") else [0, 1]
+        cameras = {i: tr.Cam(c, params=[p * (1 + a.focal_off) if k in focal(c) else p for k, p in enumerate(c["params"])]) for i, c in cameras.items()}
     pair_matches = [(i0, i1, np.stack([np.nonzero(m0 >= 0)[0], m0[m0 >= 0]], 1).astype(np.int32)) for i0, i1, m0 in pair_m0]
     rs = np.random.RandomState(1)
     start = {}
@@ -67,13 +82,38 @@ def main():
     pc = np.zeros(len(pids), dtype=np.uint8)
     n_obs = int(len(ov))
 
-    def once(**opts):
+    cam_ids = sorted(cameras)
+    shared = [cam_ids.index(images[i].camera_id) for i in ids]
+
+    def focal_error(params, view_camera):
+        """Mean relative error of the focal lengths of the cameras view_camera names, against the scene's."""
+        errs = []
+        for k in sorted(set(view_camera)):
+            t = true_cameras[images[ids[view_camera.index(k)]].camera_id]
+            n = 1 if t["model"].startswith("SIMPLE") else 2
+            errs += [abs(params[k][j] - t["params"][j]) / t["params"][j] for j in range(n)]
+        return float(np.mean(errs))
+
+    def once(mode="fixed", **opts):
+        """mode: fixed (adjust), shared (one camera per camera id) or per_image (adjust_cameras)."""
         v = B.make_views(cameras, images, ids)[1]
+        view_camera = shared if mode == "shared" else list(range(len(ids)))
+        packed = [B.camera_model(cameras[c]) for c in (cam_ids if mode == "shared" else [images[i].camera_id for i in ids])]
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        out = B.adjust(v, len(ids), vc, xyz, pc, off, ov, xy, **opts)
-        return time.perf_counter() - t0, v, out
+        if mode == "fixed":
+            out = B.adjust(v, len(ids), vc, xyz, pc, off, ov, xy, **opts)
+            params = [p for _, p in packed]
+        else:
+            params, *out = B.adjust_cameras([m for m, _ in packed], [p for _, p in packed], [mask] * len(packed), view_camera, v, len(ids), vc, xyz, pc, off,
+                                            ov, xy, **opts)
+        t = time.perf_counter() - t0
+        once.focal = (focal_error([p for _, p in packed], view_camera), focal_error(params, view_camera))
+        return t, v, tuple(out)
 
+    if mask:
+        return camera_comparison(a, once, out_head=dict(device=torch.cuda.get_device_name(0), images=len(ids), points=len(pids), observations=n_obs,
+                                                        refine=mask, focal_off=a.focal_off))
     rows = []
     for rep in range(a.reps + 1):                              # the first pass warms up (context, buffers) and is not reported
         t_full, v, (new_xyz, err, report) = once()
@@ -97,6 +137,31 @@ def main():
            "note": "wall clock of the whole call, host packing and copies included; no baseline exists (no COLMAP or Ceres, no earlier path); the "
                    "flagship path (bench.py) calls none of this code"}
     print(json.dumps({k: v for k, v in out.items() if k != "reps"}), flush=True)
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+
+
+def camera_comparison(a, once, out_head):
+    """The three modes in one run: per mode the medians over --reps of ms per LM iteration, PCG iterations per step and ms per product, and
+    the focal-length error before and after."""
+    out = dict(out_head, modes={}, note="wall clock of the whole call, host packing and copies included; the three modes in the same run of the tool")
+    for mode in ("fixed", "shared", "per_image"):
+        rows = []
+        for rep in range(a.reps + 1):                          # the first pass warms up and is not reported
+            t_full, _, (_, err, report) = once(mode)
+            focal = once.focal
+            t_lo, _, (_, _, r_lo) = once(mode, max_iterations=1, pcg_tolerance=0.0, pcg_max_iterations=10)
+            t_hi, _, (_, _, r_hi) = once(mode, max_iterations=1, pcg_tolerance=0.0, pcg_max_iterations=60)
+            if rep:
+                rows.append({"adjust_s": t_full, "ms_per_lm_iteration": 1e3 * t_full / max(report["iterations"], 1),
+                             "pcg_iterations_per_step": report["pcg_iterations"] / max(report["iterations"], 1),
+                             "ms_per_product": 1e3 * (t_hi - t_lo) / max(r_hi["pcg_iterations"] - r_lo["pcg_iterations"], 1)})
+        med = {k: float(np.median([r[k] for r in rows])) for k in rows[0]}
+        out["modes"][mode] = dict(med, lm_iterations=report["iterations"], accepted_steps=report["accepted_steps"], status=report["status"],
+                                  initial_cost=report["initial_cost"], final_cost=report["final_cost"], mean_reprojection_error_after=float(err.mean()),
+                                  focal_error_before=focal[0], focal_error_after=focal[1], reps=rows)
+        print(mode, json.dumps({k: v for k, v in out["modes"][mode].items() if k != "reps"}), flush=True)
     if a.out:
         with open(a.out, "w") as f:
             json.dump(out, f, indent=1)
