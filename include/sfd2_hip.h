@@ -85,7 +85,7 @@ typedef struct {
     int64_t n_candidates; /* N0 after NMS + threshold + border of the last extract          */
 } sfd2_timings;
 
-int sfd2_version(void);   /* 100 = rounds 1-4; 105 adds sfd2_extract_record_async, sfd2_desc_pack and host outputs with SFD2_FLAG_ASYNC; 106 adds sfd2_get_margin_status; 107 adds sfd2_get_relax_status (option "c3b_plain"); 108 adds sfd2_get_option, sfd2_device_pci_bus_id, SFD2_FLAG_DESC_STORE64; 109 adds the baseline JPEG decoder (sfd2_jpeg_*); 112 adds the SfM map (sfd2_verify_matches_batch, sfd2_build_tracks, sfd2_triangulate_tracks); 113 adds the pair selection (sfd2_pairs_retrieval, sfd2_pairs_covisibility, sfd2_pairs_poses); 114 adds sfd2_covis_clusters; 115 adds sfd2_covis_frames; 116 adds the VLAD global descriptors (sfd2_vlad_assign, sfd2_vlad_aggregate, sfd2_vlad_kmeans); 117 adds sfd2_relative_pose_batch; 118 adds sfd2_bundle_adjust; 119 adds the mapper's bookkeeping (sfd2_mapper_restrict, sfd2_mapper_filter, sfd2_mapper_visible, sfd2_mapper_assemble); 120 adds sfd2_fundamental_batch; 121 adds sfd2_homography_batch; 122 adds sfd2_match_guided_batch; 123 adds sfd2_bundle_adjust_cameras */
+int sfd2_version(void);   /* 100 = rounds 1-4; 105 adds sfd2_extract_record_async, sfd2_desc_pack and host outputs with SFD2_FLAG_ASYNC; 106 adds sfd2_get_margin_status; 107 adds sfd2_get_relax_status (option "c3b_plain"); 108 adds sfd2_get_option, sfd2_device_pci_bus_id, SFD2_FLAG_DESC_STORE64; 109 adds the baseline JPEG decoder (sfd2_jpeg_*); 112 adds the SfM map (sfd2_verify_matches_batch, sfd2_build_tracks, sfd2_triangulate_tracks); 113 adds the pair selection (sfd2_pairs_retrieval, sfd2_pairs_covisibility, sfd2_pairs_poses); 114 adds sfd2_covis_clusters; 115 adds sfd2_covis_frames; 116 adds the VLAD global descriptors (sfd2_vlad_assign, sfd2_vlad_aggregate, sfd2_vlad_kmeans); 117 adds sfd2_relative_pose_batch; 118 adds sfd2_bundle_adjust; 119 adds the mapper's bookkeeping (sfd2_mapper_restrict, sfd2_mapper_filter, sfd2_mapper_visible, sfd2_mapper_assemble); 120 adds sfd2_fundamental_batch; 121 adds sfd2_homography_batch; 122 adds sfd2_match_guided_batch; 123 adds sfd2_bundle_adjust_cameras; 124 adds sfd2_spd_solve and sfd2_ba_conf.solver (SFD2_BA_SOLVER_DENSE) */
 const char *sfd2_last_error(void);
 
 int sfd2_ctx_create(int device, sfd2_ctx **out);
@@ -814,7 +814,9 @@ int sfd2_triangulate_tracks(sfd2_ctx *ctx, const sfd2_tri_view *views, int n_vie
 
 /* ------------------------------------------------------------------------------------------------ bundle adjustment
  * Levenberg-Marquardt over camera poses and 3D points with the points eliminated (Schur complement) and the reduced camera system
- * solved by matrix-free preconditioned conjugate gradients, block-Jacobi preconditioned.  Conventions of the
+ * solved by matrix-free preconditioned conjugate gradients, block-Jacobi preconditioned, or (version 124,
+ * conf.solver = SFD2_BA_SOLVER_DENSE) formed as a dense matrix and solved by a Cholesky factorisation: an exact
+ * step instead of an inexact one, for up to SFD2_BA_DENSE_MAX_VIEWS views, sfd2_bundle_adjust only.  Conventions of the
  * SfM-map section: host arrays, the call runs on sfd2_get_stream() and synchronises before it returns, returns -1 with
  * sfd2_last_error() set on a bad argument, non-finite input or an index out of range (the message names the first offending index).
  * fp64, fixed-order sums, no floating-point atomics: the result depends on the inputs (and the flags) only, two calls give the same
@@ -828,6 +830,9 @@ int sfd2_triangulate_tracks(sfd2_ctx *ctx, const sfd2_tri_view *views, int n_vie
 #define SFD2_BA_ST_NONFINITE 4         /*   the cost of the given state is not finite: nothing was written                      */
 #define SFD2_BA_FLAG_POINT_LANE 1      /* every point's sums by one lane, whatever its track length                             */
 #define SFD2_BA_FLAG_POINT_WAVE 2      /* every point's sums by one wave (default: a wave beyond 64 observations, else a lane)  */
+#define SFD2_BA_SOLVER_PCG 0           /* conf.solver: matrix-free preconditioned conjugate gradients (a zeroed conf)            */
+#define SFD2_BA_SOLVER_DENSE 1         /*   the reduced camera system as a dense fp64 matrix, Cholesky; result.pcg_iterations = 0 */
+#define SFD2_BA_DENSE_MAX_VIEWS 2048   /* the dense solver's limit: S is stored as a full [6 n_views]^2 fp64 matrix, 1.2 GB here  */
 typedef struct {
     int32_t max_iterations;         /* LM steps tried at the most (100)                                                    */
     int32_t pcg_max_iterations;     /* conjugate-gradient iterations per step at the most (100)                            */
@@ -838,7 +843,8 @@ typedef struct {
     double pcg_tolerance;           /* PCG stops at |r_k| <= pcg_tolerance |r_0| (0.1)                                     */
     double loss_scale;              /* c of the Cauchy loss, pixels                                                        */
     double initial_lambda;          /* 1e-4                                                                                */
-    int32_t reserved[4];            /* zero                                                                                */
+    int32_t solver;                 /* SFD2_BA_SOLVER_* (0: PCG); any other value is refused                               */
+    int32_t reserved[3];            /* zero                                                                                */
 } sfd2_ba_conf;
 typedef struct {
     int32_t status;                 /* SFD2_BA_ST_*                                                                        */
@@ -875,6 +881,13 @@ int sfd2_bundle_adjust_cameras(sfd2_ctx *ctx, sfd2_ba_camera *cameras, int n_cam
                                int n_views, const uint8_t *view_constant, double *xyz, int n_points, const uint8_t *point_constant,
                                const int64_t *point_offsets, const int32_t *obs_view, const double *obs_xy, const sfd2_ba_conf *conf,
                                sfd2_ba_result *result, double *obs_error, int flags);
+
+/* (version 124) A x = b for a symmetric positive definite A by the dense solver's kernels: a blocked fp64 Cholesky factorisation on
+ * the device and two triangular solves.  Host arrays; A is [n][n] row-major and only its lower triangle is read; 1 <= n <= 6 *
+ * SFD2_BA_DENSE_MAX_VIEWS.  Returns 0 with *info = 0 and x[n] written; 0 with *info = k + 1 when pivot k is the first that is <= 0 or
+ * not finite (A is not positive definite to working precision), x untouched; -1 with sfd2_last_error() set on a bad argument or a
+ * non-finite entry of the lower triangle or of b.  Fixed-order sums: two calls give the same bytes. */
+int sfd2_spd_solve(sfd2_ctx *ctx, const double *A, int n, const double *b, double *x, int32_t *info);
 
 /* ------------------------------------------------------------------------------------------------ incremental mapper
  * The bookkeeping between relative pose, absolute pose, triangulation and bundle adjustment in a round of sfd2_amd.reconstruction

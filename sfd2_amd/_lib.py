@@ -195,7 +195,7 @@ class BaConf(ctypes.Structure):
     """sfd2_ba_conf (include/sfd2_hip.h)."""
     _fields_ = [("max_iterations", ctypes.c_int32), ("pcg_max_iterations", ctypes.c_int32), ("loss", ctypes.c_int32), ("pcg_batch", ctypes.c_int32),
                 ("gradient_tolerance", ctypes.c_double), ("function_tolerance", ctypes.c_double), ("pcg_tolerance", ctypes.c_double),
-                ("loss_scale", ctypes.c_double), ("initial_lambda", ctypes.c_double), ("reserved", ctypes.c_int32 * 4)]
+                ("loss_scale", ctypes.c_double), ("initial_lambda", ctypes.c_double), ("solver", ctypes.c_int32), ("reserved", ctypes.c_int32 * 3)]
 
 
 class BaResult(ctypes.Structure):
@@ -213,6 +213,8 @@ BA_REFINE_FOCAL, BA_REFINE_PRINCIPAL, BA_REFINE_EXTRA = 1, 2, 4
 BA_LOSS_TRIVIAL, BA_LOSS_CAUCHY = 0, 1                                              # SFD2_BA_*
 BA_ST_GRADIENT, BA_ST_FUNCTION, BA_ST_MAX_ITERATIONS, BA_ST_LAMBDA, BA_ST_NONFINITE = 0, 1, 2, 3, 4
 BA_FLAG_POINT_LANE, BA_FLAG_POINT_WAVE = 1, 2
+BA_SOLVER_PCG, BA_SOLVER_DENSE = 0, 1
+BA_DENSE_MAX_VIEWS = 2048
 MAPPER_FLAG_TRACK_LANE, MAPPER_FLAG_TRACK_WAVE = 1, 2                             # SFD2_MAPPER_*
 TRI_MAX_POINTS = 4
 TRI_ST_RANGE, TRI_ST_NOT_CONVERGED = 1, 2
@@ -259,7 +261,7 @@ EXPORTS = [
     "sfd2_assemble_2d3d", "sfd2_verify_matches_batch", "sfd2_build_tracks", "sfd2_triangulate_tracks",
     "sfd2_pairs_retrieval", "sfd2_pairs_covisibility", "sfd2_pairs_poses", "sfd2_covis_clusters",
     "sfd2_covis_frames", "sfd2_vlad_assign", "sfd2_vlad_aggregate", "sfd2_vlad_kmeans",
-    "sfd2_relative_pose_batch", "sfd2_fundamental_batch", "sfd2_homography_batch", "sfd2_match_guided_batch", "sfd2_bundle_adjust", "sfd2_bundle_adjust_cameras",
+    "sfd2_relative_pose_batch", "sfd2_fundamental_batch", "sfd2_homography_batch", "sfd2_match_guided_batch", "sfd2_bundle_adjust", "sfd2_bundle_adjust_cameras", "sfd2_spd_solve",
     "sfd2_mapper_restrict", "sfd2_mapper_filter", "sfd2_mapper_visible", "sfd2_mapper_assemble",
 ]
 
@@ -365,6 +367,7 @@ def load():
     lib.sfd2_vlad_kmeans.argtypes = [vp, vp, i64, ci, ci, ci, vp, vp, vp, pi, ci]
     lib.sfd2_bundle_adjust.argtypes = [vp, ctypes.POINTER(TriView), ci, vp, vp, ci, vp, vp, vp, vp, ctypes.POINTER(BaConf), ctypes.POINTER(BaResult), vp, ci]
     lib.sfd2_bundle_adjust_cameras.argtypes = [vp, ctypes.POINTER(BaCamera), ci, vp] + lib.sfd2_bundle_adjust.argtypes[1:]
+    lib.sfd2_spd_solve.argtypes = [vp, vp, ci, vp, vp, vp]
     lib.sfd2_mapper_restrict.argtypes = [vp, vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, ctypes.POINTER(i64), ctypes.POINTER(i64), ci]
     lib.sfd2_mapper_filter.argtypes = [vp, ctypes.POINTER(TriView), ci, vp, ci, vp, vp, vp, cd, cd, vp, vp, vp, vp, ci]
     lib.sfd2_mapper_visible.argtypes = [vp, vp, ci, vp, vp, ci, vp, vp, ci, vp, ci]

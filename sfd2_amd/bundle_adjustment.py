@@ -1,14 +1,17 @@
 """Bundle adjustment on the device (include/sfd2_hip.h sfd2_bundle_adjust): Levenberg-Marquardt over camera
-poses and 3D points, the points eliminated, the reduced camera system solved by matrix-free preconditioned conjugate gradients.
+poses and 3D points, the points eliminated, the reduced camera system solved by matrix-free preconditioned conjugate gradients
+(solver="pcg", the default) or formed as a dense matrix and solved by a Cholesky factorisation on the device (solver="dense", DESIGN.md
+section 21: up to 2048 views, constant intrinsics only).
 The joint refinement `colmap bundle_adjuster` does for a model, reduced to what is built: the loss is trivial or Cauchy; intrinsics
 stay fixed unless one of the refine options is set (sfd2_bundle_adjust_cameras).
 
   adjust          the C call on numpy arrays.
   adjust_cameras  the C call with camera intrinsics among the unknowns, on numpy arrays.
+  spd_solve       A x = b for a symmetric positive definite A by the dense solver's factor and solve kernels.
   bundle_adjust   on colmap_io records: returns new images, new points3D (error = mean reprojection error of the point) and the report;
                   with a refine option also the new cameras, first.
   main / command  python -m sfd2_amd.bundle_adjustment --input_path M --output_path O [--max_num_iterations N]
-                  [--loss trivial|cauchy] [--loss_scale S] [--constant_images FILE]
+                  [--loss trivial|cauchy] [--loss_scale S] [--constant_images FILE] [--solver pcg|dense]
                   [--refine_focal_length 0|1] [--refine_principal_point 0|1] [--refine_extra_params 0|1]
 
 Without --constant_images the two registered images with the smallest ids keep their poses.  COLMAP fixes the first image's pose and
@@ -31,7 +34,8 @@ from .pose import camera_model
 from .triangulation import make_views
 
 DEFAULTS = dict(max_iterations=100, gradient_tolerance=1e-10, function_tolerance=0.0, pcg_tolerance=0.1, pcg_max_iterations=100,
-                pcg_batch=0, loss="trivial", loss_scale=1.0, initial_lambda=1e-4)
+                pcg_batch=0, loss="trivial", loss_scale=1.0, initial_lambda=1e-4, solver="pcg")
+SOLVERS = {"pcg": _lib.BA_SOLVER_PCG, "dense": _lib.BA_SOLVER_DENSE}
 LOSSES = {"trivial": _lib.BA_LOSS_TRIVIAL, "cauchy": _lib.BA_LOSS_CAUCHY}
 STATUS = {_lib.BA_ST_GRADIENT: "gradient_tolerance", _lib.BA_ST_FUNCTION: "function_tolerance", _lib.BA_ST_MAX_ITERATIONS: "max_iterations",
           _lib.BA_ST_LAMBDA: "lambda_overflow", _lib.BA_ST_NONFINITE: "non_finite_cost"}
@@ -44,7 +48,10 @@ def _conf(options):
     o = dict(DEFAULTS, **options)
     if o["loss"] not in LOSSES:
         raise ValueError(f"loss {o['loss']!r} is not supported (one of {', '.join(LOSSES)})")
+    if o["solver"] not in SOLVERS:
+        raise ValueError(f"solver {o['solver']!r} is not supported (one of {', '.join(SOLVERS)})")
     conf = _lib.BaConf()
+    conf.solver = SOLVERS[o["solver"]]
     conf.max_iterations, conf.pcg_max_iterations = int(o["max_iterations"]), int(o["pcg_max_iterations"])
     conf.loss, conf.pcg_batch = LOSSES[o["loss"]], int(o["pcg_batch"])
     conf.gradient_tolerance, conf.function_tolerance = float(o["gradient_tolerance"]), float(o["function_tolerance"])
@@ -71,6 +78,8 @@ def adjust_cameras(cam_models, cam_params, cam_refine, view_camera, views, n_vie
     zero padded), cam_refine [n_cameras] (SFD2_BA_REFINE_* bits, 0 = constant), view_camera [n_views] (index into the cameras).  The
     views' own model / params words are not read; they leave with their camera's new values.  Returns (cam_params [n_cameras, 8], xyz,
     obs_error, report)."""
+    if options.get("solver", DEFAULTS["solver"]) == "dense":
+        raise ValueError('solver "dense" does not take camera intrinsics among the unknowns (DESIGN.md section 21): use solver "pcg" with a refine option')
     models = np.ascontiguousarray(cam_models, dtype=np.int32).reshape(-1)
     params = np.array(cam_params, dtype=np.float64).reshape(-1, 8)
     refine = np.ascontiguousarray(cam_refine, dtype=np.int32).reshape(-1)
@@ -129,8 +138,24 @@ def _adjust(cameras, views, n_views, view_constant, xyz, point_constant, point_o
         _lib.check(ctx.lib.sfd2_bundle_adjust_cameras(ctx.h, cameras[0], cameras[1], cameras[2].ctypes.data, *rest))
     report = {"status": STATUS[res.status], "iterations": int(res.iterations), "accepted_steps": int(res.accepted_steps),
               "pcg_iterations": int(res.pcg_iterations), "initial_cost": float(res.initial_cost), "final_cost": float(res.final_cost),
-              "gradient_max": float(res.gradient_max), "lambda": float(res.lambda_)}
+              "gradient_max": float(res.gradient_max), "lambda": float(res.lambda_),
+              "solver": dict((v, k) for k, v in SOLVERS.items())[conf.solver]}
     return pts, err, report
+
+
+def spd_solve(A, b, device=0):
+    """A x = b for a symmetric positive definite A [n, n] (only its lower triangle is read) and b [n], fp64, by a blocked Cholesky
+    factorisation on the device (sfd2_spd_solve).  Returns (x, info): info = 0 and the solution, or info = k + 1 for the first pivot
+    k that is not positive, with x = None.  Non-finite input raises."""
+    A = np.ascontiguousarray(A, dtype=np.float64)
+    b = np.ascontiguousarray(b, dtype=np.float64).reshape(-1)
+    if A.ndim != 2 or A.shape[0] != A.shape[1] or len(b) != A.shape[0] or len(b) < 1:
+        raise ValueError("A must be [n, n] and b [n], n >= 1")
+    x = np.zeros(len(b), dtype=np.float64)
+    info = ctypes.c_int32(0)
+    ctx = _lib.default_context(device)
+    _lib.check(ctx.lib.sfd2_spd_solve(ctx.h, A.ctypes.data, len(b), b.ctypes.data, x.ctypes.data, ctypes.byref(info)))
+    return (x if info.value == 0 else None), int(info.value)
 
 
 def pack_model(cameras, images, points3D):
@@ -168,6 +193,8 @@ def bundle_adjust(cameras, images, points3D, constant_images=(), constant_points
     one camera: images that share it share its parameters), and the return is (new cameras, new images, new points3D, report)."""
     _conf(options)
     mask = refine_mask(refine_focal_length, refine_principal_point, refine_extra_params)
+    if mask and options.get("solver", DEFAULTS["solver"]) == "dense":
+        raise ValueError('solver "dense" does not take camera intrinsics among the unknowns (DESIGN.md section 21): use solver "pcg" with a refine option')
     ids, views, pids, xyz, off, ov, xy = pack_model(cameras, images, points3D)
     if not ids:
         raise ValueError("the model has no observations")
@@ -227,7 +254,7 @@ def read_constant_images(path, images):
 
 
 def main(input_path, output_path, max_num_iterations=DEFAULTS["max_iterations"], loss="trivial", loss_scale=1.0, constant_images=None,
-         refine_focal_length=0, refine_principal_point=0, refine_extra_params=0, **options):
+         refine_focal_length=0, refine_principal_point=0, refine_extra_params=0, solver=DEFAULTS["solver"], **options):
     """Reads the model at input_path, adjusts it, writes it to output_path (with a refine option: the refined cameras too); returns the
     report."""
     input_path, output_path = Path(input_path), Path(output_path)
@@ -235,7 +262,7 @@ def main(input_path, output_path, max_num_iterations=DEFAULTS["max_iterations"],
     const = default_constant_images(images) if constant_images is None else read_constant_images(constant_images, images)
     out = bundle_adjust(cameras, images, points3D, constant_images=const, max_iterations=max_num_iterations, loss=loss, loss_scale=loss_scale,
                         refine_focal_length=bool(refine_focal_length), refine_principal_point=bool(refine_principal_point),
-                        refine_extra_params=bool(refine_extra_params), **options)
+                        refine_extra_params=bool(refine_extra_params), **({} if solver == DEFAULTS["solver"] else {"solver": solver}), **options)
     if len(out) == 4:
         cameras = out[0]
     out_images, out_points, report = out[-3:]
@@ -256,6 +283,7 @@ def parser():
     ap.add_argument("--refine_focal_length", type=int, choices=(0, 1), default=0)
     ap.add_argument("--refine_principal_point", type=int, choices=(0, 1), default=0)
     ap.add_argument("--refine_extra_params", type=int, choices=(0, 1), default=0)
+    ap.add_argument("--solver", choices=sorted(SOLVERS), default=DEFAULTS["solver"])
     return ap
 
 

@@ -1,11 +1,15 @@
 // libsfd2hip: sfd2_bundle_adjust and sfd2_bundle_adjust_cameras -- check and pack the inputs, build the by-view CSR, and drive the
 // Levenberg-Marquardt loop of bundle_kernels.hip on the context's stream.  The accept / reject decision is taken on
 // the device, so the host reads the state block once per LM iteration and once per batch of PCG iterations.  With cameras among the
-// unknowns (section 20) the same loop queues the passes of bundle_cam_kernels.hip where a pass has to know about them.
+// unknowns (section 20) the same loop queues the passes of bundle_cam_kernels.hip where a pass has to know about them.  With
+// conf->solver = SFD2_BA_SOLVER_DENSE (section 21) the conjugate gradients give way to bundle_dense_kernels.hip: the pair list is built
+// once per call (integer kernels and rocPRIM's stable radix sort), S is formed, factored and solved per step; sfd2_spd_solve runs the same
+// factor and solve kernels on a caller's matrix.
 #include "sfd2_ctx.h"
 #include "api_scratch.h"
 #include "pose_camera.h"
 #include "bundle_cam.h"
+#include <rocprim/rocprim.hpp>
 
 namespace {
 
@@ -70,7 +74,12 @@ int ba_run(sfd2_ctx *c, const std::string &F, sfd2_ba_camera *cameras, int n_cam
     if (!(conf->initial_lambda > 0) || !std::isfinite(conf->initial_lambda)) return fail(F + "initial_lambda must be positive and finite");
     if (conf->loss != SFD2_BA_LOSS_TRIVIAL && conf->loss != SFD2_BA_LOSS_CAUCHY) return fail(F + "loss must be SFD2_BA_LOSS_TRIVIAL or SFD2_BA_LOSS_CAUCHY");
     if (conf->loss == SFD2_BA_LOSS_CAUCHY && (!(conf->loss_scale > 0) || !std::isfinite(conf->loss_scale))) return fail(F + "loss_scale must be positive and finite");
-    if (conf->reserved[0] || conf->reserved[1] || conf->reserved[2] || conf->reserved[3]) return fail(F + "reserved words must be zero");
+    if (conf->solver != SFD2_BA_SOLVER_PCG && conf->solver != SFD2_BA_SOLVER_DENSE) return fail(F + "solver must be SFD2_BA_SOLVER_PCG or SFD2_BA_SOLVER_DENSE");
+    if (conf->reserved[0] || conf->reserved[1] || conf->reserved[2]) return fail(F + "reserved words must be zero");
+    const bool DENSE = conf->solver == SFD2_BA_SOLVER_DENSE;
+    if (DENSE && CAM) return fail(F + "the dense solver does not take camera intrinsics among the unknowns: solver must be SFD2_BA_SOLVER_PCG");
+    if (DENSE && n_views > SFD2_BA_DENSE_MAX_VIEWS)
+        return fail(F + "the dense solver takes at most SFD2_BA_DENSE_MAX_VIEWS = " + std::to_string(SFD2_BA_DENSE_MAX_VIEWS) + " views, got " + std::to_string(n_views));
     if (!monotone(point_offsets, n_points)) return fail(F + "point_offsets must start at 0 and not decrease");
     const int64_t O = point_offsets[n_points];
     if (O > 0x7fffffffLL) return fail(F + "more than 2^31 - 1 observations");
@@ -133,6 +142,22 @@ int ba_run(sfd2_ctx *c, const std::string &F, sfd2_ba_camera *cameras, int n_cam
         const bool wave = (flags & SFD2_BA_FLAG_POINT_WAVE) || (!(flags & SFD2_BA_FLAG_POINT_LANE) && len > SFD2_BA_LONG_TRACK);
         (wave ? long_ids : short_ids).push_back(j);
     }
+    // the dense solver's pair list: observation a pairs with every observation b of its point whose view is not beyond a's own
+    std::vector<int64_t> pair_off;
+    if (DENSE) {
+        pair_off.assign(no + 1, 0);
+        std::vector<int32_t> sorted;
+        for (int j = 0; j < n_points; ++j) {
+            sorted.assign(obs_view + point_offsets[j], obs_view + point_offsets[j + 1]);
+            std::sort(sorted.begin(), sorted.end());
+            for (int64_t o = point_offsets[j]; o < point_offsets[j + 1]; ++o)
+                pair_off[(size_t)o + 1] = pair_off[(size_t)o] + (std::upper_bound(sorted.begin(), sorted.end(), obs_view[o]) - sorted.begin());
+        }
+        if (pair_off[no] > 0x7fffffffLL) return fail(F + "the dense solver's pair list would hold more than 2^31 - 1 entries (" + std::to_string(pair_off[no]) + ")");
+    }
+    const size_t n_pairs = DENSE ? (size_t)pair_off[no] : 0, n_keys = nv * nv, ld = (6 * nv + SFD2_BA_DENSE_TILE - 1) / SFD2_BA_DENSE_TILE * SFD2_BA_DENSE_TILE;
+    unsigned key_bits = 1;
+    while (key_bits < 32 && ((size_t)1 << key_bits) < n_keys) ++key_bits;
 
     HIPCHECK(hipSetDevice(c->device));
     Carve in, ws;
@@ -153,6 +178,18 @@ int ba_run(sfd2_ctx *c, const std::string &F, sfd2_ba_camera *cameras, int n_cam
         o_camc = ws.take(sizeof(PoseCam) * nc); o_camt = ws.take(sizeof(PoseCam) * nc); o_bad = ws.take(4); o_reck = ws.take(16 * (size_t)kmax * no);
         o_W = ws.take(8 * 48 * nv); o_Cp = ws.take(8 * 36 * nv); o_gkp = ws.take(8 * SFD2_BA_CAM_K * nv); o_qkp = ws.take(8 * SFD2_BA_CAM_K * nv);
         o_C = ws.take(8 * 64 * nc); o_gk = ws.take(8 * SFD2_BA_CAM_K * nc); o_Ci = ws.take(8 * 64 * nc); o_Dk = ws.take(8 * SFD2_BA_CAM_K * nc);
+    }
+    size_t o_pf = 0, o_S = 0, o_G = 0, o_k0 = 0, o_k1 = 0, o_v0 = 0, o_v1 = 0, o_tmp = 0, o_bs = 0, o_dw = 0, o_dy = 0, o_fail = 0, tmp_sort = 0;
+    if (DENSE) {
+        if (n_pairs) {
+            uint32_t *nk = nullptr;
+            uint64_t *nl = nullptr;
+            HIPCHECK(rocprim::radix_sort_pairs(nullptr, tmp_sort, nk, nk, nl, nl, n_pairs, 0, key_bits, c->stream));
+        }
+        o_pf = in.take(8 * (no + 1));
+        o_S = ws.take(8 * ld * ld); o_G = ws.take(144 * no); o_k0 = ws.take(4 * n_pairs); o_k1 = ws.take(4 * n_pairs); o_v0 = ws.take(8 * n_pairs);
+        o_v1 = ws.take(8 * n_pairs); o_tmp = ws.take(tmp_sort); o_bs = ws.take(4 * (n_keys + 1)); o_dw = ws.take(8 * ld); o_dy = ws.take(8 * ld);
+        o_fail = ws.take(4);
     }
     HIPCHECK(hipStreamSynchronize(c->stream));
     HIPCHECK(grow(c->ba_in, in.off));
@@ -225,6 +262,23 @@ int ba_run(sfd2_ctx *c, const std::string &F, sfd2_ba_camera *cameras, int n_cam
         Q.nc = n_cameras; Q.kmax = kmax;
     }
 
+    BaDense D;
+    memset(&D, 0, sizeof(D));
+    if (DENSE) {                                             // once per call: the pair list by block, every block's start, the padding of S
+        HIPCHECK(hipMemcpyAsync(di + o_pf, pair_off.data(), 8 * (no + 1), hipMemcpyHostToDevice, s));
+        D.S = at<double>(dw, o_S); D.ld = (int64_t)ld; D.G = at<double>(dw, o_G); D.pairs = at<const uint64_t>(dw, o_v1);
+        D.blk_start = at<const int32_t>(dw, o_bs); D.w = at<double>(dw, o_dw); D.y = at<double>(dw, o_dy); D.fail = at<int32_t>(dw, o_fail);
+        ProfScope ps(c, "bundle_adjust", "ba_dense_pairs+sort", 0.0, 24.0 * (double)n_pairs);
+        launch_ba_dense_pairs(s, P, at<const int64_t>(di, o_pf), at<uint32_t>(dw, o_k0), at<uint64_t>(dw, o_v0));
+        if (n_pairs) {
+            size_t tb = tmp_sort;
+            HIPCHECK(rocprim::radix_sort_pairs(dw + o_tmp, tb, at<uint32_t>(dw, o_k0), at<uint32_t>(dw, o_k1), at<uint64_t>(dw, o_v0), at<uint64_t>(dw, o_v1),
+                                               n_pairs, 0, key_bits, s));
+        }
+        launch_ba_dense_block_start(s, at<const uint32_t>(dw, o_k1), (int64_t)n_pairs, (int64_t)n_keys, at<int32_t>(dw, o_bs));
+        launch_dense_pad(s, D.S, D.ld, 6 * n_views);
+    }
+
     const double c2 = conf->loss == SFD2_BA_LOSS_CAUCHY ? conf->loss_scale * conf->loss_scale : 1.0;
     // the state's Jacobians, blocks, gradients and max |g|: behind the start (gate none) or behind an accepted step
     auto linearise = [&](int gate, bool full, bool trial) {
@@ -271,7 +325,13 @@ int ba_run(sfd2_ctx *c, const std::string &F, sfd2_ba_camera *cameras, int n_cam
         if (iters >= conf->max_iterations) break;
         launch_ba_point_invert(s, P);
         launch_ba_view_precond(s, P);
-        if (CAM) {
+        if (DENSE) {                                         // S dc = b by a factorisation: no read of the state inside the step
+            launch_ba_view_apply(s, P, SFD2_BA_GATE_NONE, true);
+            HIPCHECK(hipMemsetAsync(D.fail, 0, 4, s));
+            launch_ba_dense_form(s, P, D);
+            launch_dense_cholesky(s, D.S, D.ld, D.fail);
+            launch_dense_solve(s, D.S, D.ld, 6 * n_views, P.b, D.w, D.y, P.x, D.fail);
+        } else if (CAM) {
             launch_bac_cam_precond(s, Q);
             launch_bac_apply(s, Q, SFD2_BA_GATE_NONE, true);
             launch_bac_pcg_init(s, Q);
@@ -279,7 +339,7 @@ int ba_run(sfd2_ctx *c, const std::string &F, sfd2_ba_camera *cameras, int n_cam
             launch_ba_view_apply(s, P, SFD2_BA_GATE_NONE, true);
             launch_ba_pcg_init(s, P);
         }
-        for (int k = 0; k < conf->pcg_max_iterations;) {
+        for (int k = 0; k < conf->pcg_max_iterations && !DENSE;) {
             for (int e = std::min(conf->pcg_max_iterations, k + batch); k < e; ++k) {
                 if (CAM) {
                     launch_bac_point_apply(s, Q, SFD2_BA_GATE_PCG, P.p);
@@ -294,7 +354,7 @@ int ba_run(sfd2_ctx *c, const std::string &F, sfd2_ba_camera *cameras, int n_cam
             HIPCHECK(read_state());
             if (hs.pcg_done) break;
         }
-        pcg_total += hs.pcg_iters;
+        if (!DENSE) pcg_total += hs.pcg_iters;
         if (CAM) {
             launch_bac_point_apply(s, Q, SFD2_BA_GATE_NONE, P.x);
             launch_bac_update_cams(s, Q);
@@ -305,6 +365,7 @@ int ba_run(sfd2_ctx *c, const std::string &F, sfd2_ba_camera *cameras, int n_cam
         linearise(SFD2_BA_GATE_NONE, false, true);
         launch_ba_reduce(s, P, SFD2_BA_GATE_NONE, P.obs_cost, O, SFD2_BA_OP_SUM, &P.st->trial_cost, false);
         if (CAM) launch_bac_veto(s, Q);
+        if (DENSE) launch_ba_dense_veto(s, P, D);            // a failed pivot: a rejected step
         launch_ba_decide_commit(s, P);
         if (CAM) launch_bac_commit_cams(s, Q);
         relinearise(SFD2_BA_GATE_ACCEPTED);
@@ -365,4 +426,43 @@ extern "C" int sfd2_bundle_adjust_cameras(sfd2_ctx *c, sfd2_ba_camera *cameras, 
     if (n_cameras < 1) return fail(F + "n_cameras must be positive");
     return ba_run(c, F, cameras, n_cameras, view_camera, views, n_views, view_constant, xyz, n_points, point_constant, point_offsets, obs_view, obs_xy, conf,
                   result, obs_error, flags);
+}
+
+// A x = b for a symmetric positive definite A by the dense solver's factor and solve kernels (bundle_dense_kernels.hip)
+extern "C" int sfd2_spd_solve(sfd2_ctx *c, const double *A, int n, const double *b, double *x, int32_t *info)
+{
+    const std::string F("sfd2_spd_solve: ");
+    if (!c || !A || !b || !x || !info) return fail(F + "null argument");
+    if (n < 1 || n > 6 * SFD2_BA_DENSE_MAX_VIEWS) return fail(F + "1 <= n <= " + std::to_string(6 * SFD2_BA_DENSE_MAX_VIEWS));
+    const size_t N = (size_t)n, ld = (N + SFD2_BA_DENSE_TILE - 1) / SFD2_BA_DENSE_TILE * SFD2_BA_DENSE_TILE;
+    for (size_t r = 0; r < N; ++r)                           // only the lower triangle is read
+        if (!all_finite(A + r * N, (int64_t)r + 1)) return fail(F + "row " + std::to_string(r) + ": non-finite entry in the lower triangle");
+    if (!all_finite(b, n)) return fail(F + "non-finite right-hand side");
+    HIPCHECK(hipSetDevice(c->device));
+    Carve ws;
+    const size_t o_A = ws.take(8 * ld * ld), o_b = ws.take(8 * N), o_w = ws.take(8 * ld), o_y = ws.take(8 * ld), o_x = ws.take(8 * N), o_fail = ws.take(4);
+    HIPCHECK(hipStreamSynchronize(c->stream));
+    HIPCHECK(grow(c->ba_ws, ws.off));
+    char *dw = c->ba_ws.as<char>();
+    hipStream_t s = c->stream;
+    double *dA = at<double>(dw, o_A);
+    int32_t *dfail = at<int32_t>(dw, o_fail);
+    HIPCHECK(hipMemcpy2DAsync(dA, 8 * ld, A, 8 * N, 8 * N, N, hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemcpyAsync(dw + o_b, b, 8 * N, hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemsetAsync(dfail, 0, 4, s));
+    {
+        ProfScope ps(c, "spd_solve", "dense_cholesky+solve", (double)N * N * N / 3.0, 8.0 * (double)ld * ld);
+        launch_dense_pad(s, dA, (int64_t)ld, n);
+        launch_dense_cholesky(s, dA, (int64_t)ld, dfail);
+        launch_dense_solve(s, dA, (int64_t)ld, n, at<const double>(dw, o_b), at<double>(dw, o_w), at<double>(dw, o_y), at<double>(dw, o_x), dfail);
+    }
+    HIPCHECK(hipGetLastError());
+    std::vector<double> hx(N);
+    int32_t hf = 0;
+    HIPCHECK(hipMemcpyAsync(&hf, dfail, 4, hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipMemcpyAsync(hx.data(), dw + o_x, 8 * N, hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
+    *info = hf;
+    if (hf == 0) memcpy(x, hx.data(), 8 * N);                // behind a failed pivot x stays as it came
+    return 0;
 }

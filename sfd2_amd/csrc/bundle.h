@@ -79,3 +79,28 @@ void launch_ba_pcg_init(hipStream_t st, const BaPtrs &P);
 void launch_ba_pcg_step(hipStream_t st, const BaPtrs &P, double tol2, int max_iters);
 void launch_ba_update(hipStream_t st, const BaPtrs &P);
 void launch_ba_decide_commit(hipStream_t st, const BaPtrs &P);
+
+// ---- the dense solver of the reduced camera system (bundle_dense_kernels.hip)
+#define SFD2_BA_DENSE_TILE 64         // the factorisation's tile; the matrix is padded to whole tiles with an identity diagonal
+
+struct BaDense {                      // the dense solver's device arrays; allocated only when it is chosen
+    double *S;                        // [ld][ld], ld = 6 nv rounded up to whole tiles; only the lower triangle is written and read
+    int64_t ld;
+    double *G;                        // [no][18]: E_o L_p^-T per observation, 6 x 3
+    const uint64_t *pairs;            // the pair list sorted by block: (a << 32) | b
+    const int32_t *blk_start;         // [nv nv + 1]: where block i nv + j starts in it
+    double *w, *y;                    // [ld] each: the solves' work vectors
+    int32_t *fail;                    // 0, or 1 + the index of the first pivot that was <= 0 or not finite
+};
+
+// once per call: the pairs of every observation from pair_off[a] on, keyed view(a) nv + view(b); where every key starts in the sorted keys
+void launch_ba_dense_pairs(hipStream_t st, const BaPtrs &P, const int64_t *pair_off, uint32_t *keys, uint64_t *vals);
+void launch_ba_dense_block_start(hipStream_t st, const uint32_t *keys, int64_t n_pairs, int64_t n_keys, int32_t *start);
+// per LM iteration: G and the lower triangle of S (behind ba_point_invert and ba_view_precond); trial_cost = inf when the pivot word is raised
+void launch_ba_dense_form(hipStream_t st, const BaPtrs &P, const BaDense &D);
+void launch_ba_dense_veto(hipStream_t st, const BaPtrs &P, const BaDense &D);
+// A [ld][ld], ld a multiple of SFD2_BA_DENSE_TILE: rows n .. ld of the lower triangle <- identity; A <- its Cholesky factor (lower triangle);
+// x[0 .. n) <- A^-1 b by the factor (w, y: ld doubles each).  *fail must be 0 before the factorisation; behind a raised word x is zero.
+void launch_dense_pad(hipStream_t st, double *A, int64_t ld, int n);
+void launch_dense_cholesky(hipStream_t st, double *A, int64_t ld, int32_t *fail);
+void launch_dense_solve(hipStream_t st, const double *A, int64_t ld, int n, const double *b, double *w, double *y, double *x, const int32_t *fail);

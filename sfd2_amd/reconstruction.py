@@ -17,10 +17,13 @@ verified matches; the points are a function of the registered views and their po
          [--reference_sfm_model R | --intrinsics LIST...] [--single_camera] [--skip_geometric_verification]
          [--min_match_score X] [--min_num_matches N] [--verification essential|fundamental|geometry]
          [--refine_focal_length 0|1] [--refine_principal_point 0|1] [--refine_extra_params 0|1] [--intrinsics_min_views N]
+         [--ba_solver pcg|dense]
 
 The refine options (default off) let every round's adjustment, from intrinsics_min_views registered views on, refine the cameras'
 intrinsics with the poses and points (bundle_adjustment.adjust_cameras): the next round triangulates, filters and
-registers with the refined cameras, and the written model carries them.
+registers with the refined cameras, and the written model carries them.  --ba_solver dense (option ba_solver, default "pcg") runs every
+adjustment with the dense solver of the reduced camera system (bundle_adjustment.adjust(solver="dense")); it holds
+the intrinsics constant, so together with a refine option it is refused.
 
 --verification fundamental (reconstruct(..., verification="fundamental")): for cameras nobody trusts, i.e. the focal-length prior.  Step 1
 verifies every pair by its fundamental matrix (two_view.verify_pairs_fundamental) and continues as
@@ -57,7 +60,7 @@ DEFAULTS = dict(max_error=4.0, min_num_matches=15, init_max_pairs=50, init_min_t
                 max_reproj_error=4.0, ba_round_iterations=25, ba_final_iterations=100, ba_loss_scale=1.0, max_reg_trials=3,
                 abs_pose_min_num_inliers=30, abs_pose_min_inlier_ratio=0.25, abs_pose_max_error=12.0, round_ratio=0.5, max_images_per_round=16,
                 seed=0, max_refine_iterations=50, max_rounds=64, fix_initial_pair=False, refine_focal_length=False, refine_principal_point=False,
-                refine_extra_params=False, intrinsics_min_views=INTRINSICS_MIN_VIEWS)
+                refine_extra_params=False, intrinsics_min_views=INTRINSICS_MIN_VIEWS, ba_solver="pcg")
 STAT_KEYS = triangulation.STAT_KEYS + ("num_input_images",)
 
 
@@ -259,6 +262,11 @@ def reconstruct(cameras, images, keypoints, pair_matches, skip_geometric_verific
     o = dict(DEFAULTS, **options)
     S = DeviceStages(device) if stages is None else stages
     mask = bundle_adjustment.refine_mask(o["refine_focal_length"], o["refine_principal_point"], o["refine_extra_params"])
+    if o["ba_solver"] not in bundle_adjustment.SOLVERS:
+        raise ValueError(f"ba_solver {o['ba_solver']!r} is not supported (one of {', '.join(bundle_adjustment.SOLVERS)})")
+    if mask and o["ba_solver"] != DEFAULTS["ba_solver"]:
+        raise ValueError('ba_solver "dense" does not go with a refine option: the dense solver holds the intrinsics constant (DESIGN.md section 21)')
+    ba_options = {} if o["ba_solver"] == DEFAULTS["ba_solver"] else {"solver": o["ba_solver"]}     # the default's calls stay as they were
     if mask:
         cameras = dict(cameras)                                                   # the refined records replace the given ones, round by round
     rep = {} if report is None else report
@@ -380,7 +388,7 @@ def reconstruct(cameras, images, keypoints, pair_matches, skip_geometric_verific
             ba = dict(ba, refined_intrinsics=True)
         else:
             xyz, _, ba = S.adjust(views, nv, vc, xyz, np.zeros(len(xyz), np.uint8), p_off, p_view, p_xy, max_iterations=int(iterations), loss="cauchy",
-                                  loss_scale=o["ba_loss_scale"])
+                                  loss_scale=o["ba_loss_scale"], **ba_options)
         tm["adjust_s"] = clock() - t
         t = clock()
         flt = S.filter(views, nv, xyz, p_off, p_view, p_xy, o["max_reproj_error"], o["min_tri_angle"])
@@ -493,7 +501,7 @@ def read_images(pairs_path, features_path, single_camera=False, reference_sfm_mo
 
 def main(sfm_dir, image_dir, pairs, features, matches, colmap_path=None, single_camera=False, skip_geometric_verification=False,
          min_match_score=None, min_num_matches=None, reference_sfm_model=None, intrinsics=(), device=0, verification="essential",
-         refine_focal_length=0, refine_principal_point=0, refine_extra_params=0, intrinsics_min_views=None, **options):
+         refine_focal_length=0, refine_principal_point=0, refine_extra_params=0, intrinsics_min_views=None, ba_solver=None, **options):
     """hloc/reconstruction.py main(): image_dir and colmap_path are accepted and unused.  Writes sfm_dir/models/0/{cameras,images,
     points3D}.bin and sfm_dir/stats.txt (one `key: value` per line; the reference writes the same keys without the newline); returns
     the statistics.  With a refine option set cameras.bin holds the refined intrinsics."""
@@ -509,6 +517,8 @@ def main(sfm_dir, image_dir, pairs, features, matches, colmap_path=None, single_
             options[key] = True
     if intrinsics_min_views is not None:
         options["intrinsics_min_views"] = int(intrinsics_min_views)
+    if ba_solver is not None:
+        options["ba_solver"] = ba_solver
     cameras, images = read_images(pairs, features, single_camera, reference_sfm_model, intrinsics)
     keypoints, pair_matches = triangulation.read_inputs(images, pairs, features, matches, min_match_score)
     logging.info("Reconstructing from %d pairs over %d images...", len(pair_matches), len(images))
@@ -551,6 +561,7 @@ def parser():
     ap.add_argument("--refine_principal_point", type=int, choices=(0, 1), default=0)
     ap.add_argument("--refine_extra_params", type=int, choices=(0, 1), default=0)
     ap.add_argument("--intrinsics_min_views", type=int, default=None)
+    ap.add_argument("--ba_solver", choices=sorted(bundle_adjustment.SOLVERS), default=DEFAULTS["ba_solver"])
     return ap
 
 

@@ -13,6 +13,11 @@ the same run: intrinsics fixed (adjust, today's call), the scene's four cameras 
 (adjust_cameras); with the mean relative focal-length error before and after.
     python tools/bundle_bench.py --refine_focal_length 1 --refine_extra_params 1 --out profiles/bundle_cam_bench.json
 
+With --solver dense the adjustment runs with both solvers of the reduced camera system in the same run, PCG first:
+per solver ms per LM iteration, LM steps tried and accepted, status, final cost, final max |g| and the pose errors; for the dense solver
+also the length of the pair list and the one-off cost of building it (a call with max_iterations=0 against the same call with PCG).
+    python tools/bundle_bench.py --solver dense --out profiles/bundle_dense_bench.json
+
 Kernel times come from a kernel trace of the same tool (no counters in that run):
     rocprofv3 --kernel-trace --stats -d DIR -o ba -- python tools/bundle_bench.py --reps 1"""
 import argparse
@@ -50,6 +55,7 @@ def main():
     ap.add_argument("--refine_principal_point", type=int, choices=(0, 1), default=0)
     ap.add_argument("--refine_extra_params", type=int, choices=(0, 1), default=0)
     ap.add_argument("--focal_off", type=float, default=0.1)
+    ap.add_argument("--solver", choices=("pcg", "dense"), default="pcg")
     a = ap.parse_args()
     import torch
     import pose_ref as pr
@@ -114,6 +120,18 @@ def main():
     if mask:
         return camera_comparison(a, once, out_head=dict(device=torch.cuda.get_device_name(0), images=len(ids), points=len(pids), observations=n_obs,
                                                         refine=mask, focal_off=a.focal_off))
+    if a.solver == "dense":
+        def errors_of(v):
+            return pose_errors({i: tr.Img(i, np.array(v[k].qvec[:]), np.array(v[k].tvec[:]), images[i].camera_id, images[i].name) for k, i in enumerate(ids)},
+                               truth, moving)
+        n_pairs = 0
+        for j in range(len(pids)):                             # (a, b) of one point with view(a) >= view(b)
+            vs = np.sort(ov[off[j]:off[j + 1]])
+            n_pairs += int(np.searchsorted(vs, vs, side="right").sum())
+        return solver_comparison(a, once, errors_of, dict(device=torch.cuda.get_device_name(0), images=len(ids), points=len(pids), observations=n_obs,
+                                                          mean_track_length=n_obs / max(len(pids), 1), pair_list_length=n_pairs,
+                                                          reduced_system_size=6 * len(ids), pose_error_before=pose_errors(images, truth, moving),
+                                                          mean_reprojection_error_before=float(np.mean([p.error for p in points3D.values()]))))
     rows = []
     for rep in range(a.reps + 1):                              # the first pass warms up (context, buffers) and is not reported
         t_full, v, (new_xyz, err, report) = once()
@@ -137,6 +155,34 @@ def main():
            "note": "wall clock of the whole call, host packing and copies included; no baseline exists (no COLMAP or Ceres, no earlier path); the "
                    "flagship path (bench.py) calls none of this code"}
     print(json.dumps({k: v for k, v in out.items() if k != "reps"}), flush=True)
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+
+
+def solver_comparison(a, once, errors_of, out_head):
+    """Both solvers in one run, PCG first: per solver the medians over --reps of the whole call and of ms per LM iteration, the report
+    and the pose errors after; for the dense solver the one-off cost of the pair list."""
+    out = dict(out_head, solvers={}, note="wall clock of the whole call, host packing and copies included; both solvers in the same run of the tool; "
+                                          "the flagship path (bench.py) calls none of this code")
+    setup = {}
+    for solver in ("pcg", "dense"):
+        rows = []
+        for rep in range(a.reps + 1):                          # the first pass warms up and is not reported
+            t_full, v, (_, err, report) = once(solver=solver)
+            t_zero = once(solver=solver, max_iterations=0)[0]
+            if rep:
+                rows.append({"adjust_s": t_full, "ms_per_lm_iteration": 1e3 * (t_full - t_zero) / max(report["iterations"], 1),
+                             "ms_per_lm_iteration_whole_call": 1e3 * t_full / max(report["iterations"], 1), "call_without_steps_s": t_zero,
+                             "pcg_iterations_per_step": report["pcg_iterations"] / max(report["iterations"], 1)})
+        med = {k: float(np.median([r[k] for r in rows])) for k in rows[0]}
+        setup[solver] = med["call_without_steps_s"]
+        out["solvers"][solver] = dict(med, lm_iterations=report["iterations"], accepted_steps=report["accepted_steps"], status=report["status"],
+                                      initial_cost=report["initial_cost"], final_cost=report["final_cost"], gradient_max=report["gradient_max"],
+                                      mean_reprojection_error_after=float(err.mean()), pose_error_after=errors_of(v), reps=rows)
+        print(solver, json.dumps({k: v for k, v in out["solvers"][solver].items() if k != "reps"}), flush=True)
+    out["pair_list_build_ms"] = 1e3 * (setup["dense"] - setup["pcg"])
+    print(json.dumps({k: v for k, v in out.items() if k != "solvers"}), flush=True)
     if a.out:
         with open(a.out, "w") as f:
             json.dump(out, f, indent=1)

@@ -4,7 +4,11 @@ tests/mapper_ref.py's numpy on the arrays of the last round -- a host restatemen
 run -- and the final model's errors after a similarity alignment of its camera centres to the truth.  No speed ratio for the mapper as a
 whole: there is no COLMAP here and no earlier path to compare with.
 
-    python tools/reconstruction_bench.py [--images 200] [--points 60000] [--window 10] [--out profiles/reconstruction_bench.json]"""
+    python tools/reconstruction_bench.py [--images 200] [--points 60000] [--window 10] [--out profiles/reconstruction_bench.json]
+
+With --ba_solver dense the mapper runs twice in the same run, first with the PCG adjustment and then with the dense
+one: per solver the rounds, the seconds per stage, the adjustment's share, the final adjustment's report and the errors after alignment.
+    python tools/reconstruction_bench.py --ba_solver dense --out profiles/reconstruction_dense_bench.json"""
 import argparse
 import json
 import os
@@ -26,6 +30,7 @@ def main():
     ap.add_argument("--window", type=int, default=10)
     ap.add_argument("--ref_candidates", type=int, default=2, help="candidates of the assemble comparison (the numpy restatement is quadratic)")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--ba_solver", choices=("pcg", "dense"), default="pcg")
     a = ap.parse_args()
     import torch
     import mapper_ref as mr
@@ -55,6 +60,32 @@ def main():
             return super().assemble(*args)
 
     RC.restrict_tracks(np.zeros(2, np.int64), np.zeros(0, np.int32), np.zeros((0, 2), np.float32), [1])      # the context, outside the clock
+    if a.ba_solver == "dense":
+        out = {"device": torch.cuda.get_device_name(0), "input_images": len(truth), "pairs": len(pair_matches), "solvers": {},
+               "note": "wall clock, host packing and copies included; both solvers in the same run of the tool, PCG first; the flagship path (bench.py) "
+                       "calls none of this code"}
+        for solver in ("pcg", "dense"):
+            rep = {}
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            images, points3D = RC.reconstruct(cameras, truth, keypoints, pair_matches, report=rep, ba_solver=solver)
+            total = time.perf_counter() - t0
+            stages = {}
+            for r in rep["rounds"] + [rep["final"]]:
+                for k, v in r["seconds"].items():
+                    stages[k] = stages.get(k, 0.0) + v
+            stages.update(verify_s=rep["verify_s"], tracks_s=rep["tracks_s"])
+            errs = mr.model_errors(images, points3D, truth)
+            errs["rotation_deg"] = float(np.degrees(errs.pop("rotation")))
+            out["solvers"][solver] = {"rounds": len(rep["rounds"]), "registered": len(images), "points": len(points3D), "observations": rep["final"]["observations"],
+                                      "total_s": total, "stage_s": stages, "adjust_share_of_total": stages.get("adjust_s", 0.0) / total,
+                                      "adjust_calls": len(rep["rounds"]) + 1, "round_adjustments": [r["ba"] for r in rep["rounds"]],
+                                      "final_adjustment": rep["final"]["ba"], "errors_after_alignment": errs}
+            print(solver, json.dumps({k: v for k, v in out["solvers"][solver].items() if k != "round_adjustments"}), flush=True)
+        if a.out:
+            with open(a.out, "w") as f:
+                json.dump(out, f, indent=1)
+        return
     S, rep = Recording(0), {}
     torch.cuda.synchronize()
     t0 = time.perf_counter()
