@@ -580,6 +580,57 @@ int sfd2_absolute_pose_batch(sfd2_ctx *ctx, const sfd2_pose_problem *problems, i
 int sfd2_pose_refine_batch(sfd2_ctx *ctx, const sfd2_pose_problem *problems, int k, const double *qvec_tvec_in,
                            const uint8_t *inlier_mask_u8, sfd2_pose_result *results, int flags);
 
+/* ------------------------------------------------------------------------------------------------ absolute pose, unknown focal
+ * (version 125) pycolmap.absolute_pose_estimation's estimate_focal_length / refine_focal_length / refine_extra_params.
+ * Focal samples: with S = num_focal_length_samples, sample i = 0..S is the given camera with its focal parameters (f, or fx and fy)
+ * multiplied by a_i = min_ratio + (max_ratio - min_ratio) (i / S)^2; the principal point and the extras stay as given.
+ * Sweep: every (problem, sample) runs the solver's RANSAC (no refinement) at its camera, threshold (max_error_px / mean focal)^2 at
+ * that camera, with the call's seed, confidence and min_inlier_ratio and both trial limits clipped to sweep_max_num_trials.
+ * Select: more inliers, then the smaller residual sum in squared pixels (fp32), then the smaller i; no sample with 3 inliers:
+ * success 0 and the camera as given.  Main run: sfd2_absolute_pose_batch at the winning camera, bit for bit (num_trials, mask, pose).
+ * Refinement with intrinsics (either refine flag): Levenberg-Marquardt as the solver's (Cauchy at 1 px, fp64, <= 100 iterations) over
+ * the pose and, with additive steps, the focal group and / or the extra group (k; k1 k2 p1 p2), never the principal point; a trial
+ * state with a non-finite word or a focal length that is not positive or outside [min_ratio, max_ratio] x the given one is rejected
+ * like a cost increase.  At most three refinements: after one, every point is re-scored in fp64 pixels (depth > 0, squared error <=
+ * max_error_px^2); if the count grew, the next refinement runs over the new mask.  The pose, the camera and the mask reported are the
+ * last refinement's, so num_inliers >= ransac_num_inliers.  Without estimate_focal_length the main run uses the given camera. */
+typedef struct {
+    int32_t estimate_focal_length, refine_focal_length, refine_extra_params;   /* 0 / non-zero                                */
+    int32_t num_focal_length_samples;      /* S, 1..64 (COLMAP: 30)                                                        */
+    double min_focal_length_ratio;         /* 0 < min <= max, finite (COLMAP: 0.2 and 5)                                   */
+    double max_focal_length_ratio;
+    int64_t sweep_max_num_trials;          /* >= 1: the sweep's cap on min_num_trials and max_num_trials                   */
+    int64_t reserved[2];                   /* zero; anything else is an error                                              */
+} sfd2_pose_focal_conf;
+typedef struct {
+    int32_t success;
+    int32_t num_inliers;            /* the count of the mask the reported pose was refined over                            */
+    int32_t num_trials;             /* of the main run                                                                     */
+    int32_t reserved;
+    double qvec[4];
+    double tvec[3];
+    double params[8];               /* the camera's parameters in COLMAP order after the sweep and the refinement          */
+    int32_t focal_sample;           /* the winning sample, -1 without a sweep or when no sample has 3 inliers              */
+    int32_t ransac_num_inliers;     /* the main run's RANSAC count                                                         */
+    double focal_factor;            /* a_focal_sample (1 without a sweep)                                                  */
+} sfd2_pose_focal_result;
+typedef struct {
+    int32_t cnt, num_trials;        /* the sample's RANSAC inliers (0 below 3) and trials                                  */
+    float sum_px;                   /* (sum fm) fm in fp32: the winner's residual sum, fm the sample's mean focal in fp32  */
+    int32_t pad;
+} sfd2_pose_sweep_record;
+
+/* As sfd2_absolute_pose_batch, with the options of focal_conf.  sweep_out: NULL, or host [k][S + 1] records (written with
+ * estimate_focal_length only). */
+int sfd2_absolute_pose_focal_batch(sfd2_ctx *ctx, const sfd2_pose_problem *problems, int k, const sfd2_pose_conf *conf,
+                                   const sfd2_pose_focal_conf *focal_conf, sfd2_pose_focal_result *results, uint8_t *inlier_mask_u8,
+                                   sfd2_pose_sweep_record *sweep_out, int flags);
+/* As sfd2_pose_refine_batch, with the camera's groups that focal_conf's refine flags select: one refinement from the given pose over
+ * the given mask, no re-scoring.  The ratios bound the focal lengths; the sweep's fields are checked and not used. */
+int sfd2_pose_refine_camera_batch(sfd2_ctx *ctx, const sfd2_pose_problem *problems, int k, const double *qvec_tvec_in,
+                                  const uint8_t *inlier_mask_u8, const sfd2_pose_focal_conf *focal_conf,
+                                  sfd2_pose_focal_result *results, int flags);
+
 /* ------------------------------------------------------------------------------------------------ relative pose
  * The calibrated two-view geometry of a matched pair, which COLMAP estimates inside matches_importer (hloc/triangulation.py:114,
  * hloc/reconstruction.py:145), for many pairs of any sizes in one launch: LO-RANSAC over the five-point solver with fp64 scoring

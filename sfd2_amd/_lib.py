@@ -102,6 +102,24 @@ class PoseResult(ctypes.Structure):
                 ("qvec", ctypes.c_double * 4), ("tvec", ctypes.c_double * 3)]
 
 
+class PoseFocalConf(ctypes.Structure):
+    """sfd2_pose_focal_conf (include/sfd2_hip.h)."""
+    _fields_ = [("estimate_focal_length", ctypes.c_int32), ("refine_focal_length", ctypes.c_int32), ("refine_extra_params", ctypes.c_int32),
+                ("num_focal_length_samples", ctypes.c_int32), ("min_focal_length_ratio", ctypes.c_double),
+                ("max_focal_length_ratio", ctypes.c_double), ("sweep_max_num_trials", ctypes.c_int64), ("reserved", ctypes.c_int64 * 2)]
+
+
+class PoseFocalResult(ctypes.Structure):
+    """sfd2_pose_focal_result (include/sfd2_hip.h)."""
+    _fields_ = PoseResult._fields_ + [("params", ctypes.c_double * 8), ("focal_sample", ctypes.c_int32), ("ransac_num_inliers", ctypes.c_int32),
+                                      ("focal_factor", ctypes.c_double)]
+
+
+class PoseSweepRecord(ctypes.Structure):
+    """sfd2_pose_sweep_record (include/sfd2_hip.h)."""
+    _fields_ = [("cnt", ctypes.c_int32), ("num_trials", ctypes.c_int32), ("sum_px", ctypes.c_float), ("pad", ctypes.c_int32)]
+
+
 class TwoViewProblem(ctypes.Structure):
     """sfd2_two_view_problem (include/sfd2_hip.h)."""
     _fields_ = [("n", ctypes.c_int32), ("model0", ctypes.c_int32), ("model1", ctypes.c_int32), ("reserved", ctypes.c_int32),
@@ -258,6 +276,7 @@ EXPORTS = [
     "sfd2_get_range_status", "sfd2_range_tensor_name", "sfd2_calibrate_range", "sfd2_get_act_exponents", "sfd2_set_act_exponents",
     "sfd2_extract_record_async", "sfd2_desc_pack", "sfd2_get_margin_status", "sfd2_get_relax_status", "sfd2_get_option", "sfd2_device_pci_bus_id",
     "sfd2_jpeg_parse", "sfd2_jpeg_prepare", "sfd2_jpeg_decode", "sfd2_absolute_pose_batch", "sfd2_pose_refine_batch",
+    "sfd2_absolute_pose_focal_batch", "sfd2_pose_refine_camera_batch",
     "sfd2_assemble_2d3d", "sfd2_verify_matches_batch", "sfd2_build_tracks", "sfd2_triangulate_tracks",
     "sfd2_pairs_retrieval", "sfd2_pairs_covisibility", "sfd2_pairs_poses", "sfd2_covis_clusters",
     "sfd2_covis_frames", "sfd2_vlad_assign", "sfd2_vlad_aggregate", "sfd2_vlad_kmeans",
@@ -348,6 +367,10 @@ def load():
     lib.sfd2_jpeg_decode.argtypes = [vp, vp, i64, ctypes.POINTER(JpegInfo), ci, vp, i64, vp, ci]
     lib.sfd2_absolute_pose_batch.argtypes = [vp, ctypes.POINTER(PoseProblem), ci, ctypes.POINTER(PoseConf), ctypes.POINTER(PoseResult), vp, ci]
     lib.sfd2_pose_refine_batch.argtypes = [vp, ctypes.POINTER(PoseProblem), ci, vp, vp, ctypes.POINTER(PoseResult), ci]
+    lib.sfd2_absolute_pose_focal_batch.argtypes = [vp, ctypes.POINTER(PoseProblem), ci, ctypes.POINTER(PoseConf), ctypes.POINTER(PoseFocalConf),
+                                                   ctypes.POINTER(PoseFocalResult), vp, vp, ci]
+    lib.sfd2_pose_refine_camera_batch.argtypes = [vp, ctypes.POINTER(PoseProblem), ci, vp, vp, ctypes.POINTER(PoseFocalConf),
+                                                  ctypes.POINTER(PoseFocalResult), ci]
     lib.sfd2_relative_pose_batch.argtypes = [vp, ctypes.POINTER(TwoViewProblem), ci, ctypes.POINTER(TwoViewConf), ctypes.POINTER(TwoViewResult), vp, vp, ci]
     lib.sfd2_fundamental_batch.argtypes = [vp, ctypes.POINTER(FundamentalProblem), ci, ctypes.POINTER(TwoViewConf), ctypes.POINTER(FundamentalResult), vp, ci]
     lib.sfd2_homography_batch.argtypes = [vp, ctypes.POINTER(HomographyProblem), ci, ctypes.POINTER(TwoViewConf), ctypes.POINTER(HomographyResult), vp, ci]

@@ -5,13 +5,15 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libsfd2hip.so")
-SOURCES = ["conv_kernels.hip", "conv2_kernels.hip", "conv3_kernels.hip", "conv3rf_kernels.hip", "conv2b_s2d_kernel.hip", "conv1x1_kernels.hip", "resblock_kernel.hip", "conv_f32_kernels.hip", "convc_kernels.hip", "rb23_c_kernel.hip", "sparse_da3_kernel.hip", "sparse_da0_kernel.hip", "fused_stem_kernel.hip", "fused_stem_c_kernel.hip", "post_kernels.hip", "util_kernels.hip", "nms4_kernels.hip", "match_kernels.hip", "match_mutual_kernel.hip", "guided_match_kernels.hip", "api_core.hip", "api_weights.hip", "api_network.hip", "api_extract.hip", "api_match.hip", "api_guided.hip", "api_graph.hip", "jpeg_parse.hip", "jpeg_kernels.hip", "api_jpeg.hip", "pose_kernels.hip", "api_pose.hip", "two_view_kernels.hip", "api_two_view.hip", "fundamental_kernels.hip", "api_fundamental.hip", "homography_kernels.hip", "api_homography.hip", "assemble_kernels.hip", "api_assemble.hip", "tri_kernels.hip", "api_triangulate.hip", "pairs_kernels.hip", "api_pairs.hip", "cluster_kernels.hip", "api_cluster.hip", "frames_kernels.hip", "api_frames.hip", "vlad_kernels.hip", "api_vlad.hip", "bundle_kernels.hip", "bundle_dense_kernels.hip", "bundle_cam_kernels.hip", "api_bundle.hip", "mapper_kernels.hip", "api_mapper.hip"]
+SOURCES = ["conv_kernels.hip", "conv2_kernels.hip", "conv3_kernels.hip", "conv3rf_kernels.hip", "conv2b_s2d_kernel.hip", "conv1x1_kernels.hip", "resblock_kernel.hip", "conv_f32_kernels.hip", "convc_kernels.hip", "rb23_c_kernel.hip", "sparse_da3_kernel.hip", "sparse_da0_kernel.hip", "fused_stem_kernel.hip", "fused_stem_c_kernel.hip", "post_kernels.hip", "util_kernels.hip", "nms4_kernels.hip", "match_kernels.hip", "match_mutual_kernel.hip", "guided_match_kernels.hip", "api_core.hip", "api_weights.hip", "api_network.hip", "api_extract.hip", "api_match.hip", "api_guided.hip", "api_graph.hip", "jpeg_parse.hip", "jpeg_kernels.hip", "api_jpeg.hip", "pose_kernels.hip", "pose_focal_kernels.hip", "api_pose.hip", "two_view_kernels.hip", "api_two_view.hip", "fundamental_kernels.hip", "api_fundamental.hip", "homography_kernels.hip", "api_homography.hip", "assemble_kernels.hip", "api_assemble.hip", "tri_kernels.hip", "api_triangulate.hip", "pairs_kernels.hip", "api_pairs.hip", "cluster_kernels.hip", "api_cluster.hip", "frames_kernels.hip", "api_frames.hip", "vlad_kernels.hip", "api_vlad.hip", "bundle_kernels.hip", "bundle_dense_kernels.hip", "bundle_cam_kernels.hip", "api_bundle.hip", "mapper_kernels.hip", "api_mapper.hip"]
 # per-source extra flags (see the header comment of each file)
 # -fno-honor-nans: without it hipcc puts a NaN-canonicalising v_max_f32 x, x in front of every fmaxf operand it cannot
 # prove quiet (the ReLUs of the epilogues: two VALU per value instead of one).  Finite inputs give identical results.
 _NN = ["-fno-honor-nans"]
 SRC_FLAGS = {"match_mutual_kernel.hip": _NN, "conv3_kernels.hip": _NN, "conv3rf_kernels.hip": _NN, "resblock_kernel.hip": _NN, "conv2_kernels.hip": _NN,
              "fused_stem_kernel.hip": _NN, "conv_kernels.hip": _NN, "conv1x1_kernels.hip": _NN, "nms4_kernels.hip": _NN, "convc_kernels.hip": _NN, "fused_stem_c_kernel.hip": _NN, "rb23_c_kernel.hip": _NN, "sparse_da3_kernel.hip": _NN, "sparse_da0_kernel.hip": _NN, "conv2b_s2d_kernel.hip": _NN}
+# sources a source includes (pose_focal_kernels.hip takes pose_run from pose_kernels.hip)
+SRC_DEPS = {"pose_focal_kernels.hip": ["pose_kernels.hip"]}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"] + \
     os.environ.get("SFD2_EXTRA_FLAGS", "").split()
 
@@ -53,7 +55,7 @@ def build_lib(force=False, verbose=False, out=None, extra_flags=()):
         s = os.path.join(CSRC, src)
         o = os.path.join(odir, src.replace(".hip", ".o"))
         objs.append(o)
-        if force or _newer(s, o) or any(_newer(d, o) for d in deps):
+        if force or _newer(s, o) or any(_newer(d, o) for d in deps + [os.path.join(CSRC, d) for d in SRC_DEPS.get(src, [])]):
             cmd = [hipcc] + FLAGS + SRC_FLAGS.get(src, []) + list(extra_flags) + ["-c", s, "-o", o]
             if verbose:
                 print(" ".join(cmd))

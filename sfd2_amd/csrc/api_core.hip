@@ -13,7 +13,7 @@ std::atomic<unsigned long long> g_alloc_gen{0};
 thread_local int g_sfd2_cu_limit = 0;       // set per network pass from the context's option "cu_limit" (sfd2_internal.h)
 
 // ------------------------------------------------------------------------------------------ basics
-extern "C" int sfd2_version(void) { return 124; }   // 124: + sfd2_spd_solve, sfd2_ba_conf.solver (SFD2_BA_SOLVER_DENSE); 123: + sfd2_bundle_adjust_cameras; 122: + sfd2_match_guided_batch; 121: + sfd2_homography_batch; 120: + sfd2_fundamental_batch; 119: + sfd2_mapper_restrict / _filter / _visible / _assemble; 118: + sfd2_bundle_adjust; 117: + sfd2_relative_pose_batch; 116: + sfd2_vlad_assign / sfd2_vlad_aggregate / sfd2_vlad_kmeans; 115: + sfd2_covis_frames; 114: + sfd2_covis_clusters; 113: + sfd2_pairs_retrieval / sfd2_pairs_covisibility / sfd2_pairs_poses; 112: + sfd2_verify_matches_batch / sfd2_build_tracks / sfd2_triangulate_tracks; 111: + sfd2_assemble_2d3d; 110: + sfd2_absolute_pose_batch / sfd2_pose_refine_batch; 109: + sfd2_jpeg_parse / _prepare / _decode; 108: + sfd2_get_option; 107: + sfd2_get_relax_status (option c3b_plain); 105: + sfd2_extract_record_async, sfd2_desc_pack, SFD2_FLAG_ASYNC with host outputs (round 5); 106: + sfd2_get_margin_status
+extern "C" int sfd2_version(void) { return 125; }   // 125: + sfd2_absolute_pose_focal_batch / sfd2_pose_refine_camera_batch; 124: + sfd2_spd_solve, sfd2_ba_conf.solver (SFD2_BA_SOLVER_DENSE); 123: + sfd2_bundle_adjust_cameras; 122: + sfd2_match_guided_batch; 121: + sfd2_homography_batch; 120: + sfd2_fundamental_batch; 119: + sfd2_mapper_restrict / _filter / _visible / _assemble; 118: + sfd2_bundle_adjust; 117: + sfd2_relative_pose_batch; 116: + sfd2_vlad_assign / sfd2_vlad_aggregate / sfd2_vlad_kmeans; 115: + sfd2_covis_frames; 114: + sfd2_covis_clusters; 113: + sfd2_pairs_retrieval / sfd2_pairs_covisibility / sfd2_pairs_poses; 112: + sfd2_verify_matches_batch / sfd2_build_tracks / sfd2_triangulate_tracks; 111: + sfd2_assemble_2d3d; 110: + sfd2_absolute_pose_batch / sfd2_pose_refine_batch; 109: + sfd2_jpeg_parse / _prepare / _decode; 108: + sfd2_get_option; 107: + sfd2_get_relax_status (option c3b_plain); 105: + sfd2_extract_record_async, sfd2_desc_pack, SFD2_FLAG_ASYNC with host outputs (round 5); 106: + sfd2_get_margin_status
 extern "C" const char *sfd2_last_error(void) { return g_err.c_str(); }
 
 extern "C" int sfd2_ctx_create(int device, sfd2_ctx **out)

@@ -355,23 +355,37 @@ __device__ __forceinline__ PoseSupport score_wg(const PoseF &p, const float4 *Xf
 }
 
 // ---------------------------------------------------------------------------------------------------------------- kernel
-__global__ __launch_bounds__(kWG) void pose_kernel(const PoseProbDev *__restrict__ probs, PoseConfDev conf, const double *__restrict__ p2,
-                                                   const double *__restrict__ p3, float4 *__restrict__ xf4g, float2 *__restrict__ xf2g,
-                                                   double2 *__restrict__ xng, double *__restrict__ hypg, const unsigned char *__restrict__ mask_in,
-                                                   unsigned char *__restrict__ mask_out, PoseResDev *__restrict__ res)
-{
-    __shared__ double red[kWaves * kNS];
-    __shared__ PoseSupport sred[kWaves];
-    const int pi = blockIdx.x, tid = threadIdx.x;
-    const PoseProbDev &pb = probs[pi];
-    const int64_t off = pb.off;
-    const int n = pb.n;
-    const PoseCam cam = pb.cam;
-    const double *P2 = p2 + 2 * off;
-    const double *P3 = p3 + 3 * off;
-    float4 *Xf = xf4g + off;
-    float2 *xf = xf2g + off;
+// pose_focal_kernels.hip builds its sweep kernel from this text (one definition of P3P, the scoring and the round / LO / stop logic): it
+// defines the two macros before it includes this file -- its own signature and problem set-up in front of the body, and its exit after step
+// 4.  Here they spell pose_kernel out as it always was, so its code object does not change.
+// What the body takes from a head, by name: red[kWaves * kNS] and sred[kWaves] (LDS); pi (the workgroup's index into hypg and res), tid; pb
+// (PoseProbDev, for thresh2 and qt); off (added to mask_in / mask_out indices), n, cam; P2, P3, Xf, xf, xn (the problem's own); conf; hypg;
+// mask_in, mask_out (may be null where conf.refine_only is 0 and the head returns in SFD2_POSE_AFTER_RANSAC); res (res[pi] is written for
+// n < 4 before any exit of the head's: a second head gives it a record nobody reads).  SFD2_POSE_AFTER_RANSAC stands where found, best
+// (cnt, sum) and trials are final and uniform over the workgroup.  An edit of the body that renames one of these breaks the second head.
+#ifndef SFD2_POSE_KERNEL_HEAD
+#define SFD2_POSE_KERNEL_IS_SOLVER
+#define SFD2_POSE_AFTER_RANSAC
+#define SFD2_POSE_KERNEL_HEAD \
+__global__ __launch_bounds__(kWG) void pose_kernel(const PoseProbDev *__restrict__ probs, PoseConfDev conf, const double *__restrict__ p2,          \
+                                                   const double *__restrict__ p3, float4 *__restrict__ xf4g, float2 *__restrict__ xf2g,             \
+                                                   double2 *__restrict__ xng, double *__restrict__ hypg, const unsigned char *__restrict__ mask_in, \
+                                                   unsigned char *__restrict__ mask_out, PoseResDev *__restrict__ res)                              \
+{                                                                                                                                                   \
+    __shared__ double red[kWaves * kNS];                                                                                                            \
+    __shared__ PoseSupport sred[kWaves];                                                                                                            \
+    const int pi = blockIdx.x, tid = threadIdx.x;                                                                                                   \
+    const PoseProbDev &pb = probs[pi];                                                                                                              \
+    const int64_t off = pb.off;                                                                                                                     \
+    const int n = pb.n;                                                                                                                             \
+    const PoseCam cam = pb.cam;                                                                                                                     \
+    const double *P2 = p2 + 2 * off;                                                                                                                \
+    const double *P3 = p3 + 3 * off;                                                                                                                \
+    float4 *Xf = xf4g + off;                                                                                                                        \
+    float2 *xf = xf2g + off;                                                                                                                        \
     double2 *xn = xng + off;
+#endif
+SFD2_POSE_KERNEL_HEAD
     PoseResDev out;
     out.q[0] = 1.0; out.q[1] = out.q[2] = out.q[3] = 0.0;
     out.t[0] = out.t[1] = out.t[2] = 0.0;
@@ -539,6 +553,7 @@ __global__ __launch_bounds__(kWG) void pose_kernel(const PoseProbDev *__restrict
         out.num_trials = (int)trials;
     }
     const bool found = best.cnt >= 3;
+    SFD2_POSE_AFTER_RANSAC
     // ---- RANSAC inliers (the reported mask and count), or the given mask
     const PoseF bf = to_f32(bR, bt);
     if (!conf.refine_only) {
@@ -645,8 +660,10 @@ __global__ __launch_bounds__(kWG) void pose_kernel(const PoseProbDev *__restrict
 
 }  // namespace
 
+#ifdef SFD2_POSE_KERNEL_IS_SOLVER
 void launch_pose(hipStream_t st, const PoseProbDev *probs, int k, const PoseConfDev &conf, const double *p2, const double *p3, float4 *xf4,
                  float2 *xf2, double2 *xn, double *hyp, const unsigned char *mask_in, unsigned char *mask_out, PoseResDev *res)
 {
     hipLaunchKernelGGL(pose_kernel, dim3(k), dim3(kWG), 0, st, probs, conf, p2, p3, xf4, xf2, xn, hyp, mask_in, mask_out, res);
 }
+#endif

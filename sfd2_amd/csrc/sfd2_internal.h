@@ -776,6 +776,45 @@ struct PoseResDev {
 void launch_pose(hipStream_t st, const PoseProbDev *probs, int k, const PoseConfDev &conf, const double *p2, const double *p3, float4 *xf4,
                  float2 *xf2, double2 *xn, double *hyp, const unsigned char *mask_in, unsigned char *mask_out, PoseResDev *res);
 
+// ------------------------------------------------------------------------------------------------ absolute pose, unknown focal (pose_focal_kernels.hip)
+#define SFD2_POSE_FOCAL_MAX_SAMPLES 64
+struct PoseFocalTabDev {              // one (problem, sample) of the sweep, made by the host: the given focal lengths times the factor
+    double f[2];
+    double thresh2;                   // (max_error_px / mean focal)^2 at that camera
+    float fm;                         // the sample's mean focal length
+    int32_t pad;
+};
+struct PoseSweepDev {                 // = sfd2_pose_sweep_record
+    int32_t cnt, num_trials;
+    float sum_px;                     // (sum fm) fm in fp32: the winner's residual sum in squared pixels
+    int32_t pad;
+};
+struct PoseFocalProbDev {             // what the refinement with intrinsics needs beside the main run's PoseProbDev
+    double f_lo[2], f_hi[2];          // [min_ratio, max_ratio] x the given camera's focal lengths
+    double max_err2;                  // max_error_px^2 (re-scoring)
+    int32_t active;                   // bit i: parameter i of (6 pose | fx fy | k1 k2 p1 p2) is refined
+    int32_t single_f;                 // the model has one f: parameter 6 moves f[0] and f[1], parameter 7 is never active
+};
+struct PoseFocalConfDev {
+    int32_t rounds;                   // refinements at the most (0: report the start), re-scoring between them
+    int32_t start_from_res;           // 1: start from the main run's result and mask, 0: from PoseProbDev::qt and the given mask
+};
+struct PoseFocalResDev {
+    double q[4], t[3];
+    double f[2], k[4];                // the refined focal lengths and k1 k2 p1 p2
+    int32_t success, num_inliers, ransac_num_inliers, num_trials;
+};
+// ns samples per problem; scratch per (problem, sample): xf4 / xf2 / xn at (sample * N + off), N the batch's correspondences; unused: k * ns
+// records nobody reads; sweep: k * ns records, zeroed by the caller (a problem of fewer than 4 points writes none)
+void launch_pose_sweep(hipStream_t st, const PoseProbDev *probs, int k, const PoseFocalTabDev *tab, int ns, const PoseConfDev &conf, const double *p2,
+                       const double *p3, float4 *xf4, float2 *xf2, double2 *xn, double *hyp, int64_t N, PoseResDev *unused, PoseSweepDev *sweep);
+// per problem the best sample (-1: none has 3 inliers) and the main run's problem: probs[i] at the winner's focal lengths and threshold
+void launch_pose_focal_select(hipStream_t st, const PoseProbDev *probs, int k, const PoseFocalTabDev *tab, int ns, const PoseSweepDev *sweep,
+                              PoseProbDev *main_probs, int32_t *sel);
+void launch_pose_cam_refine(hipStream_t st, const PoseProbDev *probs, const PoseFocalProbDev *fprobs, int k, const PoseFocalConfDev &conf,
+                            const double *p2, const double *p3, const PoseResDev *main_res, unsigned char *mask, unsigned char *mask_new,
+                            PoseFocalResDev *res);
+
 // ------------------------------------------------------------------------------------------------ relative pose (two_view_kernels.hip)
 #define SFD2_TV_WG 256                // threads of a pair's workgroup = RANSAC trials per round
 #define SFD2_TV_CAND 10               // essential matrices per trial at the most

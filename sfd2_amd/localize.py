@@ -620,6 +620,8 @@ def _cluster_steps(kpq, clusters, camera, thresh, inlier_th, points3D, obs_th, q
         keep = not (best_inliers < 8 or ret["num_inliers"] <= best_results["num_inliers"])
         upd = {"qvec": ret["qvec"], "tvec": ret["tvec"], "inlier": ret["inliers"], "num_inliers": ret["num_inliers"],
                "single_num_inliers": best_inliers, "dbname": best_dbname, "order": cluster_idx + 1}
+        if "camera" in ret:                                     # the estimator estimated or refined the intrinsics
+            upd["camera"] = ret["camera"]
         if keep:
             best_results.update(upd)
         if ret["num_inliers"] < inlier_th or best_inliers < 10:
@@ -627,14 +629,15 @@ def _cluster_steps(kpq, clusters, camera, thresh, inlier_th, points3D, obs_th, q
         if not keep:
             best_results.update(upd)
         if covis is not None:                                   # :981-1014
-            ret = last = yield ("covis", (qname, camera, covis.map_index.name_to_id[best_dbname], thresh, ret["qvec"], ret["tvec"]))
+            ret = last = yield ("covis", (qname, ret.get("camera", camera), covis.map_index.name_to_id[best_dbname], thresh, ret["qvec"],
+                                          ret["tvec"]))                # (an estimated camera is the stage's cfg, held fixed there)
             if not ret["success"]:
                 continue
         return ret["qvec"], ret["tvec"], ret["num_inliers"], best_results
     if best_results["num_inliers"] >= 10:
         if covis is not None:                                   # :1139-1265: refined from the kept pose, returned with 0 either way
-            ret = yield ("covis", (qname, camera, covis.map_index.name_to_id[best_results["dbname"]], thresh, best_results["qvec"],
-                                   best_results["tvec"]))
+            ret = yield ("covis", (qname, best_results.get("camera", camera), covis.map_index.name_to_id[best_results["dbname"]], thresh,
+                                   best_results["qvec"], best_results["tvec"]))
             return ret["qvec"], ret["tvec"], 0, best_results
         src = last if (last is not None and last["success"]) else best_results
         return src["qvec"], src["tvec"], 0, best_results
@@ -686,7 +689,9 @@ def pose_from_clusters(kpq, clusters, camera, thresh, inlier_th=50, *, points3D,
     .name, .qvec, .tvec, .point3D_ids as read_write_model returns them; matches0 from StoreMatcher.match / feature_matching_batch).
 
     Every cluster with >= 8 correspondences (:719) goes into ONE absolute_pose_estimation_batch call (estimator: a replacement
-    taking a list of (points2D, points3D, camera, thresh) and returning pose dicts; **ransac goes to the default one).  The
+    taking a list of (points2D, points3D, camera, thresh) and returning pose dicts; **ransac goes to the default one, the options
+    for a query without intrinsics included: estimate_focal_length, refine_focal_length, refine_extra_params, ...; the kept
+    result then carries 'camera', and a covis stage takes that camera, held fixed, as its cfg).  The
     sequential decisions are then replayed in cluster order: best_inliers per db image (:742-760), keep / continue (:930-966), the
     first success returns its num_inliers (:1124-1130); otherwise, when the kept result has >= 10 inliers, the pose of the LAST
     estimate made is returned with 0, as the reference does (:1132-1265 reads `ret`; if that estimate failed, the kept pose is

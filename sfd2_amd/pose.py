@@ -9,7 +9,11 @@ params in COLMAP's order -- for SIMPLE_PINHOLE (f, cx, cy), PINHOLE (fx, fy, cx,
 
 RANSAC defaults (this project's choice; pycolmap is not available to compare against): min_inlier_ratio 0.01, min_num_trials 1000,
 max_num_trials 100000, confidence 0.9999, seed 0.  The result depends on the problem and the seed only.  Nothing here computes on
-the CPU: without a GPU the calls raise."""
+the CPU: without a GPU the calls raise.
+
+Unknown focal length (sfd2_absolute_pose_focal_batch / sfd2_pose_refine_camera_batch): pycolmap's estimate_focal_length,
+refine_focal_length and refine_extra_params as keyword-only arguments.  With all three False the calls above run and their dicts come
+back unchanged."""
 import ctypes
 
 import numpy as np
@@ -23,6 +27,10 @@ from . import _lib
 
 CAMERA_MODELS = {"SIMPLE_PINHOLE": (0, 3), "PINHOLE": (1, 4), "SIMPLE_RADIAL": (2, 4), "OPENCV": (4, 8)}
 DEFAULTS = dict(min_inlier_ratio=0.01, min_num_trials=1000, max_num_trials=100000, confidence=0.9999, seed=0)
+FOCAL_DEFAULTS = dict(num_focal_length_samples=30, min_focal_length_ratio=0.2, max_focal_length_ratio=5.0, sweep_max_num_trials=1024)
+
+
+SWEEP_DTYPE = np.dtype([("cnt", np.int32), ("num_trials", np.int32), ("sum_px", np.float32), ("pad", np.int32)])   # sfd2_pose_sweep_record
 
 
 def camera_model(camera):
@@ -72,9 +80,40 @@ def _result(r, mask=None):
     return out
 
 
+def _focal_conf(estimate_focal_length, refine_focal_length, refine_extra_params, num_focal_length_samples, min_focal_length_ratio,
+                max_focal_length_ratio, sweep_max_num_trials):
+    fc = _lib.PoseFocalConf()
+    fc.estimate_focal_length, fc.refine_focal_length, fc.refine_extra_params = int(bool(estimate_focal_length)), int(bool(refine_focal_length)), \
+        int(bool(refine_extra_params))
+    fc.num_focal_length_samples = int(num_focal_length_samples)
+    fc.min_focal_length_ratio, fc.max_focal_length_ratio = float(min_focal_length_ratio), float(max_focal_length_ratio)
+    fc.sweep_max_num_trials = int(sweep_max_num_trials)
+    return fc
+
+
+def _focal_result(r, camera, mask=None):
+    """_result, with the camera (a copy of the given dict with the returned params) and the sweep's choice."""
+    out = _result(r, mask)
+    cam = dict(camera)
+    mid = camera_model(camera)[0]
+    n = next(cnt for m, cnt in CAMERA_MODELS.values() if m == mid)
+    cam["params"] = [float(v) for v in r.params[:n]]
+    out["camera"] = cam
+    if mask is not None:
+        out["focal_sample"] = int(r.focal_sample)
+        out["focal_factor"] = float(r.focal_factor)
+        out["ransac_num_inliers"] = int(r.ransac_num_inliers)
+    return out
+
+
 def absolute_pose_estimation_batch(problems, max_error_px=12.0, min_inlier_ratio=DEFAULTS["min_inlier_ratio"],
                                    min_num_trials=DEFAULTS["min_num_trials"], max_num_trials=DEFAULTS["max_num_trials"],
-                                   confidence=DEFAULTS["confidence"], seed=DEFAULTS["seed"], device=0):
+                                   confidence=DEFAULTS["confidence"], seed=DEFAULTS["seed"], device=0, *, estimate_focal_length=False,
+                                   refine_focal_length=False, refine_extra_params=False,
+                                   num_focal_length_samples=FOCAL_DEFAULTS["num_focal_length_samples"],
+                                   min_focal_length_ratio=FOCAL_DEFAULTS["min_focal_length_ratio"],
+                                   max_focal_length_ratio=FOCAL_DEFAULTS["max_focal_length_ratio"],
+                                   sweep_max_num_trials=FOCAL_DEFAULTS["sweep_max_num_trials"], return_sweep=False):
     """problems: a list of (points2D [n,2], points3D [n,3], camera) or (points2D, points3D, camera, max_error_px).  One device call;
     returns one dict per problem, as absolute_pose_estimation does."""
     keep, probs = [], []
@@ -87,6 +126,24 @@ def absolute_pose_estimation_batch(problems, max_error_px=12.0, min_inlier_ratio
     ctx = _lib.default_context(device)
     arr = (_lib.PoseProblem * k)(*probs)
     conf = _lib.PoseConf(float(min_inlier_ratio), int(min_num_trials), int(max_num_trials), float(confidence), int(seed) & (2 ** 64 - 1))
+    if estimate_focal_length or refine_focal_length or refine_extra_params:
+        fc = _focal_conf(estimate_focal_length, refine_focal_length, refine_extra_params, num_focal_length_samples, min_focal_length_ratio,
+                         max_focal_length_ratio, sweep_max_num_trials)
+        res = (_lib.PoseFocalResult * k)()
+        total = sum(pr.n for pr in probs)
+        mask = np.zeros(max(total, 1), dtype=np.uint8)
+        want_sweep = bool(return_sweep and estimate_focal_length)
+        ns = max(fc.num_focal_length_samples, 0) + 1
+        sweep = np.zeros((k, ns), dtype=SWEEP_DTYPE) if want_sweep else None
+        _lib.check(ctx.lib.sfd2_absolute_pose_focal_batch(ctx.h, arr, k, ctypes.byref(conf), ctypes.byref(fc), res, mask.ctypes.data,
+                                                          sweep.ctypes.data if want_sweep else None, 0))
+        out, o = [], 0
+        for i, pr in enumerate(probs):
+            out.append(_focal_result(res[i], problems[i][2], mask[o:o + pr.n].copy()))
+            if want_sweep:
+                out[-1]["sweep"] = sweep[i].copy()
+            o += pr.n
+        return out
     res = (_lib.PoseResult * k)()
     total = sum(pr.n for pr in probs)
     mask = np.zeros(max(total, 1), dtype=np.uint8)
@@ -100,16 +157,24 @@ def absolute_pose_estimation_batch(problems, max_error_px=12.0, min_inlier_ratio
 
 def absolute_pose_estimation(points2D, points3D, camera, max_error_px=12.0, min_inlier_ratio=DEFAULTS["min_inlier_ratio"],
                              min_num_trials=DEFAULTS["min_num_trials"], max_num_trials=DEFAULTS["max_num_trials"],
-                             confidence=DEFAULTS["confidence"], seed=DEFAULTS["seed"], device=0):
+                             confidence=DEFAULTS["confidence"], seed=DEFAULTS["seed"], device=0, **focal):
     """pycolmap.absolute_pose_estimation(points2D, points3D, camera, max_error_px) (localize_cv2.py:731): LO-RANSAC over P3P, then
     the Cauchy refinement in pixels.  Returns {'success', 'qvec', 'tvec', 'num_inliers', 'inliers' (bool [n]), 'num_trials'};
-    num_inliers and inliers are the RANSAC winner's, the pose the refined one.  Fewer than 4 correspondences: success False."""
+    num_inliers and inliers are the RANSAC winner's, the pose the refined one.  Fewer than 4 correspondences: success False.
+    **focal: absolute_pose_estimation_batch's keyword-only arguments (estimate_focal_length, refine_focal_length, refine_extra_params,
+    num_focal_length_samples, min_focal_length_ratio, max_focal_length_ratio, sweep_max_num_trials, return_sweep).  With one of the
+    first three the dict adds 'camera' (the given dict with the estimated params), 'focal_sample', 'focal_factor' and
+    'ransac_num_inliers' ('sweep' on request: [S + 1] records cnt / num_trials / sum_px); num_inliers and inliers are then those of
+    the mask the returned pose and camera were refined over."""
     return absolute_pose_estimation_batch([(points2D, points3D, camera)], max_error_px, min_inlier_ratio, min_num_trials,
-                                          max_num_trials, confidence, seed, device)[0]
+                                          max_num_trials, confidence, seed, device, **focal)[0]
 
 
-def pose_refinement_batch(problems, device=0):
-    """problems: a list of (tvec, qvec, points2D, points3D, inlier_mask, camera).  One device call; a list of pose_refinement's dicts."""
+def pose_refinement_batch(problems, device=0, *, refine_focal_length=False, refine_extra_params=False,
+                          min_focal_length_ratio=FOCAL_DEFAULTS["min_focal_length_ratio"],
+                          max_focal_length_ratio=FOCAL_DEFAULTS["max_focal_length_ratio"]):
+    """problems: a list of (tvec, qvec, points2D, points3D, inlier_mask, camera).  One device call; a list of pose_refinement's dicts.
+    With a refine flag the camera's focal and / or extra parameters are refined with the pose and each dict adds 'camera'."""
     keep, probs, qt, masks = [], [], [], []
     for tvec, qvec, p2, p3, m, cam in problems:
         pr = _problem(p2, p3, cam, 1.0, keep)
@@ -128,13 +193,20 @@ def pose_refinement_batch(problems, device=0):
     mask = np.ascontiguousarray(np.concatenate(masks + [np.zeros(1, np.uint8)]))
     ctx = _lib.default_context(device)
     arr = (_lib.PoseProblem * k)(*probs)
+    if refine_focal_length or refine_extra_params:
+        fc = _focal_conf(False, refine_focal_length, refine_extra_params, FOCAL_DEFAULTS["num_focal_length_samples"], min_focal_length_ratio,
+                         max_focal_length_ratio, FOCAL_DEFAULTS["sweep_max_num_trials"])
+        fres = (_lib.PoseFocalResult * k)()
+        _lib.check(ctx.lib.sfd2_pose_refine_camera_batch(ctx.h, arr, k, qt.ctypes.data, mask.ctypes.data, ctypes.byref(fc), fres, 0))
+        return [_focal_result(fres[i], problems[i][5]) for i in range(k)]
     res = (_lib.PoseResult * k)()
     _lib.check(ctx.lib.sfd2_pose_refine_batch(ctx.h, arr, k, qt.ctypes.data, mask.ctypes.data, res, 0))
     return [_result(res[i]) for i in range(k)]
 
 
-def pose_refinement(tvec, qvec, points2D, points3D, inlier_mask, camera, device=0):
+def pose_refinement(tvec, qvec, points2D, points3D, inlier_mask, camera, device=0, **focal):
     """pycolmap.pose_refinement(tvec, qvec, points2D, points3D, inlier_mask, camera) (localize_cv2.py:451): the refinement of
     absolute_pose_estimation alone, started from the given pose, over the correspondences the mask selects (intrinsics fixed).
-    Returns {'success', 'qvec', 'tvec'}."""
-    return pose_refinement_batch([(tvec, qvec, points2D, points3D, inlier_mask, camera)], device)[0]
+    Returns {'success', 'qvec', 'tvec'}; with refine_focal_length / refine_extra_params (**focal, see pose_refinement_batch) also
+    'camera'."""
+    return pose_refinement_batch([(tvec, qvec, points2D, points3D, inlier_mask, camera)], device, **focal)[0]

@@ -17,6 +17,7 @@ verified matches; the points are a function of the registered views and their po
          [--reference_sfm_model R | --intrinsics LIST...] [--single_camera] [--skip_geometric_verification]
          [--min_match_score X] [--min_num_matches N] [--verification essential|fundamental|geometry]
          [--refine_focal_length 0|1] [--refine_principal_point 0|1] [--refine_extra_params 0|1] [--intrinsics_min_views N]
+         [--abs_pose_estimate_focal_length 0|1]
          [--ba_solver pcg|dense]
 
 The refine options (default off) let every round's adjustment, from intrinsics_min_views registered views on, refine the cameras'
@@ -60,7 +61,7 @@ DEFAULTS = dict(max_error=4.0, min_num_matches=15, init_max_pairs=50, init_min_t
                 max_reproj_error=4.0, ba_round_iterations=25, ba_final_iterations=100, ba_loss_scale=1.0, max_reg_trials=3,
                 abs_pose_min_num_inliers=30, abs_pose_min_inlier_ratio=0.25, abs_pose_max_error=12.0, round_ratio=0.5, max_images_per_round=16,
                 seed=0, max_refine_iterations=50, max_rounds=64, fix_initial_pair=False, refine_focal_length=False, refine_principal_point=False,
-                refine_extra_params=False, intrinsics_min_views=INTRINSICS_MIN_VIEWS, ba_solver="pcg")
+                refine_extra_params=False, intrinsics_min_views=INTRINSICS_MIN_VIEWS, ba_solver="pcg", abs_pose_estimate_focal_length=False)
 STAT_KEYS = triangulation.STAT_KEYS + ("num_input_images",)
 
 
@@ -196,6 +197,13 @@ class DeviceStages:
         """cand: the view index of every problem (the device call does not need it)."""
         return pose.absolute_pose_estimation_batch(problems, max_error_px, min_inlier_ratio=min_inlier_ratio, seed=seed, device=self.device)
 
+    def absolute_pose_focal(self, problems, cand, max_error_px, min_inlier_ratio, seed):
+        """absolute_pose for views of a camera nobody has seen yet: the focal length is swept and refined, the extras
+        stay as given; each result carries 'camera'."""
+        from . import pose
+        return pose.absolute_pose_estimation_batch(problems, max_error_px, min_inlier_ratio=min_inlier_ratio, seed=seed, device=self.device,
+                                                   estimate_focal_length=True, refine_focal_length=True)
+
 
 # ---------------------------------------------------------------------------------------------------------------- the mapper
 def _blank_views(cameras, cam_ids):
@@ -253,7 +261,11 @@ def reconstruct(cameras, images, keypoints, pair_matches, skip_geometric_verific
     the matches of two_view.decide_two_view_geometry's choice stay, so a planar or rotation-only pair keeps its matches
     through H; a pair labelled panoramic, planar_or_panoramic or degenerate is no initial pair (planar is: the five-point pose holds on a
     plane).  The map then starts as with "fundamental".  With one of the options refine_focal_length, refine_principal_point,
-    refine_extra_params set the return is (cameras, images, points3D): the camera records with the refined intrinsics first."""
+    refine_extra_params set the return is (cameras, images, points3D): the camera records with the refined intrinsics first.  Option
+    abs_pose_estimate_focal_length: a candidate whose camera id has no registered view is registered through
+    stages.absolute_pose_focal, and on registration the camera record and every view of that camera id take the returned parameters; of
+    several candidates of a round that share such a camera the first to register sets it, the others wait for the next round without
+    losing a try.  The return then is (cameras, images, points3D) as well."""
     if verification not in ("essential", "fundamental", "geometry"):
         raise ValueError(f"unknown verification {verification!r}")
     unknown = set(options) - set(DEFAULTS)
@@ -267,7 +279,8 @@ def reconstruct(cameras, images, keypoints, pair_matches, skip_geometric_verific
     if mask and o["ba_solver"] != DEFAULTS["ba_solver"]:
         raise ValueError('ba_solver "dense" does not go with a refine option: the dense solver holds the intrinsics constant (DESIGN.md section 21)')
     ba_options = {} if o["ba_solver"] == DEFAULTS["ba_solver"] else {"solver": o["ba_solver"]}     # the default's calls stay as they were
-    if mask:
+    focal = bool(o["abs_pose_estimate_focal_length"])
+    if mask or focal:
         cameras = dict(cameras)                                                   # the refined records replace the given ones, round by round
     rep = {} if report is None else report
     order = sorted(images, key=lambda i: (images[i].name, i))                    # view k <-> input id order[k] <-> output id k + 1
@@ -416,14 +429,42 @@ def reconstruct(cameras, images, keypoints, pair_matches, skip_geometric_verific
         problems = [(prob["points2D"][po[c]:po[c + 1]], prob["points3D"][po[c]:po[c + 1]], cameras[images[order[v]].camera_id])
                     for c, v in enumerate(cand)]
         t = clock()
-        res = S.absolute_pose(problems, list(cand), o["abs_pose_max_error"], o["abs_pose_min_inlier_ratio"], o["seed"])
+        unseen = []                                                               # candidates of a camera no registered view has: its focal length is a prior
+        if focal:
+            seen = {images[order[k]].camera_id for k in np.flatnonzero(registered)}
+            unseen = [c for c, v in enumerate(cand) if images[order[v]].camera_id not in seen]
+        if unseen:
+            known = [c for c in range(len(cand)) if c not in set(unseen)]
+            res = [None] * len(cand)
+            if known:
+                for c, r in zip(known, S.absolute_pose([problems[c] for c in known], [cand[c] for c in known], o["abs_pose_max_error"],
+                                                       o["abs_pose_min_inlier_ratio"], o["seed"])):
+                    res[c] = r
+            for c, r in zip(unseen, S.absolute_pose_focal([problems[c] for c in unseen], [cand[c] for c in unseen], o["abs_pose_max_error"],
+                                                          o["abs_pose_min_inlier_ratio"], o["seed"])):
+                res[c] = r
+            rnd["focal_candidates"] = [order[cand[c]] for c in unseen]
+        else:
+            res = S.absolute_pose(problems, list(cand), o["abs_pose_max_error"], o["abs_pose_min_inlier_ratio"], o["seed"])
         rnd["seconds"]["absolute_pose_s"] = clock() - t
+        set_now = set()                                                           # cameras a candidate of this round has set
         for c, (v, r) in enumerate(zip(cand, res)):
             n = int(po[c + 1] - po[c])
+            cid = images[order[v]].camera_id
+            if c in unseen and cid in set_now:                                    # estimated at the prior another candidate has replaced: next round
+                continue
             if r["success"] and r["num_inliers"] >= o["abs_pose_min_num_inliers"] and n > 0 and r["num_inliers"] / n >= o["abs_pose_min_inlier_ratio"]:
                 _set_pose(views[v], r["qvec"], r["tvec"])
                 registered[v] = True
                 rnd["registered"].append(order[v])
+                if c in unseen:                                                   # the record and the views, as the adjustment's path does
+                    cam = cameras[cid]
+                    params = camera_model(r["camera"])[1]
+                    cameras[cid] = colmap_io.Camera(cam["id"], cam["model"], cam["width"], cam["height"], params[:len(cam["params"])])
+                    for k in np.flatnonzero(view_camera == cam_index[cid]):
+                        for i in range(8):
+                            views[k].params[i] = float(params[i])
+                    set_now.add(cid)
             else:
                 tries[v] += 1
 
@@ -455,7 +496,7 @@ def reconstruct(cameras, images, keypoints, pair_matches, skip_geometric_verific
         pid = int(pid_of_row[r])
         points3D[pid] = colmap_io.Point3D(pid, M["xyz"][r].copy(), np.zeros(3, np.uint8), float(flt["point_error"][r]), (node_view[a:b] + 1).astype(np.int32),
                                           node_idx[a:b].astype(np.int32))
-    if mask:
+    if mask or focal:
         return cameras, out_images, points3D
     return out_images, points3D
 
@@ -501,7 +542,8 @@ def read_images(pairs_path, features_path, single_camera=False, reference_sfm_mo
 
 def main(sfm_dir, image_dir, pairs, features, matches, colmap_path=None, single_camera=False, skip_geometric_verification=False,
          min_match_score=None, min_num_matches=None, reference_sfm_model=None, intrinsics=(), device=0, verification="essential",
-         refine_focal_length=0, refine_principal_point=0, refine_extra_params=0, intrinsics_min_views=None, ba_solver=None, **options):
+         refine_focal_length=0, refine_principal_point=0, refine_extra_params=0, intrinsics_min_views=None, ba_solver=None,
+         abs_pose_estimate_focal_length=0, **options):
     """hloc/reconstruction.py main(): image_dir and colmap_path are accepted and unused.  Writes sfm_dir/models/0/{cameras,images,
     points3D}.bin and sfm_dir/stats.txt (one `key: value` per line; the reference writes the same keys without the newline); returns
     the statistics.  With a refine option set cameras.bin holds the refined intrinsics."""
@@ -512,7 +554,7 @@ def main(sfm_dir, image_dir, pairs, features, matches, colmap_path=None, single_
     if min_num_matches is not None:
         options["min_num_matches"] = int(min_num_matches)
     for key, value in (("refine_focal_length", refine_focal_length), ("refine_principal_point", refine_principal_point),
-                       ("refine_extra_params", refine_extra_params)):
+                       ("refine_extra_params", refine_extra_params), ("abs_pose_estimate_focal_length", abs_pose_estimate_focal_length)):
         if value:
             options[key] = True
     if intrinsics_min_views is not None:
@@ -561,6 +603,7 @@ def parser():
     ap.add_argument("--refine_principal_point", type=int, choices=(0, 1), default=0)
     ap.add_argument("--refine_extra_params", type=int, choices=(0, 1), default=0)
     ap.add_argument("--intrinsics_min_views", type=int, default=None)
+    ap.add_argument("--abs_pose_estimate_focal_length", type=int, choices=(0, 1), default=0)
     ap.add_argument("--ba_solver", choices=sorted(bundle_adjustment.SOLVERS), default=DEFAULTS["ba_solver"])
     return ap
 
