@@ -47,17 +47,6 @@ bool to_cam(const sfd2_pose_problem &p, PoseCam &c, double &mean_focal, std::str
     return true;
 }
 
-// COLMAP ComputeNumTrials (sample size 3, dyn_num_trials_multiplier 3)
-double num_trials(double inlier_ratio, double confidence)
-{
-    const double nom = 1.0 - confidence;
-    if (nom <= 0) return 1e300;
-    const double den = 1.0 - inlier_ratio * inlier_ratio * inlier_ratio;
-    if (den <= 0) return 1.0;
-    if (den == 1.0 || std::fabs(std::log(den)) < 1e-16) return 1e300;
-    return std::ceil(std::log(nom) / std::log(den) * 3.0);
-}
-
 // checks the problems and lays them out one behind the other: pd[k], total = their correspondences; -1 with the message
 int pack(const std::string &F, const sfd2_pose_problem *problems, int k, const double *qt_in, std::vector<PoseProbDev> &pd, int64_t &total)
 {
@@ -110,14 +99,15 @@ hipError_t upload_points(sfd2_ctx *c, const sfd2_pose_problem *problems, const s
     return hipMemcpyAsync(p3d, p3.data(), 24 * total, hipMemcpyHostToDevice, c->stream);
 }
 
-// COLMAP's RANSAC: max_num_trials limited by the trial count of an assumed min_inlier_ratio (kNumSamples = 100000); both limits at most cap
+// the device's options: the trial limits of sample size 3 (api_scratch.h), both at most cap
 PoseConfDev trial_conf(const sfd2_pose_conf &conf, int64_t cap)
 {
     PoseConfDev d;
     memset(&d, 0, sizeof(d));
-    const double dyn = num_trials(std::floor(conf.min_inlier_ratio * 100000) / 100000.0, conf.confidence);
-    d.max_trials = std::max<int64_t>(1, std::min<double>((double)std::min(conf.max_num_trials, cap), dyn));
-    d.min_trials = std::min(std::min(conf.min_num_trials, cap), d.max_trials);
+    const double r = floored_ratio(conf.min_inlier_ratio);
+    const TrialLimits t = trial_limits(conf.confidence, conf.min_num_trials, conf.max_num_trials, cap, r * r * r);
+    d.max_trials = t.max_trials;
+    d.min_trials = t.min_trials;
     d.confidence = conf.confidence;
     d.seed = conf.seed;
     d.refine_only = 0;
@@ -190,10 +180,8 @@ extern "C" int sfd2_absolute_pose_batch(sfd2_ctx *c, const sfd2_pose_problem *pr
     if (!c || !conf || (k > 0 && (!problems || !results))) return fail("sfd2_absolute_pose_batch: null argument");
     if (k < 0) return fail("sfd2_absolute_pose_batch: negative k");
     if (flags != 0) return fail("sfd2_absolute_pose_batch: unknown flags");
-    if (!(conf->confidence >= 0 && conf->confidence <= 1) || !(conf->min_inlier_ratio >= 0 && conf->min_inlier_ratio <= 1))
-        return fail("sfd2_absolute_pose_batch: confidence and min_inlier_ratio must lie in [0, 1]");
-    if (conf->max_num_trials < 1 || conf->max_num_trials > 1000000000 || conf->min_num_trials < 0)
-        return fail("sfd2_absolute_pose_batch: trial limits out of range (1 <= max_num_trials <= 1e9, min_num_trials >= 0)");
+    if (const char *bad = ransac_conf_error(conf->confidence, conf->min_inlier_ratio, conf->min_num_trials, conf->max_num_trials))
+        return fail(std::string("sfd2_absolute_pose_batch") + bad);
     int64_t total = 0;
     for (int i = 0; i < k; ++i) total += std::max(problems[i].n, 0);
     if (total > 0 && !inlier_mask_u8) return fail("sfd2_absolute_pose_batch: null inlier mask");
@@ -280,10 +268,8 @@ extern "C" int sfd2_absolute_pose_focal_batch(sfd2_ctx *c, const sfd2_pose_probl
     if (!c || !conf || !fc || (k > 0 && (!problems || !results))) return fail(F + ": null argument");
     if (k < 0) return fail(F + ": negative k");
     if (flags != 0) return fail(F + ": unknown flags");
-    if (!(conf->confidence >= 0 && conf->confidence <= 1) || !(conf->min_inlier_ratio >= 0 && conf->min_inlier_ratio <= 1))
-        return fail(F + ": confidence and min_inlier_ratio must lie in [0, 1]");
-    if (conf->max_num_trials < 1 || conf->max_num_trials > 1000000000 || conf->min_num_trials < 0)
-        return fail(F + ": trial limits out of range (1 <= max_num_trials <= 1e9, min_num_trials >= 0)");
+    if (const char *bad = ransac_conf_error(conf->confidence, conf->min_inlier_ratio, conf->min_num_trials, conf->max_num_trials))
+        return fail(F + bad);
     if (check_focal_conf(F, fc) != 0) return -1;
     std::vector<PoseProbDev> pd;
     int64_t total = 0;

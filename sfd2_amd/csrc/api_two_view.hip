@@ -2,21 +2,6 @@
 #include "sfd2_ctx.h"
 #include "api_scratch.h"
 
-namespace {
-
-// COLMAP ComputeNumTrials (sample size 5, dyn_num_trials_multiplier 3)
-double num_trials(double inlier_ratio, double confidence)
-{
-    const double nom = 1.0 - confidence;
-    if (nom <= 0) return 1e300;
-    const double den = 1.0 - std::pow(inlier_ratio, 5);
-    if (den <= 0) return 1.0;
-    if (den == 1.0 || std::fabs(std::log(den)) < 1e-16) return 1e300;
-    return std::ceil(std::log(nom) / std::log(den) * 3.0);
-}
-
-}  // namespace
-
 extern "C" int sfd2_relative_pose_batch(sfd2_ctx *c, const sfd2_two_view_problem *problems, int k, const sfd2_two_view_conf *conf,
                                         sfd2_two_view_result *results, uint8_t *inlier_mask_u8, double *tri_angle_deg, int flags)
 {
@@ -24,17 +9,15 @@ extern "C" int sfd2_relative_pose_batch(sfd2_ctx *c, const sfd2_two_view_problem
     if (!c || !conf || (k > 0 && (!problems || !results))) return fail(F + ": null argument");
     if (k < 0) return fail(F + ": negative k");
     if (flags != 0) return fail(F + ": unknown flags");
-    if (!(conf->confidence >= 0 && conf->confidence <= 1) || !(conf->min_inlier_ratio >= 0 && conf->min_inlier_ratio <= 1))
-        return fail(F + ": confidence and min_inlier_ratio must lie in [0, 1]");
-    if (conf->max_num_trials < 1 || conf->max_num_trials > 1000000000 || conf->min_num_trials < 0)
-        return fail(F + ": trial limits out of range (1 <= max_num_trials <= 1e9, min_num_trials >= 0)");
+    if (const char *bad = ransac_conf_error(conf->confidence, conf->min_inlier_ratio, conf->min_num_trials, conf->max_num_trials))
+        return fail(F + bad);
     if (conf->min_num_inliers < 0) return fail(F + ": negative min_num_inliers");
     TvConfDev d;
     memset(&d, 0, sizeof(d));
-    // COLMAP's RANSAC: max_num_trials limited by the trial count of an assumed min_inlier_ratio (kNumSamples = 100000)
-    const double dyn = num_trials(std::floor(conf->min_inlier_ratio * 100000) / 100000.0, conf->confidence);
-    d.max_trials = std::max<int64_t>(1, std::min<double>((double)conf->max_num_trials, dyn));
-    d.min_trials = std::min(conf->min_num_trials, d.max_trials);
+    const double p_all = std::pow(floored_ratio(conf->min_inlier_ratio), 5);                 // sample size 5
+    const TrialLimits t = trial_limits(conf->confidence, conf->min_num_trials, conf->max_num_trials, INT64_MAX, p_all);
+    d.max_trials = t.max_trials;
+    d.min_trials = t.min_trials;
     d.confidence = conf->confidence;
     d.seed = conf->seed;
     d.min_num_inliers = conf->min_num_inliers;

@@ -7,12 +7,15 @@ a Gauss-Newton run depends on the chart), the final Levenberg-Marquardt and the 
 second solver written from the same text -- Gauss-Jordan, modified Gram-Schmidt, the bracketing root finder -- against which route A
 is measured on the CPU (tests/test_fundamental_ref_host.py).  Also the committed cases the GPU tests (tests/test_gpu_fundamental.py)
 and the CPU checks share."""
+import functools
+
 import numpy as np
 
 import pose_ref as pr
+import ransac_ref as rr
 import two_view_ref as tv
 
-ROUND = 256
+ROUND = rr.ROUND
 LO_STEPS, LO_GN, REF_ITERS, POLISH = 8, 3, 50, 3
 RANK_MIN = 1e-12             # route A: sigma_7 / sigma_1 of the 7 x 9 system at or below which a sample gives no hypothesis
 PIVOT_MIN = 1e-12            # route B (and the kernel): a pivot at or below this times max|A|
@@ -31,44 +34,15 @@ F_MEASURED = 6.0e-9
 F_TOL = 100 * F_MEASURED
 F_CEILING = 1e-6
 EXACT_SUM = 1e-24            # a sum of squared Sampson errors (normalised) below this is that of an exact solution (rounding only)
-_M64 = (1 << 64) - 1
-mix64 = pr.mix64
+mix64 = rr.mix64
 _hom = tv._hom
 sampson_f64 = tv.sampson_f64
 support = tv.support
 
 
-# ------------------------------------------------------------------------------------------------------------ sampling
-def sample_k(seed, trial, n, k=7):
-    """k distinct indices in [0, n) from (seed, trial) only, on Python ints (two_view_ref.sample5's scheme)."""
-    h = mix64((seed & _M64) ^ mix64(trial & _M64))
-    out = []
-    for i in range(k):
-        if i:
-            h = mix64(h)
-        v = h % (n - i)
-        for c in sorted(out):
-            if v >= c:
-                v += 1
-        out.append(v)
-    return tuple(out)
-
-
-def sample_kv(seed, trials, n, k=7):
-    """sample_k for an array of trials (np.uint64 arithmetic): int64 [T, k]."""
-    t = np.asarray(trials, dtype=np.int64).astype(np.uint64)
-    h = pr._mix64v(np.uint64(seed & _M64) ^ pr._mix64v(t))
-    cols = []
-    for i in range(k):
-        if i:
-            h = pr._mix64v(h)
-        v = (h % np.uint64(n - i)).astype(np.int64)
-        if cols:
-            srt = np.sort(np.stack(cols, 1), axis=1)
-            for p in range(i):
-                v = v + (v >= srt[:, p])
-        cols.append(v)
-    return np.stack(cols, 1)
+# the sampling on integers is ransac_ref's (one scheme for every sample size), at sample size 7 unless told otherwise
+sample_k = lambda seed, trial, n, k=7: rr.sample_k(seed, trial, n, k)            # noqa: E731
+sample_kv = lambda seed, trials, n, k=7: rr.sample_kv(seed, trials, n, k)        # noqa: E731
 
 
 # ------------------------------------------------------------------------------------------------------------ seven-point, route A
@@ -277,18 +251,6 @@ def normal_equations(ch, x0, x1, w):
     return J.T @ J, J.T @ r, float(r @ r)
 
 
-def solve7(H, g, lam=0.0):
-    """d of (H + lam diag H + 1e-15 max diag H) d = -g, and whether the system was positive definite and finite."""
-    dg = np.diag(H)
-    if not (np.isfinite(H).all() and np.isfinite(g).all() and dg.max() > 0):
-        return np.zeros(7), False
-    A = H + np.diag(lam * dg + 1e-15 * dg.max())
-    if not np.linalg.eigvalsh(A)[0] > 0:
-        return np.zeros(7), False
-    d = -np.linalg.solve(A, g)
-    return d, bool(np.isfinite(d).all())
-
-
 def apply_update(ch, d):
     out = dict(ch, f=ch["f"].copy())
     out["f"][ch["free"]] += d[:5]
@@ -297,101 +259,34 @@ def apply_update(ch, d):
 
 
 # ------------------------------------------------------------------------------------------------------------ LO-RANSAC
-def num_trials_needed(inlier_ratio, confidence, multiplier=3.0):
-    """COLMAP's ComputeNumTrials for sample size 7."""
-    nom = 1.0 - confidence
-    if nom <= 0:
-        return np.inf
-    den = 1.0 - inlier_ratio ** 7
-    if den <= 0:
-        return 1.0
-    if den == 1.0 or abs(np.log(den)) < 1e-16:
-        return np.inf
-    return float(np.ceil(np.log(nom) / np.log(den) * multiplier))
-
-
-def trial_limits(min_inlier_ratio, min_num_trials, max_num_trials, confidence, multiplier=3.0):
-    dyn = num_trials_needed(np.floor(min_inlier_ratio * 100000) / 100000.0, confidence, multiplier)
-    mx = int(max(1, min(float(max_num_trials), dyn)))
-    return min(int(min_num_trials), mx), mx
-
-
-def _in_band(e, th2):
-    return bool(np.any(np.abs(e - th2) <= BAND * th2))
-
-
-def _close(a, b):
-    return abs(a - b) <= BAND * max(abs(a), abs(b)) or max(abs(a), abs(b)) < EXACT_SUM
+num_trials_needed, trial_limits = rr.trial_rule(7)       # COLMAP's ComputeNumTrials and trial limits for sample size 7
 
 
 def _distinct(Fa, Fb):
     return float(_fdist(Fa, Fb)) > 1e-8
 
 
-def _lo_tie_matters(e, th2):
-    return bool(np.any(np.abs(e - th2) <= 1e-3 * th2))
+def _lo_step(carried, F, inl, x0, x1):
+    """One re-estimation: LO_GN Gauss-Newton steps over the inliers on a new chart of the current best."""
+    ch, ok = make_chart(F)
+    for _ in range(LO_GN):
+        if not ok:
+            return None
+        H, g, _ = normal_equations(ch, x0, x1, inl)
+        d, ok = rr.damped_solve(H, g)
+        if ok:
+            ch = apply_update(ch, d)
+    return (carried, chart_matrix(ch)) if ok else None
 
 
-def lo_ransac_ref(x0, x1, th2, min_inlier_ratio=0.25, min_num_trials=0, max_num_trials=10000, confidence=0.999, seed=0, multiplier=3.0,
-                  lo=True, smaller_sum=True, drop_root=False, solver=seven_point_ref):
-    """The rounds on normalised points (two_view_ref.lo_ransac_ref with sample size 7 and the chart above).  Returns {'F' (None without
-    a hypothesis), 'cnt', 'sum', 'trials', 'banded', 'why', 'either' (the other matrices that fit every point to rounding as the best
-    one does)}.  multiplier, lo, smaller_sum, drop_root: the rule breaks of the host test."""
-    n = len(x0)
-    mn, mx = trial_limits(min_inlier_ratio, min_num_trials, max_num_trials, confidence, multiplier)
-    best, bF, why, trials, rnd = (-1, 0.0, np.inf), None, [], 0, 0
-    either = []
-    sg = 1.0 if smaller_sum else -1.0
-    while True:
-        tr = np.arange(rnd * ROUND, min((rnd + 1) * ROUND, mx))
-        idx = sample_kv(seed, tr, n)
-        Fs, owner, near = solver(x0[idx], x1[idx], drop_root)
-        if len(Fs):
-            cnt, sm, _, err = support(Fs, x0, x1, th2)
-            order = np.lexsort((np.arange(len(Fs)), tr[owner], sg * sm, -cnt))
-            w = order[0]
-            win = (int(cnt[w]), float(sm[w]), int(tr[owner[w]]))
-            if (win[0], -sg * win[1], -win[2]) > (best[0], -sg * best[1], -best[2]):
-                rivals = [k for k in order[1:] if cnt[k] == cnt[w] and _close(sm[k], sm[w]) and _distinct(Fs[k], Fs[w])]
-                # a winner that fits its inliers to rounding (n = 7: every root of every sample holds all points; n = 8 with a
-                # wrong match: every sample without it holds its 7) is ordered among its like by rounding alone: those rivals are
-                # reported, and any one of them is a right answer (reason (b) of section 13)
-                exact = win[1] < EXACT_SUM
-                either = []
-                for k in rivals if exact else []:
-                    if all(_distinct(Fs[k], Fo) for Fo in either):
-                        either.append(Fs[k])
-                why += ["rival"] * int(bool(rivals) and not exact) + ["threshold"] * int(_in_band(err[w], th2)) + ["near"] * int(near[owner[w]])
-                why += ["tie"] * int(best[0] == win[0] and _close(best[1], win[1]))
-                best, bF = win, Fs[w]
-                for _ in range(LO_STEPS if lo else 0):
-                    ch, ok = make_chart(bF)
-                    inl = (sampson_f64(bF, x0, x1) <= th2).astype(np.float64)
-                    for _ in range(LO_GN):
-                        if not ok:
-                            break
-                        H, g, _ = normal_equations(ch, x0, x1, inl)
-                        d, ok = solve7(H, g)
-                        if ok:
-                            ch = apply_update(ch, d)
-                    if not ok:
-                        break
-                    Fn = chart_matrix(ch)
-                    c, s, _, e = support(Fn, x0, x1, th2)
-                    tie = int(c) == best[0] and _close(float(s), best[1]) and _distinct(Fn, bF) and _lo_tie_matters(e, th2)
-                    why += ["lo threshold"] * int(_in_band(e, th2)) + ["lo tie"] * int(tie)
-                    if not (c > best[0] or (c == best[0] and sg * s < sg * best[1])):
-                        break
-                    best, bF = (int(c), float(s), best[2]), Fn
-            elif win[0] == best[0] and _close(win[1], best[1]) and _distinct(Fs[w], bF):
-                why.append("tie")
-        trials = min((rnd + 1) * ROUND, mx)
-        if trials >= mx:
-            break
-        if trials >= mn and best[0] > 0 and trials >= num_trials_needed(best[0] / n, confidence, multiplier):
-            break
-        rnd += 1
-    return {"F": bF, "cnt": best[0], "sum": best[1], "trials": trials, "banded": bool(why), "why": why, "either": either}
+# The rounds are ransac_ref.lo_ransac's.  A winner that fits its inliers to rounding is exact whatever their number (n = 8 with a wrong
+# match: every sample without it holds its 7); the local optimisation carries nothing from step to step.
+MODEL = rr.Model(name="F", sample_size=7, solver=seven_point_ref, support=support, error=sampson_f64, distinct=_distinct, band=BAND,
+                 exact_sum=EXACT_SUM, lo_steps=LO_STEPS, lo_start=lambda F: None, lo_step=_lo_step, rule_breaks=("drop_root",))
+
+
+# lo_ransac_ref(x0, x1, th2, **conf): {'F' (None without a hypothesis), 'cnt', 'sum', 'trials', 'banded', 'why', 'either'}; solver: the route.
+lo_ransac_ref = functools.partial(rr.lo_ransac, MODEL)
 
 
 def final_stage(F, mask, x0, x1):
@@ -401,25 +296,8 @@ def final_stage(F, mask, x0, x1):
     if not ok:
         return None, np.inf
     w = mask.astype(np.float64)
-    H, g, c = normal_equations(ch, x0, x1, w)
-    lam = 1e-4
-    for _ in range(REF_ITERS):
-        d, ok = solve7(H, g, lam)
-        if not ok:
-            break
-        cn_ = apply_update(ch, d)
-        Hn, gn, cn = normal_equations(cn_, x0, x1, w)
-        step = float(np.sum(d * d))
-        if np.isfinite(cn) and cn <= c:
-            ch, H, g, c = cn_, Hn, gn, cn
-            lam = max(lam * 0.1, 1e-12)
-            if step < 1e-26:
-                break
-        else:
-            lam *= 10.0
-            if lam > 1e12 or step < 1e-26:
-                break
-    d, ok = solve7(H, g)
+    ch, H, g = rr.levenberg_marquardt(ch, lambda c: normal_equations(c, x0, x1, w), rr.damped_solve, apply_update, REF_ITERS)
+    d, ok = rr.damped_solve(H, g)
     scale = np.sqrt(np.sum(ch["f"] ** 2) + ch["a"] ** 2 + ch["b"] ** 2)
     return chart_matrix(ch), (float(np.linalg.norm(d)) / scale if ok else np.inf)
 
@@ -492,13 +370,7 @@ def compare(r, ref, worst):
 
 
 # ------------------------------------------------------------------------------------------------------------ scenes and cases
-_cache = {}
-
-
-def _cached(key, make):
-    if key not in _cache:
-        _cache[key] = make()
-    return _cache[key]
+_cached = rr.make_cached()
 
 
 CAM0 = {"model": "PINHOLE", "width": 1024, "height": 768, "params": [800.0, 800.0, 512.0, 384.0]}

@@ -6,13 +6,16 @@ rule, the 8-parameter chart of the refinement, the final Levenberg-Marquardt and
 the closed form of item 3, written from the same text, against which route A is measured on the CPU
 (tests/test_homography_ref_host.py).  Also the committed cases the GPU tests (tests/test_gpu_homography.py) and the CPU checks share,
 and the scenes of the E / F / H decision."""
+import functools
+
 import numpy as np
 
 import fundamental_ref as fr
 import pose_ref as pr
+import ransac_ref as rr
 import two_view_ref as tv
 
-ROUND = 256
+ROUND = rr.ROUND
 LO_STEPS, LO_GN, REF_ITERS = 8, 3, 50
 COLLINEAR = 1e-12            # a triple product at or below this times the three vectors' norms: no hypothesis
 NEAR = pr.NEAR               # a degeneracy measure within this factor of its threshold is too close to call
@@ -29,8 +32,8 @@ H_TOL = 100 * H_MEASURED
 H_CEILING = 1e-6
 EXACT_SUM = 1e-24            # a sum of squared transfer errors (normalised) below this is that of an exact solution (rounding only)
 _hom = tv._hom
-sample_k = lambda seed, trial, n: fr.sample_k(seed, trial, n, 4)          # noqa: E731
-sample_kv = lambda seed, trials, n: fr.sample_kv(seed, trials, n, 4)      # noqa: E731
+sample_k = lambda seed, trial, n: rr.sample_k(seed, trial, n, 4)          # noqa: E731
+sample_kv = lambda seed, trials, n: rr.sample_kv(seed, trials, n, 4)      # noqa: E731
 _unit = fr._unit
 _hdist = fr._fdist           # distance of unit-norm matrices up to sign
 
@@ -143,18 +146,6 @@ def normal_equations(H, free, x0, x1, w):
         return J.T @ J, J.T @ r, float(r @ r)
 
 
-def solve8(Hm, g, lam=0.0):
-    """d of (H + lam diag H + 1e-15 max diag H) d = -g, and whether the system was positive definite and finite."""
-    dg = np.diag(Hm)
-    if not (np.isfinite(Hm).all() and np.isfinite(g).all() and dg.max() > 0):
-        return np.zeros(8), False
-    A = Hm + np.diag(lam * dg + 1e-15 * dg.max())
-    if not np.linalg.eigvalsh(A)[0] > 0:
-        return np.zeros(8), False
-    d = -np.linalg.solve(A, g)
-    return d, bool(np.isfinite(d).all())
-
-
 def apply_update(H, free, d):
     h = np.asarray(H, np.float64).reshape(9).copy()
     h[free] += d
@@ -162,116 +153,36 @@ def apply_update(H, free, d):
 
 
 # ------------------------------------------------------------------------------------------------------------ LO-RANSAC
-def num_trials_needed(inlier_ratio, confidence, multiplier=3.0):
-    """COLMAP's ComputeNumTrials for sample size 4."""
-    nom = 1.0 - confidence
-    if nom <= 0:
-        return np.inf
-    den = 1.0 - inlier_ratio ** 4
-    if den <= 0:
-        return 1.0
-    if den == 1.0 or abs(np.log(den)) < 1e-16:
-        return np.inf
-    return float(np.ceil(np.log(nom) / np.log(den) * multiplier))
-
-
-def trial_limits(min_inlier_ratio, min_num_trials, max_num_trials, confidence, multiplier=3.0):
-    dyn = num_trials_needed(np.floor(min_inlier_ratio * 100000) / 100000.0, confidence, multiplier)
-    mx = int(max(1, min(float(max_num_trials), dyn)))
-    return min(int(min_num_trials), mx), mx
-
-
-def _in_band(e, th2):
-    with np.errstate(invalid="ignore"):
-        return bool(np.any(np.abs(e - th2) <= BAND * th2))
-
-
-def _close(a, b):
-    return abs(a - b) <= BAND * max(abs(a), abs(b)) or max(abs(a), abs(b)) < EXACT_SUM
+num_trials_needed, trial_limits = rr.trial_rule(4)       # COLMAP's ComputeNumTrials and trial limits for sample size 4
 
 
 def _distinct(Ha, Hb):
     return float(_hdist(Ha, Hb)) > 1e-8
 
 
-def _lo_tie_matters(e, th2):
-    with np.errstate(invalid="ignore"):
-        return bool(np.any(np.abs(e - th2) <= 1e-3 * th2))
+def _lo_step(carried, H, inl, x0, x1):
+    """One re-estimation: LO_GN Gauss-Newton steps over the inliers on a new chart of the current best, on the matrix itself."""
+    fix, free, ok = make_chart(H)
+    for _ in range(LO_GN):
+        if not ok:
+            return None
+        Hm, g, _ = normal_equations(H, free, x0, x1, inl)
+        d, ok = rr.damped_solve(Hm, g)
+        if ok:
+            H = apply_update(H, free, d)
+    return (carried, H) if ok else None
 
 
-def lo_ransac_ref(x0, x1, th2, min_inlier_ratio=0.25, min_num_trials=0, max_num_trials=10000, confidence=0.999, seed=0, multiplier=3.0,
-                  lo=True, smaller_sum=True, solver=four_point_dlt):
-    """The rounds on normalised points (fundamental_ref.lo_ransac_ref with sample size 4 and the chart above).  Returns {'H' (None without
-    a hypothesis), 'cnt', 'sum', 'trials', 'banded', 'why', 'either' (the other matrices that fit their inliers to rounding as the best
-    one does)}.  multiplier, lo, smaller_sum: the rule breaks of the host test."""
-    n = len(x0)
-    mn, mx = trial_limits(min_inlier_ratio, min_num_trials, max_num_trials, confidence, multiplier)
-    best, bH, why, trials, rnd = (-1, 0.0, np.inf), None, [], 0, 0
-    either = []
-    sg = 1.0 if smaller_sum else -1.0
-    while True:
-        tr = np.arange(rnd * ROUND, min((rnd + 1) * ROUND, mx))
-        idx = sample_kv(seed, tr, n)
-        Hs, owner, near = solver(x0[idx], x1[idx])
-        # a sample too close to the collinearity threshold may or may not give a hypothesis: reason (c)
-        if near.any():
-            why.append("near")
-        if len(Hs):
-            cnt, sm, err = support(Hs, x0, x1, th2)
-            order = np.lexsort((tr[owner], sg * sm, -cnt))
-            w = order[0]
-            win = (int(cnt[w]), float(sm[w]), int(tr[owner[w]]))
-            if (win[0], -sg * win[1], -win[2]) > (best[0], -sg * best[1], -best[2]):
-                rivals = [k for k in order[1:] if cnt[k] == cnt[w] and _close(sm[k], sm[w]) and _distinct(Hs[k], Hs[w])]
-                # a winner that fits its inliers to rounding (n = 4: every sample holds all points; n = 5 with a wrong match: every
-                # sample holds its 4) is ordered among its like by rounding alone: those rivals are reported, and any one of them is
-                # a right answer (reason (b) of section 13)
-                # The same holds across rounds: an exact winner that replaces an exact best of as many
-                # points does so by rounding alone, and the earlier best and its like stay right answers.
-                exact = win[1] < EXACT_SUM
-                carried = exact and best[0] == win[0] and best[1] < EXACT_SUM
-                either = ([bH] + either) if carried else []
-                either = [Ho for Ho in either if _distinct(Ho, Hs[w])]
-                for k in rivals if exact else []:
-                    if all(_distinct(Hs[k], Ho) for Ho in either):
-                        either.append(Hs[k])
-                why += ["rival"] * int(bool(rivals) and not exact) + ["threshold"] * int(_in_band(err[w], th2))
-                why += ["tie"] * int(best[0] == win[0] and _close(best[1], win[1]) and not carried)
-                best, bH = win, Hs[w]
-                for _ in range(LO_STEPS if lo else 0):
-                    fix, free, ok = make_chart(bH)
-                    with np.errstate(invalid="ignore"):
-                        inl = (transfer_f64(bH, x0, x1) <= th2).astype(np.float64)
-                    Hn = bH
-                    for _ in range(LO_GN):
-                        if not ok:
-                            break
-                        Hm, g, _ = normal_equations(Hn, free, x0, x1, inl)
-                        d, ok = solve8(Hm, g)
-                        if ok:
-                            Hn = apply_update(Hn, free, d)
-                    if not ok:
-                        break
-                    c, s, e = support(Hn, x0, x1, th2)
-                    tie = int(c) == best[0] and _close(float(s), best[1]) and _distinct(Hn, bH) and _lo_tie_matters(e, th2)
-                    why += ["lo threshold"] * int(_in_band(e, th2)) + ["lo tie"] * int(tie)
-                    if not (c > best[0] or (c == best[0] and sg * s < sg * best[1])):
-                        break
-                    best, bH = (int(c), float(s), best[2]), Hn
-            elif win[0] == best[0] and _close(win[1], best[1]) and _distinct(Hs[w], bH):
-                if win[1] < EXACT_SUM and best[1] < EXACT_SUM:              # exact fits of as many points in a later round
-                    for k in order:
-                        if cnt[k] == cnt[w] and sm[k] < EXACT_SUM and all(_distinct(Hs[k], Ho) for Ho in [bH] + either):
-                            either.append(Hs[k])
-                else:
-                    why.append("tie")
-        trials = min((rnd + 1) * ROUND, mx)
-        if trials >= mx:
-            break
-        if trials >= mn and best[0] > 0 and trials >= num_trials_needed(best[0] / n, confidence, multiplier):
-            break
-        rnd += 1
-    return {"H": bH, "cnt": best[0], "sum": best[1], "trials": trials, "banded": bool(why), "why": why, "either": either}
+# The rounds are ransac_ref.lo_ransac's.  A winner that fits its inliers to rounding is exact whatever their number (n = 5 with a wrong
+# match: every sample without it holds its 4), and here alone such fits are carried across rounds and "near" is said of any sample
+# of the round (a sample too close to the collinearity threshold may or may not give a hypothesis: reason (c)); an error may be NaN.
+MODEL = rr.Model(name="H", sample_size=4, solver=four_point_dlt, support=support, error=transfer_f64, distinct=_distinct,
+                 band=BAND, exact_sum=EXACT_SUM, lo_steps=LO_STEPS, lo_start=lambda H: None, lo_step=_lo_step,
+                 nan_errors=True, carries_exact=True, near_any_sample=True)
+
+
+# lo_ransac_ref(x0, x1, th2, **conf): {'H' (None without a hypothesis), 'cnt', 'sum', 'trials', 'banded', 'why', 'either'}; solver: the route.
+lo_ransac_ref = functools.partial(rr.lo_ransac, MODEL)
 
 
 def final_stage(H, mask, x0, x1):
@@ -281,25 +192,8 @@ def final_stage(H, mask, x0, x1):
         return None
     w = mask.astype(np.float64)
     H = np.asarray(H, np.float64).reshape(3, 3)
-    Hm, g, c = normal_equations(H, free, x0, x1, w)
-    lam = 1e-4
-    for _ in range(REF_ITERS):
-        d, ok = solve8(Hm, g, lam)
-        if not ok:
-            break
-        Hc = apply_update(H, free, d)
-        Hn, gn, cn = normal_equations(Hc, free, x0, x1, w)
-        step = float(np.sum(d * d))
-        if np.isfinite(cn) and cn <= c:
-            H, Hm, g, c = Hc, Hn, gn, cn
-            lam = max(lam * 0.1, 1e-12)
-            if step < 1e-26:
-                break
-        else:
-            lam *= 10.0
-            if lam > 1e12 or step < 1e-26:
-                break
-    return H
+    return rr.levenberg_marquardt(H, lambda M: normal_equations(M, free, x0, x1, w), rr.damped_solve,
+                                  lambda M, d: apply_update(M, free, d), REF_ITERS)[0]
 
 
 def normalisation(p0, p1):
@@ -372,8 +266,7 @@ def compare(r, ref, worst):
 
 
 # ------------------------------------------------------------------------------------------------------------ scenes and cases
-_cache = {}
-_cached = lambda key, make: _cache[key] if key in _cache else _cache.setdefault(key, make())      # noqa: E731
+_cached = rr.make_cached()
 CAM0, CAM1 = fr.CAM0, fr.CAM1
 
 

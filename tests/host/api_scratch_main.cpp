@@ -1,11 +1,18 @@
 // Stand-alone check of sfd2_amd/csrc/api_scratch.h (tests/test_api_scratch_host.py builds it with -fsanitize=address,undefined and runs it).
 // Every array lives on the heap at exactly its logical length, so a read past its end is an AddressSanitizer report.
+// After its own checks it answers one request per line of standard input (numbers through strtod / strtoll: hexadecimal floats pass unchanged):
+//   limits p_all_inliers confidence min_num_trials max_num_trials cap -> "min_trials max_trials"        trial_limits
+//   check confidence min_inlier_ratio min_num_trials max_num_trials   -> ransac_conf_error's text, or "ok"
 #include "../../sfd2_amd/csrc/api_scratch.h"
 
 #include <cstdio>
+#include <cstdlib>
 #include <initializer_list>
+#include <iostream>
 #include <limits>
 #include <memory>
+#include <sstream>
+#include <string>
 
 static int failures = 0;
 #define CHECK(cond)                                                       \
@@ -32,6 +39,19 @@ template <typename T> void finite_cases()
     CHECK(!all_finite(heap<T>({inf, T(0)}).get(), 2));
     CHECK(!all_finite(heap<T>({T(0), T(1), -inf}).get(), 3));
     CHECK(all_finite(heap<T>({T(0), nan}).get(), 1));          // the count bounds what is looked at
+}
+
+static double next_double(std::istringstream &in)
+{
+    std::string w;
+    in >> w;
+    return std::strtod(w.c_str(), nullptr);
+}
+static int64_t next_int(std::istringstream &in)
+{
+    std::string w;
+    in >> w;
+    return std::strtoll(w.c_str(), nullptr, 0);
 }
 
 int main()
@@ -80,7 +100,32 @@ int main()
     // ---- all_finite, float and double
     finite_cases<float>();
     finite_cases<double>();
+    // ---- the trial limits: the parts that need no reference (the grid against the restatement comes in through the requests)
+    CHECK(floored_ratio(0.5000099) == 0.5 && floored_ratio(0.25) == 0.25 && floored_ratio(1.0) == 1.0 && floored_ratio(0.0) == 0.0);
+    CHECK(num_trials(0.5, 1.0) == 1e300 && num_trials(0.0, 0.999) == 1e300 && num_trials(1.0, 0.999) == 1.0);
+    CHECK(ransac_conf_error(0.999, 0.25, 0, 10000) == nullptr && ransac_conf_error(0.0, 1.0, 0, 1) == nullptr);
+    CHECK(ransac_conf_error(std::numeric_limits<double>::quiet_NaN(), 0.25, 0, 10000) != nullptr);
     if (failures) return 1;
+    std::string line;
+    while (std::getline(std::cin, line)) {
+        std::istringstream in(line);
+        std::string cmd;
+        in >> cmd;
+        if (cmd == "limits") {
+            const double p_all = next_double(in), confidence = next_double(in);
+            const int64_t mn = next_int(in), mx = next_int(in), cap = next_int(in);
+            const TrialLimits t = trial_limits(confidence, mn, mx, cap, p_all);
+            std::printf("%lld %lld\n", (long long)t.min_trials, (long long)t.max_trials);
+        } else if (cmd == "check") {
+            const double confidence = next_double(in), ratio = next_double(in);
+            const int64_t mn = next_int(in), mx = next_int(in);
+            const char *bad = ransac_conf_error(confidence, ratio, mn, mx);
+            std::printf("%s\n", bad ? bad : "ok");
+        } else {
+            std::fprintf(stderr, "bad request: %s\n", line.c_str());
+            return 2;
+        }
+    }
     std::puts("api_scratch: ok");
     return 0;
 }

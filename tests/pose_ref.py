@@ -4,6 +4,8 @@ an independent fp64 P3P, the fp32 inlier test, the LO-RANSAC rounds and their st
 tests of tests/test_gpu_pose.py and the CPU checks of tests/test_pose_ref_host.py share."""
 import numpy as np
 
+import ransac_ref as rr
+
 PARAMS = {   # COLMAP parameter order
     "SIMPLE_PINHOLE": [800.0, 320.0, 240.0],
     "PINHOLE": [810.0, 790.0, 321.0, 239.0],
@@ -221,7 +223,7 @@ def refine_cauchy(cam, qvec, tvec, x, X, mask, iters=500):
 # specification and not from the kernel's code.  numpy, fp64 except where the specification says fp32.
 # =====================================================================================================================
 MODELS = ["SIMPLE_PINHOLE", "PINHOLE", "SIMPLE_RADIAL", "OPENCV"]
-ROUND = 256                  # trials per round
+ROUND = rr.ROUND             # trials per round
 LO_STEPS, LO_GN = 8, 3       # re-estimations per improvement, Gauss-Newton steps per re-estimation
 COLLINEAR_MIN = 1e-10        # |d12 x d13|^2 / (a12 a13) at or below which a sample gives no pose
 COPLANAR_MIN = 1e-12         # |det[y0 y1 y2]| at or below which a sample gives no pose
@@ -235,58 +237,10 @@ ROOT_SEP = 1e-3              # depth solutions closer than this (relative) are t
 # correct fp32 evaluation.  The same width is used for "equal" residual sums (fp32 sums of <= a few hundred terms).
 BAND = 1e-4
 
-_M64 = (1 << 64) - 1
-
-
-def mix64(z):
-    """splitmix64's output function on a Python int (mod 2^64)."""
-    z = (z + 0x9E3779B97F4A7C15) & _M64
-    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
-    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
-    return z ^ (z >> 31)
-
-
-def sample3(seed, trial, n):
-    """Three distinct indices in [0, n) from (seed, trial) only: h0 = mix64(seed ^ mix64(trial)), h1 = mix64(h0), h2 = mix64(h1);
-    i0 = h0 mod n, i1 = h1 mod (n - 1) skipping i0, i2 = h2 mod (n - 2) skipping both."""
-    h0 = mix64((seed & _M64) ^ mix64(trial & _M64))
-    h1 = mix64(h0)
-    h2 = mix64(h1)
-    i0 = h0 % n
-    i1 = h1 % (n - 1)
-    if i1 >= i0:
-        i1 += 1
-    i2 = h2 % (n - 2)
-    lo, hi = min(i0, i1), max(i0, i1)
-    if i2 >= lo:
-        i2 += 1
-    if i2 >= hi:
-        i2 += 1
-    return i0, i1, i2
-
-
-def _mix64v(z):
-    with np.errstate(over="ignore"):
-        z = z + np.uint64(0x9E3779B97F4A7C15)
-        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-        return z ^ (z >> np.uint64(31))
-
-
-def sample3v(seed, trials, n):
-    """sample3 for an array of trials (np.uint64 arithmetic): int64 [T, 3]."""
-    t = np.asarray(trials, dtype=np.int64).astype(np.uint64)
-    h0 = _mix64v(np.uint64(seed & _M64) ^ _mix64v(t))
-    h1 = _mix64v(h0)
-    h2 = _mix64v(h1)
-    i0 = (h0 % np.uint64(n)).astype(np.int64)
-    i1 = (h1 % np.uint64(n - 1)).astype(np.int64)
-    i1 += i1 >= i0
-    i2 = (h2 % np.uint64(n - 2)).astype(np.int64)
-    lo, hi = np.minimum(i0, i1), np.maximum(i0, i1)
-    i2 += i2 >= lo
-    i2 += i2 >= hi
-    return np.stack([i0, i1, i2], 1)
+# the sampling on integers is ransac_ref's, at sample size 3: i0 = h0 mod n, i1 = h1 mod (n - 1) skipping i0, i2 = h2 mod (n - 2) skipping both
+mix64, _mix64v = rr.mix64, rr._mix64v
+sample3 = lambda seed, trial, n: rr.sample_k(seed, trial, n, 3)          # noqa: E731
+sample3v = lambda seed, trials, n: rr.sample_kv(seed, trials, n, 3)      # noqa: E731
 
 
 # ------------------------------------------------------------------------------------------------------------ P3P (fp64)
@@ -471,25 +425,7 @@ def score_f32(pose, Xc, xn, th2, order="point"):
 
 
 # ------------------------------------------------------------------------------------------------------------ LO-RANSAC
-def num_trials_needed(inlier_ratio, confidence, multiplier=3.0):
-    """COLMAP's ComputeNumTrials for sample size 3: ceil(multiplier * log(1 - confidence) / log(1 - ratio^3))."""
-    nom = 1.0 - confidence
-    if nom <= 0:
-        return np.inf
-    den = 1.0 - inlier_ratio ** 3
-    if den <= 0:
-        return 1.0
-    if den == 1.0 or abs(np.log(den)) < 1e-16:
-        return np.inf
-    return float(np.ceil(np.log(nom) / np.log(den) * multiplier))
-
-
-def trial_limits(min_inlier_ratio, min_num_trials, max_num_trials, confidence, multiplier=3.0):
-    """(min_trials, max_trials): max_num_trials limited by the trial count of min_inlier_ratio floored to 1e-5 steps (COLMAP's
-    RANSAC), at least 1; min_num_trials clamped to it."""
-    dyn = num_trials_needed(np.floor(min_inlier_ratio * 100000) / 100000.0, confidence, multiplier)
-    mx = int(max(1, min(float(max_num_trials), dyn)))
-    return min(int(min_num_trials), mx), mx
+num_trials_needed, trial_limits = rr.trial_rule(3)       # COLMAP's ComputeNumTrials and trial limits for sample size 3
 
 
 def _exp_so3(w):
@@ -660,13 +596,7 @@ RANSAC_CASES = [(12, 0.0, "SIMPLE_PINHOLE", 1, 12.0), (12, 0.25, "PINHOLE", 101,
 RANSAC_CONF = dict(min_num_trials=0, confidence=0.9999)
 THRESH = 12.0
 FAR_OFFSET = (4e5, 5e6, 100.0)
-_cache = {}
-
-
-def _cached(key, make):
-    if key not in _cache:
-        _cache[key] = make()
-    return _cache[key]
+_cached = rr.make_cached()
 
 
 def ransac_cases():

@@ -1,22 +1,10 @@
-"""The restatement of the fundamental-matrix estimator (tests/fundamental_ref.py) on its own, on the CPU: the sampling, both seven-point
-routes against generating matrices and against each other, the closed-form trial counts, the derived band and F tolerance, the caps
-on left-out cases, the chart, and that breaking a rule changes a compared quantity on the committed cases."""
+"""The restatement of the fundamental-matrix estimator (tests/fundamental_ref.py) on its own, on the CPU: both
+seven-point routes against generating matrices and against each other, the closed-form trial counts, the derived band and F tolerance, the caps
+on left-out cases, the chart, and that breaking a rule changes a compared quantity on the committed cases.  The sampling is checked
+at every sample size in tests/test_ransac_ref_host.py."""
 import numpy as np
 
 import fundamental_ref as fr
-
-
-def test_sampling_on_integers():
-    for n in (7, 8, 9, 40, 300, 2 ** 31 - 1):
-        for trial in (0, 1, 255, 256, 10 ** 9):
-            s = fr.sample_k(12345, trial, n)
-            assert len(set(s)) == 7 and all(0 <= i < n for i in s)
-            assert tuple(fr.sample_kv(12345, [trial], n)[0]) == s
-    assert sorted(fr.sample_k(0, 0, 7)) == list(range(7))
-    # the scheme is two_view_ref.sample5's: the first five draws of a sample of seven are the sample of five
-    assert fr.sample_k(3, 17, 40)[:5] == fr.tv.sample5(3, 17, 40)
-    hist = np.bincount(fr.sample_kv(3, np.arange(20000), 14).ravel(), minlength=14)
-    assert hist.min() > 9500 and hist.max() < 10500
 
 
 def _exact_samples(count):

@@ -1,21 +1,11 @@
-"""The restatement of the homography estimator (tests/homography_ref.py) on its own, on the CPU: the sampling, both four-point routes
+"""The restatement of the homography estimator (tests/homography_ref.py) on its own, on the CPU: both four-point routes
 against generating matrices and against each other, the closed-form trial counts, the chart, the derived band and H tolerance, the
-caps on left-out cases, the margins of the decision's scenes, and that breaking a rule changes a compared quantity."""
+caps on left-out cases, the margins of the decision's scenes, and that breaking a rule changes a compared quantity.  The sampling is checked
+at every sample size in tests/test_ransac_ref_host.py."""
 import numpy as np
 
 import homography_ref as hr
 from sfd2_amd import two_view
-
-
-def test_sampling_on_integers():
-    for n in (4, 5, 6, 40, 300, 2 ** 31 - 1):
-        for trial in (0, 1, 255, 256, 10 ** 9):
-            s = hr.sample_k(12345, trial, n)
-            assert len(set(s)) == 4 and all(0 <= i < n for i in s)
-            assert tuple(hr.sample_kv(12345, [trial], n)[0]) == s
-    assert sorted(hr.sample_k(0, 0, 4)) == list(range(4))
-    # one scheme for every sample size: the first four draws of a sample of five are the sample of four
-    assert hr.tv.sample5(3, 17, 40)[:4] == hr.sample_k(3, 17, 40)
 
 
 def _exact_samples(count, rotation=False):

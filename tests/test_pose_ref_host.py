@@ -1,4 +1,5 @@
-"""The restatement of the pose solver (tests/pose_ref.py: mix64 / sample3, p3p_ref, score_f32, lo_ransac_ref) checked on its own,
+"""The restatement of the pose solver (tests/pose_ref.py: p3p_ref, score_f32, lo_ransac_ref; its sampling is checked with the other
+estimators' in tests/test_ransac_ref_host.py) checked on its own,
 without a GPU and without the library: against generating poses, closed-form trial counts and its own deliberately broken
 variants.  The caps on what the GPU tests of tests/test_gpu_pose.py may leave out are asserted here, on the committed seeds."""
 import numpy as np
@@ -6,20 +7,6 @@ import pytest
 
 import pose_ref as pr
 from test_gpu_pose import _check_accuracy
-
-
-def test_mix64_and_sample3():
-    assert pr.mix64(0) == 0xE220A8397B1DCDAF                       # splitmix64's first output for state 0
-    for n in (3, 4, 5, 257):
-        for seed in (0, 0xDEADBEEFCAFEF00D):
-            v = pr.sample3v(seed, np.arange(10000), n)
-            assert v.min() >= 0 and v.max() < n
-            assert (v[:, 0] != v[:, 1]).all() and (v[:, 0] != v[:, 2]).all() and (v[:, 1] != v[:, 2]).all()
-            for i in range(0, 10000, 997):
-                assert tuple(v[i]) == pr.sample3(seed, i, n)
-            if n > 3:
-                assert len({tuple(r) for r in v}) > min(1000, n * (n - 1) * (n - 2) // 2)       # and they do vary
-    assert not np.array_equal(pr.sample3v(0, np.arange(64), 257), pr.sample3v(1, np.arange(64), 257))
 
 
 def test_undistort_is_converged_and_jacobian_is_right():

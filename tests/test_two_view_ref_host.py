@@ -1,25 +1,12 @@
-"""The restatement of the relative pose solver (tests/two_view_ref.py) on its own, on the CPU: the sampling, the five-point solver
+"""The restatement of the relative pose solver (tests/two_view_ref.py) on its own, on the CPU: the five-point solver
 against generating matrices, the closed-form trial counts, the derived band, the caps on banded and left-out cases, and that
-breaking a rule changes a compared quantity on the committed cases."""
+breaking a rule changes a compared quantity on the committed cases.  The sampling is checked
+at every sample size in tests/test_ransac_ref_host.py."""
 import numpy as np
 import pytest
 
 import pose_ref as pr
 import two_view_ref as tv
-
-
-def test_sampling_on_integers():
-    assert tv.mix64(0) == 0xE220A8397B1DCDAF and tv.mix64(1) == 0x910A2DEC89025CC1      # splitmix64's first outputs
-    for n in (5, 6, 7, 40, 300, 2 ** 31 - 1):
-        for trial in (0, 1, 255, 256, 10 ** 9):
-            s = tv.sample5(12345, trial, n)
-            assert len(set(s)) == 5 and all(0 <= i < n for i in s)
-            assert tuple(tv.sample5v(12345, [trial], n)[0]) == s
-    assert sorted(tv.sample5(0, 0, 5)) == [0, 1, 2, 3, 4]
-    assert tv.sample5(0, 0, 40) != tv.sample5(1, 0, 40) and tv.sample5(0, 0, 40) != tv.sample5(0, 1, 40)
-    # every index is drawn about equally often
-    hist = np.bincount(tv.sample5v(3, np.arange(20000), 10).ravel(), minlength=10)
-    assert hist.min() > 9500 and hist.max() < 10500
 
 
 def test_five_point_against_the_generating_matrix():
@@ -104,16 +91,6 @@ def test_breaking_a_rule_changes_a_compared_quantity(rule):
     for (p0, p1, c0, c1, _, _, th), ref in [list(zip(tv.ransac_cases(), tv.ransac_refs()))[k] for k in (2, 4, 7, 9)]:
         changed += _differs(tv.relative_pose_ref(p0, p1, c0, c1, th, **broken), ref)
     assert changed >= 1
-
-
-def test_seeds_are_64_bits_without_a_sign():
-    for n in (5, 60, 4096):
-        for trial in (0, 255, 256, 10 ** 9):
-            for seed in tv.SEED_RUNS:
-                assert tuple(tv.sample5v(seed, [trial], n)[0]) == tv.sample5(seed, trial, n)
-            assert tv.sample5(-1, trial, n) == tv.sample5(2 ** 64 - 1, trial, n) == tuple(tv.sample5v(-1, [trial], n)[0])
-    # the top bit reaches the draw
-    assert tv.sample5(2 ** 63, 0, 60) != tv.sample5(0, 0, 60) and tv.sample5(2 ** 64 - 1, 0, 60) != tv.sample5(2 ** 63 - 1, 0, 60)
 
 
 def test_edge_tables_stay_within_their_caps():

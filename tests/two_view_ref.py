@@ -5,11 +5,14 @@ its chart, and runs its own QR iteration and inverse iteration on the action mat
 the LO-RANSAC rounds with their support order and stopping rule, the final refinement, the cheirality choice and the triangulation
 angles; and the committed cases the GPU tests (tests/test_gpu_two_view.py, tests/test_gpu_two_view_edges.py) and the CPU checks
 (tests/test_two_view_ref_host.py) share.  Everything is batched over hypotheses so that a round of 256 trials is a handful of numpy calls."""
+import functools
+
 import numpy as np
 
 import pose_ref as pr
+import ransac_ref as rr
 
-ROUND = 256
+ROUND = rr.ROUND
 POLISH, LO_STEPS, LO_GN, REF_ITERS = 3, 8, 3, 50
 RANK_MIN = 1e-12             # sigma_5 / sigma_1 of the 5 x 9 system at or below which a sample gives no hypothesis
 NEAR = pr.NEAR               # a degeneracy measure within this factor of its threshold is too close to call
@@ -24,42 +27,10 @@ EXACT_SUM = 1e-24            # a sum of squared Sampson errors below this is tha
 # depends on which steps rounding let pass (`cost <= cost before` in a flat valley), and two implementations end apart by about the
 # step that remains: a case whose remaining Gauss-Newton step is longer than a hundredth of the pose tolerance is too close to call.
 REFINE_LEFT = 1e-8
-_M64 = (1 << 64) - 1
-mix64 = pr.mix64
-
-
-# ------------------------------------------------------------------------------------------------------------ sampling
-def sample5(seed, trial, n):
-    """Five distinct indices in [0, n) from (seed, trial) only, on Python ints: h_0 = mix64(seed ^ mix64(trial)), h_k = mix64(h_k-1);
-    draw k is h_k mod (n - k), stepped over the earlier indices in ascending order."""
-    h = mix64((seed & _M64) ^ mix64(trial & _M64))
-    out = []
-    for k in range(5):
-        if k:
-            h = mix64(h)
-        v = h % (n - k)
-        for c in sorted(out):
-            if v >= c:
-                v += 1
-        out.append(v)
-    return tuple(out)
-
-
-def sample5v(seed, trials, n):
-    """sample5 for an array of trials (np.uint64 arithmetic): int64 [T, 5]."""
-    t = np.asarray(trials, dtype=np.int64).astype(np.uint64)
-    h = pr._mix64v(np.uint64(seed & _M64) ^ pr._mix64v(t))
-    cols = []
-    for k in range(5):
-        if k:
-            h = pr._mix64v(h)
-        v = (h % np.uint64(n - k)).astype(np.int64)
-        if cols:
-            srt = np.sort(np.stack(cols, 1), axis=1)
-            for p in range(k):
-                v = v + (v >= srt[:, p])
-        cols.append(v)
-    return np.stack(cols, 1)
+mix64 = rr.mix64
+# the sampling on integers is ransac_ref's, at sample size 5
+sample5 = lambda seed, trial, n: rr.sample_k(seed, trial, n, 5)          # noqa: E731
+sample5v = lambda seed, trials, n: rr.sample_kv(seed, trials, n, 5)      # noqa: E731
 
 
 # ------------------------------------------------------------------------------------------------------------ small algebra
@@ -271,35 +242,8 @@ def five_point_ref(x0, x1, drop_root=False, polish=POLISH):
 
 
 # ------------------------------------------------------------------------------------------------------------ LO-RANSAC
-def num_trials_needed(inlier_ratio, confidence, multiplier=3.0):
-    """COLMAP's ComputeNumTrials for sample size 5."""
-    nom = 1.0 - confidence
-    if nom <= 0:
-        return np.inf
-    den = 1.0 - inlier_ratio ** 5
-    if den <= 0:
-        return 1.0
-    if den == 1.0 or abs(np.log(den)) < 1e-16:
-        return np.inf
-    return float(np.ceil(np.log(nom) / np.log(den) * multiplier))
-
-
-def trial_limits(min_inlier_ratio, min_num_trials, max_num_trials, confidence, multiplier=3.0):
-    dyn = num_trials_needed(np.floor(min_inlier_ratio * 100000) / 100000.0, confidence, multiplier)
-    mx = int(max(1, min(float(max_num_trials), dyn)))
-    return min(int(min_num_trials), mx), mx
-
-
+num_trials_needed, trial_limits = rr.trial_rule(5)       # COLMAP's ComputeNumTrials and trial limits for sample size 5
 DEFAULTS = dict(min_inlier_ratio=0.25, min_num_trials=0, max_num_trials=10000, confidence=0.999, seed=0)
-
-
-def _in_band(e, th2):
-    return bool(np.any(np.abs(e - th2) <= BAND * th2))
-
-
-def _close(a, b):
-    """Two sums of squared errors are too close to order: within the band of each other, or both an exact fit's (rounding only)."""
-    return abs(a - b) <= BAND * max(abs(a), abs(b)) or max(abs(a), abs(b)) < EXACT_SUM
 
 
 def _distinct(Ea, Eb):
@@ -309,67 +253,21 @@ def _distinct(Ea, Eb):
     return min(np.linalg.norm(a - b), np.linalg.norm(a + b)) > 1e-8
 
 
-def _lo_tie_matters(e, th2):
-    """A re-estimate that ties with its predecessor (the local optimisation has converged: same count, sums within the band) may be
-    accepted or not; the two matrices differ by the last step only, which matters when a point is within 1e-3 of the threshold."""
-    return bool(np.any(np.abs(e - th2) <= 1e-3 * th2))
+def _lo_step(pose, E, inl, x0, x1):
+    """One re-estimation: LO_GN Gauss-Newton steps over the inliers from the pose carried so far."""
+    R, t, ok = gauss_newton(pose[0], pose[1], x0[None], x1[None], LO_GN, inl[None])
+    return ((R, t), (skew(t) @ R)[0]) if ok[0] else None
 
 
-def lo_ransac_ref(x0, x1, th2, min_inlier_ratio=0.25, min_num_trials=0, max_num_trials=10000, confidence=0.999, seed=0, multiplier=3.0,
-                  lo=True, smaller_sum=True, drop_root=False, dead_lanes=False):
-    """The rounds on normalised points.  Returns {'E' (None without a hypothesis), 'cnt', 'sum', 'trials', 'banded', 'why' (the reasons),
-    'either' (the other matrices that fit every point to rounding as the best one does)}.  multiplier, lo, smaller_sum, drop_root,
-    dead_lanes (a partial round runs all its 256 trials): the rule breaks of the host test."""
-    n = len(x0)
-    mn, mx = trial_limits(min_inlier_ratio, min_num_trials, max_num_trials, confidence, multiplier)
-    best, bE, why, trials, rnd = (-1, 0.0, np.inf), None, [], 0, 0
-    either = []
-    sg = 1.0 if smaller_sum else -1.0
-    while True:
-        tr = np.arange(rnd * ROUND, (rnd + 1) * ROUND if dead_lanes else min((rnd + 1) * ROUND, mx))
-        idx = sample5v(seed, tr, n)
-        Es, owner, near, _ = five_point_ref(x0[idx], x1[idx], drop_root)
-        if len(Es):
-            cnt, sm, _, err = support(Es, x0, x1, th2)
-            order = np.lexsort((tr[owner], sg * sm, -cnt))
-            w = order[0]
-            win = (int(cnt[w]), float(sm[w]), int(tr[owner[w]]))
-            if (win[0], -sg * win[1], -win[2]) > (best[0], -sg * best[1], -best[2]):
-                rivals = [k for k in order[1:] if cnt[k] == cnt[w] and _close(sm[k], sm[w]) and _distinct(Es[k], Es[w])]
-                # A winner that fits every point to rounding (n = 5: each of the sample's solutions does; a planar scene: both
-                # plane-consistent ones do) is ordered among its like by rounding alone.  Those rivals are not a reason to leave
-                # the case out: they are reported, and any one of them is a right answer.
-                exact = win[0] == n and win[1] < EXACT_SUM
-                either = []
-                for k in rivals if exact else []:
-                    if all(_distinct(Es[k], Eo) for Eo in either):
-                        either.append(Es[k])
-                why += ["rival"] * int(bool(rivals) and not exact) + ["threshold"] * int(_in_band(err[w], th2)) + ["near"] * int(near[owner[w]])
-                why += ["tie"] * int(best[0] == win[0] and _close(best[1], win[1]))
-                best, bE = win, Es[w]
-                if lo:
-                    R, t = decompose(bE[None])
-                    for _ in range(LO_STEPS):
-                        inl = (sampson_f64(bE, x0, x1) <= th2).astype(np.float64)
-                        R, t, ok = gauss_newton(R, t, x0[None], x1[None], LO_GN, inl[None])
-                        if not ok[0]:
-                            break
-                        En = (skew(t) @ R)[0]
-                        c, s, _, e = support(En, x0, x1, th2)
-                        tie = int(c) == best[0] and _close(float(s), best[1]) and _distinct(En, bE) and _lo_tie_matters(e, th2)
-                        why += ["lo threshold"] * int(_in_band(e, th2)) + ["lo tie"] * int(tie)
-                        if not (c > best[0] or (c == best[0] and sg * s < sg * best[1])):
-                            break
-                        best, bE = (int(c), float(s), best[2]), En
-            elif win[0] == best[0] and _close(win[1], best[1]) and _distinct(Es[w], bE):
-                why.append("tie")
-        trials = min((rnd + 1) * ROUND, mx)
-        if trials >= mx:
-            break
-        if trials >= mn and best[0] > 0 and trials >= num_trials_needed(best[0] / n, confidence, multiplier):
-            break
-        rnd += 1
-    return {"E": bE, "cnt": best[0], "sum": best[1], "trials": trials, "banded": bool(why), "why": why, "either": either}
+# The rounds are ransac_ref.lo_ransac's.  E decomposes once when a hypothesis wins and carries (R, t) through the LO_STEPS; a winner is
+# exact only when it holds all n points (a sample's other solutions hold its five and little else).
+MODEL = rr.Model(name="E", sample_size=5, solver=five_point_ref, support=support, error=sampson_f64, distinct=_distinct, band=BAND,
+                 exact_sum=EXACT_SUM, lo_steps=LO_STEPS, lo_start=lambda E: decompose(E[None]), lo_step=_lo_step,
+                 rule_breaks=("drop_root", "dead_lanes"), exact_needs_all=True)
+
+
+# lo_ransac_ref(x0, x1, th2, **conf): {'E' (None without a hypothesis), 'cnt', 'sum', 'trials', 'banded', 'why', 'either'}.
+lo_ransac_ref = functools.partial(rr.lo_ransac, MODEL)
 
 
 # ------------------------------------------------------------------------------------------------------------ final stage
@@ -394,26 +292,16 @@ def final_stage(E, mask, x0, x1, slots=SLOTS):
     """Levenberg-Marquardt over the masked correspondences from decompose(E), then the first slot with the most masked points in
     front of both cameras.  Returns (R, t, angles [n] with NaN outside, chosen, other = the same four of the slot -E would have
     led to, None when that is the same slot; left = the length of the Gauss-Newton step that remains at the returned pose)."""
-    R, t = decompose(E[None])
     w = mask.astype(np.float64)[None]
-    H, g, c = normal_equations(R, t, x0[None], x1[None], w)
-    lam = 1e-4
-    for _ in range(REF_ITERS):
+
+    def system(pose):                                      # a batch of one
+        H, g, c = normal_equations(pose[0], pose[1], x0[None], x1[None], w)
+        return H, g, c[0]
+
+    def solve(H, g, lam):
         d, ok = solve5(H, g, lam)
-        if not ok[0]:
-            break
-        Rn, tn = apply_update(R, t, d)
-        Hn, gn, cn = normal_equations(Rn, tn, x0[None], x1[None], w)
-        step = float(np.sum(d * d))
-        if np.isfinite(cn[0]) and cn[0] <= c[0]:
-            R, t, H, g, c = Rn, tn, Hn, gn, cn
-            lam = max(lam * 0.1, 1e-12)
-            if step < 1e-26:
-                break
-        else:
-            lam *= 10.0
-            if lam > 1e12 or step < 1e-26:
-                break
+        return d, ok[0]
+    (R, t), H, g = rr.levenberg_marquardt(decompose(E[None]), system, solve, lambda pose, d: apply_update(pose[0], pose[1], d), REF_ITERS)
     d, ok = solve5(H, g)
     left = float(np.linalg.norm(d[0])) if ok[0] else np.inf
     R, t = R[0], t[0]
@@ -470,13 +358,7 @@ def relative_pose_ref(p0, p1, cam0, cam1, max_error_px=4.0, min_num_inliers=15, 
 
 
 # ------------------------------------------------------------------------------------------------------------ scenes and cases
-_cache = {}
-
-
-def _cached(key, make):
-    if key not in _cache:
-        _cache[key] = make()
-    return _cache[key]
+_cached = rr.make_cached()
 
 
 def two_view_scene(rs, cam0, cam1, n, outlier_ratio=0.0, noise_px=0.0, baseline=None, px0=None, forward=False, planar=False):
@@ -637,7 +519,7 @@ def probe_expect(family):
             k = int(np.argmin(dist))
             cnt, sm, _, err = support(Eh, x0, x1, th2)
             exact = np.flatnonzero((cnt == len(x0)) & (sm < EXACT_SUM))
-            if near[h] or _in_band(err, th2):
+            if near[h] or bool(np.any(np.abs(err - th2) <= BAND * th2)):
                 exp.append((None, []))
             elif not (dist[k] < 1e-6 and k in exact):
                 exp.append((False, []))
